@@ -15,7 +15,10 @@ streams a GPU owns.
   ranks longest first (sharding.plan_sequences); N = 4: 00+02+05+06, otherwise 00..10 (with --bin 11 for config #5).
 
 Prints ONE JSON line on rank 0.  At N = 1 the line also carries: `exact_mode` (whole sequences per stream),
-`pcie_inclusive` (host images through vslam_process_host), `cpu_baseline` (the oracle on the host cores)."""
+`pcie_inclusive` (host images through vslam_process_host), `cpu_baseline` (the oracle on the host cores).
+
+--dump-outputs DIR writes what the timed path computed in its last step (poses, frame infos, a fixed sample of the keypoints,
+descriptors and points) to DIR/*.npy; the inputs depend only on the arguments, so two builds can be compared output for output."""
 import argparse
 import ctypes as C
 import json
@@ -53,6 +56,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-pcie", action="store_true")
     ap.add_argument("--no-shim", action="store_true")
     ap.add_argument("--only-shim", action="store_true", help="print the shim_path block alone (one JSON line) and stop")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/*.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -127,6 +132,45 @@ def algorithmic_bytes(cfg, B, stats):
     # (those re-reads are register / LDS resident: M < 512 lanes, one measurement per lane, nothing of them reaches HBM)
     extra["k_frame_hbm_only"] = (per_frame["k_frame"] - I * M * 64) * B
     return {k: v * B for k, v in per_frame.items()}, extra
+
+
+DUMP_SAMPLE_STREAMS = 16        # streams whose keypoints and points --dump-outputs writes (a fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(api, poses, streams, out_dir, seed=0):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as .npy files in out_dir (rank 0's streams).
+      poses.npy       float64 [streams][12]  camera_left_to_world (3x4, row-major) of each stream's last frame, as the timed path
+                                             copied it out (`poses`)
+      frame_info.npy  float64 [streams][F]   the fields of vslam_frame_info in struct order, arrays flattened in place
+      keypoints.npy   float32 [n][37]        stream, side (0 left, 1 right), x, y, score, 32 descriptor bytes
+      points.npy      float64 [n][17]        stream, kp (4), meta (6), camera-frame xyz (3), landmark xyz (3)
+    keypoints.npy and points.npy cover a fixed sample of DUMP_SAMPLE_STREAMS streams drawn with `seed`; every value in them is
+    exact in its dtype.  The inputs of a bench run depend only on its arguments, so two builds can be compared file by file."""
+    streams = list(streams)
+    pick = sorted(int(i) for i in np.random.default_rng(seed).choice(len(streams), min(DUMP_SAMPLE_STREAMS, len(streams)), replace=False))
+    info = []
+    for s in streams:
+        d = api.frame_info(s).as_dict()
+        info.append(np.concatenate([np.ravel(np.asarray(v, np.float64)) for v in d.values()]))
+    kps, pts = [], []
+    for i in pick:
+        s = streams[i]
+        for side in (0, 1):
+            xy, score, desc = api.keypoints(s, side)
+            kps.append(np.hstack([np.full((len(xy), 1), s, np.float32), np.full((len(xy), 1), side, np.float32), xy.astype(np.float32),
+                                  score[:, None].astype(np.float32), desc.astype(np.float32)]))
+        p = api.points(s)
+        pts.append(np.hstack([np.full((len(p["kp"]), 1), s, np.float64), p["kp"], p["meta"], p["cam"], p["lm"]]))
+    out = {"poses": np.asarray(poses, np.float64).reshape(len(streams), 12), "frame_info": np.stack(info),
+           "keypoints": np.concatenate(kps).reshape(-1, 37), "points": np.concatenate(pts).reshape(-1, 17)}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def frame_stats(api, streams):
@@ -358,6 +402,8 @@ class Bench(object):
         stats, flags = frame_stats(api, range(B))
         if comm is not None:
             comm.destroy()
+        if a.dump_outputs and rank == 0:
+            dump_outputs(api, pose_send[K - 1, :B].cpu().numpy(), range(B), a.dump_outputs)
 
         # instrumented pass: per-kernel device time with HIP events on the context's HIP streams
         api.enable_timers(True)
@@ -517,7 +563,7 @@ class Bench(object):
         return out
 
     # ------------------------------------------------------------------------------------------------------------------
-    def run_sequences(self, seq_ids, steps, warmup, api=None, label=None):
+    def run_sequences(self, seq_ids, steps, warmup, api=None, label=None, dump_dir=""):
         """Exact mode: whole sequences, one per stream, longest first over the ranks; every stream runs start to end on its
         own (results identical to the sequential run), shorter ones switch off when they end.  steps = 0: whole sequences."""
         cfg, world, rank = self.cfg, self.world, self.rank
@@ -579,6 +625,10 @@ class Bench(object):
         frames = self.sum_over_ranks(frames)
         live = [s for s in range(B) if my_len[s] >= K] or [0]
         stats, flags = frame_stats(api, live)
+        if dump_dir and rank == 0:
+            ran = [s for s in range(B) if my_len[s] > 0]         # each stream's last frame: K - 1, or its sequence's end
+            last = pose_send[ran, [min(K, my_len[s]) - 1 for s in ran]].cpu().numpy()
+            dump_outputs(api, last, ran, dump_dir)
         out = {"sequences": ["%02d" % i for i in seq_ids], "frames": int(frames), "seconds": round(elapsed, 4),
                "frames_per_s": round(frames / elapsed, 2), "steps": K, "streams_per_gpu": B,
                "rank_loads": load, "ms_per_step": round(elapsed / max(K, 1) * 1e3, 4),
@@ -592,7 +642,7 @@ class Bench(object):
         seq_ids = [0, 2, 5, 6] if self.world == 4 else list(range(11))
         if a.sequences:
             seq_ids = [int(x) for x in a.sequences.split(",")]
-        res, api, _ = self.run_sequences(seq_ids, a.steps, a.warmup, api=self.api)
+        res, api, _ = self.run_sequences(seq_ids, a.steps, a.warmup, api=self.api, dump_dir=a.dump_outputs)
         if self.rank != 0:
             return None
         K = res["steps"]

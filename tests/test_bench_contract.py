@@ -1,5 +1,6 @@
 """bench.py's measurement contract, the parts that need no GPU: the roofline's algorithmic bytes are SURVEY.md 8(d)'s rows and
-nothing else, and a counter file is reported only for the build it was recorded on."""
+nothing else, a counter file is reported only for the build it was recorded on, and --dump-outputs writes the same files for
+the same readbacks."""
 import importlib
 import json
 import os
@@ -83,3 +84,61 @@ def test_sq_utilisation_formula_and_build_tie(bench, monkeypatch, tmp_path):
     (prof / bench.SQ_SUMMARY).write_text(json.dumps(rec))
     util, note = bench.sq_utilisation()
     assert util == {} and "recorded on source" in note
+
+
+def test_dump_outputs_writes_what_the_caller_receives(bench, tmp_path):
+    import numpy as np
+    from vslam_pose_estimation_framework_amd.capi import FrameInfo
+
+    class FakeApi(object):
+        """Readbacks of a context with 40 streams; every value derived from the stream index."""
+        def frame_info(self, s):
+            fi = FrameInfo()
+            fi.n_points, fi.total_error = 3 * s, 0.5 * s
+            fi.camera_left_to_world[11] = s
+            return fi
+
+        def keypoints(self, s, side):
+            n = 5 + s + side
+            return (np.full((n, 2), s, np.int16), np.arange(n, dtype=np.int32), np.full((n, 32), 255 - side, np.uint8))
+
+        def points(self, s):
+            n = 2 + s % 3
+            return dict(kp=np.full((n, 4), -s, np.int16), meta=np.full((n, 6), 1 << 20, np.int32), cam=np.full((n, 3), 0.1 * s),
+                        lm=np.full((n, 3), 1e3 + s))
+
+    api, streams = FakeApi(), list(range(40))
+    poses = np.arange(40 * 12, dtype=np.float64).reshape(40, 12)
+    shapes = bench.dump_outputs(api, poses, streams, str(tmp_path / "a"))
+    bench.dump_outputs(api, poses, streams, str(tmp_path / "b"))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["frame_info.npy", "keypoints.npy", "points.npy", "poses.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)      # same arguments, same sample, same files
+        assert list(a.shape) == shapes[n[:-4]]
+        total += a.nbytes
+    assert total <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "poses.npy"), poses)
+    info = np.load(tmp_path / "a" / "frame_info.npy")
+    width = sum(len(v) if isinstance(v, list) else 1 for v in FrameInfo().as_dict().values())
+    assert info.shape == (40, width)
+    col = 0
+    for name, v in FrameInfo().as_dict().items():                   # struct order, arrays flattened in place
+        if name == "n_points":
+            assert np.array_equal(info[:, col], 3.0 * np.arange(40))
+        if name == "total_error":
+            assert np.array_equal(info[:, col], 0.5 * np.arange(40))
+        if name == "camera_left_to_world":
+            assert np.array_equal(info[:, col + 11], np.arange(40.0))
+        col += len(v) if isinstance(v, list) else 1
+    kp = np.load(tmp_path / "a" / "keypoints.npy")
+    sampled = sorted(set(kp[:, 0].astype(int)))
+    assert len(sampled) == bench.DUMP_SAMPLE_STREAMS
+    for s in sampled:
+        rows = kp[kp[:, 0] == s]
+        assert len(rows) == (5 + s) + (6 + s) and set(rows[:, 1]) == {0, 1}
+        assert np.all(rows[rows[:, 1] == 1, 5:] == 254) and np.all(rows[:, 2:4] == s)
+    pts = np.load(tmp_path / "a" / "points.npy")
+    assert sorted(set(pts[:, 0].astype(int))) == sampled and np.all(pts[:, 5:11] == 1 << 20)

@@ -1,5 +1,5 @@
 import os, sys, time
-ROOT = "/root/repo" if os.path.isdir("/root/repo/tests") else os.getcwd()
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from _oracle import Oracle
