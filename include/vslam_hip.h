@@ -56,7 +56,8 @@ typedef enum { VSLAM_LOCALIZING = 0, VSLAM_TRACKING = 1 } vslam_tracker_status; 
 /* All parameters the hot path reads.  Names follow the reference's YAML keys
  * (configurations/configuration_kitti.yaml:49-134, src/types/parameters.h:64-330). */
 typedef struct vslam_config {
-  /* camera (src/types/camera.h): left == right intrinsics for a rectified pair */
+  /* camera (src/types/camera.h): left == right intrinsics for a rectified pair.  With vslam_set_rectification the
+     context takes raw pairs and these describe the RECTIFIED pair the maps produce (rows x cols, K = P1, baseline from P2) */
   int32_t rows, cols;
   double K[9];          /* cameraMatrix(), row-major                                        */
   double baseline_h[3]; /* Camera::baselineHomogeneous() of the right camera: (-fx*B, 0, 0) */
@@ -190,6 +191,32 @@ int vslam_process_device(vslam_ctx* ctx, const uint8_t* left, const uint8_t* rig
                          int32_t row_stride_bytes, size_t image_stride_bytes);
 int vslam_process_host(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right,
                        int32_t row_stride_bytes, size_t image_stride_bytes);
+/* ---- rectification of raw, distorted stereo pairs (opt-in) ---------------------------------------------------------------
+ * A context gets one rig, shared by all its streams, as two fixed-point remap maps per side at the RECTIFIED size (cfg rows x cols),
+ * in the format cv::convertMaps(..., CV_16SC2) / initUndistortRectifyMap(..., CV_16SC2) produce [recalled], so a caller that has
+ * OpenCV passes its own maps unchanged:
+ *   map_xy: int16 [rows][cols][2] = (ix >> 5, iy >> 5), ix = rint(32 u), iy = rint(32 v), (u, v) the source coordinate in the raw image
+ *   map_a : uint16 [rows][cols]   = (iy & 31) * 32 + (ix & 31); values >= 1024 are rejected (VSLAM_ERR_INVALID)
+ * Interpolation is cv::remap INTER_LINEAR, BORDER_CONSTANT 0 [recalled], in integers: ax = a & 31, ay = a >> 5,
+ *   w00 = (32-ax)(32-ay)*32, w01 = ax(32-ay)*32, w10 = (32-ax)ay*32, w11 = ax*ay*32 (sum 32768),
+ *   p_ij = raw[y0+i][x0+j] inside the raw image, else 0;  out = (sum w*p + 16384) >> 15.
+ * While rectification is set, vslam_process_host, vslam_process_device and vslam_frame_begin take RAW images of raw_rows x raw_cols
+ * (row stride >= raw_cols); one kernel (k_rectify) rectifies every stream's pair ahead of the detector, on the image queue.  Device
+ * images are read by that kernel only: they must stay valid until it has run, not until the frame ends.  Everything downstream
+ * reports rectified coordinates (keypoints, views, points, poses of the rectified left camera).  Rectification survives vslam_reset
+ * and vslam_reset_stream(s).
+ * vslam_set_rectification: all four map pointers NULL turns it off.  Host pointers, copied to the device before the call returns
+ *   (it synchronises the context).  VSLAM_ERR_STATE between vslam_frame_begin and the end of that frame.
+ * vslam_get_rectified_images: the rectified pair the last submitted frame of `stream` was processed on (rows*cols bytes each, dense);
+ *   VSLAM_ERR_STATE when rectification is off or no frame has been submitted since it was set.  Synchronises.
+ * vslam_remap_u8: the same remap stand-alone on host images (like vslam_resize_linear_u8): src is rows x cols with row_stride bytes
+ *   per row, dst is dst_rows x dst_cols (dense), the maps are dst-sized. */
+int vslam_set_rectification(vslam_ctx* ctx, int32_t raw_rows, int32_t raw_cols,
+                            const int16_t* map_xy_left, const uint16_t* map_a_left,
+                            const int16_t* map_xy_right, const uint16_t* map_a_right);
+int vslam_get_rectified_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
+int vslam_remap_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride,
+                   const int16_t* map_xy, const uint16_t* map_a, int32_t dst_rows, int32_t dst_cols, uint8_t* dst);
 /* Block until all queued work of the context is done; returns the sticky HIP error state (VSLAM_ERR_HIP once a runtime
  * call has failed, else VSLAM_OK; capacity overflows are reported in vslam_frame_info.error_flags, see VSLAM_ERR_CAPACITY). */
 int vslam_synchronize(vslam_ctx* ctx);

@@ -6,6 +6,7 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
                               [--format kitti|tum] [--gt poses.txt] [--max-frames N] [--config kitti|euroc]
                               [--chunks B [--overlap 6]]   frame-sharded mode: B chunks side by side (approximate at the seams)
     python tools/run_kitti.py <EuRoC dir with mav0/cam0 mav0/cam1> --format tum --out traj.txt   (ground truth found in mav0/)
+    python tools/run_kitti.py <EuRoC dir> --rectify --format tum --out traj.txt   raw images: rectified on the GPU from mav0/cam{0,1}/sensor.yaml
 
 The sequence runs in exact mode (one stream, whole sequence, bit-for-bit the reference port's arithmetic); images are
 uploaded frame by frame through vslam_process_host.  With --gt (KITTI 3x4 rows) the ATE-RMSE after rigid alignment is
@@ -23,7 +24,7 @@ import numpy as np  # noqa: E402
 from vslam_pose_estimation_framework_amd import evaluation, hip, io_formats  # noqa: E402
 
 
-def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log):
+def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -32,7 +33,9 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log):
     steps = max(e - s for (s, f, e) in plan)
     cfg.max_history_frames = steps + 2
     api.create(cfg, device, len(plan))
-    rows, cols = int(cfg.rows), int(cfg.cols)
+    if rect is not None:
+        api.set_rectification(rect)
+    rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
     Lb = np.zeros((len(plan), rows, cols), np.uint8)
     Rb = np.zeros_like(Lb)
     live = [True] * len(plan)
@@ -55,8 +58,10 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log):
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6):
+        chunks=0, overlap=6, rectify=False):
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
+    if rectify and not euroc:
+        raise SystemExit("--rectify: a KITTI odometry folder is already rectified (it takes raw EuRoC / ASL folders with sensor.yaml)")
     seq = io_formats.EurocSequence(seq_dir) if euroc else io_formats.KittiSequence(seq_dir)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
@@ -64,21 +69,41 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     left, right = seq.pair(0)
     api = hip.load()
     cfg = api.default_config("euroc" if euroc and which == "kitti" else which)
-    if euroc:
+    rect = None
+    if rectify:
+        from vslam_pose_estimation_framework_amd import rectify as rectify_mod
+        raw = seq.raw_calibration()
+        if raw is None:
+            raise SystemExit("--rectify: no mav0/cam0/sensor.yaml and mav0/cam1/sensor.yaml under %s" % seq_dir)
+        if (raw[0].rows, raw[0].cols) != left.shape:
+            raise SystemExit("--rectify: sensor.yaml says %dx%d, the images are %dx%d" % (raw[0].rows, raw[0].cols, left.shape[0], left.shape[1]))
+        rect = rectify_mod.rectification(*raw)
+        rectify_mod.apply_to_config(cfg, rect)
+        log("rectifying on the GPU: raw %dx%d -> %dx%d, f %.3f px, baseline %.4f m" % (
+            rect.raw_rows, rect.raw_cols, rect.rows, rect.cols, rect.P1[0, 0], -rect.P2[0, 3] / rect.P1[0, 0]))
+    elif euroc:
         cal = seq.calibration()       # a rectified export may carry its P0 / P1; otherwise the EuRoC values of the default config
         if cal is not None:
             io_formats.apply_calib(cfg, cal[0], cal[1], left.shape[0], left.shape[1])
         else:
             cfg.rows, cfg.cols = int(left.shape[0]), int(left.shape[1])
+            try:
+                raw = seq.raw_calibration()
+            except (ValueError, KeyError):
+                raw = None
+            if raw is not None and (np.any(raw[0].dist != 0) or np.any(raw[1].dist != 0)):
+                log("note: sensor.yaml describes distorted raw cameras and there is no calib.txt; --rectify rectifies them on the GPU")
     else:
         io_formats.apply_calib(cfg, seq.K, seq.baseline, left.shape[0], left.shape[1])
     t0 = time.perf_counter()
     flags = 0
     if chunks > 1:
-        poses, flags = run_chunked(api, cfg, seq, n, chunks, overlap, device, log)
+        poses, flags = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect)
     else:
         cfg.max_history_frames = 512
         api.create(cfg, device, 1)
+        if rect is not None:
+            api.set_rectification(rect)
         for k in range(n):
             if k:
                 left, right = seq.pair(k)
@@ -124,8 +149,10 @@ def main():
     ap.add_argument("--overlap", type=int, default=6, help="warm-up frames per chunk in frame-sharded mode")
     ap.add_argument("--layout", choices=("kitti", "euroc"), default="kitti", help="folder layout (a folder with mav0/ is taken as EuRoC / ASL)")
     ap.add_argument("--asl-gt", default=None, help="ASL ground-truth csv for the trajectory_analyzer step (needs --format tum --out)")
+    ap.add_argument("--rectify", action="store_true", help="EuRoC / ASL folder of raw images: undistort and rectify them on the GPU from mav0/cam{0,1}/sensor.yaml")
     a = ap.parse_args()
-    run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap)
+    run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
+        rectify=a.rectify)
 
 
 if __name__ == "__main__":

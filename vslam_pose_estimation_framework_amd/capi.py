@@ -172,6 +172,7 @@ class CApi(object):
         self.ctx = ctx
         self.cfg = cfg.copy()
         self.n_streams = n_streams
+        self.rect = None
         return self
 
     def destroy(self):
@@ -213,7 +214,10 @@ class CApi(object):
         if left.ndim == 2:
             left, right = left[None], right[None]
         assert left.shape == right.shape and left.shape[0] == self.n_streams
-        assert left.shape[1] == self.cfg.rows and left.shape[2] >= self.cfg.cols
+        if getattr(self, "rect", None) is not None:      # rectifying context: raw images
+            assert left.shape[1] == self.rect.raw_rows and left.shape[2] >= self.rect.raw_cols, (left.shape, self.rect.raw_rows, self.rect.raw_cols)
+        else:
+            assert left.shape[1] == self.cfg.rows and left.shape[2] >= self.cfg.cols
         stride = left.shape[2]
         self.check(self.fn("process_host")(self.ctx, _p(left, C.c_uint8), _p(right, C.c_uint8),
                                            C.c_int32(stride), C.c_size_t(left.shape[1] * stride)))
@@ -224,6 +228,29 @@ class CApi(object):
 
     def synchronize(self):
         self.check(self.fn("synchronize")(self.ctx))
+
+    # -- rectification of raw pairs (vslam_set_rectification) ---------------------------------------------------------
+    def set_rectification(self, rect):
+        """rect: rectify.Rectification (its maps at the context's rows x cols), or None to switch rectification off."""
+        if rect is None:
+            self.check(self.fn("set_rectification")(self.ctx, C.c_int32(0), C.c_int32(0), None, None, None, None))
+            self.rect = None
+            return
+        if (rect.rows, rect.cols) != (self.cfg.rows, self.cfg.cols):
+            raise ValueError("set_rectification: maps are %dx%d, the context is %dx%d" % (rect.rows, rect.cols, self.cfg.rows, self.cfg.cols))
+        xl, al = np.ascontiguousarray(rect.map_xy_left, np.int16), np.ascontiguousarray(rect.map_a_left, np.uint16)
+        xr, ar = np.ascontiguousarray(rect.map_xy_right, np.int16), np.ascontiguousarray(rect.map_a_right, np.uint16)
+        self.check(self.fn("set_rectification")(self.ctx, C.c_int32(rect.raw_rows), C.c_int32(rect.raw_cols), _p(xl, C.c_int16), _p(al, C.c_uint16),
+                                                _p(xr, C.c_int16), _p(ar, C.c_uint16)))
+        self.rect = rect
+
+    def rectified_images(self, stream=0):
+        """The rectified pair the last submitted frame of `stream` was processed on."""
+        rows, cols = int(self.cfg.rows), int(self.cfg.cols)
+        L = np.zeros((rows, cols), np.uint8)
+        R = np.zeros((rows, cols), np.uint8)
+        self.check(self.fn("get_rectified_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
+        return L, R
 
     # -- readback -----------------------------------------------------------------------------
     def frame_info(self, stream=0):
@@ -561,6 +588,18 @@ class CApi(object):
         dst = np.zeros((int(dst_rows), int(dst_cols)), np.uint8)
         self.check(self.fn("resize_linear_u8")(*self._ctx_args(), _p(img, C.c_uint8), C.c_int32(img.shape[0]), C.c_int32(img.shape[1]),
                                                C.c_int32(img.shape[1]), _p(dst, C.c_uint8), C.c_int32(dst.shape[0]), C.c_int32(dst.shape[1])))
+        return dst
+
+    def remap_u8(self, image, map_xy, map_a, cols=None):
+        """vslam_remap_u8: image is rows x stride (cols <= stride bytes used), the maps give the output size."""
+        img = np.ascontiguousarray(image, np.uint8)
+        mxy = np.ascontiguousarray(map_xy, np.int16)
+        ma = np.ascontiguousarray(map_a, np.uint16)
+        assert mxy.shape[:2] == ma.shape and mxy.shape[2] == 2
+        cols = img.shape[1] if cols is None else int(cols)
+        dst = np.zeros(ma.shape, np.uint8)
+        self.check(self.fn("remap_u8")(*self._ctx_args(), _p(img, C.c_uint8), C.c_int32(img.shape[0]), C.c_int32(cols), C.c_int32(img.shape[1]),
+                                       _p(mxy, C.c_int16), _p(ma, C.c_uint16), C.c_int32(ma.shape[0]), C.c_int32(ma.shape[1]), _p(dst, C.c_uint8)))
         return dst
 
     def harris_angle(self, image, xy):

@@ -14,6 +14,7 @@
 #include "kernels_orb.h"
 #include "kernels_landmark.h"
 #include "kernels_report.h"
+#include "kernels_rectify.h"
 
 #define VS_API extern "C" __attribute__((visibility("default")))
 
@@ -94,6 +95,14 @@ struct vslam_ctx {
                    // 2: two phase launches around the wide recovery kernel
                    // 4: phase launches around the wide recovery kernel, the landmark refinement in workgroups of its own inside the last one (fastest up to VS_SPLIT4_MAX_STREAMS streams)
   bool lm_published = false;                            // vslam_prune_recover has published the frame's history (one stream): vslam_compute runs the landmark refinement beside the stereo stage
+  // rectification of raw input pairs (vslam_set_rectification): maps at the rectified size, padded to map_stride entries per row, and
+  // the raw slabs [step parity][left/right] host images are copied into (B x raw_rows x raw_stride each).  k_rectify writes the rectified
+  // pair into upload[parity], so everything downstream, and the two-parity lifetime of the image slabs, is unchanged.
+  struct Rect { bool on = false, have_frame = false; int raw_rows = 0, raw_cols = 0, raw_stride = 0, map_stride = 0; size_t raw_stream_stride = 0;
+                int16_t* map_xy[2] = {nullptr, nullptr}; uint16_t* map_a[2] = {nullptr, nullptr};
+                uint8_t* raw[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+                const uint8_t* src[2] = {nullptr, nullptr}; int32_t src_row_stride = 0; size_t src_stream_stride = 0;   // this step's raw input
+                std::vector<void*> mem; } rect;
   int sticky = VSLAM_OK;
 };
 
@@ -572,6 +581,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (auto& e : c->scratch) vslam_destroy(e.t);
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
+  for (void* p : c->rect.mem) (void)hipFree(p);
   tmp_free(c);
   depth_map_free(c);
   if (c->report) (void)hipHostFree(c->report);
@@ -694,6 +704,17 @@ static int launch_image_pipeline(vslam_ctx* c) {
     // the image products of this set were last read by the frame kernel two steps ago; the detector thresholds come
     // from the controller in k_emit of the previous step (other image stream)
     if (g.frm_pending[set] && st != g.st_frm) HIP_TRY(c, hipStreamWaitEvent(st, g.ev_frm[set], 0));
+    if (c->rect.on) {
+      // raw pair -> rectified pair in upload[set] (the slab the wait above has freed), ahead of the detector
+      const vslam_ctx::Rect& q = c->rect;
+      RectArgs ra;
+      for (int k = 0; k < 2; ++k) { ra.src[k] = q.src[k]; ra.map_xy[k] = q.map_xy[k]; ra.map_a[k] = q.map_a[k]; ra.dst[k] = c->upload[set][k]; }
+      ra.src_stream_stride = q.src_stream_stride; ra.src_row_stride = q.src_row_stride; ra.src_rows = q.raw_rows; ra.src_cols = q.raw_cols;
+      ra.map_stride = q.map_stride; ra.dst_stream_stride = c->up_stream_stride; ra.dst_row_stride = c->up_stride;
+      ra.rows = d.c.rows; ra.cols = d.c.cols; ra.s0 = g.s0; ra.n = g.n; ra.sides = 2;
+      std::memcpy(ra.active, c->buf.active, sizeof ra.active);
+      hipLaunchKernelGGL(k_rectify, dim3((d.c.cols + 255) / 256, (d.c.rows + 3) / 4, 2 * ((g.n + VS_RECT_SB - 1) / VS_RECT_SB)), dim3(256), 0, st, ra);
+    }
     if (g.emit_pending[set ^ 1] && (g.st_img != g.st_img2 || c->img_override)) HIP_TRY(c, hipStreamWaitEvent(st, g.ev_emit[set ^ 1], 0));
     dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * g.n);
     const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
@@ -727,6 +748,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
     if (st != g.st_frm) { HIP_TRY(c, hipEventRecord(g.ev_img[set], st)); HIP_TRY(c, hipStreamWaitEvent(g.st_frm, g.ev_img[set], 0)); }
   }
   c->last_set = set;
+  if (c->rect.on) c->rect.have_frame = true;
   return VSLAM_OK;
 }
 static int frame_done(vslam_ctx* c) {
@@ -794,15 +816,20 @@ static int set_images_device(vslam_ctx* c, const uint8_t* L, const uint8_t* R, i
   c->buf.img_stream_stride = image_stride;
   return VSLAM_OK;
 }
-static int upload_images(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride) {
+// where a step's input images live on the device
+struct ImgLoc { const uint8_t* p[2]; int32_t row_stride; size_t stream_stride; };
+// Host images of all streams (rows x cols each) into the device slabs dst[left/right] (dst_stride bytes per row, dst_stream_stride per
+// stream); *out receives where they landed: one copy per side keeps the caller's strides.
+static int upload_to(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, int rows, int cols,
+                     uint8_t* const dst[2], int32_t dst_stride, size_t dst_stream_stride, ImgLoc* out) {
   if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");
-  if (row_stride < c->cfg.c.cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
+  if (row_stride < cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
   // Host images of all streams in one (nearly) dense block: one copy per side, the caller's strides kept on the device
   // (2 B strided 2-D copies per step cost more in submission than in transfer).
-  const size_t span = (size_t)(c->B - 1) * image_stride + (size_t)(c->cfg.c.rows - 1) * row_stride + c->cfg.c.cols;   // last byte the caller owns
-  const size_t dense = (size_t)c->B * c->cfg.c.rows * c->cfg.c.cols;
-  const bool ordered = c->B == 1 || image_stride >= (size_t)c->cfg.c.rows * row_stride;
-  if (c->groups.size() == 1 && ordered && span <= (size_t)c->B * c->up_stream_stride && span <= dense + dense / 8) {
+  const size_t span = (size_t)(c->B - 1) * image_stride + (size_t)(rows - 1) * row_stride + cols;   // last byte the caller owns
+  const size_t dense = (size_t)c->B * rows * cols;
+  const bool ordered = c->B == 1 || image_stride >= (size_t)rows * row_stride;
+  if (c->groups.size() == 1 && ordered && span <= (size_t)c->B * dst_stream_stride && span <= dense + dense / 8) {
     hipStream_t st = c->img_override ? c->img_override : (c->parity ? c->groups[0].st_img2 : c->groups[0].st_img);
     // A small pageable source (the literal drop-in: one cv::Mat pair per call) goes through pinned memory of the context: the
     // runtime's own staging of a pageable hipMemcpyAsync costs ~0.12 ms of host time per 467 KB image here, a memcpy into a pinned
@@ -828,45 +855,72 @@ static int upload_images(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32
         }
         unsigned char* stage = c->pin_img[c->parity];
         std::memcpy(stage, L, span);
-        HIP_TRY(c, hipMemcpyAsync(c->upload[c->parity][0], stage, span, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(dst[0], stage, span, hipMemcpyHostToDevice, st));
         std::memcpy(stage + half, R, span);
-        HIP_TRY(c, hipMemcpyAsync(c->upload[c->parity][1], stage + half, span, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(dst[1], stage + half, span, hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipEventRecord(c->pin_ev[c->parity], st));
         c->pin_used[c->parity] = true;
-        return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], row_stride, image_stride);
+        *out = {{dst[0], dst[1]}, row_stride, image_stride};
+        return VSLAM_OK;
       }
     }
-    HIP_TRY(c, hipMemcpyAsync(c->upload[c->parity][0], L, span, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->upload[c->parity][1], R, span, hipMemcpyHostToDevice, st));
-    return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], row_stride, image_stride);
+    HIP_TRY(c, hipMemcpyAsync(dst[0], L, span, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(dst[1], R, span, hipMemcpyHostToDevice, st));
+    *out = {{dst[0], dst[1]}, row_stride, image_stride};
+    return VSLAM_OK;
   }
-  if (row_stride <= c->up_stride) {
+  if (row_stride <= dst_stride) {
     // one contiguous copy per image, rows keep the caller's stride (a pitched host-to-device copy is issued row by row
     // by the runtime: measured 0.13 GB/s against 43 GB/s for the plain copy)
     for (int s = 0; s < c->B; ++s) {
       const vslam_ctx::Group& gg = c->groups[group_of(c, s)];
       hipStream_t st = c->parity ? gg.st_img2 : gg.st_img;
-      const size_t bytes = (size_t)(c->cfg.c.rows - 1) * row_stride + c->cfg.c.cols;
-      HIP_TRY(c, hipMemcpyAsync(c->upload[c->parity][0] + s * c->up_stream_stride, L + s * image_stride, bytes, hipMemcpyHostToDevice, st));
-      HIP_TRY(c, hipMemcpyAsync(c->upload[c->parity][1] + s * c->up_stream_stride, R + s * image_stride, bytes, hipMemcpyHostToDevice, st));
+      const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
+      HIP_TRY(c, hipMemcpyAsync(dst[0] + s * dst_stream_stride, L + s * image_stride, bytes, hipMemcpyHostToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(dst[1] + s * dst_stream_stride, R + s * image_stride, bytes, hipMemcpyHostToDevice, st));
     }
-    return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], row_stride, c->up_stream_stride);
+    *out = {{dst[0], dst[1]}, row_stride, dst_stream_stride};
+    return VSLAM_OK;
   }
   for (int s = 0; s < c->B; ++s) {
     const vslam_ctx::Group& gg = c->groups[group_of(c, s)];
     hipStream_t st = c->parity ? gg.st_img2 : gg.st_img;
-    HIP_TRY(c, hipMemcpy2DAsync(c->upload[c->parity][0] + s * c->up_stream_stride, c->up_stride, L + s * image_stride, row_stride,
-                                c->cfg.c.cols, c->cfg.c.rows, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpy2DAsync(c->upload[c->parity][1] + s * c->up_stream_stride, c->up_stride, R + s * image_stride, row_stride,
-                                c->cfg.c.cols, c->cfg.c.rows, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpy2DAsync(dst[0] + s * dst_stream_stride, dst_stride, L + s * image_stride, row_stride,
+                                cols, rows, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpy2DAsync(dst[1] + s * dst_stream_stride, dst_stride, R + s * image_stride, row_stride,
+                                cols, rows, hipMemcpyHostToDevice, st));
   }
+  *out = {{dst[0], dst[1]}, dst_stride, dst_stream_stride};
+  return VSLAM_OK;
+}
+static int upload_images(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride) {
+  ImgLoc o;
+  const int rc = upload_to(c, L, R, row_stride, image_stride, c->cfg.c.rows, c->cfg.c.cols, c->upload[c->parity], c->up_stride, c->up_stream_stride, &o);
+  return rc != VSLAM_OK ? rc : set_images_device(c, o.p[0], o.p[1], o.row_stride, o.stream_stride);
+}
+// Raw input of a rectifying context: host images go to the raw slabs of this step's parity, device images are read in place (by k_rectify
+// only); the image pipeline reads the rectified pair k_rectify leaves in upload[parity].
+static int set_raw_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
+  vslam_ctx::Rect& q = c->rect;
+  if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");
+  if (row_stride < q.raw_cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than the raw image width");
+  ImgLoc o = {{L, R}, row_stride, image_stride};
+  if (!on_device) {
+    const int rc = upload_to(c, L, R, row_stride, image_stride, q.raw_rows, q.raw_cols, q.raw[c->parity], q.raw_stride, q.raw_stream_stride, &o);
+    if (rc != VSLAM_OK) return rc;
+  }
+  q.src[0] = o.p[0]; q.src[1] = o.p[1]; q.src_row_stride = o.row_stride; q.src_stream_stride = o.stream_stride;
   return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], c->up_stride, c->up_stream_stride);
+}
+static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
+  if (c->rect.on) return set_raw_inputs(c, L, R, row_stride, image_stride, on_device);
+  return on_device ? set_images_device(c, L, R, row_stride, image_stride) : upload_images(c, L, R, row_stride, image_stride);
 }
 
 VS_API int vslam_process_device(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->sticky != VSLAM_OK) return c->sticky;
-  int rc = set_images_device(c, L, R, row_stride, image_stride);
+  int rc = set_inputs(c, L, R, row_stride, image_stride, true);
   if (rc != VSLAM_OK) return rc;
   rc = flush_pending(c);
   if (rc != VSLAM_OK) return rc;
@@ -878,7 +932,7 @@ VS_API int vslam_process_host(vslam_ctx* c, const uint8_t* L, const uint8_t* R, 
   if (!c) return VSLAM_ERR_INVALID;
   if (c->sticky != VSLAM_OK) return c->sticky;
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = upload_images(c, L, R, row_stride, image_stride);
+  int rc = set_inputs(c, L, R, row_stride, image_stride, false);
   if (rc != VSLAM_OK) return rc;
   rc = flush_pending(c);
   if (rc != VSLAM_OK) return rc;
@@ -887,12 +941,123 @@ VS_API int vslam_process_host(vslam_ctx* c, const uint8_t* L, const uint8_t* R, 
   return launch_frame(c);
 }
 
+// ---- rectification of raw input pairs ------------------------------------------------------------
+// Host maps in the CV_16SC2 + CV_16UC1 layout -> device maps with rows padded to a multiple of 4 entries (the padding is zero: in range,
+// never stored), so that every lane's 16-B / 8-B map loads are aligned and inside the allocation.
+static int rect_maps_ok(const uint16_t* map_a, size_t n) {
+  for (size_t i = 0; i < n; ++i) if (map_a[i] >= 1024) return 0;
+  return 1;
+}
+static void rect_pad_maps(const int16_t* xy, const uint16_t* fa, int rows, int cols, int ms, std::vector<int16_t>& pxy, std::vector<uint16_t>& pa) {
+  pxy.assign((size_t)rows * ms * 2, 0);
+  pa.assign((size_t)rows * ms, 0);
+  for (int r = 0; r < rows; ++r) {
+    std::memcpy(&pxy[(size_t)r * ms * 2], xy + (size_t)r * cols * 2, (size_t)cols * 4);
+    std::memcpy(&pa[(size_t)r * ms], fa + (size_t)r * cols, (size_t)cols * 2);
+  }
+}
+static void rect_free(vslam_ctx* c) {
+  for (void* p : c->rect.mem) (void)hipFree(p);
+  c->rect = vslam_ctx::Rect();
+}
+VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_cols, const int16_t* xyL, const uint16_t* aL, const int16_t* xyR,
+                                   const uint16_t* aR) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification called inside a frame");
+  const bool off = !xyL && !aL && !xyR && !aR;
+  if (!off && (!xyL || !aL || !xyR || !aR)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification: all four maps or none");
+  if (!off && (raw_rows < 1 || raw_cols < 1 || raw_rows > 32767 || raw_cols > 32767))
+    return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification: invalid raw image dimensions");
+  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols;
+  if (!off && (!rect_maps_ok(aL, (size_t)rows * cols) || !rect_maps_ok(aR, (size_t)rows * cols)))
+    return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification: interpolation table index >= 1024");
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the old maps and raw slabs
+  rect_free(c);
+  if (off) return VSLAM_OK;
+  vslam_ctx::Rect& q = c->rect;
+  q.raw_rows = raw_rows; q.raw_cols = raw_cols;
+  q.raw_stride = (raw_cols + 63) & ~63;
+  q.raw_stream_stride = (size_t)raw_rows * q.raw_stride;
+  q.map_stride = (cols + 3) & ~3;
+  auto get = [&](void** p, size_t bytes) -> hipError_t {
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 1));
+    if (e == hipSuccess) q.mem.push_back(*p);
+    return e;
+  };
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    e = get((void**)&q.map_xy[k], (size_t)rows * q.map_stride * 4);
+    if (e == hipSuccess) e = get((void**)&q.map_a[k], (size_t)rows * q.map_stride * 2);
+    for (int p = 0; p < 2 && e == hipSuccess; ++p) e = get((void**)&q.raw[p][k], (size_t)c->B * q.raw_stream_stride);
+  }
+  std::vector<int16_t> pxy;
+  std::vector<uint16_t> pa;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    rect_pad_maps(k ? xyR : xyL, k ? aR : aL, rows, cols, q.map_stride, pxy, pa);
+    e = hipMemcpy(q.map_xy[k], pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(q.map_a[k], pa.data(), pa.size() * 2, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
+  q.on = true;
+  return VSLAM_OK;
+}
+VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, const int16_t* map_xy,
+                          const uint16_t* map_a, int32_t drows, int32_t dcols, uint8_t* dst) {
+  tmp_reset(c);
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  if (!src || !dst || !map_xy || !map_a || rows < 1 || cols < 1 || row_stride < cols || drows < 1 || dcols < 1)
+    return fail(c, VSLAM_ERR_INVALID, "remap: bad argument");
+  if (!rect_maps_ok(map_a, (size_t)drows * dcols)) return fail(c, VSLAM_ERR_INVALID, "remap: interpolation table index >= 1024");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int ms = (dcols + 3) & ~3;
+  std::vector<int16_t> pxy;
+  std::vector<uint16_t> pa;
+  rect_pad_maps(map_xy, map_a, drows, dcols, ms, pxy, pa);
+  uint8_t *ds = nullptr, *dd = nullptr;
+  int16_t* dxy = nullptr;
+  uint16_t* da = nullptr;
+  hipError_t e = tmp_get(c, (void**)&ds, (size_t)rows * row_stride);
+  if (e == hipSuccess) e = tmp_alloc(c, &dxy, pxy.size());
+  if (e == hipSuccess) e = tmp_alloc(c, &da, pa.size());
+  if (e == hipSuccess) e = tmp_get(c, (void**)&dd, (size_t)drows * ms);
+  if (e == hipSuccess) e = hipMemcpyAsync(ds, src, (size_t)(rows - 1) * row_stride + cols, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dxy, pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(da, pa.data(), pa.size() * 2, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    RectArgs ra;
+    std::memset(&ra, 0, sizeof ra);
+    ra.src[0] = ds; ra.src_row_stride = row_stride; ra.src_rows = rows; ra.src_cols = cols;
+    ra.map_xy[0] = dxy; ra.map_a[0] = da; ra.map_stride = ms;
+    ra.dst[0] = dd; ra.dst_row_stride = ms; ra.dst_stream_stride = (size_t)drows * ms;
+    ra.rows = drows; ra.cols = dcols; ra.s0 = 0; ra.n = 1; ra.sides = 1; ra.active[0] = 1u;
+    hipLaunchKernelGGL(k_rectify, dim3((dcols + 255) / 256, (drows + 3) / 4, 1), dim3(256), 0, c->stream, ra);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy2DAsync(dst, dcols, dd, ms, dcols, drows, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
+  return VSLAM_OK;
+}
+
 // ---- read-back -----------------------------------------------------------------------------------
 static int check_stream(vslam_ctx* c, int s) {
   if (!c) return VSLAM_ERR_INVALID;
   if (s < 0 || s >= c->B) return fail(c, VSLAM_ERR_INVALID, "stream index out of range");
   { int rc = flush_pending(c); if (rc) return rc; }
   sync_all(c);   // read-back: every group's queued work must have finished
+  return VSLAM_OK;
+}
+VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_rectified_images: null output");
+  if (!c->rect.on || !c->rect.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_rectified_images: no frame has been rectified since vslam_set_rectification");
+  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols;
+  for (int k = 0; k < 2; ++k)
+    HIP_TRY(c, hipMemcpy2D(k ? right : left, cols, c->upload[c->last_set][k] + (size_t)s * c->up_stream_stride, c->up_stride, cols, rows,
+                           hipMemcpyDeviceToHost));
   return VSLAM_OK;
 }
 template <typename T>
@@ -2130,7 +2295,7 @@ VS_API int vslam_frame_begin(vslam_ctx* c, const uint8_t* L, const uint8_t* R, i
   c->img_override = (c->B == 1 && c->groups.size() == 1) ? c->groups[0].st_frm : nullptr;
   c->report_xy_seq = -1;
   c->lm_published = false;
-  int rc = on_device ? set_images_device(c, L, R, row_stride, image_stride) : upload_images(c, L, R, row_stride, image_stride);
+  int rc = set_inputs(c, L, R, row_stride, image_stride, on_device != 0);
   if (rc == VSLAM_OK) rc = launch_image_pipeline(c);
   c->img_override = nullptr;
   if (rc != VSLAM_OK) return rc;

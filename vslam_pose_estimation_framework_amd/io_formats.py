@@ -325,6 +325,27 @@ class EurocSequence(object):
         path = os.path.join(self.root, "calib.txt")
         return parse_kitti_calib(path) if os.path.exists(path) else None
 
+    def raw_calibration(self):
+        """The raw rig from `mav0/cam{0,1}/sensor.yaml`: (left CameraModel, right CameraModel, R, T) with X1 = R X0 + T, the
+        cam0 -> cam1 transform inv(T_BS1) T_BS0; None when the files are absent.  Feed it to rectify.rectification()."""
+        from . import rectify
+        paths = [os.path.join(self.base, cam, "sensor.yaml") for cam in ("cam0", "cam1")]
+        if not all(os.path.exists(p) for p in paths):
+            return None
+        cams, T_BS = [], []
+        for p in paths:
+            y = read_sensor_yaml(p)
+            model = str(y.get("camera_model", "pinhole"))
+            if model != "pinhole":
+                raise ValueError("%s: camera_model %r is not supported (pinhole only)" % (p, model))
+            fu, fv, cu, cv = [float(v) for v in y["intrinsics"]]
+            cols, rows = [int(v) for v in y["resolution"]]
+            K = np.array([[fu, 0, cu], [0, fv, cv], [0, 0, 1]], np.float64)
+            cams.append(rectify.CameraModel(K, y["distortion_coefficients"], rows, cols, str(y.get("distortion_model", "radial-tangential"))))
+            T_BS.append(np.array(y["T_BS"]["data"], np.float64).reshape(4, 4))
+        T10 = np.linalg.inv(T_BS[1]) @ T_BS[0]
+        return cams[0], cams[1], T10[:3, :3].copy(), T10[:3, 3].copy()
+
     @property
     def ground_truth_path(self):
         for sub in ("state_groundtruth_estimate0", "leica0"):
@@ -332,6 +353,62 @@ class EurocSequence(object):
             if os.path.exists(p):
                 return p
         return None
+
+
+def _yaml_value(text):
+    text = text.strip()
+    if text.startswith("["):
+        return [_yaml_value(v) for v in text.strip("[]").split(",") if v.strip()]
+    try:
+        return int(text)
+    except ValueError:
+        pass
+    try:
+        return float(text)
+    except ValueError:
+        return text.strip("'\"")
+
+
+def read_sensor_yaml(path):
+    """The keys of an ASL `sensor.yaml` this package reads (`T_BS: {rows, cols, data: [...]}`, `resolution`, `intrinsics`,
+    `distortion_model`, `distortion_coefficients`, ...): `key: value` lines, one level of nesting by indentation, bracketed
+    lists that may span lines, `#` comments.  Not a general YAML parser."""
+    out, parent, pending = {}, None, None
+    with open(path) as f:
+        lines = f.read().splitlines()
+    for line in lines:
+        body = line.split("#", 1)[0].rstrip()
+        if not body.strip() or body.strip() == "%YAML:1.0" or body.strip() == "---":
+            continue
+        if pending is not None:                       # continuation of a bracketed list
+            target, key, acc = pending
+            acc += " " + body.strip()
+            if "]" in acc:
+                target[key] = _yaml_value(acc)
+                pending = None
+            else:
+                pending = (target, key, acc)
+            continue
+        indent = len(body) - len(body.lstrip())
+        key, _, val = body.strip().partition(":")
+        key, val = key.strip(), val.strip()
+        if indent == 0:
+            parent = None
+        target = out if indent == 0 or parent is None else out[parent]
+        if not val:
+            if indent == 0:
+                out[key] = {}
+                parent = key
+            continue
+        if val.startswith("!!"):                        # OpenCV-style type tag (e.g. !!opencv-matrix): the mapping follows
+            out[key] = {}
+            parent = key
+            continue
+        if val.startswith("[") and "]" not in val:
+            pending = (target, key, val)
+            continue
+        target[key] = _yaml_value(val)
+    return out
 
 
 # ---- trajectory writers -----------------------------------------------------------------------------------------------
