@@ -47,7 +47,7 @@ typedef enum {
                                small.  Overflow of a context's device-resident buffers inside vslam_process_* / the
                                stage calls is NOT a return code: processing continues on the truncated lists and the
                                frame's vslam_frame_info.error_flags reports it per stream (bit 0 keypoints, bit 1 points,
-                               bit 2 history) */
+                               bit 2 history, bit 3 landmark map) */
   VSLAM_ERR_STATE = -5      /* call sequence violated (e.g. track before frame_begin)       */
 } vslam_status;
 
@@ -143,7 +143,8 @@ typedef struct vslam_frame_info {
   int32_t track_broken;        /* breakTrack() happened                                       */
   int32_t fallback;            /* _fallbackEstimate() was used                                */
   int32_t window_pixels;       /* _projection_tracking_distance_pixels after the frame        */
-  int32_t error_flags;         /* bit0 keypoint capacity, bit1 point capacity, bit2 history   */
+  int32_t error_flags;         /* bit0 keypoint capacity, bit1 point capacity, bit2 history,  */
+                               /* bit3 (value 8) landmark map capacity (vslam_enable_map)     */
   double tau_track;            /* _current_descriptor_distance_tracking after the frame       */
   double tau_triangulation;    /* _current_maximum_descriptor_distance_triangulation          */
   double camera_left_to_world[12];  /* frame pose (robotToWorld with identity robot offset)   */
@@ -288,6 +289,33 @@ int vslam_get_track_result(vslam_ctx* ctx, int stream, int32_t cap, int32_t* n_t
                            int32_t* lost);
 int vslam_get_frame_points(vslam_ctx* ctx, int stream, int in_progress, int32_t cap, int32_t* n, int16_t* kp, int32_t* meta,
                            double* cam, double* lm, uint8_t* desc);
+/* ---- landmark map (opt-in; WorldMap::landmarks(), world_map.cpp:74-77, world_map.h:116) --------------------------------------
+ * Every landmark a stream creates is kept on the device for the rest of its sequence, indexed by a dense id, as WorldMap::_landmarks
+ * keeps it by Landmark::identifier().  Open loop only: no local maps, merging or relocalization.
+ * Id rule, per stream and frame, in the order of the frame's points (vslam_get_points):
+ *   id = the predecessor's id           if the point has a predecessor (meta previous_index >= 0) that carries an id;
+ *   else the stream's next id           if the point carries a landmark (landmark_updates > 0);
+ *   else none.
+ * Ids start at 0 and follow point order within a frame (Landmark::identifier() of a fresh reference process, by intent).  Entry `id`:
+ *   xyz  : 3 double   Landmark::coordinates() (world) after its last update
+ *   info : 3 int32    first_frame (the frame that created it), last_frame (its last update, _last_update), updates (landmark_updates
+ *                     then, Landmark::_number_of_updates); frame indices are 0-based per stream, as in vslam_get_poses
+ *   desc : 32 bytes   left descriptor of the last update (the last entry of Landmark::_descriptors)
+ * One kernel behind every frame of vslam_process_* / vslam_frame_finish writes them; the stage calls of the shim (vslam_track ..
+ * vslam_compute) and the RGB-D tracker do not.  A context without a map launches nothing for it.
+ * vslam_enable_map: allocates `capacity_per_stream` entries per stream and clears every map (a map enabled mid-sequence starts with the
+ *   landmarks of the next frame); 0 frees the store and turns the map off.  Synchronises; VSLAM_ERR_STATE inside a frame.  When a
+ *   stream's map is full, landmarks created after that get no entry for their whole life, and the frame that refused one reports
+ *   error_flags bit 3 (value 8).
+ * vslam_reset clears every map, vslam_reset_stream(s) the affected streams' maps; a stream switched off by vslam_set_stream_active
+ *   keeps its map unchanged.
+ * vslam_get_map_size: entries of `stream`'s map.  vslam_get_map: entries first_id .. first_id + n - 1, n = min(cap, size - first_id)
+ *   (a caller fetches what is new since its last call); any output pointer may be NULL.  Both synchronise, VSLAM_ERR_STATE without a
+ *   map. */
+int vslam_enable_map(vslam_ctx* ctx, int32_t capacity_per_stream);
+int vslam_get_map_size(vslam_ctx* ctx, int stream, int32_t* n);
+int vslam_get_map(vslam_ctx* ctx, int stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz,
+                  int32_t* info /* first_frame, last_frame, updates per entry */, uint8_t* desc);
 /* Pinned (page-locked) host memory.  Host images handed to vslam_process_host / vslam_frame_begin from ordinary (pageable) memory
  * are staged through a pinned buffer of the context first (one memcpy per image, ~30 us per 467 KB); images that already live in
  * memory from vslam_host_alloc (e.g. the cv::Mat a loader decodes into, constructed on such a buffer) are copied to the device

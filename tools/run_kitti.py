@@ -7,6 +7,7 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
                               [--chunks B [--overlap 6]]   frame-sharded mode: B chunks side by side (approximate at the seams)
     python tools/run_kitti.py <EuRoC dir with mav0/cam0 mav0/cam1> --format tum --out traj.txt   (ground truth found in mav0/)
     python tools/run_kitti.py <EuRoC dir> --rectify --format tum --out traj.txt   raw images: rectified on the GPU from mav0/cam{0,1}/sensor.yaml
+    python tools/run_kitti.py <sequence dir> --map map.ply   the landmark map as well (binary PLY: x y z id first_frame last_frame updates)
 
 The sequence runs in exact mode (one stream, whole sequence, bit-for-bit the reference port's arithmetic); images are
 uploaded frame by frame through vslam_process_host.  With --gt (KITTI 3x4 rows) the ATE-RMSE after rigid alignment is
@@ -24,7 +25,10 @@ import numpy as np  # noqa: E402
 from vslam_pose_estimation_framework_amd import evaluation, hip, io_formats  # noqa: E402
 
 
-def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None):
+MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
+
+
+def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -35,6 +39,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None):
     api.create(cfg, device, len(plan))
     if rect is not None:
         api.set_rectification(rect)
+    if want_map:
+        api.enable_map(MAP_ENTRIES_PER_FRAME * steps)
     rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
     Lb = np.zeros((len(plan), rows, cols), np.uint8)
     Rb = np.zeros_like(Lb)
@@ -54,11 +60,12 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None):
     for c in range(len(plan)):
         flags |= api.frame_info(c).error_flags
     chunks = [api.poses(c, 0, en - st) for c, (st, fi, en) in enumerate(plan)]
-    return np.asarray(sharding.assemble_trajectory(chunks, plan)).reshape(n, 12), flags
+    lm_map = sharding.assemble_map([api.map(c) for c in range(len(plan))], chunks, plan) if want_map else None
+    return np.asarray(sharding.assemble_trajectory(chunks, plan)).reshape(n, 12), flags, lm_map
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6, rectify=False):
+        chunks=0, overlap=6, rectify=False, map_path=None):
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
     if rectify and not euroc:
         raise SystemExit("--rectify: a KITTI odometry folder is already rectified (it takes raw EuRoC / ASL folders with sensor.yaml)")
@@ -98,12 +105,14 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     t0 = time.perf_counter()
     flags = 0
     if chunks > 1:
-        poses, flags = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect)
+        poses, flags, lm_map = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=bool(map_path))
     else:
         cfg.max_history_frames = 512
         api.create(cfg, device, 1)
         if rect is not None:
             api.set_rectification(rect)
+        if map_path:
+            api.enable_map(MAP_ENTRIES_PER_FRAME * n)
         for k in range(n):
             if k:
                 left, right = seq.pair(k)
@@ -114,6 +123,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
                 log("frame %6d  status %s  points %5d  tracked %5d  inliers %5d" % (
                     k, "tracking" if fi.status == 1 else "localizing", fi.n_points, fi.n_tracked, fi.n_inliers))
         poses = api.poses(0, 0, n)
+        lm_map = api.map(0) if map_path else None
     dt = time.perf_counter() - t0
     api.destroy()
     log("%d frames in %.2f s (%.1f frames/s incl. PNG decode and upload), error flags %d" % (n, dt, n / dt, flags))
@@ -124,6 +134,13 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             io_formats.write_trajectory_kitti(out_path, poses)
         log("trajectory (%s) -> %s" % (fmt, out_path))
     result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses}
+    if map_path:
+        if flags & 8:
+            log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
+        io_formats.write_ply(map_path, lm_map["xyz"], id=lm_map["id"], first_frame=lm_map["first_frame"], last_frame=lm_map["last_frame"],
+                             updates=lm_map["updates"])
+        log("landmark map: %d landmarks -> %s" % (len(lm_map["id"]), map_path))
+        result["map"] = lm_map
     if gt_path:
         gt = io_formats.read_trajectory_kitti(gt_path)[:n]
         result["ate_rmse_aligned"] = evaluation.ate_rmse(poses[:len(gt)], gt)
@@ -150,9 +167,10 @@ def main():
     ap.add_argument("--layout", choices=("kitti", "euroc"), default="kitti", help="folder layout (a folder with mav0/ is taken as EuRoC / ASL)")
     ap.add_argument("--asl-gt", default=None, help="ASL ground-truth csv for the trajectory_analyzer step (needs --format tum --out)")
     ap.add_argument("--rectify", action="store_true", help="EuRoC / ASL folder of raw images: undistort and rectify them on the GPU from mav0/cam{0,1}/sensor.yaml")
+    ap.add_argument("--map", default=None, help="write the landmark map (every landmark of the run, world frame) to this binary PLY file")
     a = ap.parse_args()
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
-        rectify=a.rectify)
+        rectify=a.rectify, map_path=a.map)
 
 
 if __name__ == "__main__":

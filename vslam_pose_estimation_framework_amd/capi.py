@@ -281,6 +281,29 @@ class CApi(object):
         k = n.value
         return dict(kp=kp[:k].copy(), meta=meta[:k].copy(), cam=cam[:k].copy(), lm=lm[:k].copy())
 
+    # -- landmark map (vslam_enable_map) ------------------------------------------------------------------------------
+    def enable_map(self, capacity_per_stream):
+        """Keep every landmark of every stream on the device (capacity_per_stream entries each); 0 turns the map off."""
+        self.check(self.fn("enable_map")(self.ctx, C.c_int32(int(capacity_per_stream))))
+
+    def map_size(self, stream=0):
+        n = C.c_int32()
+        self.check(self.fn("get_map_size")(self.ctx, C.c_int(stream), C.byref(n)))
+        return n.value
+
+    def map(self, stream=0, first=0):
+        """Landmarks first .. of `stream`: dict of numpy arrays id, xyz [n, 3] (world), first_frame, last_frame, updates, desc [n, 32]."""
+        cap = max(self.map_size(stream) - int(first), 0)
+        n = C.c_int32()
+        xyz = np.zeros((max(cap, 1), 3), np.float64)
+        info = np.zeros((max(cap, 1), 3), np.int32)
+        desc = np.zeros((max(cap, 1), 32), np.uint8)
+        self.check(self.fn("get_map")(self.ctx, C.c_int(stream), C.c_int32(int(first)), C.c_int32(cap), C.byref(n), _p(xyz, C.c_double),
+                                      _p(info, C.c_int32), _p(desc, C.c_uint8)))
+        k = n.value
+        return dict(id=np.arange(int(first), int(first) + k, dtype=np.int32), xyz=xyz[:k].copy(), first_frame=info[:k, 0].copy(),
+                    last_frame=info[:k, 1].copy(), updates=info[:k, 2].copy(), desc=desc[:k].copy())
+
     def aligner_result(self, stream=0):
         cap = int(self.cfg.max_points)
         n = C.c_int32()

@@ -15,6 +15,7 @@
 #include "kernels_landmark.h"
 #include "kernels_report.h"
 #include "kernels_rectify.h"
+#include "kernels_map.h"
 
 #define VS_API extern "C" __attribute__((visibility("default")))
 
@@ -103,6 +104,8 @@ struct vslam_ctx {
                 uint8_t* raw[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
                 const uint8_t* src[2] = {nullptr, nullptr}; int32_t src_row_stride = 0; size_t src_stream_stride = 0;   // this step's raw input
                 std::vector<void*> mem; } rect;
+  // the landmark map (vslam_enable_map, kernels_map.h): off while cap == 0; its own allocations, freed by vslam_enable_map(0) and destroy
+  struct MapStore { int32_t cap = 0; DevMap d{}; std::vector<void*> mem; } map;
   int sticky = VSLAM_OK;
 };
 
@@ -343,6 +346,7 @@ static int init_state(vslam_ctx* c) {
   HIP_TRY(c, hipMemcpyAsync(c->buf.st, st.data(), sizeof(StreamState) * c->B, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->buf.info, 0, sizeof(vslam_frame_info) * c->B, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->buf.n_points, 0, sizeof(int32_t) * c->B * 2, c->stream));
+  if (c->map.cap) HIP_TRY(c, hipMemsetAsync(c->map.d.count, 0, sizeof(int32_t) * c->B, c->stream));
   sync_all(c);
   for (int q = 0; q < 2; ++q) {
     HIP_TRY(c, hipMemsetAsync(c->sets[q].n_kp, 0, sizeof(int32_t) * c->B * 2, c->stream));
@@ -582,6 +586,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
   for (void* p : c->rect.mem) (void)hipFree(p);
+  for (void* p : c->map.mem) (void)hipFree(p);
   tmp_free(c);
   depth_map_free(c);
   if (c->report) (void)hipHostFree(c->report);
@@ -635,6 +640,8 @@ VS_API int vslam_reset_streams(vslam_ctx* c, int32_t n, const int32_t* streams) 
         c->evpool.push_back(e);
       }
       hipLaunchKernelGGL(k_reset_stream_trk, dim3(1), dim3(64), 0, g.st_frm, c->cfg, c->buf, l);
+      if (c->map.cap)     // the stream's map starts over with its sequence (frame 0 never reads the previous frame's ids)
+        for (int i = 0; i < l.n; ++i) HIP_TRY(c, hipMemsetAsync(c->map.d.count + l.ids[i], 0, sizeof(int32_t), g.st_frm));
       l.n = 0;
       return VSLAM_OK;
     };
@@ -804,6 +811,8 @@ static int launch_frame(vslam_ctx* c) {
       { KernelTimer t(c, 6, g.st_frm); hipLaunchKernelGGL(k_update_landmarks, dim3((c->cfg.MAXP + 255) / 256, g.n), dim3(256), 0, g.st_frm, c->cfg, bs, 1); }
       { KernelTimer t(c, 4, g.st_frm); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 2); }
     }
+    // the landmark map, behind the frame's last launch (sequence 4: behind the refinement workgroups of k_tail_lm as well)
+    if (c->map.cap) hipLaunchKernelGGL(k_map_commit, dim3(g.n), dim3(VS_MAP_WG), 0, g.st_frm, c->cfg, bs, c->map.d);
   }
   HIP_TRY(c, hipGetLastError());
   return frame_done(c);
@@ -1137,6 +1146,72 @@ VS_API int vslam_get_points(vslam_ctx* c, int s, int32_t cap, int32_t* n, int16_
 VS_API int vslam_get_frame_points(vslam_ctx* c, int s, int in_progress, int32_t cap, int32_t* n, int16_t* kp, int32_t* meta, double* cam,
                                   double* lm, uint8_t* desc) {
   return get_points_impl(c, s, in_progress, cap, n, kp, meta, cam, lm, desc);
+}
+// ---- the landmark map (kernels_map.h) -------------------------------------------------------------
+static void map_free(vslam_ctx* c) {
+  for (void* p : c->map.mem) (void)hipFree(p);
+  c->map.mem.clear();
+  c->map.d = DevMap{};
+  c->map.cap = 0;
+}
+template <typename T>
+static hipError_t map_alloc(vslam_ctx* c, T** p, size_t count) {
+  const hipError_t e = hipMalloc((void**)p, count * sizeof(T));
+  if (e == hipSuccess) c->map.mem.push_back(*p);
+  return e;
+}
+VS_API int vslam_enable_map(vslam_ctx* c, int32_t cap) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (cap < 0) return fail(c, VSLAM_ERR_INVALID, "vslam_enable_map: negative capacity");
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_enable_map called inside a frame");
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                        // no commit of the old store may still be in flight
+  map_free(c);
+  if (cap == 0) return VSLAM_OK;
+  const size_t B = (size_t)c->B, n = B * (size_t)cap;
+  DevMap d{};
+  d.cap = cap; d.B = c->B;
+  hipError_t e = map_alloc(c, &d.xyz, n * 3);
+  if (e == hipSuccess) e = map_alloc(c, &d.info, n * 3);
+  if (e == hipSuccess) e = map_alloc(c, &d.desc, n * 32);
+  if (e == hipSuccess) e = map_alloc(c, &d.count, B);
+  if (e == hipSuccess) e = map_alloc(c, &d.ids, 2 * B * (size_t)c->cfg.MAXP);
+  if (e == hipSuccess) e = hipMemsetAsync(d.xyz, 0, n * 3 * sizeof(double), c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d.info, 0, n * 3 * sizeof(int32_t), c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d.desc, 0, n * 32, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d.count, 0, B * sizeof(int32_t), c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d.ids, 0xff, 2 * B * (size_t)c->cfg.MAXP * sizeof(int32_t), c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { map_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_enable_map: ") + hipGetErrorString(e)); }
+  c->map.d = d;
+  c->map.cap = cap;
+  return VSLAM_OK;
+}
+static int map_size(vslam_ctx* c, int s, int32_t* n) {
+  int rc = check_stream(c, s);
+  if (rc) return rc;
+  if (!c->map.cap) return fail(c, VSLAM_ERR_STATE, "the landmark map is not enabled (vslam_enable_map)");
+  HIP_TRY(c, d2h(c, n, c->map.d.count + s, 1));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VSLAM_OK;
+}
+VS_API int vslam_get_map_size(vslam_ctx* c, int s, int32_t* n) {
+  if (c && !n) return fail(c, VSLAM_ERR_INVALID, "vslam_get_map_size: null output");
+  return map_size(c, s, n);
+}
+VS_API int vslam_get_map(vslam_ctx* c, int s, int32_t first_id, int32_t cap, int32_t* n, double* xyz, int32_t* info, uint8_t* desc) {
+  if (c && (!n || first_id < 0 || cap < 0)) return fail(c, VSLAM_ERR_INVALID, "vslam_get_map: null count, negative first id or capacity");
+  int32_t size = 0;
+  int rc = map_size(c, s, &size);
+  if (rc) return rc;
+  const int32_t cnt = std::max(0, std::min(cap, size - first_id));
+  *n = cnt;
+  const size_t o = (size_t)s * c->map.cap + (size_t)first_id;
+  HIP_TRY(c, d2h(c, xyz, c->map.d.xyz + o * 3, (size_t)cnt * 3));
+  HIP_TRY(c, d2h(c, info, c->map.d.info + o * 3, (size_t)cnt * 3));
+  HIP_TRY(c, d2h(c, desc, c->map.d.desc + o * 32, (size_t)cnt * 32));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VSLAM_OK;
 }
 VS_API int vslam_get_track_result(vslam_ctx* c, int s, int32_t cap, int32_t* n_tracked, int32_t* out4, int32_t* n_lost, int32_t* lost) {
   int rc = check_stream(c, s);

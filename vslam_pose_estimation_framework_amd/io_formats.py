@@ -412,6 +412,65 @@ def read_sensor_yaml(path):
 
 
 # ---- trajectory writers -----------------------------------------------------------------------------------------------
+PLY_INT_FIELDS = ("id", "first_frame", "last_frame", "updates")
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def write_ply(path, xyz, **ints):
+    """Binary little-endian PLY point cloud: x y z (double) plus one int property per keyword (default: the landmark map's
+    id, first_frame, last_frame, updates; missing ones are written as -1)."""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    n = xyz.shape[0]
+    names = list(PLY_INT_FIELDS) + [k for k in ints if k not in PLY_INT_FIELDS]
+    dt = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8")] + [(k, "<i4") for k in names])
+    rec = np.zeros(n, dt)
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    for k in names:
+        rec[k] = np.asarray(ints[k], np.int32).reshape(n) if k in ints else -1
+    head = ["ply", "format binary_little_endian 1.0", "comment landmark map", "element vertex %d" % n,
+            "property double x", "property double y", "property double z"] + ["property int %s" % k for k in names] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_ply(path):
+    """The vertex element of a binary little-endian PLY with scalar properties -> dict: xyz [n, 3] float64 and every other property
+    as an array of its own type."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("%s: not a PLY file" % path)
+    body = data.index(b"\n", end) + 1
+    fmt, n, props, elem = None, 0, [], None
+    for line in data[:end].decode("ascii").splitlines():
+        w = line.split()
+        if not w:
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elem = w[1]
+            if elem == "vertex":
+                n = int(w[2])
+            elif props or n:
+                raise ValueError("%s: only a vertex element is supported" % path)
+        elif w[0] == "property" and elem == "vertex":
+            if w[1] == "list" or w[1] not in _PLY_TYPES:
+                raise ValueError("%s: unsupported property %r" % (path, line))
+            props.append((w[2], "<" + _PLY_TYPES[w[1]]))
+    if fmt != "binary_little_endian":
+        raise ValueError("%s: format %s (binary_little_endian expected)" % (path, fmt))
+    rec = np.frombuffer(data, np.dtype(props), count=n, offset=body)
+    out = {"xyz": np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float64)}
+    for k, _ in props:
+        if k not in ("x", "y", "z"):
+            out[k] = rec[k].copy()
+    return out
+
+
 def write_trajectory_kitti(path, poses):
     with open(path, "w") as f:
         for T in np.asarray(poses, np.float64).reshape(-1, 12):

@@ -115,24 +115,65 @@ def _seam_anchor(G, P, start, first, seam_frames):
     return np.hstack([Rm, t.reshape(3, 1)])
 
 
-def assemble_trajectory(chunk_poses, plan, seam_frames=1):
-    """chunk_poses[c]: array [n_processed_c, 3, 4] (camera-to-chunk-world), plan from plan_chunks.
-    Returns [total, 3, 4] in the first chunk's world frame.  seam_frames: how many of the chunk's last warm-up frames the
-    seam transform is estimated from (1 = the frame before the chunk's own range alone)."""
+def _assemble(chunk_poses, plan, seam_frames):
+    """The assembled trajectory and, per chunk, the transform chunk-world -> first chunk's world (None for an empty chunk)."""
     total = plan[-1][2]
     G = np.zeros((total, 3, 4))
     anchor = np.hstack([np.eye(3), np.zeros((3, 1))])
+    anchors = []
     for c, (start, first, end) in enumerate(plan):
         P = np.asarray(chunk_poses[c]).reshape(-1, 3, 4)
         if end <= first:
+            anchors.append(None)
             continue
         if c > 0 and first > start:
             anchor = _seam_anchor(G, P, start, first, seam_frames)
         elif c > 0:
             anchor = mul34(G[first - 1], inv34(P[0])) if first > 0 else anchor
+        anchors.append(anchor)
         for f in range(first, end):
             G[f] = mul34(anchor, P[f - start])
-    return G
+    return G, anchors
+
+
+def assemble_trajectory(chunk_poses, plan, seam_frames=1):
+    """chunk_poses[c]: array [n_processed_c, 3, 4] (camera-to-chunk-world), plan from plan_chunks.
+    Returns [total, 3, 4] in the first chunk's world frame.  seam_frames: how many of the chunk's last warm-up frames the
+    seam transform is estimated from (1 = the frame before the chunk's own range alone)."""
+    return _assemble(chunk_poses, plan, seam_frames)[0]
+
+
+def assemble_map(chunk_maps, chunk_poses, plan, seam_frames=1):
+    """Landmark maps of the chunks (capi.CApi.map: xyz in the chunk's world, frame indices counted from the chunk's first processed
+    frame) -> one map in the first chunk's world frame, through the seam transforms of assemble_trajectory.  A landmark is kept only
+    when the chunk created it inside its own range (first_frame in [first_unique, end)): what a chunk creates in its warm-up frames
+    duplicates the preceding chunk's landmarks.  Frame indices become global frame numbers, ids are renumbered 0 .. n-1 in chunk order.
+    Returns dict: id, xyz [n, 3], first_frame, last_frame, updates, chunk (and desc [n, 32] when every chunk map has descriptors)."""
+    _, anchors = _assemble(chunk_poses, plan, seam_frames)
+    parts = {k: [] for k in ("xyz", "first_frame", "last_frame", "updates", "chunk", "desc")}
+    with_desc = all("desc" in m for m in chunk_maps)
+    for c, (start, first, end) in enumerate(plan):
+        if anchors[c] is None:
+            continue
+        m = chunk_maps[c]
+        ff = np.asarray(m["first_frame"], np.int64) + start
+        keep = (ff >= first) & (ff < end)
+        xyz = np.asarray(m["xyz"], np.float64).reshape(-1, 3)[keep]
+        A = anchors[c]
+        parts["xyz"].append(xyz @ A[:, :3].T + A[:, 3])
+        parts["first_frame"].append(ff[keep])
+        parts["last_frame"].append(np.asarray(m["last_frame"], np.int64)[keep] + start)
+        parts["updates"].append(np.asarray(m["updates"], np.int64)[keep])
+        parts["chunk"].append(np.full(int(keep.sum()), c, np.int64))
+        if with_desc:
+            parts["desc"].append(np.asarray(m["desc"], np.uint8).reshape(-1, 32)[keep])
+    out = {"xyz": np.concatenate(parts["xyz"]) if parts["xyz"] else np.zeros((0, 3))}
+    for k in ("first_frame", "last_frame", "updates", "chunk"):
+        out[k] = (np.concatenate(parts[k]) if parts[k] else np.zeros(0, np.int64)).astype(np.int32)
+    if with_desc:
+        out["desc"] = np.concatenate(parts["desc"]) if parts["desc"] else np.zeros((0, 32), np.uint8)
+    out["id"] = np.arange(out["xyz"].shape[0], dtype=np.int32)
+    return out
 
 
 def gather_poses(local_poses, group=None):
