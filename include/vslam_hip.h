@@ -385,7 +385,8 @@ int vslam_get_timers(vslam_ctx* ctx, double seconds[8]);
 int vslam_enable_timers(vslam_ctx* ctx, int on);
 /* Per-kernel device time (HIP events on the context stream, recorded while timers are enabled):
  * accumulated milliseconds and launch counts of k_fast_box, k_emit, k_brief, k_track_candidates, k_frame (its
- * three phase launches together, counted once), k_recover_brief, k_update_landmarks, k_stereo_dist.
+ * phase launches together, counted once), k_recover_brief, slot 6 (reserved, always 0: it timed k_update_landmarks,
+ * a kernel no launch sequence uses any more), k_stereo_dist.
  * Used by bench.py for the roofline of the dominant kernel.  Synchronises; vslam_enable_timers(ctx,1)
  * clears the accumulators.  Stage path of a one-stream context (vslam_frame_begin): the image pipeline is timed by three events
  * instead of two per kernel, so k_fast_box's figure covers k_emit as well (ms[0] + ms[1] = keypoint detection either way) and

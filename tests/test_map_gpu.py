@@ -130,7 +130,8 @@ def test_map_same_under_every_launch_sequence_and_does_not_perturb_tracking():
     cfg = o.config_for_scene(scenes[0])
     ref = create_hip(cfg, 3)                                   # the library's own launch sequence, map on
     plain = create_hip(cfg, 3)                                 # never enables the map
-    forced = [create_hip(cfg, 3, split=sp) for sp in range(5)]
+    splits = (0, 4)
+    forced = [create_hip(cfg, 3, split=sp) for sp in splits]
     ctxs = [ref] + forced
     try:
         for h in ctxs:
@@ -148,7 +149,7 @@ def test_map_same_under_every_launch_sequence_and_does_not_perturb_tracking():
         for s in range(3):
             np.testing.assert_array_equal(ref.poses(s, 0, 40), plain.poses(s, 0, 40))
             assert ref.map_size(s) > 50
-            for sp, h in enumerate(forced):
+            for sp, h in zip(splits, forced):
                 _maps_equal(ref, h, s, "VSLAM_SPLIT=%d stream %d" % (sp, s))
         with pytest.raises(Exception):
             plain.map_size(0)                                  # no map: VSLAM_ERR_STATE

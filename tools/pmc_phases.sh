@@ -1,15 +1,16 @@
 #!/bin/bash
-# Where does the frame kernel's HBM traffic come from?  The same bench command with VSLAM_SPLIT=1: the frame runs as three phase
-# launches of k_frame (0: track resolution + aligner + prune, 1: recovery gates + landmark bookkeeping, 2: landmark refinement tail +
-# stereo sweep + binning + report) around the wide k_recover_brief and k_update_landmarks kernels, so FETCH_SIZE / WRITE_SIZE
-# (separate rocprofv3 --pmc passes, kernel-trace only) can be read per phase.  k_frame dispatches are told apart by their order
-# inside a step (p0, p1, p2).  Run on the GPU box from the repo root:  bash tools/pmc_phases.sh <tag>
+# Where does the frame kernel's HBM traffic come from?  The same bench command with VSLAM_SPLIT=4 (launch sequence 4 forced at the
+# bench's stream count): the frame runs as k_frame phase 0 (track resolution + aligner + prune + recovery projection), the wide
+# k_recover_brief, k_frame phase 4 (recovery append + history + the count of active landmarks) and k_tail_lm (stereo sweep + binning +
+# report, the landmark refinement in workgroups of its own beside it), so FETCH_SIZE / WRITE_SIZE (separate rocprofv3 --pmc passes,
+# kernel-trace only) can be read per phase.  k_frame dispatches are told apart by their order inside a step (p0, p4).
+# Run on the GPU box from the repo root:  bash tools/pmc_phases.sh <tag>
 set -e
 TAG=${1:-run}
 OUT=$PWD/gpurun_out/pmcph_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-export VSLAM_SPLIT=1
+export VSLAM_SPLIT=4
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -- python3 bench.py --no-cpu --no-exact --no-pcie --no-ate --no-shim --steps 8 > $OUT/$C.log 2>&1
 done
@@ -29,7 +30,7 @@ for cname in ("FETCH_SIZE", "WRITE_SIZE"):
     for r in rows:
         k = r["Kernel_Name"].split("(")[0]
         if k == "k_frame":
-            k = "k_frame_phase%d" % (nframe % 3)
+            k = "k_frame_phase%d" % (4 * (nframe % 2))
             nframe += 1
         acc[k][0] += float(r["Counter_Value"]); acc[k][1] += 1
     for k, (v, n) in acc.items():
@@ -39,7 +40,7 @@ streams = None
 for line in open(out + "/FETCH_SIZE.log"):
     if line.startswith("{") and "streams_per_gpu" in line:
         streams = json.loads(line)["config"]["streams_per_gpu"]
-json.dump({"streams": streams, "source_sha16": buildinfo.source_sha16(), "launch_sequence": "VSLAM_SPLIT=1: k_frame phase 0 / k_recover_brief / k_frame phase 1 / k_update_landmarks / k_frame phase 2",
+json.dump({"streams": streams, "source_sha16": buildinfo.source_sha16(), "launch_sequence": "VSLAM_SPLIT=4: k_frame phase 0 / k_recover_brief / k_frame phase 4 / k_tail_lm",
            "counters": "FETCH_SIZE / WRITE_SIZE as reported (KB per launch), separate --pmc passes; wide 16 B/lane reads are tallied at half their bytes on gfx950 (MI355X_MICROARCH.md)",
            "per_launch_KB": res}, open(out + "/summary.json", "w"), indent=1)
 print(json.dumps(res, indent=1))

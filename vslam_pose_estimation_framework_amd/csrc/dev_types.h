@@ -65,7 +65,7 @@ struct DevCfg {
 struct FrameCarry {
   int32_t status, status0, win, attempts, broken, fallback, n_after_prune, aligner_valid, n_tracked_landmarks;
   int32_t n_cur, n_lost, n_recovered, n_active;
-  int32_t lm_pb, lm_f;    // point buffer and frame index of the frame whose landmarks k_update_landmarks refines (it may run beside the frame's last phase, which advances StreamState::cur / frame_count)
+  int32_t lm_pb, lm_f;    // point buffer and frame index of the frame whose landmarks lm_teams_body refines (it runs beside the frame's last phase, which advances StreamState::cur / frame_count)
   double tau_track, tau_gen, tau_tri;
   double prior[12];
   unsigned long long t0;

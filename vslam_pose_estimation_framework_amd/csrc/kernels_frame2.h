@@ -301,8 +301,7 @@ __device__ __forceinline__ void wg_recover_brief(const DevCfg& c, const DevBuf& 
   }
 }
 
-template <int NT, class SH>
-__device__ __forceinline__ void wg_recover_append_t(const DevCfg& c, const DevBuf& b, int s, SH& sh, int pb_prev, int pb_cur) {
+__device__ __forceinline__ void wg_recover_append(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_prev, int pb_cur) {
   const int tid = threadIdx.x;
   const PtView pv = pts_of(c, b, s, pb_prev);
   const PtView cv = pts_of(c, b, s, pb_cur);
@@ -310,7 +309,7 @@ __device__ __forceinline__ void wg_recover_append_t(const DevCfg& c, const DevBu
   const int32_t* rec = b.rec + (size_t)s * c.MAXP * 6;
   const uint8_t* rdesc = b.rec_desc + (size_t)s * c.MAXP * 64;
   const int nl = sh.n_lost;
-  const int per = (nl + NT - 1) / NT;
+  const int per = (nl + VS_WG - 1) / VS_WG;
   const int q0 = tid * per, q1 = min(q0 + per, nl);
   int cnt = 0;
   for (int q = q0; q < q1; ++q) cnt += rec[6 * q] == 1 ? 1 : 0;
@@ -339,10 +338,6 @@ __device__ __forceinline__ void wg_recover_append_t(const DevCfg& c, const DevBu
   __syncthreads();
   if (tid == 0) { sh.flag = total; sh.n_cur = min(sh.n_cur + total, c.MAXP); }
   __syncthreads();
-}
-
-__device__ __forceinline__ void wg_recover_append(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_prev, int pb_cur) {
-  wg_recover_append_t<VS_WG, FrameShared>(c, b, s, sh, pb_prev, pb_cur);
 }
 
 // whole recovery inside one workgroup (stage path)
@@ -380,35 +375,26 @@ __global__ __launch_bounds__(256) void k_recover_brief(const DevCfg c, const Dev
   for (int q = wave; q < nl; q += nwaves) recover_brief_wave(c, b, s, st.cur, q, lane, st.fc.tau_gen, st.fc.tau_tri);
 }
 
-// _updatePoints (pose_tracker_3d.cpp:475-520): one thread per framepoint; landmark creation = mean of the
-// track's world coordinates (landmark.cpp:19-31), update = Gauss-Newton over all measurements of the
-// track (landmark.cpp:66-167).  Measurements are reached by walking the per-frame `prev` links of the
-// history ring (frame f, index i) -> (f-1, prev[i]).
-// landmark of framepoint i of the current frame: creation = mean of the track's world coordinates
-// (Landmark::Landmark, landmark.cpp:19-31), otherwise Gauss-Newton refinement over all measurements of the track
-// (Landmark::update, :66-167).  Returns true when the point carries an active landmark afterwards.
-// LDS variant (fused frame kernel): the poses of the last VS_LM_CN frames are staged once per workgroup and the first
-// VS_LM_CN measurements of the point's track once per point (the chain walk is a chase of dependent HBM loads, and the
-// Gauss-Newton rounds would repeat it); longer tracks continue in HBM from where the cache ends.  Same order of accumulation,
-// same bits.
+// _updatePoints' landmark part (pose_tracker_3d.cpp:475-520) for framepoint i of the current frame: creation = mean of the track's world
+// coordinates (Landmark::Landmark, landmark.cpp:19-31), otherwise Gauss-Newton refinement over all measurements of the track (Landmark::update,
+// :66-167).  Measurements are reached by walking the per-frame `prev` links of the history ring (frame f, index i) -> (f-1, prev[i]).  Returns
+// true when the point carries an active landmark afterwards.
+// The poses of the last VS_LM_NP frames are staged in LDS once per workgroup and the first VS_LM_CN measurements of the point's track once per
+// point (the chain walk is a chase of dependent HBM loads, and the Gauss-Newton rounds would repeat it); longer tracks continue in HBM from where
+// the cache ends.  Same order of accumulation, same bits.
 #ifndef VS_LM_CN
 #define VS_LM_CN 6
 #endif
 #define VS_LM_NP 48   // world_to_camera of the last VS_LM_NP frames staged in LDS (one copy for all points of the frame)
-template <int NT, int CN>
-struct LmCacheT { static constexpr int kCN = CN; static constexpr int kBatch = NT >= 512 ? 4 : 2; double w2c[VS_LM_NP][12]; double rtr[VS_LM_NP][9]; double cam[NT][CN][4]; };
+struct LmCache { double w2c[VS_LM_NP][12]; double rtr[VS_LM_NP][9]; double cam[VS_WG][VS_LM_CN][4]; };
 // R^T R of world_to_camera k (J^T J of every measurement taken in that frame: a property of the frame, symmetric to the bit) next to the staged poses
-template <class LC>
-__device__ __forceinline__ void lm_stage_rtr(LC* lc, int f, int hcap, int nthreads) {
-  for (int t = threadIdx.x; t < VS_LM_NP * 9; t += nthreads) {
+__device__ __forceinline__ void lm_stage_rtr(LmCache* lc, int f, int hcap) {
+  for (int t = threadIdx.x; t < VS_LM_NP * 9; t += VS_WG) {
     const int k = t / 9, e = t - 9 * k, rr = e / 3, cc = e - 3 * rr;
     if (f - k >= 0 && k < hcap) { const double* W = lc->w2c[k]; lc->rtr[k][e] = (W[rr] * W[cc] + W[4 + rr] * W[4 + cc]) + W[8 + rr] * W[8 + cc]; }
   }
 }
-typedef LmCacheT<VS_WG, VS_LM_CN> LmCache;
-template <bool LDS, class LC = LmCache>
-__device__ __forceinline__ bool landmark_point_t(const DevCfg& c, const DevBuf& b, int s, const PtView& cv, int f, int i, LC* lc) {
-  constexpr int VS_LM_CN_ = LC::kCN;
+__device__ __forceinline__ bool landmark_point(const DevCfg& c, const DevBuf& b, int s, const PtView& cv, int f, int i, LmCache* lc) {
   const double* w2c_cur = hpose_of(c, b, s, f) + 12;
   {
     int32_t* m = cv.meta + (size_t)i * META;
@@ -481,22 +467,22 @@ __device__ __forceinline__ bool landmark_point_t(const DevCfg& c, const DevBuf& 
         }
       }
       auto index_at = [&](int k) -> int { return k == 0 ? i : (int)tr[k - 1]; };   // k < n_direct
-      // the first VS_LM_CN_ measurements into the thread's LDS slots, once
+      // the first VS_LM_CN measurements into the thread's LDS slots, once
       int ncache = 0, ffc = f, iic = i;
-      if constexpr (LDS) {
+      {
         double (*slot)[4] = lc->cam[threadIdx.x];
         if (c.trail) {
-          const int nc = min(min(len, VS_LM_CN_), n_direct);
-          double mv[VS_LM_CN_][4];
+          const int nc = min(min(len, VS_LM_CN), n_direct);
+          double mv[VS_LM_CN][4];
 #pragma unroll
-          for (int k = 0; k < VS_LM_CN_; ++k)
+          for (int k = 0; k < VS_LM_CN; ++k)
             if (k < nc) { const double* mc = hcam_of(c, b, s, f - k) + 4 * (size_t)index_at(k); mv[k][0] = mc[0]; mv[k][1] = mc[1]; mv[k][2] = mc[2]; mv[k][3] = mc[3]; }
 #pragma unroll
-          for (int k = 0; k < VS_LM_CN_; ++k)
+          for (int k = 0; k < VS_LM_CN; ++k)
             if (k < nc) { slot[k][0] = mv[k][0]; slot[k][1] = mv[k][1]; slot[k][2] = mv[k][2]; slot[k][3] = mv[k][3]; }
           ncache = nc;
         } else {
-          for (int k = 0; k < len && k < VS_LM_CN_; ++k) {
+          for (int k = 0; k < len && k < VS_LM_CN; ++k) {
             const double* mc = hcam_of(c, b, s, ffc) + 4 * (size_t)iic;
             slot[k][0] = mc[0]; slot[k][1] = mc[1]; slot[k][2] = mc[2]; slot[k][3] = mc[3];
             ++ncache;
@@ -515,13 +501,13 @@ __device__ __forceinline__ bool landmark_point_t(const DevCfg& c, const DevBuf& 
         double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bv[3] = {0, 0, 0};
         double err = 0;
         int n_out = 0;
-        if constexpr (LDS) {
+        {
           const double (*slot)[4] = lc->cam[threadIdx.x];
           for (int k = 0; k < ncache; ++k) accumulate(lc->w2c[k], lc->rtr[k], slot[k], H, bv, err, n_out);   // frame f - k
         }
         if (c.trail) {
           // directly addressed measurements, four at a time: their (independent) loads are in flight together
-          constexpr int NB = LC::kBatch;     // loads in flight together (fewer in the small-register tail kernel)
+          constexpr int NB = 4;     // loads in flight together
           for (int k0 = ncache; k0 < n_direct; k0 += NB) {
             double mc[NB][4];
 #pragma unroll
@@ -534,12 +520,8 @@ __device__ __forceinline__ bool landmark_point_t(const DevCfg& c, const DevBuf& 
             for (int u = 0; u < NB; ++u) {
               const int k = k0 + u;
               if (k < n_direct) {
-                if constexpr (LDS) {
-                  if (k < VS_LM_NP) accumulate(lc->w2c[k], lc->rtr[k], mc[u], H, bv, err, n_out);
-                  else accumulate(hpose_of(c, b, s, f - k) + 12, nullptr, mc[u], H, bv, err, n_out);
-                } else {
-                  accumulate(hpose_of(c, b, s, f - k) + 12, nullptr, mc[u], H, bv, err, n_out);
-                }
+                if (k < VS_LM_NP) accumulate(lc->w2c[k], lc->rtr[k], mc[u], H, bv, err, n_out);
+                else accumulate(hpose_of(c, b, s, f - k) + 12, nullptr, mc[u], H, bv, err, n_out);
               }
             }
           }
@@ -585,20 +567,13 @@ __device__ __forceinline__ bool landmark_point_t(const DevCfg& c, const DevBuf& 
   return true;
 }
 
-__device__ __forceinline__ bool landmark_point(const DevCfg& c, const DevBuf& b, int s, const PtView& cv, int f, int i) {
-  return landmark_point_t<false, LmCache>(c, b, s, cv, f, i, (LmCache*)nullptr);
-}
-
 // Landmark::update of a LONG track by a team of eight lanes (fused frame kernel).  One lane per landmark walks a chain of ~65
 // dependent fp64 operations per measurement and round; the longest track of the frame (dozens of measurements, three rounds)
 // kept the phase waiting for one wavefront.  Only the thirteen ADDITIONS into H, b and the error have to happen in the list's
 // order: the eight lanes evaluate eight consecutive measurements at once (projection, residual, kernel, om * R^T R, om * R^T e),
 // park the terms in LDS, and every lane adds the eight terms in list order into its own copy of the sums — the same operations on
-// the same operands in the same order as landmark_point_t's serial loop, an eighth of the multiplications on the critical path.
+// the same operands in the same order as landmark_point's serial loop, an eighth of the multiplications on the critical path.
 // Measurements beyond the trail (k >= n_direct: only reachable through the `prev` links) follow serially on every lane alike.
-#ifndef VS_LM_TEAMS
-#define VS_LM_TEAMS 1
-#endif
 #define VS_LM_TEAM_G 8          // lanes per team
 #ifndef VS_LM_TEAM_WAVES
 #define VS_LM_TEAM_WAVES 2      // wavefronts of the workgroup that run teams when the frame has long tracks (16 teams at a time)
@@ -623,7 +598,7 @@ __device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, 
   double wv[3] = {cv.lm[3 * (size_t)i], cv.lm[3 * (size_t)i + 1], cv.lm[3 * (size_t)i + 2]};
   for (int q = 0; q < 3; ++q) wpos[q] = wv[q];
   const double kern = c.c.landmark_maximum_error_squared_meters;
-  // directly addressed measurements (landmark_point_t's n_direct)
+  // directly addressed measurements (landmark_point's n_direct)
   const uint16_t* tr = cv.trail + (size_t)i * VS_TRAIL;
   int n_direct = 1;
   bool ended = false;
@@ -640,7 +615,7 @@ __device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, 
     }
   }
   // this lane's measurements of the directly addressed part (k = gl, gl + 8, ...) into its LDS slots, all loads in flight, once
-  constexpr int NG = LmCache::kCN;                       // groups whose measurements have a slot (k < 8 * NG)
+  constexpr int NG = VS_LM_CN;                       // groups whose measurements have a slot (k < 8 * NG)
   double (*slot)[4] = lc->cam[threadIdx.x];
   {
     double mv[NG][4];
@@ -718,7 +693,7 @@ __device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, 
       }
     }
     if (!ended) {
-      // beyond the trail: the serial loop of landmark_point_t, on every lane of the team alike
+      // beyond the trail: the serial loop of landmark_point, on every lane of the team alike
       int ff = ffc, ii = iic;
       for (int k = n_direct; k < len; ++k) {
         const double* W = hpose_of(c, b, s, ff) + 12;
@@ -810,7 +785,7 @@ __device__ __forceinline__ void wg_publish_history(const DevCfg& c, const DevBuf
 
 // Landmark creation / refinement of the frame's points inside the stream's workgroup (PoseTracker3D::_updatePoints' landmark part): the poses of the
 // last VS_LM_NP frames and every lane's first measurements staged in the LDS arena, short tracks one lane each, long tracks a team of eight lanes
-// (landmark_point_t<true> / landmark_team).  Returns the number of active landmarks (block-uniform).  Used by k_frame's fused launches and by the
+// (landmark_point / landmark_team).  Returns the number of active landmarks (block-uniform).  Used by k_frame's fused launches and by the
 // stage path's UPDATE / COMPUTE stages; history of frame f must have been published (wg_publish_history).
 __device__ __forceinline__ int wg_landmarks_lds(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_cur, int f, unsigned char* arena) {
   const int tid = threadIdx.x;
@@ -820,16 +795,12 @@ __device__ __forceinline__ int wg_landmarks_lds(const DevCfg& c, const DevBuf& b
   LmCache* lc = reinterpret_cast<LmCache*>(arena);
   for (int t = tid; t < VS_LM_NP * 12; t += VS_WG) { const int k = t / 12; if (f - k >= 0 && k < c.HCAP) lc->w2c[k][t - 12 * k] = hpose_of(c, b, s, f - k)[12 + t - 12 * k]; }
   __syncthreads();
-  lm_stage_rtr(lc, f, c.HCAP, VS_WG);
+  lm_stage_rtr(lc, f, c.HCAP);
   // The points that carry a landmark (track long enough: creation or refinement) are compacted into a work list first: ~40 % of
   // the frame's points, one per thread in a single round instead of two half-empty ones (a thread's refinement is a serial chain).
-#if VS_LM_TEAMS
   static_assert(sizeof(LmCache) + VS_LM_TEAM_LDS + 4096 <= VS_ARENA, "landmark cache + team terms must leave room for the work lists");
   constexpr int LIST_CAP = (VS_ARENA - (int)sizeof(LmCache) - VS_LM_TEAM_LDS) / 2;
   LmTerm* team_terms = reinterpret_cast<LmTerm*>(arena + VS_ARENA - VS_LM_TEAM_LDS);
-#else
-  constexpr int LIST_CAP = (VS_ARENA - (int)sizeof(LmCache)) / 2;
-#endif
   uint16_t* work = reinterpret_cast<uint16_t*>(arena + sizeof(LmCache));
   const bool listed = sh.n_cur <= LIST_CAP && sh.n_cur <= 65535;
   if (tid == 0) { sh.flag = 0; sh.n_proj = 0; }       // n_proj (recovery is over): the count of long tracks
@@ -840,11 +811,7 @@ __device__ __forceinline__ int wg_landmarks_lds(const DevCfg& c, const DevBuf& b
       const int i = i0 + tid;
       const int32_t* mi = cvu.meta + (size_t)min(i, sh.n_cur - 1) * META;
       const bool need = i < sh.n_cur && mi[M_TLEN] >= c.c.minimum_track_length_for_landmark_creation;
-#if VS_LM_TEAMS
       const bool lng = need && landmark_is_long(c, mi);
-#else
-      const bool lng = false;
-#endif
       const unsigned long long m = __ballot(need && !lng), ml = __ballot(lng);
       int base = 0, basel = 0;
       if ((tid & 63) == 0 && m) base = atomicAdd(&sh.flag, __popcll(m));
@@ -855,7 +822,6 @@ __device__ __forceinline__ int wg_landmarks_lds(const DevCfg& c, const DevBuf& b
     }
     __syncthreads();
     const int n_work = sh.flag;
-#if VS_LM_TEAMS
     const int n_long = sh.n_proj;
     const int team_waves = min(VS_LM_TEAM_WAVES, (n_long + 64 / VS_LM_TEAM_G - 1) / (64 / VS_LM_TEAM_G));
     const int wv_ = tid >> 6;
@@ -864,13 +830,10 @@ __device__ __forceinline__ int wg_landmarks_lds(const DevCfg& c, const DevBuf& b
       for (int q = team; q < n_long; q += team_waves * (64 / VS_LM_TEAM_G))
         active += (landmark_team(c, b, s, cvu, f, work[LIST_CAP - 1 - q], lc, team_terms + team * VS_LM_TEAM_G, gl) && gl == 0) ? 1 : 0;
     } else {
-      for (int q = tid - 64 * team_waves; q < n_work; q += VS_WG - 64 * team_waves) active += landmark_point_t<true>(c, b, s, cvu, f, work[q], lc) ? 1 : 0;
+      for (int q = tid - 64 * team_waves; q < n_work; q += VS_WG - 64 * team_waves) active += landmark_point(c, b, s, cvu, f, work[q], lc) ? 1 : 0;
     }
-#else
-    for (int q = tid; q < n_work; q += VS_WG) active += landmark_point_t<true>(c, b, s, cvu, f, work[q], lc) ? 1 : 0;
-#endif
   } else {
-    for (int i = tid; i < sh.n_cur; i += VS_WG) active += landmark_point_t<true>(c, b, s, cvu, f, i, lc) ? 1 : 0;
+    for (int i = tid; i < sh.n_cur; i += VS_WG) active += landmark_point(c, b, s, cvu, f, i, lc) ? 1 : 0;
   }
   int total;
   block_exclusive_scan(active, sh.scan, &total);
@@ -890,30 +853,14 @@ __device__ __forceinline__ void wg_update_points(const DevCfg& c, const DevBuf& 
   __syncthreads();
 }
 
-// fused path: one thread per framepoint of every stream
-// count: 1 = the kernel also counts the frame's active landmarks into FrameCarry::n_active (it runs BETWEEN phase 1 and phase 2); 0 = phase 4 has
-// counted them (a point is active iff its track is long enough: the refinement's outcome does not enter) and the kernel runs BESIDE phase 2
-__global__ __launch_bounds__(256) void k_update_landmarks(const DevCfg c, const DevBuf b, int count) {
-  const int s = b.s0 + blockIdx.y;
-  if (!vs_active(b, s)) return;
-  StreamState& st = b.st[s];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = st.fc.n_cur;
-  if (blockIdx.x * blockDim.x >= n) return;
-  const PtView cv = pts_of(c, b, s, st.fc.lm_pb);
-  const bool act = i < n && landmark_point(c, b, s, cv, st.fc.lm_f, i);
-  const int cnt = __popcll(__ballot(act));
-  if (count && (threadIdx.x & 63) == 0 && cnt) atomicAdd(&st.fc.n_active, cnt);
-}
-
 // The same refinement spread over `gridDim.x` workgroups per stream, each with the frame workgroup's own machinery (poses of the last VS_LM_NP frames
-// and every lane's first measurements in LDS, teams of eight lanes for long tracks: landmark_team / landmark_point_t<true>, i.e. the operations of
+// and every lane's first measurements in LDS, teams of eight lanes for long tracks: landmark_team / landmark_point, i.e. the operations of
 // k_frame's landmark phase in the same order): launch sequence 4 (k_tail_lm) and the stage path of a one-stream context (k_stage_lm) run it beside the
-// frame's last phase / stage, inside the same launch, where the wide one-thread-per-track kernel above (56 us for one KITTI-sized stream) would be
-// longer than what it hides behind.
-// share g of G of stream s; n_short / n_long_sh / scan: workgroup-shared scratch (two counters, 17 ints); tick: the share-0 workgroup adds its duration to the
-// stream's landmark chronometer (the callers that are not timed by HIP events)
-__device__ __forceinline__ void lm_teams_body(const DevCfg& c, const DevBuf& b, int s, int g, int G, int count, bool tick, unsigned char* arena, int& n_short, int& n_long_sh, int* scan) {
+// frame's last phase / stage, inside the same launch, where a wide one-thread-per-track kernel (56 us for one KITTI-sized stream) would be longer
+// than what it hides behind.
+// share g of G of stream s; n_short / n_long_sh: workgroup-shared counters.  The share-0 workgroup adds its duration to the stream's landmark
+// chronometer (neither caller is timed by HIP events).
+__device__ __forceinline__ void lm_teams_body(const DevCfg& c, const DevBuf& b, int s, int g, int G, unsigned char* arena, int& n_short, int& n_long_sh) {
   const int tid = threadIdx.x;
   const unsigned long long t_begin = wall_clock64();
   StreamState& st = b.st[s];
@@ -923,14 +870,9 @@ __device__ __forceinline__ void lm_teams_body(const DevCfg& c, const DevBuf& b, 
   for (int t = tid; t < VS_LM_NP * 12; t += VS_WG) { const int k = t / 12; if (f - k >= 0 && k < c.HCAP) lc->w2c[k][t - 12 * k] = hpose_of(c, b, s, f - k)[12 + t - 12 * k]; }
   if (tid == 0) { n_short = 0; n_long_sh = 0; }
   __syncthreads();
-  lm_stage_rtr(lc, f, c.HCAP, VS_WG);
-  int active = 0;
-#if VS_LM_TEAMS
+  lm_stage_rtr(lc, f, c.HCAP);
   constexpr int LIST_CAP = (VS_ARENA - (int)sizeof(LmCache) - VS_LM_TEAM_LDS) / 2;
   LmTerm* team_terms = reinterpret_cast<LmTerm*>(arena + VS_ARENA - VS_LM_TEAM_LDS);
-#else
-  constexpr int LIST_CAP = (VS_ARENA - (int)sizeof(LmCache)) / 2;
-#endif
   uint16_t* work = reinterpret_cast<uint16_t*>(arena + sizeof(LmCache));
   const bool listed = n_cur <= LIST_CAP && n_cur <= 65535;
   __syncthreads();
@@ -941,11 +883,7 @@ __device__ __forceinline__ void lm_teams_body(const DevCfg& c, const DevBuf& b, 
       const int i = i0 + tid;
       const int32_t* mi = cvu.meta + (size_t)min(i, n_cur - 1) * META;
       const bool need = i < n_cur && (i % G) == g && mi[M_TLEN] >= c.c.minimum_track_length_for_landmark_creation;
-#if VS_LM_TEAMS
       const bool lng = need && landmark_is_long(c, mi);
-#else
-      const bool lng = false;
-#endif
       const unsigned long long m = __ballot(need && !lng), ml = __ballot(lng);
       int base = 0, basel = 0;
       if ((tid & 63) == 0 && m) base = atomicAdd(&n_short, __popcll(m));
@@ -956,29 +894,19 @@ __device__ __forceinline__ void lm_teams_body(const DevCfg& c, const DevBuf& b, 
     }
     __syncthreads();
     const int n_work = n_short;
-#if VS_LM_TEAMS
     const int n_long = n_long_sh;
     constexpr int TEAMS = VS_LM_TEAM_WAVES * (64 / VS_LM_TEAM_G);      // teams of a workgroup
     if ((tid >> 6) < VS_LM_TEAM_WAVES) {
       const int team = tid / VS_LM_TEAM_G, gl = tid % VS_LM_TEAM_G;
-      for (int q = team; q < n_long; q += TEAMS)
-        active += (landmark_team(c, b, s, cvu, f, work[LIST_CAP - 1 - q], lc, team_terms + team * VS_LM_TEAM_G, gl) && gl == 0) ? 1 : 0;
+      for (int q = team; q < n_long; q += TEAMS) landmark_team(c, b, s, cvu, f, work[LIST_CAP - 1 - q], lc, team_terms + team * VS_LM_TEAM_G, gl);
     } else {
       constexpr int SH = VS_WG - 64 * VS_LM_TEAM_WAVES;
-      for (int q = tid - 64 * VS_LM_TEAM_WAVES; q < n_work; q += SH) active += landmark_point_t<true>(c, b, s, cvu, f, work[q], lc) ? 1 : 0;
+      for (int q = tid - 64 * VS_LM_TEAM_WAVES; q < n_work; q += SH) landmark_point(c, b, s, cvu, f, work[q], lc);
     }
-#else
-    for (int q = tid; q < n_work; q += VS_WG) active += landmark_point_t<true>(c, b, s, cvu, f, work[q], lc) ? 1 : 0;
-#endif
   } else {
-    for (int i = g * VS_WG + tid; i < n_cur; i += G * VS_WG) active += landmark_point_t<true>(c, b, s, cvu, f, i, lc) ? 1 : 0;
+    for (int i = g * VS_WG + tid; i < n_cur; i += G * VS_WG) landmark_point(c, b, s, cvu, f, i, lc);
   }
-  if (count) {
-    int total;
-    block_exclusive_scan(active, scan, &total);
-    if (tid == 0 && total) atomicAdd(&st.fc.n_active, total);
-  }
-  if (tick && g == 0 && tid == 0) st.ticks[3] += wall_clock64() - t_begin;
+  if (g == 0 && tid == 0) st.ticks[3] += wall_clock64() - t_begin;
 }
 // sdist[i][k], k < 16: Hamming distance of left feature i to right feature g0 + w0 + k of its row [g0, g1), where the
 // window [w0, m) holds the (up to 16) nearest right features at or left of the left feature: m = number of right
@@ -1017,10 +945,8 @@ __device__ __forceinline__ void stereo_dist_row(const uint8_t* descL, const uint
 // compute() (stereo_framepoint_generator.cpp:135-462): stereo sweep with one thread per image row (rows are
 // independent: the right cursor only moves inside a row), then the order-dependent bin competition with
 // one thread per bin, then emission in bin-grid row-major order.
-// FULL: the arena can hold the whole staging / the 32-bit bin tables (the 512-thread frame kernel); false compiles those paths out
-template <int NT, class SH, bool FULL = true>
-__device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, int s, SH& sh, int pb_cur, double tau_tri, int f,
-                            unsigned char* arena, int arena_bytes) {
+__device__ __forceinline__ void wg_stereo(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_cur, double tau_tri, int f,
+                          unsigned char* arena, int arena_bytes) {
   const int tid = threadIdx.x;
   const PtView cv = pts_of(c, b, s, pb_cur);
   const int rows = c.c.rows, CW1 = c.CW + 1;
@@ -1048,7 +974,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
   //      window (more than 16 unconsumed right features behind the left feature) needs the reference's explicit scan.
   const int nLp = (nL + 7) & ~7, nRp = (nR + 7) & ~7, rowsp = (rows + 8) & ~7;
   const size_t stage_bytes = (size_t)4 * 2 * rowsp + (size_t)(8 + 4 + 4 + 2 + 1 + 1) * nLp + (size_t)(2 + 1) * nRp;
-  const bool staged = FULL && stage_bytes <= (size_t)arena_bytes;
+  const bool staged = stage_bytes <= (size_t)arena_bytes;
   // the distance rows of the first pass (from k_stereo_dist of the image pipeline) ride along when they fit
   const bool sd_lds = staged && ((stage_bytes + 15) & ~(size_t)15) + (size_t)16 * nL <= (size_t)arena_bytes;
   unsigned long long* ssuf = reinterpret_cast<unsigned long long*>(arena);   // step A: suffix-argmin nibbles
@@ -1070,22 +996,22 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
     const int o = c.offsets[oi];
     uint8_t* sdist = b.sdist + (size_t)s * c.NMAX * 16;
     if (staged) {
-      for (int r = tid; r <= rows; r += NT) {
+      for (int r = tid; r <= rows; r += VS_WG) {
         srL[r] = r < rows ? rcL[(size_t)r * CW1] : rcL[(size_t)(rows - 1) * CW1 + c.CW];
         srR[r] = r < rows ? rcR[(size_t)r * CW1] : rcR[(size_t)(rows - 1) * CW1 + c.CW];
       }
 #pragma unroll 4
-      for (int i = tid; i < nL; i += NT) { sxyL[i] = reinterpret_cast<const uint32_t*>(kxyL)[i]; suL[i] = usedL[i]; }
+      for (int i = tid; i < nL; i += VS_WG) { sxyL[i] = reinterpret_cast<const uint32_t*>(kxyL)[i]; suL[i] = usedL[i]; }
 #pragma unroll 4
-      for (int g = tid; g < nR; g += NT) { sxR[g] = kxyR[2 * g]; suR[g] = usedR[g]; }
+      for (int g = tid; g < nR; g += VS_WG) { sxR[g] = kxyR[2 * g]; suR[g] = usedR[g]; }
       if (oi == 0 && sd_lds) {
 #pragma unroll 4
-        for (int i = tid; i < nL; i += NT) sd4[i] = reinterpret_cast<const uint4*>(sdist)[i];
+        for (int i = tid; i < nL; i += VS_WG) sd4[i] = reinterpret_cast<const uint4*>(sdist)[i];
       }
       __syncthreads();
       // distances of the first pass came from k_stereo_dist (image pipeline); later offsets recompute them here
       if (oi > 0) {
-        for (int i = tid; i < nL; i += NT) {
+        for (int i = tid; i < nL; i += VS_WG) {
           if (suL[i]) continue;
           const int rr = (int)(sxyL[i] >> 16) - o;
           if (rr < 0 || rr >= rows) continue;
@@ -1098,7 +1024,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
       auto steps_ab = [&](auto sd_tag) {
         constexpr bool SD = decltype(sd_tag)::value;
         // ---- step A ---------------------------------------------------------------------------------------------------
-        for (int i = tid; i < nL; i += NT) {
+        for (int i = tid; i < nL; i += VS_WG) {
           unsigned long long suf = 0;
           unsigned val = 0;
           int m = 0;
@@ -1129,7 +1055,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         }
         __syncthreads();
         // ---- step B ---------------------------------------------------------------------------------------------------
-        for (int r = tid; r < rows; r += NT) {
+        for (int r = tid; r < rows; r += VS_WG) {
           const int rr = r - o;  // right row: L.row == R.row + o
           const bool rv = rr >= 0 && rr < rows;
           const int l0 = srL[r], l1 = srL[r + 1];
@@ -1195,7 +1121,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         }
         const int nLb = ((l1 - l0) + 7) & ~7, nRb = ((g1 - g0) + 7) & ~7, rbn = r1 - r0, rbp = (rbn + 8) & ~7;
         if (need > (size_t)arena_bytes) {   // a single row beyond the arena (cannot happen below ~600 features in one row): reference loop on HBM
-          for (int i = l0 + tid; i < l1; i += NT) match[2 * i] = -1;
+          for (int i = l0 + tid; i < l1; i += VS_WG) match[2 * i] = -1;
           __syncthreads();
           if (tid == 0) {
             const int rr = r0 - o;
@@ -1218,7 +1144,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
             }
           }
           __syncthreads();
-          const int perb = (l1 - l0 + NT - 1) / NT;
+          const int perb = (l1 - l0 + VS_WG - 1) / VS_WG;
           const int i0 = l0 + tid * perb, i1 = min(i0 + perb, l1);
           int cnt = 0;
           for (int i = i0; i < i1; ++i) cnt += match[2 * i] >= 0 ? 1 : 0;
@@ -1246,12 +1172,12 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         uint8_t* buR = buL + nLb;
         uint8_t* bmL = buR + nRb;
         __syncthreads();   // the previous band's arrays are dead
-        for (int q = tid; q <= rbn; q += NT) { brL[q] = rsL(r0 + q); brR[q] = rsR(min(max(r0 + q - o, 0), rows)); }
-        for (int i = l0 + tid; i < l1; i += NT) { bxyL[i - l0] = reinterpret_cast<const uint32_t*>(kxyL)[i]; buL[i - l0] = usedL[i]; }
-        for (int g = g0 + tid; g < g1; g += NT) { bxR[g - g0] = kxyR[2 * g]; buR[g - g0] = usedR[g]; }
+        for (int q = tid; q <= rbn; q += VS_WG) { brL[q] = rsL(r0 + q); brR[q] = rsR(min(max(r0 + q - o, 0), rows)); }
+        for (int i = l0 + tid; i < l1; i += VS_WG) { bxyL[i - l0] = reinterpret_cast<const uint32_t*>(kxyL)[i]; buL[i - l0] = usedL[i]; }
+        for (int g = g0 + tid; g < g1; g += VS_WG) { bxR[g - g0] = kxyR[2 * g]; buR[g - g0] = usedR[g]; }
         __syncthreads();
         if (oi > 0) {   // later offsets recompute their distance rows (the first pass came from k_stereo_dist)
-          for (int i = l0 + tid; i < l1; i += NT) {
+          for (int i = l0 + tid; i < l1; i += VS_WG) {
             if (buL[i - l0]) continue;
             const int q = (int)(bxyL[i - l0] >> 16) - r0, rr = r0 + q - o;
             if (rr < 0 || rr >= rows) continue;
@@ -1260,7 +1186,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
           __syncthreads();
         }
         // ---- step A (band) ----
-        for (int i = l0 + tid; i < l1; i += NT) {
+        for (int i = l0 + tid; i < l1; i += VS_WG) {
           unsigned long long suf = 0;
           unsigned val = 0;
           int m = 0;
@@ -1286,7 +1212,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         }
         __syncthreads();
         // ---- step B (band): one thread per row ----
-        for (int q = tid; q < rbn; q += NT) {
+        for (int q = tid; q < rbn; q += VS_WG) {
           const int rr = r0 + q - o;
           const bool rv = rr >= 0 && rr < rows;
           const int a0 = brL[q], a1 = brL[q + 1];
@@ -1328,7 +1254,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         __syncthreads();
         // append the band's matches in sorted-left order
         {
-          const int perb = (l1 - l0 + NT - 1) / NT;
+          const int perb = (l1 - l0 + VS_WG - 1) / VS_WG;
           const int i0 = l0 + tid * perb, i1 = min(i0 + perb, l1);
           int cnt = 0;
           for (int i = i0; i < i1; ++i) cnt += bmatch[i - l0] >= 0 ? 1 : 0;
@@ -1353,9 +1279,9 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
       continue;   // this offset's matches are appended
     } else {
       // no usable arena: the reference's loop on HBM, one thread per row
-      for (int i = tid; i < nL; i += NT) match[2 * i] = -1;
+      for (int i = tid; i < nL; i += VS_WG) match[2 * i] = -1;
       __syncthreads();
-      for (int r = tid; r < rows; r += NT) {
+      for (int r = tid; r < rows; r += VS_WG) {
         const int rr = r - o;  // right row: L.row == R.row + o
         if (rr < 0 || rr >= rows) continue;
         const int l0 = rcL[(size_t)r * CW1], l1 = rcL[(size_t)r * CW1 + c.CW];
@@ -1384,7 +1310,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
     }
     DBG_STAMP(0);
     // append the matches of this offset in sorted-left order; mark both features used (prune)
-    const int per = (nL + NT - 1) / NT;
+    const int per = (nL + VS_WG - 1) / VS_WG;
     const int i0 = tid * per, i1 = min(i0 + per, nL);
     int cnt = 0;
     for (int i = i0; i < i1; ++i) cnt += (staged ? smatch[i] : match[2 * i]) >= 0 ? 1 : 0;
@@ -1408,7 +1334,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
   int added = 0;
   if (c.c.enable_keypoint_binning) {
     // working arrays of the bin competition: in LDS (the sweep's staging is dead by now) when they fit, else in HBM
-    const bool bl = FULL && ((size_t)3 * (nb + 1) + (size_t)4 * n_cand) * 4 <= (size_t)arena_bytes;
+    const bool bl = ((size_t)3 * (nb + 1) + (size_t)4 * n_cand) * 4 <= (size_t)arena_bytes;
     // small arenas: the same competition on 16-bit tables (bin cursors two to a word, candidate lists as u16) — 4 (nb + 2) + 8 n_cand
     // + a few bytes, e.g. 15 KB for 2158 bins and 800 candidates
     const size_t cw_words = ((size_t)nb + 2) / 2, occ_words = ((size_t)nb + 2) / 2;
@@ -1421,15 +1347,15 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
       uint16_t* cbin16 = items + n_cand;                                     // [n_cand] bin of candidate q
       auto half = [&](int k) -> int { return (int)((__hip_atomic_load(cw + (k >> 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (16 * (k & 1))) & 0xFFFFu); };
       __syncthreads();
-      for (int k = tid; k < (int)cw_words; k += NT) cw[k] = 0u;
-      for (int k = tid; k < (int)occ_words; k += NT) reinterpret_cast<uint32_t*>(occ16)[k] = 0xFFFFFFFFu;
+      for (int k = tid; k < (int)cw_words; k += VS_WG) cw[k] = 0u;
+      for (int k = tid; k < (int)occ_words; k += VS_WG) reinterpret_cast<uint32_t*>(occ16)[k] = 0xFFFFFFFFu;
       __syncthreads();
-      for (int j = tid; j < n_tracked; j += NT) {      // tracked points seed the grid: a tracked occupant is never replaced
+      for (int j = tid; j < n_tracked; j += VS_WG) {      // tracked points seed the grid: a tracked occupant is never replaced
         const int rb = min((int)rint((double)cv.kp[4 * (size_t)j + 1] / bin), c.rows_bin - 1);
         const int cb = min((int)rint((double)cv.kp[4 * (size_t)j] / bin), c.cols_bin - 1);
         occ16[rb * c.cols_bin + cb] = (int16_t)-2;
       }
-      for (int q = tid; q < n_cand; q += NT) {
+      for (int q = tid; q < n_cand; q += VS_WG) {
         const int4 e = *reinterpret_cast<const int4*>(sc + 4 * q);
         const int lxy = *reinterpret_cast<const int32_t*>(kxyL + 2 * e.x);
         const int xl = (int16_t)(lxy & 0xFFFF), yl = lxy >> 16;
@@ -1442,7 +1368,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
       }
       __syncthreads();
       {   // counts -> exclusive starts, in place
-        const int perb = (nb + NT - 1) / NT;
+        const int perb = (nb + VS_WG - 1) / VS_WG;
         const int k0 = tid * perb, k1 = min(k0 + perb, nb);
         int cnt = 0;
         for (int k = k0; k < k1; ++k) cnt += half(k);
@@ -1452,13 +1378,13 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         for (int k = k0; k < k1; ++k) { const int m = ch[k]; ch[k] = (uint16_t)off; off += m; }
       }
       __syncthreads();
-      for (int q = tid; q < n_cand; q += NT) {          // fill: the cursor of bin k moves from its start to its end
+      for (int q = tid; q < n_cand; q += VS_WG) {          // fill: the cursor of bin k moves from its start to its end
         const int k = cbin16[q];
         const uint32_t old = atomicAdd(cw + (k >> 1), 1u << (16 * (k & 1)));
         items[(old >> (16 * (k & 1))) & 0xFFFFu] = (uint16_t)q;
       }
       __syncthreads();
-      for (int k = tid; k < nb; k += NT) {              // one thread per bin replays its candidates in sweep order
+      for (int k = tid; k < nb; k += VS_WG) {              // one thread per bin replays its candidates in sweep order
         if (occ16[k] != -1) continue;                   // tracked occupant
         const int i0 = k ? half(k - 1) : 0, m = half(k) - i0;
         int win = -1, wdisp = 0, wdist = 0, last = -1;
@@ -1473,7 +1399,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
         occ16[k] = (int16_t)win;
       }
       __syncthreads();
-      const int per = (nb + NT - 1) / NT;
+      const int per = (nb + VS_WG - 1) / VS_WG;
       const int k0 = tid * per, k1 = min(k0 + per, nb);
       int cnt = 0;
       for (int k = k0; k < k1; ++k) cnt += occ16[k] >= 0 ? 1 : 0;
@@ -1482,7 +1408,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
       for (int k = k0; k < k1; ++k) { const int q = occ16[k]; if (q >= 0) items[off++] = (uint16_t)q; }
       __syncthreads();
       if (n_tracked + total > c.MAXP && tid == 0) atomicOr(&b.st[s].error_flags, 2);
-      for (int t = tid; t < total && n_tracked + t < c.MAXP; t += NT) {
+      for (int t = tid; t < total && n_tracked + t < c.MAXP; t += VS_WG) {
         const int4 e = *reinterpret_cast<const int4*>(sc + 4 * items[t]);
         materialize_point(c, b, s, cv, n_tracked + t, e.x, e.y, e.z, e.w, -1, 0);
       }
@@ -1495,16 +1421,16 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
     int32_t* cbin = bl ? bitems + n_cand : match;              // [n_cand][2]: bin id, (disparity << 16 | distance)
     int32_t* emit_q = bl ? cbin + 2 * n_cand : match + 2 * (size_t)c.NMAX;   // [<= n_cand] winners in bin order
     __syncthreads();
-    for (int k = tid; k < nb; k += NT) { occ[k] = -1; bcnt[k] = 0; }
+    for (int k = tid; k < nb; k += VS_WG) { occ[k] = -1; bcnt[k] = 0; }
     __syncthreads();
     // tracked points seed the grid; later points overwrite earlier ones -> keep the largest index
-    for (int j = tid; j < n_tracked; j += NT) {
+    for (int j = tid; j < n_tracked; j += VS_WG) {
       const int rb = min((int)rint((double)cv.kp[4 * (size_t)j + 1] / bin), c.rows_bin - 1);
       const int cb = min((int)rint((double)cv.kp[4 * (size_t)j] / bin), c.cols_bin - 1);
       atomicMax(occ + rb * c.cols_bin + cb, j);
     }
     // bin id / disparity / distance of every candidate, once; per-bin counts
-    for (int q = tid; q < n_cand; q += NT) {
+    for (int q = tid; q < n_cand; q += VS_WG) {
       const int4 e = *reinterpret_cast<const int4*>(sc + 4 * q);
       const int lxy = *reinterpret_cast<const int32_t*>(kxyL + 2 * e.x);
       const int xl = (int16_t)(lxy & 0xFFFF), yl = lxy >> 16;
@@ -1519,7 +1445,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
     DBG_STAMP(2);
     // per-bin candidate lists by counting sort (arrival order inside a bin is arbitrary, restored by a tiny sort)
     {
-      const int perb = (nb + NT - 1) / NT;
+      const int perb = (nb + VS_WG - 1) / VS_WG;
       const int k0 = tid * perb, k1 = min(k0 + perb, nb);
       int cnt = 0;
       for (int k = k0; k < k1; ++k) cnt += ld_relaxed(bcnt + k);   // written by atomics: read past the vector L1
@@ -1529,13 +1455,13 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
       if (tid == 0) bstart[nb] = total;
     }
     __syncthreads();
-    for (int q = tid; q < n_cand; q += NT) {
+    for (int q = tid; q < n_cand; q += VS_WG) {
       const int k = cbin[2 * q];
       bitems[bstart[k] + atomicAdd(bcnt + k, 1)] = q;
     }
     __syncthreads();
     // one thread per bin replays its candidates in sweep order (the rule is not an argmax)
-    for (int k = tid; k < nb; k += NT) {
+    for (int k = tid; k < nb; k += VS_WG) {
       const int o0 = ld_relaxed(occ + k);
       if (o0 >= 0) { occ[k] = -2 - o0; continue; }  // tracked occupant: never replaced
       const int i0 = bstart[k], m = bstart[k + 1] - i0;
@@ -1554,7 +1480,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
     __syncthreads();
     DBG_STAMP(3);
     // winners in bin-grid row-major order, then one thread per new point
-    const int per = (nb + NT - 1) / NT;
+    const int per = (nb + VS_WG - 1) / VS_WG;
     const int k0 = tid * per, k1 = min(k0 + per, nb);
     int cnt = 0;
     for (int k = k0; k < k1; ++k) cnt += occ[k] >= 0 ? 1 : 0;
@@ -1563,14 +1489,14 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
     for (int k = k0; k < k1; ++k) { const int q = occ[k]; if (q >= 0) emit_q[off++] = q; }
     __syncthreads();
     if (n_tracked + total > c.MAXP && tid == 0) atomicOr(&b.st[s].error_flags, 2);
-    for (int t = tid; t < total && n_tracked + t < c.MAXP; t += NT) {
+    for (int t = tid; t < total && n_tracked + t < c.MAXP; t += VS_WG) {
       const int4 e = *reinterpret_cast<const int4*>(sc + 4 * emit_q[t]);
       materialize_point(c, b, s, cv, n_tracked + t, e.x, e.y, e.z, e.w, -1, 0);
     }
     added = total;
     }   // !bc
   } else {
-    for (int q = tid; q < n_cand; q += NT) {
+    for (int q = tid; q < n_cand; q += VS_WG) {
       const int j = n_tracked + q;
       if (j < c.MAXP) materialize_point(c, b, s, cv, j, sc[4 * q], sc[4 * q + 1], sc[4 * q + 2], sc[4 * q + 3], -1, 0);
       else atomicOr(&b.st[s].error_flags, 2);
@@ -1583,7 +1509,7 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
   // history of the appended points
   double* hc = hcam_of(c, b, s, f);
   int32_t* hp = hprev_of(c, b, s, f);
-  for (int j = n_tracked + tid; j < n_final; j += NT) {
+  for (int j = n_tracked + tid; j < n_final; j += VS_WG) {
     { const double x = cv.cam[3 * (size_t)j], y = cv.cam[3 * (size_t)j + 1], z = cv.cam[3 * (size_t)j + 2];
       reinterpret_cast<double2*>(hc + 4 * (size_t)j)[0] = make_double2(x, y); reinterpret_cast<double2*>(hc + 4 * (size_t)j)[1] = make_double2(z, 1 / z); }
     hp[j] = -1;
@@ -1591,11 +1517,6 @@ __device__ __forceinline__ void wg_stereo_t(const DevCfg& c, const DevBuf& b, in
   }
   if (tid == 0) { sh.n_cand = added; sh.n_cur = n_final; }
   __syncthreads();
-}
-
-__device__ __forceinline__ void wg_stereo(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_cur, double tau_tri, int f,
-                          unsigned char* arena, int arena_bytes) {
-  wg_stereo_t<VS_WG, FrameShared>(c, b, s, sh, pb_cur, tau_tri, f, arena, arena_bytes);
 }
 
 // L-R Hamming distances of the first epipolar pass for every left feature of every stream (image pipeline): the window
@@ -1663,18 +1584,17 @@ __device__ __forceinline__ void frame_phase2(const DevCfg& c, const DevBuf& b, i
   }
 }
 
-// The frame is processed by three phase launches of this kernel with wide kernels in between (fused path):
+// The frame's steps:
 //   phase 0  track resolution, registration (aligner, recursion, fallback / break), prune, recovery projection
-//   [k_recover_brief]   BRIEF of the projected lost points, all streams, one wavefront each
-//   phase 1  recovery append, history publication
-//   [k_update_landmarks] landmark creation / refinement, one thread per framepoint; [k_stereo_dist] L-R distances
-//   phase 2  status switch, stereo sweep + binning + emission, report
-// phase < 0 runs everything in one launch (the wide steps inside the workgroup).
-// phase 4 = phase 1 + the count of active landmarks: the refinement then runs in workgroups of its own BESIDE phase 2 (k_tail_lm, launch sequence 4, few streams:
-// nothing of phase 2 reads what the refinement writes — landmark coordinates and update counts of the tracked points; the next frame's phase 0 does).
-// phase 3 = phases 1 and 2 in one launch with the landmark refinement inside the workgroup: with phase 0 and the wide recovery
-// kernel in front this is the two-launch sequence used for few streams (the ~140 recovery patches of a frame spread over the
-// idle CUs: 67 -> 9 us; the wide landmark kernel, one thread per track, is slower than the workgroup's LDS-cached one).
+//   phase 1  recovery BRIEF + append, history publication
+//   phase 2  landmark creation / refinement, status switch, stereo sweep + binning + emission, report
+// phase < 0 runs everything in one launch (launch sequence 0, many streams).  Launch sequence 4 (up to VS_SPLIT4_MAX_STREAMS streams) runs
+//   phase 0      this kernel
+//   [k_recover_brief]  BRIEF of the projected lost points, all streams, one wavefront each (the ~140 recovery patches of a frame spread over
+//                      the idle CUs: 67 -> 9 us)
+//   phase 4      this kernel: phase 1 without the BRIEF, plus the count of active landmarks
+//   [k_tail_lm]  phase 2 with the landmark refinement in workgroups of its own BESIDE it (nothing of phase 2 reads what the refinement
+//                writes — landmark coordinates and update counts of the tracked points; the next frame's phase 0 does)
 // The configuration and the buffer table arrive as pointers into the CONSTANT address space (device-resident copies the
 // context uploads once): passed by value, the ~60 pointers of DevBuf are all loaded in the prologue, cannot stay in the
 // 100-odd SGPRs and are parked in VGPR lanes — 1900 v_readlane instructions kernel-wide, ~190 in every aligner round.
@@ -1686,9 +1606,6 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
   const DevBuf& b = *(const DevBuf*)bp;
   __shared__ FrameShared sh;
   __shared__ __align__(16) unsigned char arena[VS_ARENA];
-#ifdef VS_FRAME_PRIO
-  __builtin_amdgcn_s_setprio(VS_FRAME_PRIO);   // co-scheduled builds: the latency-bound frame wavefronts issue ahead of the image kernels' wavefronts on their SIMD
-#endif
   const int s = b.s0 + xcd_local_stream(blockIdx.x, gridDim.x, b.xcd_rot), tid = threadIdx.x;
   if (!vs_active(b, s)) return;
   StreamState& st = b.st[s];
@@ -1775,7 +1692,7 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
           fall = true;
         } else {
           const unsigned long long ta = wall_clock64();
-          wg_align(c, b, s, sh, pb_prev, false, prior, arena, VS_ARENA);
+          wg_align(c, b, s, sh, pb_prev, false, prior);
           if (tid == 0) st.ticks[1] += wall_clock64() - ta;
           aligner_valid = true;
           if (sh.inl < c.c.minimum_number_of_landmarks_to_track) fall = true; else accept = true;
@@ -1792,7 +1709,7 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
           }
         } else {
           const unsigned long long ta = wall_clock64();
-          wg_align(c, b, s, sh, pb_prev, true, prior, arena, VS_ARENA);
+          wg_align(c, b, s, sh, pb_prev, true, prior);
           if (tid == 0) st.ticks[1] += wall_clock64() - ta;
           aligner_valid = true;
           if (sh.inl > c.c.minimum_number_of_landmarks_to_track) {
@@ -1864,7 +1781,7 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
   if (phase == 0) return;
   }  // phase 0
 
-  if (phase == 1 || phase < 0 || phase == 3 || phase == 4) {   // ========================== phase 1 (4: + the count of active landmarks) ==========================
+  {   // ========================== phase 1 (4: + the count of active landmarks) ==========================
     if (tid == 0) { sh.n_cur = fc.n_cur; sh.n_lost = fc.n_lost; sh.flag = 0; }
     __syncthreads();
     if (has_prev && c.c.enable_landmark_recovery) {
@@ -1881,7 +1798,7 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
     __syncthreads();
     if (phase == 4) {
       // the landmark kernel will run BESIDE phase 2: the number of active landmarks — what the status switch needs — is the number of points
-      // whose track is long enough for a landmark (landmark_point_t returns false for nothing else)
+      // whose track is long enough for a landmark (landmark_point returns false for nothing else)
       const PtView cvc = pts_of(c, b, s, pb_cur);
       int active = 0;
       for (int i = tid; i < sh.n_cur; i += VS_WG) active += cvc.meta[(size_t)i * META + M_TLEN] >= c.c.minimum_track_length_for_landmark_creation ? 1 : 0;
@@ -1890,13 +1807,12 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
       if (tid == 0) fc.n_active = total;
       return;
     }
-    if (phase == 1) return;
   }
 
-  // ============================================== phase 2 ==============================================
+  // ========================================= phase 2 (fused) =========================================
   if (tid == 0) { sh.n_cur = fc.n_cur; sh.n_cand = 0; }
   __syncthreads();
-  if (phase < 0 || phase == 3) {
+  {
     const unsigned long long tu = wall_clock64();
     const int total = wg_landmarks_lds(c, b, s, sh, pb_cur, f, arena);
     if (tid == 0) { fc.n_active = total; st.ticks[3] += wall_clock64() - tu; }
@@ -1928,114 +1844,10 @@ __global__ VS_FRAME_BOUNDS void k_tail_lm(ConstDevCfg* cp, ConstDevBuf* bp, int 
     const int i = (int)blockIdx.x - n, sl = i / G;
     const int s = b.s0 + sl;
     if (!vs_active(b, s)) return;
-    lm_teams_body(c, b, s, i - sl * G, G, 0, true, arena, sh.flag, sh.n_proj, sh.scan);
+    lm_teams_body(c, b, s, i - sl * G, G, arena, sh.flag, sh.n_proj);
   }
 }
 
-// ==============================================================================================
-// The frame's TAIL as a kernel of its own (launch sequence 3: k_track_candidates, k_frame phase 0, k_recover_brief, k_tail):
-// recovery append, history, landmark creation / refinement, status switch, stereo sweep + binning + emission, report — everything
-// after registration and pruning.  None of it needs the aligner's 245 registers, so this kernel is shaped to fit the HOLE ONE
-// image-kernel workgroup leaves on a busy CU (tools/probe/cosched.hip: 256 threads, <= 128 VGPRs, <= ~22 KB LDS start within
-// microseconds beside k_fast_box's flood; anything with 512 threads, more registers or more LDS waits until the flood's grid is
-// exhausted): it runs BESIDE the image pipeline of the next frame instead of on CUs of its own.  Its wavefronts raise their
-// priority: a latency-bound chain loses nothing beside VALU-busy neighbours (same probe) and should not queue behind them.
-// Same device functions as k_frame's phases 1-2, instantiated for 256 threads, the landmark cache one measurement deep, the
-// stereo sweep band by band and the bin competition on 16-bit tables (wg_stereo_t).
-// ==============================================================================================
-#define VS_TAIL_WG 256
-#ifndef VS_TAIL_ARENA
-#define VS_TAIL_ARENA 17408
-#endif
-struct TailShared { int scan[17]; int flag; int n_lost, n_cur, n_cand; };
-__global__ __launch_bounds__(VS_TAIL_WG, 4) void k_tail(ConstDevCfg* cp, ConstDevBuf* bp) {
-  const DevCfg& c = *(const DevCfg*)cp;
-  const DevBuf& b = *(const DevBuf*)bp;
-  __shared__ TailShared sh;
-  __shared__ __align__(16) unsigned char arena[VS_TAIL_ARENA];
-  __builtin_amdgcn_s_setprio(2);
-  const int s = b.s0 + xcd_local_stream(blockIdx.x, gridDim.x, b.xcd_rot), tid = threadIdx.x;
-  if (!vs_active(b, s)) return;
-  StreamState& st = b.st[s];
-  vslam_frame_info& info = b.info[s];
-  const int f = st.frame_count;
-  const int has_prev = st.has_prev;
-  const int pb_prev = st.cur, pb_cur = st.cur ^ 1;
-  FrameCarry& fc = st.fc;
-  if (tid == 0) { sh.n_cur = fc.n_cur; sh.n_lost = fc.n_lost; sh.flag = 0; sh.n_cand = 0; }
-  __syncthreads();
-  if (has_prev && c.c.enable_landmark_recovery) {
-    const unsigned long long tr = wall_clock64();
-    wg_recover_append_t<VS_TAIL_WG, TailShared>(c, b, s, sh, pb_prev, pb_cur);
-    if (tid == 0) { st.ticks[2] += wall_clock64() - tr; fc.n_recovered = sh.flag; }
-  }
-  wg_publish_history(c, b, s, sh.n_cur, pb_cur, f);
-  __syncthreads();
-  // ---- _updatePoints: landmarks --------------------------------------------------------------------------------------
-  int n_active = 0;
-  {
-    const unsigned long long tu = wall_clock64();
-    const PtView cvu = pts_of(c, b, s, pb_cur);
-    typedef LmCacheT<VS_TAIL_WG, 1> LC;
-    static_assert(sizeof(LC) + 1024 <= VS_TAIL_ARENA, "landmark cache + work list must fit the tail's arena");
-    LC* lc = reinterpret_cast<LC*>(arena);
-    for (int t = tid; t < VS_LM_NP * 12; t += VS_TAIL_WG) { const int k = t / 12; if (f - k >= 0 && k < c.HCAP) lc->w2c[k][t - 12 * k] = hpose_of(c, b, s, f - k)[12 + t - 12 * k]; }
-    __syncthreads();
-    lm_stage_rtr(lc, f, c.HCAP, VS_TAIL_WG);
-    constexpr int LIST_CAP = (VS_TAIL_ARENA - (int)sizeof(LC)) / 2;
-    uint16_t* work = reinterpret_cast<uint16_t*>(arena + sizeof(LC));
-    int active = 0;
-    // the points that carry a landmark, compacted into a work list (LIST_CAP points of the frame at a time): one per thread
-    for (int c0 = 0; c0 < sh.n_cur; c0 += LIST_CAP) {
-      const int c1 = min(c0 + LIST_CAP, sh.n_cur);
-      __syncthreads();
-      if (tid == 0) sh.flag = 0;
-      __syncthreads();
-      for (int i0 = c0; i0 < c1; i0 += VS_TAIL_WG) {
-        const int i = i0 + tid;
-        const bool need = i < c1 && cvu.meta[(size_t)i * META + M_TLEN] >= c.c.minimum_track_length_for_landmark_creation;
-        const unsigned long long m = __ballot(need);
-        int base = 0;
-        if ((tid & 63) == 0 && m) base = atomicAdd(&sh.flag, __popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (need) work[base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)(i - c0);
-      }
-      __syncthreads();
-      const int n_work = sh.flag;
-      for (int q = tid; q < n_work; q += VS_TAIL_WG) active += landmark_point_t<true, LC>(c, b, s, cvu, f, c0 + work[q], lc) ? 1 : 0;
-    }
-    block_exclusive_scan(active, sh.scan, &n_active);
-    if (tid == 0) { fc.n_active = n_active; sh.flag = 0; st.ticks[3] += wall_clock64() - tu; }
-    __syncthreads();
-  }
-  int status = fc.status;
-  if (n_active > c.c.minimum_number_of_landmarks_to_track) status = VSLAM_TRACKING;
-  const double tau_tri2 = fc.tau_tri;
-  const unsigned long long ts = wall_clock64();
-  wg_stereo_t<VS_TAIL_WG, TailShared, false>(c, b, s, sh, pb_cur, tau_tri2, f, arena, VS_TAIL_ARENA);
-  if (tid == 0) {
-    st.ticks[4] += wall_clock64() - ts;
-    const double* c2w = hpose_of(c, b, s, f);
-    *pts_of(c, b, s, pb_cur).n = sh.n_cur;
-    st.status = status; st.win = fc.win; st.tau_track = fc.tau_track; st.tau_tri = tau_tri2;
-    for (int k = 0; k < 12; ++k) { st.prior[k] = fc.prior[k]; st.pose[k] = c2w[k]; }
-    st.n_tracked_landmarks_prev = n_active;
-    st.frame_count = f + 1; st.has_prev = 1; st.cur = pb_cur; st.aligner_valid = fc.aligner_valid;
-    info.frame_index = f + 1; info.status = status; info.status_at_start = fc.status0;
-    info.n_keypoints_left = b.n_kp[s * 2]; info.n_keypoints_right = b.n_kp[s * 2 + 1];
-    int rl = 0, rr = 0;
-    for (int r = 0; r < c.n_regions; ++r) { rl += b.iinfo[s].raw_count[0][r]; rr += b.iinfo[s].raw_count[1][r]; info.thresholds[r] = b.iinfo[s].thr_after[r]; }
-    for (int r = c.n_regions; r < VSLAM_MAX_REGIONS; ++r) info.thresholds[r] = 0;
-    info.n_detected_left = rl; info.n_detected_right = rr;
-    info.track_attempts = fc.attempts; info.n_after_prune = fc.n_after_prune; info.n_recovered = fc.n_recovered;
-    info.n_active_landmarks = n_active; info.n_new_stereo = sh.n_cand; info.n_points = sh.n_cur;
-    info.track_broken = fc.broken; info.fallback = fc.fallback; info.window_pixels = fc.win;
-    info.error_flags = st.error_flags; info.tau_track = fc.tau_track; info.tau_triangulation = tau_tri2;
-    for (int k = 0; k < 12; ++k) { info.camera_left_to_world[k] = c2w[k]; info.previous_to_current[k] = fc.prior[k]; }
-    if (f < VS_POSE_LOG) { double* pl = b.pose_log + ((size_t)s * VS_POSE_LOG + f) * 12; for (int k = 0; k < 12; ++k) pl[k] = c2w[k]; }
-    st.dbg[8] += wall_clock64() - fc.t0;
-  }
-}
 
 // recoverPoints on caller-provided lost points (vslam_stereo_recover): previous buffer 0 holds the lost points' descriptors,
 // landmarks and landmark flags, the lost list is 0..n-1, survivors are appended to buffer 1 from its start.
@@ -2117,7 +1929,7 @@ __device__ __forceinline__ void stage_body(const DevCfg& c, const DevBuf& b, int
     double T0[12];
     for (int k = 0; k < 12; ++k) T0[k] = st.prior[k];
     const unsigned long long t0 = wall_clock64();
-    wg_align(c, b, s, sh, pb_prev, arg != 0, T0, arena, VS_ARENA);
+    wg_align(c, b, s, sh, pb_prev, arg != 0, T0);
     if (tid == 0) {
       st.ticks[1] += wall_clock64() - t0;
       st.al_n = sh.n_trk; st.al_inliers = sh.inl; st.al_outliers = sh.outl; st.al_iterations = sh.its; st.al_converged = sh.conv;
@@ -2246,7 +2058,7 @@ __global__ __launch_bounds__(VS_WG) void k_stage_lm(const DevCfg c, const DevBuf
   const int i = (int)blockIdx.x - n, sl = i / G;
   const int s = b.s0 + sl;
   if (!vs_active(b, s)) return;
-  lm_teams_body(c, b, s, i - sl * G, G, 0, true, arena, sh.flag, sh.n_proj, sh.scan);
+  lm_teams_body(c, b, s, i - sl * G, G, arena, sh.flag, sh.n_proj);
 }
 
 // vslam_reset_stream, asynchronous: the stream state has an image-pipeline half (the detector thresholds, written by k_emit

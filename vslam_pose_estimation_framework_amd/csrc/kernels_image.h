@@ -249,10 +249,6 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
       if (cand) queue[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)((r << 8) | cc);
     }
   };
-#ifndef VS_PROBE
-#define VS_PROBE 0
-#endif
-  if (VS_PROBE & 1) { /* probe build: no pretest, no candidates */ } else
   if (uni_thr != -2) {
     // uniform threshold (the usual tile): four pixels per lane from aligned dwords, the compass differences in packed
     // i16 (v_perm_b32 unpacks, v_pk_sub/min/max_i16).  16 lanes per region row (dwords 1..16 = region columns 1..64), four rows
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
     static_assert((VS_TILE_H + 2) * 2 <= 256, "one pass over the halo columns");
   }
   __syncthreads();
-  if (!(VS_PROBE & 2)) {
+  {
     const int nq = qn;
     for (int q = tid; 2 * q < nq; q += 256) {
       const int e0 = queue[2 * q], e1 = (2 * q + 1 < nq) ? queue[2 * q + 1] : e0;
@@ -369,7 +365,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
   }
   __syncthreads();   // every reader of the candidate queue is done: its memory becomes the horizontal sums
   // ---- horizontal 9-sums, four outputs per thread from three aligned dwords -----------------------------------------
-  const bool want_box = !(VS_PROBE & 4) && c.c.descriptor_type == VSLAM_DESCRIPTOR_BRIEF;   // ORB samples the Gaussian image instead
+  const bool want_box = c.c.descriptor_type == VSLAM_DESCRIPTOR_BRIEF;   // ORB samples the Gaussian image instead
   if (want_box)
   for (int i = tid; i < (VS_TILE_H + 8) * 16; i += 256) {
     const int r = i >> 4, q = i & 15;

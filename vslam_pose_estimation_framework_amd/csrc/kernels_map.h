@@ -13,7 +13,7 @@
 // reference process (_updatePoints creates landmarks in point order); that correspondence is the intent, it is not pinned here.
 // The ids of the previous frame are only read when the stream has one (frame index > 0).
 //
-// Which points were updated this frame: landmark_point_t runs on every point whose track is long enough (M_TLEN >=
+// Which points were updated this frame: landmark_point runs on every point whose track is long enough (M_TLEN >=
 // minimum_track_length_for_landmark_creation) and leaves M_LMUP > 0 on each of them; a point with M_LMUP > 0 inherited it from a
 // predecessor whose track was already long enough.  So "carries a landmark" and "its landmark was updated this frame" are the same
 // set, M_LMUP > 0, and every point with an id is in it.  Each such point writes its landmark's slot: coordinates (p_lm), the update

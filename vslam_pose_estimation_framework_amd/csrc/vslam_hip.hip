@@ -31,24 +31,21 @@ struct vslam_ctx {
   DevBuf buf;
   int device = 0;
   int B = 0;
-  hipStream_t stream = nullptr;       // tracker kernels (k_track_candidates, k_frame, stages) + read-back
-  hipStream_t stream_img = nullptr;   // image pipeline (k_fast_box, k_emit, k_brief) + uploads
+  hipStream_t stream = nullptr;       // frame queue: tracker kernels (k_track_candidates, k_frame, stages) + read-back
+  hipStream_t stream_img = nullptr;   // image queue: image pipeline (k_fast_box, k_emit, k_brief) + uploads; the frame queue itself under
+                                      // VSLAM_IMG_STREAMS=0 and on a caller's stream (vslam_set_hip_stream)
   bool own_stream = false;
+  hipEvent_t ev_img[2] = {nullptr, nullptr}, ev_frm[2] = {nullptr, nullptr};   // [product set]: image pipeline done / frame queue done with the set
+  bool frm_pending[2] = {false, false};
+  int q0_frm = 0, q0_img = 0;         // XCD that block 0 of a launch on the queue runs on (calibrate_queues)
   // image products are double-buffered: frame t+1 is detected/described while frame t is tracked
   struct ImgSet { uint16_t* box; uint8_t* score8; unsigned long long* mask; int16_t* kp_xy; uint8_t* kp_score; uint8_t* desc;
                   int32_t* n_kp; int32_t* rowcell; uint8_t* used; uint8_t* sdist; ImgInfo* iinfo; } sets[2];
   int parity = 0, last_set = 0;
-  // streams are processed in G independent groups, each with its own pair of HIP streams: a slow stream only
-  // delays its own group, the other groups' kernels fill the idle CUs
-  // st_img: image pipeline of even steps (and uploads), st_img2: image pipeline of odd steps, so that BRIEF of step t
-  // overlaps FAST of step t+1 (FAST(t+1) only waits for the threshold controller in k_emit(t))
-  struct Group { int s0, n; hipStream_t st_frm, st_img, st_img2; hipEvent_t ev_img[2], ev_frm[2], ev_emit[2]; bool frm_pending[2], emit_pending[2];
-                 int q0_frm = 0, q0_img = 0, q0_img2 = 0; };   // XCD that block 0 of a launch on the queue runs on (calibrate_queues)
-  std::vector<Group> groups;
   std::string err;
   std::vector<void*> allocs;
   DevCfg* d_cfg = nullptr;            // device-resident copies read by k_frame through the constant address space
-  DevBuf* d_bufs = nullptr;           // [2 product sets][groups]
+  DevBuf* d_bufs = nullptr;           // [2 product sets]
   uint8_t* upload[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [step parity][left/right]
   int up_stride = 0;
   size_t up_stream_stride = 0;
@@ -82,8 +79,6 @@ struct vslam_ctx {
   // stage path of a one-stream context: the image pipeline runs on the frame queue itself (the caller waits for every stage, so a
   // second queue buys no overlap and costs an event round trip per frame) and is timed by three events instead of two per kernel
   hipStream_t img_override = nullptr;
-  bool xcd_affinity = true;      // VSLAM_XCD_AFFINITY=0: block ids as the runtime deals them (measurement aid)
-  int xcd_skew = 0;              // VSLAM_XCD_SKEW=k: the image queues' streams k XCDs away from their frame workgroups (measurement aid)
   bool img_on_frm_queue = false;
   int report_seq = 0;                                  // stamps every report launch; the header carries it back
   int report_xy_seq = -1;                              // the early coordinates-only keypoint report of the frame in flight (-1: none)
@@ -92,9 +87,8 @@ struct vslam_ctx {
   struct Pending { int flags = 0; int status = 0, win = 0; double tau = 0; double prior[12], pose[12]; } pend;
   unsigned char* pin_img[2] = {nullptr, nullptr}; size_t pin_img_bytes = 0;     // [step parity]: left | right
   hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false};
-  int split = 0;   // 0: one frame launch; 1: three phase launches with wide recovery / landmark kernels in between (measured slower);
-                   // 2: two phase launches around the wide recovery kernel
-                   // 4: phase launches around the wide recovery kernel, the landmark refinement in workgroups of its own inside the last one (fastest up to VS_SPLIT4_MAX_STREAMS streams)
+  int split = 0;   // launch sequence of the frame: 0 one fused k_frame launch; 4 phase launches around the wide recovery kernel, the landmark
+                   // refinement in workgroups of its own inside the last one (fastest up to VS_SPLIT4_MAX_STREAMS streams)
   bool lm_published = false;                            // vslam_prune_recover has published the frame's history (one stream): vslam_compute runs the landmark refinement beside the stereo stage
   // rectification of raw input pairs (vslam_set_rectification): maps at the rectified size, padded to map_stride entries per row, and
   // the raw slabs [step parity][left/right] host images are copied into (B x raw_rows x raw_stride each).  k_rectify writes the rectified
@@ -199,16 +193,12 @@ static void harvest_events(vslam_ctx* c) {
 
 
 static void sync_all(vslam_ctx* c) {
-  for (auto& g : c->groups) { (void)hipStreamSynchronize(g.st_img); (void)hipStreamSynchronize(g.st_img2); (void)hipStreamSynchronize(g.st_frm); }
+  (void)hipStreamSynchronize(c->stream_img);
+  (void)hipStreamSynchronize(c->stream);
 }
-static int group_of(const vslam_ctx* c, int s) {
-  for (size_t i = 0; i < c->groups.size(); ++i) if (s >= c->groups[i].s0 && s < c->groups[i].s0 + c->groups[i].n) return (int)i;
-  return 0;
-}
-static DevBuf buf_set(const vslam_ctx* c, int set, int s0 = 0, int q0 = 0) {
+static DevBuf buf_set(const vslam_ctx* c, int set, int q0 = 0) {
   DevBuf b = c->buf;
-  b.s0 = s0;
-  b.xcd_rot = c->xcd_affinity ? ((q0 - s0) & 7) : 0;     // dev_types.h: stream s on physical XCD s % 8 whatever queue the launch goes to
+  b.xcd_rot = q0 & 7;     // dev_types.h: stream s on physical XCD s % 8 whatever queue the launch goes to
   const vslam_ctx::ImgSet& q = c->sets[set];
   b.box = q.box; b.score8 = q.score8; b.mask = q.mask; b.kp_xy = q.kp_xy; b.kp_score = q.kp_score; b.desc = q.desc;
   b.n_kp = q.n_kp; b.rowcell = q.rowcell; b.used = q.used; b.sdist = q.sdist; b.iinfo = q.iinfo;
@@ -324,10 +314,8 @@ static void fresh_stream_state(const vslam_ctx* c, StreamState& x) {
   tf_identity(x.pose);
 }
 static int upload_buffer_tables(vslam_ctx* c) {
-  const size_t G = c->groups.size();
-  std::vector<DevBuf> hb(2 * G);
-  for (int q = 0; q < 2; ++q) for (size_t g = 0; g < G; ++g) hb[q * G + g] = buf_set(c, q, c->groups[g].s0, c->groups[g].q0_frm);
-  HIP_TRY(c, hipMemcpy(c->d_bufs, hb.data(), sizeof(DevBuf) * 2 * G, hipMemcpyHostToDevice));
+  const DevBuf hb[2] = {buf_set(c, 0, c->q0_frm), buf_set(c, 1, c->q0_frm)};
+  HIP_TRY(c, hipMemcpy(c->d_bufs, hb, sizeof hb, hipMemcpyHostToDevice));
   return VSLAM_OK;
 }
 static int init_state(vslam_ctx* c) {
@@ -351,7 +339,7 @@ static int init_state(vslam_ctx* c) {
   for (int q = 0; q < 2; ++q) {
     HIP_TRY(c, hipMemsetAsync(c->sets[q].n_kp, 0, sizeof(int32_t) * c->B * 2, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->sets[q].iinfo, 0, sizeof(ImgInfo) * c->B, c->stream));
-    for (auto& g : c->groups) { g.frm_pending[q] = false; g.emit_pending[q] = false; }
+    c->frm_pending[q] = false;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->parity = 0; c->last_set = 0;
@@ -359,12 +347,18 @@ static int init_state(vslam_ctx* c) {
   return VSLAM_OK;
 }
 
+// the queues' events, and the queues themselves unless they are the caller's
 static void destroy_streams(vslam_ctx* c) {
-  for (auto& g : c->groups) {
-    for (int q = 0; q < 2; ++q) { if (g.ev_img[q]) (void)hipEventDestroy(g.ev_img[q]); if (g.ev_frm[q]) (void)hipEventDestroy(g.ev_frm[q]); if (g.ev_emit[q]) (void)hipEventDestroy(g.ev_emit[q]); }
-    if (c->own_stream) { if (g.st_img != g.st_frm) (void)hipStreamDestroy(g.st_img); if (g.st_img2 != g.st_img) (void)hipStreamDestroy(g.st_img2); (void)hipStreamDestroy(g.st_frm); }
+  for (int q = 0; q < 2; ++q) {
+    if (c->ev_img[q]) (void)hipEventDestroy(c->ev_img[q]);
+    if (c->ev_frm[q]) (void)hipEventDestroy(c->ev_frm[q]);
+    c->ev_img[q] = c->ev_frm[q] = nullptr;
   }
-  c->groups.clear();
+  if (c->own_stream) {
+    if (c->stream_img && c->stream_img != c->stream) (void)hipStreamDestroy(c->stream_img);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+  }
+  c->stream = c->stream_img = nullptr;
 }
 static int create_internal(const vslam_config* cfg, int device, int n_streams, vslam_ctx** out);
 static int init_state(vslam_ctx* c);
@@ -411,17 +405,13 @@ __global__ void k_xcc_probe(int* out) {
   if (threadIdx.x == 0) *out = (int)(v & 7u);
 }
 static int calibrate_queues(vslam_ctx* c) {
-  if (const char* e = getenv("VSLAM_XCD_AFFINITY")) c->xcd_affinity = atoi(e) != 0;
-  if (const char* e = getenv("VSLAM_XCD_SKEW")) c->xcd_skew = atoi(e) & 7;
   int* d = nullptr;
-  if (hipMalloc(&d, 3 * sizeof(int)) != hipSuccess) return VSLAM_OK;     // affinity is an optimisation: without it rot stays 0
-  for (auto& g : c->groups) {
-    int h[3] = {0, 0, 0};
-    hipStream_t q[3] = {g.st_frm, g.st_img, g.st_img2};
-    bool ok = true;
-    for (int k = 0; k < 3 && ok; ++k) { hipLaunchKernelGGL(k_xcc_probe, dim3(1), dim3(64), 0, q[k], d + k); ok = hipStreamSynchronize(q[k]) == hipSuccess; }
-    if (ok && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) { g.q0_frm = h[0]; g.q0_img = (h[1] + c->xcd_skew) & 7; g.q0_img2 = (h[2] + c->xcd_skew) & 7; }
-  }
+  if (hipMalloc(&d, 2 * sizeof(int)) != hipSuccess) return VSLAM_OK;     // affinity is an optimisation: without it rot stays 0
+  int h[2] = {0, 0};
+  hipStream_t q[2] = {c->stream, c->stream_img};
+  bool ok = true;
+  for (int k = 0; k < 2 && ok; ++k) { hipLaunchKernelGGL(k_xcc_probe, dim3(1), dim3(64), 0, q[k], d + k); ok = hipStreamSynchronize(q[k]) == hipSuccess; }
+  if (ok && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) { c->q0_frm = h[0]; c->q0_img = h[1]; }
   (void)hipFree(d);
   return VSLAM_OK;
 }
@@ -447,41 +437,20 @@ static int create_internal(const vslam_config* cfg, int device, int n_streams, v
   c->B = n_streams;
   derive_cfg(*cfg, n_streams, &c->cfg);
   {
-    int G = 1;   // measured on MI355X: concurrent HIP streams did not overlap the per-group kernels (1 group is fastest)
-    if (const char* e = getenv("VSLAM_GROUPS")) G = atoi(e);
-    G = std::max(1, std::min(std::min(G, 16), n_streams));
-    for (int g = 0; g < G; ++g) {
-      vslam_ctx::Group q;
-      for (int k = 0; k < 2; ++k) { q.ev_img[k] = nullptr; q.ev_frm[k] = nullptr; q.ev_emit[k] = nullptr; }
-      q.s0 = (int)((long long)n_streams * g / G);
-      q.n = (int)((long long)n_streams * (g + 1) / G) - q.s0;
-      // VSLAM_PRIO (measurement aid): 1 = frame stream at the highest queue priority, image stream at the lowest; 2 = the reverse
-      int p_lo = 0, p_hi = 0, prio = 0;
-      if (const char* e = getenv("VSLAM_PRIO")) prio = atoi(e);
-      (void)hipDeviceGetStreamPriorityRange(&p_lo, &p_hi);
-      const int pf = prio == 1 ? p_hi : (prio == 2 ? p_lo : 0), pi = prio == 1 ? p_lo : (prio == 2 ? p_hi : 0);
-      bool ok = hipStreamCreateWithPriority(&q.st_frm, hipStreamNonBlocking, pf) == hipSuccess &&
-                hipStreamCreateWithPriority(&q.st_img, hipStreamNonBlocking, pi) == hipSuccess &&
-                hipStreamCreateWithPriority(&q.st_img2, hipStreamNonBlocking, pi) == hipSuccess;
-      // a second image stream (BRIEF(t) overlapping FAST(t+1)) measured slower on MI355X: opt-in only
-      if (ok && !(getenv("VSLAM_IMG_STREAMS") && atoi(getenv("VSLAM_IMG_STREAMS")) == 2)) { (void)hipStreamDestroy(q.st_img2); q.st_img2 = q.st_img; }
-      // VSLAM_IMG_STREAMS=0: everything on one HIP stream (no overlap) — measurement aid for stand-alone kernel times
-      if (ok && getenv("VSLAM_IMG_STREAMS") && atoi(getenv("VSLAM_IMG_STREAMS")) == 0) { (void)hipStreamDestroy(q.st_img); q.st_img = q.st_img2 = q.st_frm; }
-      for (int k = 0; k < 2 && ok; ++k)
-        ok = hipEventCreateWithFlags(&q.ev_img[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&q.ev_frm[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&q.ev_emit[k], hipEventDisableTiming) == hipSuccess;
-      q.frm_pending[0] = q.frm_pending[1] = false;
-      q.emit_pending[0] = q.emit_pending[1] = false;
-      if (!ok) { c->own_stream = true; destroy_streams(c); delete c; return fail(nullptr, VSLAM_ERR_HIP, "hipStreamCreate failed"); }
-      c->groups.push_back(q);
-    }
-    c->stream = c->groups[0].st_frm;
-    c->stream_img = c->groups[0].st_img;
+    // one frame queue and one image queue for all streams (stream groups on queues of their own, a second image queue
+    // and queue priorities were measured and removed)
+    bool ok = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, 0) == hipSuccess &&
+              hipStreamCreateWithPriority(&c->stream_img, hipStreamNonBlocking, 0) == hipSuccess;
+    // VSLAM_IMG_STREAMS=0: everything on one HIP stream (no overlap) — measurement aid for stand-alone kernel times
+    if (ok && getenv("VSLAM_IMG_STREAMS") && atoi(getenv("VSLAM_IMG_STREAMS")) == 0) { (void)hipStreamDestroy(c->stream_img); c->stream_img = c->stream; }
+    for (int k = 0; k < 2 && ok; ++k)
+      ok = hipEventCreateWithFlags(&c->ev_img[k], hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&c->ev_frm[k], hipEventDisableTiming) == hipSuccess;
     c->own_stream = true;
+    if (!ok) { destroy_streams(c); delete c; return fail(nullptr, VSLAM_ERR_HIP, "hipStreamCreate failed"); }
     c->split = n_streams <= VS_SPLIT4_MAX_STREAMS ? 4 : 0;
-    if (const char* e = getenv("VSLAM_SPLIT")) c->split = std::max(0, std::min(4, atoi(e)));
-    if (c->split == 4 && c->groups.size() != 1) c->split = 2;     // one stream group only
+    // test hook: VSLAM_SPLIT=0 / 4 forces that launch sequence, any other value leaves the choice to the library
+    if (const char* e = getenv("VSLAM_SPLIT")) { const int v = atoi(e); if (v == 0 || v == 4) c->split = v; }
   }
   const DevCfg& d = c->cfg;
   DevBuf& b = c->buf;
@@ -529,7 +498,7 @@ static int create_internal(const vslam_config* cfg, int device, int n_streams, v
   if (e != hipSuccess) {
     std::string msg = std::string("vslam_create: hipMalloc failed: ") + hipGetErrorString(e);
     for (void* p : c->allocs) (void)hipFree(p);
-    destroy_streams(c);     // every group's streams and events, not only the first group's
+    destroy_streams(c);
     delete c;
     return fail(nullptr, VSLAM_ERR_HIP, msg);
   }
@@ -538,10 +507,9 @@ static int create_internal(const vslam_config* cfg, int device, int n_streams, v
   for (int i = 0; i < 6; ++i) (void)hipEventCreate(&c->ev[i]);
   {
     // the frame kernel's view of the configuration and of the buffer table (image pointers excluded: it never reads them)
-    const size_t G = c->groups.size();
     calibrate_queues(c);
     e = dalloc(c, &c->d_cfg, 1);
-    if (e == hipSuccess) e = dalloc(c, &c->d_bufs, 2 * G);
+    if (e == hipSuccess) e = dalloc(c, &c->d_bufs, 2);
     if (e == hipSuccess) e = hipMemcpy(c->d_cfg, &c->cfg, sizeof(DevCfg), hipMemcpyHostToDevice);
     if (e == hipSuccess && upload_buffer_tables(c) != VSLAM_OK) e = hipErrorUnknown;
     if (e != hipSuccess) {
@@ -594,10 +562,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (int i = 0; i < 6; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   harvest_events(c);
   for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
-  for (auto& g : c->groups) {
-    for (int q = 0; q < 2; ++q) { (void)hipEventDestroy(g.ev_img[q]); (void)hipEventDestroy(g.ev_frm[q]); (void)hipEventDestroy(g.ev_emit[q]); }
-    if (c->own_stream) { if (g.st_img != g.st_frm) (void)hipStreamDestroy(g.st_img); if (g.st_img2 != g.st_img) (void)hipStreamDestroy(g.st_img2); (void)hipStreamDestroy(g.st_frm); }
-  }
+  destroy_streams(c);
   delete c;
 }
 VS_API int vslam_reset(vslam_ctx* c) {
@@ -625,34 +590,25 @@ VS_API int vslam_reset_streams(vslam_ctx* c, int32_t n, const int32_t* streams) 
   if (n == 0) return VSLAM_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   if (c->B == 1) { c->pend.flags = 0; c->report_have = 0; }     // the one stream starts over: pending setters belong to the old sequence
-  // no host synchronisation: each half of the state is reset in order on the HIP stream(s) that own it, one launch per
-  // half for up to 63 streams of a group
-  for (auto& g : c->groups) {
-    ResetList l;
+  // no host synchronisation: each half of the state is reset in order on the HIP stream that owns it, one launch per
+  // half for up to 63 streams
+  ResetList l;
+  l.n = 0;
+  auto flush = [&]() -> int {
+    if (!l.n) return VSLAM_OK;
+    hipLaunchKernelGGL(k_reset_stream_img, dim3(1), dim3(64), 0, c->stream_img, c->cfg, c->buf, l);
+    hipLaunchKernelGGL(k_reset_stream_trk, dim3(1), dim3(64), 0, c->stream, c->cfg, c->buf, l);
+    if (c->map.cap)     // the stream's map starts over with its sequence (frame 0 never reads the previous frame's ids)
+      for (int i = 0; i < l.n; ++i) HIP_TRY(c, hipMemsetAsync(c->map.d.count + l.ids[i], 0, sizeof(int32_t), c->stream));
     l.n = 0;
-    auto flush = [&]() -> int {
-      if (!l.n) return VSLAM_OK;
-      hipLaunchKernelGGL(k_reset_stream_img, dim3(1), dim3(64), 0, g.st_img, c->cfg, c->buf, l);
-      if (g.st_img2 != g.st_img) {   // two image streams alternate: the second one must see the reset as well
-        hipEvent_t e = ev_get(c);
-        HIP_TRY(c, hipEventRecord(e, g.st_img));
-        HIP_TRY(c, hipStreamWaitEvent(g.st_img2, e, 0));
-        c->evpool.push_back(e);
-      }
-      hipLaunchKernelGGL(k_reset_stream_trk, dim3(1), dim3(64), 0, g.st_frm, c->cfg, c->buf, l);
-      if (c->map.cap)     // the stream's map starts over with its sequence (frame 0 never reads the previous frame's ids)
-        for (int i = 0; i < l.n; ++i) HIP_TRY(c, hipMemsetAsync(c->map.d.count + l.ids[i], 0, sizeof(int32_t), g.st_frm));
-      l.n = 0;
-      return VSLAM_OK;
-    };
-    for (int i = 0; i < n; ++i) {
-      if (streams[i] < g.s0 || streams[i] >= g.s0 + g.n) continue;
-      l.ids[l.n++] = streams[i];
-      if (l.n == 63) { int rc = flush(); if (rc) return rc; }
-    }
-    int rc = flush();
-    if (rc) return rc;
+    return VSLAM_OK;
+  };
+  for (int i = 0; i < n; ++i) {
+    l.ids[l.n++] = streams[i];
+    if (l.n == 63) { int rc = flush(); if (rc) return rc; }
   }
+  int rc = flush();
+  if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
   return VSLAM_OK;
 }
@@ -660,35 +616,26 @@ VS_API int vslam_reset_stream(vslam_ctx* c, int s) { const int32_t id = s; retur
 VS_API int vslam_copy_current_poses_device(vslam_ctx* c, double* dst) {
   if (!c || !dst) return VSLAM_ERR_INVALID;
   { int rc = flush_pending(c); if (rc) return rc; }
-  for (auto& g : c->groups)
-    hipLaunchKernelGGL(k_gather_poses, dim3((g.n * 12 + 255) / 256), dim3(256), 0, g.st_frm, buf_set(c, c->last_set, g.s0), g.n, dst + (size_t)g.s0 * 12);
+  hipLaunchKernelGGL(k_gather_poses, dim3((c->B * 12 + 255) / 256), dim3(256), 0, c->stream, buf_set(c, c->last_set), c->B, dst);
   HIP_TRY(c, hipGetLastError());
   return VSLAM_OK;
 }
 VS_API int vslam_set_hip_stream(vslam_ctx* c, void* s) {
   if (!c) return VSLAM_ERR_INVALID;
   sync_all(c);
-  for (auto& g : c->groups) {
-    for (int q = 0; q < 2; ++q) { (void)hipEventDestroy(g.ev_img[q]); (void)hipEventDestroy(g.ev_frm[q]); (void)hipEventDestroy(g.ev_emit[q]); }
-    if (c->own_stream) { if (g.st_img != g.st_frm) (void)hipStreamDestroy(g.st_img); if (g.st_img2 != g.st_img) (void)hipStreamDestroy(g.st_img2); (void)hipStreamDestroy(g.st_frm); }
-  }
-  c->groups.clear();
-  // one caller stream: a single group, image pipeline and tracker run back to back on it
-  vslam_ctx::Group q;
-  q.s0 = 0; q.n = c->B; q.st_frm = (hipStream_t)s; q.st_img = (hipStream_t)s; q.st_img2 = (hipStream_t)s;
-  for (int k = 0; k < 2; ++k) { (void)hipEventCreateWithFlags(&q.ev_img[k], hipEventDisableTiming); (void)hipEventCreateWithFlags(&q.ev_frm[k], hipEventDisableTiming); (void)hipEventCreateWithFlags(&q.ev_emit[k], hipEventDisableTiming); }
-  q.frm_pending[0] = q.frm_pending[1] = false;
-  q.emit_pending[0] = q.emit_pending[1] = false;
-  c->groups.push_back(q);
-  c->stream = q.st_frm; c->stream_img = q.st_img;
+  destroy_streams(c);
+  // one caller stream: image pipeline and tracker run back to back on it
+  c->stream = c->stream_img = (hipStream_t)s;
+  for (int k = 0; k < 2; ++k) { (void)hipEventCreateWithFlags(&c->ev_img[k], hipEventDisableTiming); (void)hipEventCreateWithFlags(&c->ev_frm[k], hipEventDisableTiming); }
+  c->frm_pending[0] = c->frm_pending[1] = false;
   c->own_stream = false;
   calibrate_queues(c);      // the caller's queue has its own first XCD
-  // the frame kernel's buffer table for the single group
   return upload_buffer_tables(c);
 }
 VS_API int vslam_synchronize(vslam_ctx* c) {
   if (!c) return VSLAM_ERR_INVALID;
-  for (auto& g : c->groups) { HIP_TRY(c, hipStreamSynchronize(g.st_img)); HIP_TRY(c, hipStreamSynchronize(g.st_img2)); HIP_TRY(c, hipStreamSynchronize(g.st_frm)); }
+  HIP_TRY(c, hipStreamSynchronize(c->stream_img));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return c->sticky;
 }
 
@@ -697,71 +644,66 @@ VS_API int vslam_synchronize(vslam_ctx* c) {
 static int launch_image_pipeline(vslam_ctx* c) {
   const DevCfg& d = c->cfg;
   const int set = c->parity;
-  for (auto& g : c->groups) {
-    hipStream_t st = c->img_override ? c->img_override : (set ? g.st_img2 : g.st_img);
-    const DevBuf bs = buf_set(c, set, g.s0, c->img_override ? g.q0_frm : (set ? g.q0_img2 : g.q0_img));
-    if (!c->img_override && c->img_on_frm_queue) {
-      // the last frame's image pipeline ran on the frame queue (stage path) and left no event behind: a caller that switches to
-      // the fused path mid-sequence pays one synchronisation here, once
-      HIP_TRY(c, hipStreamSynchronize(g.st_frm));
-      c->img_on_frm_queue = false;
-    }
-    if (c->img_override) c->img_on_frm_queue = true;
-    const bool coarse = c->img_override != nullptr;     // stage path: detection = [k_fast_box .. k_emit], extraction = k_brief: three events
-    // the image products of this set were last read by the frame kernel two steps ago; the detector thresholds come
-    // from the controller in k_emit of the previous step (other image stream)
-    if (g.frm_pending[set] && st != g.st_frm) HIP_TRY(c, hipStreamWaitEvent(st, g.ev_frm[set], 0));
-    if (c->rect.on) {
-      // raw pair -> rectified pair in upload[set] (the slab the wait above has freed), ahead of the detector
-      const vslam_ctx::Rect& q = c->rect;
-      RectArgs ra;
-      for (int k = 0; k < 2; ++k) { ra.src[k] = q.src[k]; ra.map_xy[k] = q.map_xy[k]; ra.map_a[k] = q.map_a[k]; ra.dst[k] = c->upload[set][k]; }
-      ra.src_stream_stride = q.src_stream_stride; ra.src_row_stride = q.src_row_stride; ra.src_rows = q.raw_rows; ra.src_cols = q.raw_cols;
-      ra.map_stride = q.map_stride; ra.dst_stream_stride = c->up_stream_stride; ra.dst_row_stride = c->up_stride;
-      ra.rows = d.c.rows; ra.cols = d.c.cols; ra.s0 = g.s0; ra.n = g.n; ra.sides = 2;
-      std::memcpy(ra.active, c->buf.active, sizeof ra.active);
-      hipLaunchKernelGGL(k_rectify, dim3((d.c.cols + 255) / 256, (d.c.rows + 3) / 4, 2 * ((g.n + VS_RECT_SB - 1) / VS_RECT_SB)), dim3(256), 0, st, ra);
-    }
-    if (g.emit_pending[set ^ 1] && (g.st_img != g.st_img2 || c->img_override)) HIP_TRY(c, hipStreamWaitEvent(st, g.ev_emit[set ^ 1], 0));
-    dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * g.n);
-    const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (coarse && c->timers) { e0 = ev_get(c); (void)hipEventRecord(e0, st); }
-    { KernelTimer t(c, 0, st, true, !coarse); hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, st, c->cfg, bs); }
-    { KernelTimer t(c, 1, st, true, !coarse); hipLaunchKernelGGL(k_emit, dim3(g.n, 2), dim3(512), 0, st, c->cfg, bs, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 1); }
-    if (e0) { e1 = ev_get(c); (void)hipEventRecord(e1, st); c->evrec.push_back({e0, e1, 0, true}); c->kern_n[1] += 1; }
-    if (c->img_override && c->report && c->B == 1) {
-      // stage path with a view reader: coordinates and scores leave for the host as soon as k_emit has written them, so that the caller
-      // builds its cv::KeyPoint lists while k_brief / k_stereo_dist / k_begin still run (vslam_view_keypoints_xy)
-      c->report_xy_seq = ++c->report_seq;
-      hipLaunchKernelGGL(k_report, dim3(8), dim3(256), 0, st, c->cfg, bs, 0, (int)VS_REPORT_KEYPOINTS_XY, 0, c->report_xy_seq, c->rl, c->report_dev, c->report_done);
-    }
-    if (g.st_img != g.st_img2 && !c->img_override) { HIP_TRY(c, hipEventRecord(g.ev_emit[set], st)); g.emit_pending[set] = true; }
-    else g.emit_pending[set] = false;
-    if (orb) {   // cv::ORB::create() as extractor: Gaussian image (in the box image's memory), steered tests per keypoint
-      KernelTimer t(c, 2, st, true, !coarse);
-      Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = d.gauss7[i];
-      hipLaunchKernelGGL(k_gauss7, g1, dim3(256), 0, st, c->cfg, bs, gk);
-      hipLaunchKernelGGL(k_orb_describe, dim3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, 2 * g.n), dim3(256), 0, st, c->cfg, bs, d.orb_cos, d.orb_sin);
-    } else {
-      dim3 g3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, 2 * g.n);
-      KernelTimer t(c, 2, st, true, !coarse); hipLaunchKernelGGL(k_brief, g3, dim3(256), 0, st, c->cfg, bs);
-    }
-    if (e1) { hipEvent_t e2 = ev_get(c); (void)hipEventRecord(e2, st); hipEvent_t e1b = e1; c->evshared.push_back({e1b, e2, 2}); }
-    // left-right descriptor distances of the first epipolar pass: a product of the images alone, so it is computed
-    // here, wide, instead of inside the per-stream frame workgroup
-    { KernelTimer t(c, 7, st, true, !coarse); hipLaunchKernelGGL(k_stereo_dist, dim3((d.NMAX + 255) / 256, g.n), dim3(256), 0, st, c->cfg, bs); }
-    HIP_TRY(c, hipGetLastError());
-    if (st != g.st_frm) { HIP_TRY(c, hipEventRecord(g.ev_img[set], st)); HIP_TRY(c, hipStreamWaitEvent(g.st_frm, g.ev_img[set], 0)); }
+  const int n = c->B;
+  hipStream_t st = c->img_override ? c->img_override : c->stream_img;
+  const DevBuf bs = buf_set(c, set, c->img_override ? c->q0_frm : c->q0_img);
+  if (!c->img_override && c->img_on_frm_queue) {
+    // the last frame's image pipeline ran on the frame queue (stage path) and left no event behind: a caller that switches to
+    // the fused path mid-sequence pays one synchronisation here, once
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->img_on_frm_queue = false;
   }
+  if (c->img_override) c->img_on_frm_queue = true;
+  const bool coarse = c->img_override != nullptr;     // stage path: detection = [k_fast_box .. k_emit], extraction = k_brief: three events
+  // the image products of this set were last read by the frame kernel two steps ago; the detector thresholds come
+  // from the controller in k_emit of the previous step (same queue)
+  if (c->frm_pending[set] && st != c->stream) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_frm[set], 0));
+  if (c->rect.on) {
+    // raw pair -> rectified pair in upload[set] (the slab the wait above has freed), ahead of the detector
+    const vslam_ctx::Rect& q = c->rect;
+    RectArgs ra;
+    for (int k = 0; k < 2; ++k) { ra.src[k] = q.src[k]; ra.map_xy[k] = q.map_xy[k]; ra.map_a[k] = q.map_a[k]; ra.dst[k] = c->upload[set][k]; }
+    ra.src_stream_stride = q.src_stream_stride; ra.src_row_stride = q.src_row_stride; ra.src_rows = q.raw_rows; ra.src_cols = q.raw_cols;
+    ra.map_stride = q.map_stride; ra.dst_stream_stride = c->up_stream_stride; ra.dst_row_stride = c->up_stride;
+    ra.rows = d.c.rows; ra.cols = d.c.cols; ra.s0 = 0; ra.n = n; ra.sides = 2;
+    std::memcpy(ra.active, c->buf.active, sizeof ra.active);
+    hipLaunchKernelGGL(k_rectify, dim3((d.c.cols + 255) / 256, (d.c.rows + 3) / 4, 2 * ((n + VS_RECT_SB - 1) / VS_RECT_SB)), dim3(256), 0, st, ra);
+  }
+  dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * n);
+  const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (coarse && c->timers) { e0 = ev_get(c); (void)hipEventRecord(e0, st); }
+  { KernelTimer t(c, 0, st, true, !coarse); hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, st, c->cfg, bs); }
+  { KernelTimer t(c, 1, st, true, !coarse); hipLaunchKernelGGL(k_emit, dim3(n, 2), dim3(512), 0, st, c->cfg, bs, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 1); }
+  if (e0) { e1 = ev_get(c); (void)hipEventRecord(e1, st); c->evrec.push_back({e0, e1, 0, true}); c->kern_n[1] += 1; }
+  if (c->img_override && c->report && c->B == 1) {
+    // stage path with a view reader: coordinates and scores leave for the host as soon as k_emit has written them, so that the caller
+    // builds its cv::KeyPoint lists while k_brief / k_stereo_dist / k_begin still run (vslam_view_keypoints_xy)
+    c->report_xy_seq = ++c->report_seq;
+    hipLaunchKernelGGL(k_report, dim3(8), dim3(256), 0, st, c->cfg, bs, 0, (int)VS_REPORT_KEYPOINTS_XY, 0, c->report_xy_seq, c->rl, c->report_dev, c->report_done);
+  }
+  if (orb) {   // cv::ORB::create() as extractor: Gaussian image (in the box image's memory), steered tests per keypoint
+    KernelTimer t(c, 2, st, true, !coarse);
+    Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = d.gauss7[i];
+    hipLaunchKernelGGL(k_gauss7, g1, dim3(256), 0, st, c->cfg, bs, gk);
+    hipLaunchKernelGGL(k_orb_describe, dim3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, 2 * n), dim3(256), 0, st, c->cfg, bs, d.orb_cos, d.orb_sin);
+  } else {
+    dim3 g3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, 2 * n);
+    KernelTimer t(c, 2, st, true, !coarse); hipLaunchKernelGGL(k_brief, g3, dim3(256), 0, st, c->cfg, bs);
+  }
+  if (e1) { hipEvent_t e2 = ev_get(c); (void)hipEventRecord(e2, st); hipEvent_t e1b = e1; c->evshared.push_back({e1b, e2, 2}); }
+  // left-right descriptor distances of the first epipolar pass: a product of the images alone, so it is computed
+  // here, wide, instead of inside the per-stream frame workgroup
+  { KernelTimer t(c, 7, st, true, !coarse); hipLaunchKernelGGL(k_stereo_dist, dim3((d.NMAX + 255) / 256, n), dim3(256), 0, st, c->cfg, bs); }
+  HIP_TRY(c, hipGetLastError());
+  if (st != c->stream) { HIP_TRY(c, hipEventRecord(c->ev_img[set], st)); HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_img[set], 0)); }
   c->last_set = set;
   if (c->rect.on) c->rect.have_frame = true;
   return VSLAM_OK;
 }
 static int frame_done(vslam_ctx* c) {
   const int set = c->last_set;
-  for (auto& g : c->groups)
-    if (g.st_img != g.st_frm) { HIP_TRY(c, hipEventRecord(g.ev_frm[set], g.st_frm)); g.frm_pending[set] = true; }
+  if (c->stream_img != c->stream) { HIP_TRY(c, hipEventRecord(c->ev_frm[set], c->stream)); c->frm_pending[set] = true; }
   c->parity = set ^ 1;
   return VSLAM_OK;
 }
@@ -769,51 +711,31 @@ static int frame_done(vslam_ctx* c) {
 // Localizing stream searches 101 x 101 windows by appearance, a Tracking stream ~31 x 31), so the points are spread over
 // many small blocks — about one previous point per 16-lane group at ~700 points — and the hardware scheduler balances
 // them: 0.154 -> 0.086 ms back to back at 160 streams of mixed phase against 12 blocks per stream (profiles/r02_*).
-static int cand_blocks(const vslam_ctx* c, int n_streams) {
-  if (const char* e = getenv("VSLAM_CAND_GX")) return std::max(1, atoi(e));
-  (void)c;
-  return std::max(4, std::min(128, 7040 / std::max(n_streams, 1)));
-}
+static int cand_blocks(int n_streams) { return std::max(4, std::min(128, 7040 / std::max(n_streams, 1))); }
+// blocks per stream of k_recover_brief (four wavefronts each, one lost point per wavefront)
+static int recover_blocks(int n_streams) { return std::max(4, std::min(64, 1024 / std::max(n_streams, 1))); }
 static int launch_frame(vslam_ctx* c) {
-  size_t gi = 0;
-  for (auto& g : c->groups) {
-    const DevBuf bs = buf_set(c, c->last_set, g.s0, g.q0_frm);
-    ConstDevCfg* kc = (ConstDevCfg*)c->d_cfg;
-    ConstDevBuf* kb = (ConstDevBuf*)(c->d_bufs + c->last_set * c->groups.size() + gi++);
-    const int gx = cand_blocks(c, g.n);
-    { KernelTimer t(c, 3, g.st_frm); hipLaunchKernelGGL(k_track_candidates, dim3(gx, g.n), dim3(256), 0, g.st_frm, c->cfg, bs, -1); }
-    if (!c->split || (c->split == 2 && !c->cfg.c.enable_landmark_recovery)) {
-      KernelTimer t(c, 4, g.st_frm);
-      hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, -1);
-    } else if (c->split == 3) {
-      // registration + prune on CUs of its own (the aligner needs the whole register file), then the tail co-scheduled with the
-      // image pipeline of the next frame (k_tail)
-      { KernelTimer t(c, 4, g.st_frm); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 0); }
-      if (c->cfg.c.enable_landmark_recovery) { KernelTimer t(c, 5, g.st_frm); hipLaunchKernelGGL(k_recover_brief, dim3(std::max(4, std::min(64, 1024 / std::max(g.n, 1))), g.n), dim3(256), 0, g.st_frm, c->cfg, bs); }
-      { KernelTimer t(c, 6, g.st_frm); hipLaunchKernelGGL(k_tail, dim3(g.n), dim3(VS_TAIL_WG), 0, g.st_frm, kc, kb); }
-    } else if (c->split == 4) {
-      // few streams on an otherwise idle chip: the landmark refinement (a serial chain per track) leaves the frame's critical path — it runs in
-      // workgroups of its own beside the stereo sweep, inside the frame's last launch
-      { KernelTimer t(c, 4, g.st_frm, false); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 0); }
-      if (c->cfg.c.enable_landmark_recovery) { KernelTimer t(c, 5, g.st_frm); hipLaunchKernelGGL(k_recover_brief, dim3(std::max(4, std::min(64, 1024 / std::max(g.n, 1))), g.n), dim3(256), 0, g.st_frm, c->cfg, bs); }
-      { KernelTimer t(c, 4, g.st_frm, false); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 4); }
-      // phase 2 and the landmark refinement in ONE launch: n frame workgroups + G refinement workgroups per stream (k_tail_lm)
-      { KernelTimer t(c, 4, g.st_frm); const int G = std::max(1, std::min(16, 64 / std::max(g.n, 1)));
-        hipLaunchKernelGGL(k_tail_lm, dim3(g.n * (1 + G)), dim3(VS_WG), 0, g.st_frm, kc, kb, g.n, G); }
-    } else if (c->split == 2) {
-      { KernelTimer t(c, 4, g.st_frm, false); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 0); }
-      { KernelTimer t(c, 5, g.st_frm); hipLaunchKernelGGL(k_recover_brief, dim3(std::max(4, std::min(64, 1024 / std::max(g.n, 1))), g.n), dim3(256), 0, g.st_frm, c->cfg, bs); }
-      { KernelTimer t(c, 4, g.st_frm); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 3); }
-    } else {
-      { KernelTimer t(c, 4, g.st_frm, false); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 0); }
-      if (c->cfg.c.enable_landmark_recovery) { KernelTimer t(c, 5, g.st_frm); hipLaunchKernelGGL(k_recover_brief, dim3(std::max(4, std::min(64, 1024 / std::max(g.n, 1))), g.n), dim3(256), 0, g.st_frm, c->cfg, bs); }
-      { KernelTimer t(c, 4, g.st_frm, false); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 1); }
-      { KernelTimer t(c, 6, g.st_frm); hipLaunchKernelGGL(k_update_landmarks, dim3((c->cfg.MAXP + 255) / 256, g.n), dim3(256), 0, g.st_frm, c->cfg, bs, 1); }
-      { KernelTimer t(c, 4, g.st_frm); hipLaunchKernelGGL(k_frame, dim3(g.n), dim3(VS_WG), 0, g.st_frm, kc, kb, 2); }
-    }
-    // the landmark map, behind the frame's last launch (sequence 4: behind the refinement workgroups of k_tail_lm as well)
-    if (c->map.cap) hipLaunchKernelGGL(k_map_commit, dim3(g.n), dim3(VS_MAP_WG), 0, g.st_frm, c->cfg, bs, c->map.d);
+  const int n = c->B;
+  hipStream_t st = c->stream;
+  const DevBuf bs = buf_set(c, c->last_set, c->q0_frm);
+  ConstDevCfg* kc = (ConstDevCfg*)c->d_cfg;
+  ConstDevBuf* kb = (ConstDevBuf*)(c->d_bufs + c->last_set);
+  { KernelTimer t(c, 3, st); hipLaunchKernelGGL(k_track_candidates, dim3(cand_blocks(n), n), dim3(256), 0, st, c->cfg, bs, -1); }
+  if (c->split == 0) {
+    KernelTimer t(c, 4, st);
+    hipLaunchKernelGGL(k_frame, dim3(n), dim3(VS_WG), 0, st, kc, kb, -1);
+  } else {
+    // few streams on an otherwise idle chip: the landmark refinement (a serial chain per track) leaves the frame's critical path — it runs in
+    // workgroups of its own beside the stereo sweep, inside the frame's last launch
+    { KernelTimer t(c, 4, st, false); hipLaunchKernelGGL(k_frame, dim3(n), dim3(VS_WG), 0, st, kc, kb, 0); }
+    if (c->cfg.c.enable_landmark_recovery) { KernelTimer t(c, 5, st); hipLaunchKernelGGL(k_recover_brief, dim3(recover_blocks(n), n), dim3(256), 0, st, c->cfg, bs); }
+    { KernelTimer t(c, 4, st, false); hipLaunchKernelGGL(k_frame, dim3(n), dim3(VS_WG), 0, st, kc, kb, 4); }
+    // phase 2 and the landmark refinement in ONE launch: n frame workgroups + G refinement workgroups per stream (k_tail_lm)
+    { KernelTimer t(c, 4, st); const int G = std::max(1, std::min(16, 64 / std::max(n, 1)));
+      hipLaunchKernelGGL(k_tail_lm, dim3(n * (1 + G)), dim3(VS_WG), 0, st, kc, kb, n, G); }
   }
+  // the landmark map, behind the frame's last launch (sequence 4: behind the refinement workgroups of k_tail_lm as well)
+  if (c->map.cap) hipLaunchKernelGGL(k_map_commit, dim3(n), dim3(VS_MAP_WG), 0, st, c->cfg, bs, c->map.d);
   HIP_TRY(c, hipGetLastError());
   return frame_done(c);
 }
@@ -838,8 +760,8 @@ static int upload_to(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t r
   const size_t span = (size_t)(c->B - 1) * image_stride + (size_t)(rows - 1) * row_stride + cols;   // last byte the caller owns
   const size_t dense = (size_t)c->B * rows * cols;
   const bool ordered = c->B == 1 || image_stride >= (size_t)rows * row_stride;
-  if (c->groups.size() == 1 && ordered && span <= (size_t)c->B * dst_stream_stride && span <= dense + dense / 8) {
-    hipStream_t st = c->img_override ? c->img_override : (c->parity ? c->groups[0].st_img2 : c->groups[0].st_img);
+  if (ordered && span <= (size_t)c->B * dst_stream_stride && span <= dense + dense / 8) {
+    hipStream_t st = c->img_override ? c->img_override : c->stream_img;
     // A small pageable source (the literal drop-in: one cv::Mat pair per call) goes through pinned memory of the context: the
     // runtime's own staging of a pageable hipMemcpyAsync costs ~0.12 ms of host time per 467 KB image here, a memcpy into a pinned
     // buffer + a true asynchronous copy ~0.03 ms; the left image's DMA runs while the right one is being staged.
@@ -882,22 +804,18 @@ static int upload_to(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t r
     // one contiguous copy per image, rows keep the caller's stride (a pitched host-to-device copy is issued row by row
     // by the runtime: measured 0.13 GB/s against 43 GB/s for the plain copy)
     for (int s = 0; s < c->B; ++s) {
-      const vslam_ctx::Group& gg = c->groups[group_of(c, s)];
-      hipStream_t st = c->parity ? gg.st_img2 : gg.st_img;
       const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
-      HIP_TRY(c, hipMemcpyAsync(dst[0] + s * dst_stream_stride, L + s * image_stride, bytes, hipMemcpyHostToDevice, st));
-      HIP_TRY(c, hipMemcpyAsync(dst[1] + s * dst_stream_stride, R + s * image_stride, bytes, hipMemcpyHostToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(dst[0] + s * dst_stream_stride, L + s * image_stride, bytes, hipMemcpyHostToDevice, c->stream_img));
+      HIP_TRY(c, hipMemcpyAsync(dst[1] + s * dst_stream_stride, R + s * image_stride, bytes, hipMemcpyHostToDevice, c->stream_img));
     }
     *out = {{dst[0], dst[1]}, row_stride, dst_stream_stride};
     return VSLAM_OK;
   }
   for (int s = 0; s < c->B; ++s) {
-    const vslam_ctx::Group& gg = c->groups[group_of(c, s)];
-    hipStream_t st = c->parity ? gg.st_img2 : gg.st_img;
     HIP_TRY(c, hipMemcpy2DAsync(dst[0] + s * dst_stream_stride, dst_stride, L + s * image_stride, row_stride,
-                                cols, rows, hipMemcpyHostToDevice, st));
+                                cols, rows, hipMemcpyHostToDevice, c->stream_img));
     HIP_TRY(c, hipMemcpy2DAsync(dst[1] + s * dst_stream_stride, dst_stride, R + s * image_stride, row_stride,
-                                cols, rows, hipMemcpyHostToDevice, st));
+                                cols, rows, hipMemcpyHostToDevice, c->stream_img));
   }
   *out = {{dst[0], dst[1]}, dst_stride, dst_stream_stride};
   return VSLAM_OK;
@@ -2345,7 +2263,7 @@ static int flush_pending(vslam_ctx* c) {
   if (!c->pend.flags) return VSLAM_OK;
   const int fl = c->pend.flags;
   c->pend.flags = 0;
-  hipStream_t q = c->groups[0].st_frm;
+  hipStream_t q = c->stream;
   if (fl & 1) { D12 p; std::memcpy(p.v, c->pend.prior, sizeof p.v); hipLaunchKernelGGL(k_set_tracker_state, dim3(1), dim3(1), 0, q, c->buf, 0, c->pend.status, c->pend.win, c->pend.tau, p); }
   if (fl & 2) { D12 p; std::memcpy(p.v, c->pend.pose, sizeof p.v); hipLaunchKernelGGL(k_set_pose, dim3(1), dim3(1), 0, q, c->buf, 0, p); }
   HIP_TRY(c, hipGetLastError());
@@ -2353,13 +2271,13 @@ static int flush_pending(vslam_ctx* c) {
 }
 static int launch_begin(vslam_ctx* c) {
   const StageIo io = stage_io(c, 0, 0);
-  for (auto& g : c->groups) hipLaunchKernelGGL(k_begin, dim3(g.n), dim3(256), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0, g.q0_frm), io);
+  hipLaunchKernelGGL(k_begin, dim3(c->B), dim3(256), 0, c->stream, c->cfg, buf_set(c, c->last_set, c->q0_frm), io);
   HIP_TRY(c, hipGetLastError());
   return VSLAM_OK;
 }
 static int launch_stage(vslam_ctx* c, int stage, int arg, int report = 0, int in_progress = 0) {
   const StageIo io = stage_io(c, report, in_progress);
-  for (auto& g : c->groups) hipLaunchKernelGGL(k_stage, dim3(g.n), dim3(VS_WG), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0, g.q0_frm), stage, arg, io);
+  hipLaunchKernelGGL(k_stage, dim3(c->B), dim3(VS_WG), 0, c->stream, c->cfg, buf_set(c, c->last_set, c->q0_frm), stage, arg, io);
   HIP_TRY(c, hipGetLastError());
   return VSLAM_OK;
 }
@@ -2367,7 +2285,7 @@ VS_API int vslam_frame_begin(vslam_ctx* c, const uint8_t* L, const uint8_t* R, i
   if (!c) return VSLAM_ERR_INVALID;
   if (c->sticky != VSLAM_OK) return c->sticky;
   HIP_TRY(c, hipSetDevice(c->device));
-  c->img_override = (c->B == 1 && c->groups.size() == 1) ? c->groups[0].st_frm : nullptr;
+  c->img_override = c->B == 1 ? c->stream : nullptr;
   c->report_xy_seq = -1;
   c->lm_published = false;
   int rc = set_inputs(c, L, R, row_stride, image_stride, on_device != 0);
@@ -2379,9 +2297,8 @@ VS_API int vslam_frame_begin(vslam_ctx* c, const uint8_t* L, const uint8_t* R, i
   if (rc == VSLAM_OK && c->report) {
     // a caller that reads stage views wants the keypoints next (initialize() fills Frame::keypoints / descriptors): packed right
     // behind k_begin, no host round trip in between
-    const vslam_ctx::Group& g = c->groups[0];
     const int seq = ++c->report_seq;
-    hipLaunchKernelGGL(k_report, dim3(32), dim3(256), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0), 0, (int)VS_REPORT_KEYPOINTS, 0, seq, c->rl, c->report_dev, c->report_done);
+    hipLaunchKernelGGL(k_report, dim3(32), dim3(256), 0, c->stream, c->cfg, buf_set(c, c->last_set), 0, (int)VS_REPORT_KEYPOINTS, 0, seq, c->rl, c->report_dev, c->report_done);
     HIP_TRY(c, hipGetLastError());
     c->report_have = VS_REPORT_KEYPOINTS; c->report_have_ip = 0; c->report_have_stream = 0; c->report_have_seq = seq;
   }
@@ -2404,10 +2321,7 @@ VS_API int vslam_frame_restore(vslam_ctx* c) {
 VS_API int vslam_track(vslam_ctx* c, int by_appearance) {
   NEED_FRAME("vslam_track");
   { int rc = flush_pending(c); if (rc) return rc; }     // the candidate kernel reads prior / window / distance before the stage kernel runs
-  for (auto& g : c->groups) {
-    const int gx = cand_blocks(c, g.n);
-    hipLaunchKernelGGL(k_track_candidates, dim3(gx, g.n), dim3(256), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0, g.q0_frm), by_appearance ? 1 : 0);
-  }
+  hipLaunchKernelGGL(k_track_candidates, dim3(cand_blocks(c->B), c->B), dim3(256), 0, c->stream, c->cfg, buf_set(c, c->last_set, c->q0_frm), by_appearance ? 1 : 0);
   return launch_stage(c, VS_STAGE_TRACK, by_appearance ? 1 : 0, VS_REPORT_TRACK);
 }
 VS_API int vslam_align(vslam_ctx* c, int inverse_depth) { NEED_FRAME("vslam_align"); return launch_stage(c, VS_STAGE_ALIGN, inverse_depth, VS_REPORT_ALIGNER); }
@@ -2418,8 +2332,7 @@ VS_API int vslam_prune_recover(vslam_ctx* c) {
   // descriptors go through every CU's memory pipe instead of one (59 -> ~25 us for one stream)
   int rc = launch_stage(c, VS_STAGE_PRUNE_PROJECT, 1);
   if (rc != VSLAM_OK) return rc;
-  for (auto& g : c->groups)
-    hipLaunchKernelGGL(k_recover_brief, dim3(std::max(4, std::min(64, 1024 / std::max(g.n, 1))), g.n), dim3(256), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0, g.q0_frm));
+  hipLaunchKernelGGL(k_recover_brief, dim3(recover_blocks(c->B), c->B), dim3(256), 0, c->stream, c->cfg, buf_set(c, c->last_set, c->q0_frm));
   HIP_TRY(c, hipGetLastError());
   // one stream: the stage also publishes the frame's history, so that vslam_compute can run the landmark refinement beside the stereo stage
   // instead of in front of it
@@ -2443,13 +2356,12 @@ VS_API int vslam_compute(vslam_ctx* c) {     // vslam_update_points + vslam_ster
     // spread over several workgroups) runs BESIDE the stereo stage in the same launch (k_stage_lm); the stage only counts the active landmarks.
     // The report — it carries the landmark update counts — is packed by the next launch on the queue.
     c->lm_published = false;
-    vslam_ctx::Group& g = c->groups[0];
     const StageIo io = stage_io(c, 0, 0);
-    { hipLaunchKernelGGL(k_stage_lm, dim3(g.n * (1 + 16)), dim3(VS_WG), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0, g.q0_frm), (int)VS_STAGE_STEREO_COUNT, 0, io, g.n, 16); }
+    hipLaunchKernelGGL(k_stage_lm, dim3(c->B * (1 + 16)), dim3(VS_WG), 0, c->stream, c->cfg, buf_set(c, c->last_set, c->q0_frm), (int)VS_STAGE_STEREO_COUNT, 0, io, c->B, 16);
     HIP_TRY(c, hipGetLastError());
     if (c->report) {
       const int seq = ++c->report_seq;
-      hipLaunchKernelGGL(k_report, dim3(16), dim3(256), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0), 0, (int)VS_REPORT_POINTS, 0, seq, c->rl, c->report_dev, c->report_done);
+      hipLaunchKernelGGL(k_report, dim3(16), dim3(256), 0, c->stream, c->cfg, buf_set(c, c->last_set), 0, (int)VS_REPORT_POINTS, 0, seq, c->rl, c->report_dev, c->report_done);
       HIP_TRY(c, hipGetLastError());
       c->report_have = VS_REPORT_POINTS; c->report_have_ip = 0; c->report_have_stream = 0; c->report_have_seq = seq;
     }
@@ -2474,7 +2386,7 @@ VS_API int vslam_set_tracker_state(vslam_ctx* c, int s, int status, const double
   }
   D12 p;
   std::memcpy(p.v, prior, sizeof p.v);
-  hipLaunchKernelGGL(k_set_tracker_state, dim3(1), dim3(1), 0, c->groups[group_of(c, s)].st_frm, c->buf, s, status, win, tau, p);
+  hipLaunchKernelGGL(k_set_tracker_state, dim3(1), dim3(1), 0, c->stream, c->buf, s, status, win, tau, p);
   HIP_TRY(c, hipGetLastError());
   return VSLAM_OK;
 }
@@ -2485,7 +2397,7 @@ VS_API int vslam_set_pose(vslam_ctx* c, int s, const double pose[12]) {
   if (c->B == 1) { c->pend.flags |= 2; std::memcpy(c->pend.pose, pose, sizeof c->pend.pose); return VSLAM_OK; }
   D12 p;
   std::memcpy(p.v, pose, sizeof p.v);
-  hipLaunchKernelGGL(k_set_pose, dim3(1), dim3(1), 0, c->groups[group_of(c, s)].st_frm, c->buf, s, p);
+  hipLaunchKernelGGL(k_set_pose, dim3(1), dim3(1), 0, c->stream, c->buf, s, p);
   HIP_TRY(c, hipGetLastError());
   return VSLAM_OK;
 }
@@ -2534,7 +2446,6 @@ static int report_run(vslam_ctx* c, int s, int what, int in_progress, const Repo
   if (c->sticky != VSLAM_OK) return c->sticky;
   rc = report_ready(c);
   if (rc) return rc;
-  const vslam_ctx::Group& g = c->groups[group_of(c, s)];
   int seq = c->report_have_seq;
   const bool folded = c->report_have == what && c->report_have_ip == in_progress && c->report_have_stream == s && !c->pend.flags;
   if (!folded) {      // the stage was launched before the report buffer existed, or something else ran since: pack it now
@@ -2542,7 +2453,7 @@ static int report_run(vslam_ctx* c, int s, int what, int in_progress, const Repo
     if (rc) return rc;
     seq = ++c->report_seq;
     const int blocks = what == VS_REPORT_KEYPOINTS ? 32 : (what == VS_REPORT_POINTS ? 16 : 4);
-    hipLaunchKernelGGL(k_report, dim3(blocks), dim3(256), 0, g.st_frm, c->cfg, buf_set(c, c->last_set, g.s0), s, what, in_progress, seq, c->rl, c->report_dev, c->report_done);
+    hipLaunchKernelGGL(k_report, dim3(blocks), dim3(256), 0, c->stream, c->cfg, buf_set(c, c->last_set), s, what, in_progress, seq, c->rl, c->report_dev, c->report_done);
     HIP_TRY(c, hipGetLastError());
     c->report_have = what; c->report_have_ip = in_progress; c->report_have_stream = s; c->report_have_seq = seq;
   }
@@ -2556,7 +2467,7 @@ static int report_run(vslam_ctx* c, int s, int what, int in_progress, const Repo
     if (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) == seq) { seen = true; break; }
     __builtin_ia32_pause();
   }
-  if (!seen) HIP_TRY(c, hipStreamSynchronize(g.st_frm));
+  if (!seen) HIP_TRY(c, hipStreamSynchronize(c->stream));
   *hdr = h;
   if (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) != seq || h->what != what) return fail(c, VSLAM_ERR_STATE, "stage report is stale (the stream is inactive?)");
   if ((*hdr)->info.error_flags) c->err = "device buffer capacity exceeded (error_flags != 0)";
@@ -2564,12 +2475,12 @@ static int report_run(vslam_ctx* c, int s, int what, int in_progress, const Repo
 }
 VS_API int vslam_view_keypoints(vslam_ctx* c, int s, vslam_keypoints_view* out);
 // polls a report flag (bounded), falling back to an ordinary synchronisation of the queue
-static int report_wait(vslam_ctx* c, const vslam_ctx::Group& g, const int32_t* flag, int seq) {
+static int report_wait(vslam_ctx* c, const int32_t* flag, int seq) {
   for (long spin = 0; spin < 4000000L; ++spin) {
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return VSLAM_OK;
     __builtin_ia32_pause();
   }
-  HIP_TRY(c, hipStreamSynchronize(g.st_frm));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VSLAM_OK;
 }
 VS_API int vslam_view_keypoints_xy(vslam_ctx* c, int s, vslam_keypoints_view* out) {
@@ -2579,7 +2490,7 @@ VS_API int vslam_view_keypoints_xy(vslam_ctx* c, int s, vslam_keypoints_view* ou
   if (c->sticky != VSLAM_OK) return c->sticky;
   if (!c->report || s != 0 || c->report_xy_seq < 0 || !c->frame_begun) return vslam_view_keypoints(c, s, out);   // no early report in flight: the full one
   const ReportHeader* h = reinterpret_cast<const ReportHeader*>(c->report);
-  rc = report_wait(c, c->groups[0], &h->seq_xy, c->report_xy_seq);
+  rc = report_wait(c, &h->seq_xy, c->report_xy_seq);
   if (rc) return rc;
   if (__atomic_load_n(&h->seq_xy, __ATOMIC_ACQUIRE) != c->report_xy_seq) return fail(c, VSLAM_ERR_STATE, "early keypoint report is stale (the stream is inactive?)");
   for (int d = 0; d < 2; ++d) {
