@@ -47,7 +47,7 @@ typedef enum {
                                small.  Overflow of a context's device-resident buffers inside vslam_process_* / the
                                stage calls is NOT a return code: processing continues on the truncated lists and the
                                frame's vslam_frame_info.error_flags reports it per stream (bit 0 keypoints, bit 1 points,
-                               bit 2 history, bit 3 landmark map) */
+                               bit 2 history, bit 3 landmark map, bit 4 observation log) */
   VSLAM_ERR_STATE = -5      /* call sequence violated (e.g. track before frame_begin)       */
 } vslam_status;
 
@@ -145,6 +145,7 @@ typedef struct vslam_frame_info {
   int32_t window_pixels;       /* _projection_tracking_distance_pixels after the frame        */
   int32_t error_flags;         /* bit0 keypoint capacity, bit1 point capacity, bit2 history,  */
                                /* bit3 (value 8) landmark map capacity (vslam_enable_map)     */
+                               /* bit4 (value 16) observation log capacity (vslam_enable_observations) */
   double tau_track;            /* _current_descriptor_distance_tracking after the frame       */
   double tau_triangulation;    /* _current_maximum_descriptor_distance_triangulation          */
   double camera_left_to_world[12];  /* frame pose (robotToWorld with identity robot offset)   */
@@ -316,6 +317,37 @@ int vslam_enable_map(vslam_ctx* ctx, int32_t capacity_per_stream);
 int vslam_get_map_size(vslam_ctx* ctx, int stream, int32_t* n);
 int vslam_get_map(vslam_ctx* ctx, int stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz,
                   int32_t* info /* first_frame, last_frame, updates per entry */, uint8_t* desc);
+/* ---- landmark observations (opt-in, on top of the landmark map) -------------------------------------------------------------
+ * Which landmark was seen in which frame at which pixels: with vslam_get_poses and vslam_get_map, the input of a mapping or
+ * bundle-adjustment back end, written on the device without a host round trip per frame.
+ * Rule, per stream and frame: once the frame's map ids are final, every point that carries an id appends one entry to the stream's
+ * log, in the order of the frame's points (vslam_get_points).  Entry (16 bytes on the device):
+ *   id    : int32      the landmark's map id (entry `id` of vslam_get_map)
+ *   frame : int32      0-based per stream, as in vslam_get_poses and the map's first_frame / last_frame
+ *   kp    : 4 int16    xL, yL, xR, yR: the point's keypoints, the values vslam_get_points reports as kp
+ * The log is sorted by frame, then by point order, and is deterministic.  A landmark's observations start with the frame that
+ * created its map entry (first_frame) and end with last_frame: the earlier points of its track, from before
+ * minimum_track_length_for_landmark_creation was reached, carry no id and are NOT logged.
+ * One kernel behind the map's writes them, on vslam_process_* / vslam_frame_finish; the stage calls of the shim and the RGB-D
+ * tracker do not.  A context without a log launches and allocates nothing for it.
+ * vslam_enable_observations: allocates `capacity_per_stream` entries per stream and clears every log (a log enabled mid-sequence
+ *   starts with the next frame); 0 frees the store and turns the log off.  Synchronises.  VSLAM_ERR_STATE without a map
+ *   (vslam_enable_map first) and inside a frame, VSLAM_ERR_INVALID for a negative capacity.  Once a stream's log is full, later
+ *   entries are dropped (the log holds exactly the first `capacity` entries), and every frame that dropped one reports error_flags
+ *   bit 4 (value 16).
+ * The log follows the map: vslam_reset clears every log, vslam_reset_stream(s) the affected streams' logs, a stream switched off by
+ *   vslam_set_stream_active keeps its log unchanged; vslam_enable_map(ctx, 0) turns the log off as well, and vslam_enable_map with a
+ *   new capacity (ids start at 0 again) clears every log.
+ * vslam_get_observation_count: entries of `stream`'s log.  vslam_get_observations: entries first .. first + n - 1,
+ *   n = min(cap, count - first) (a caller fetches what is new since its last call); id_frame receives (id, frame) pairs; any output
+ *   pointer may be NULL.  Both synchronise, VSLAM_ERR_STATE without a log.
+ * vslam_get_point_ids: the map id, or -1, of every point of the finished frame, in vslam_get_points order (e.g. for a viewer that
+ *   colours tracks).  Needs the map only, not the log; synchronises; VSLAM_ERR_CAPACITY when cap < n. */
+int vslam_enable_observations(vslam_ctx* ctx, int32_t capacity_per_stream);
+int vslam_get_observation_count(vslam_ctx* ctx, int stream, int32_t* n);
+int vslam_get_observations(vslam_ctx* ctx, int stream, int32_t first, int32_t cap, int32_t* n,
+                           int32_t* id_frame /* n*2: id, frame */, int16_t* kp /* n*4: xL, yL, xR, yR */);
+int vslam_get_point_ids(vslam_ctx* ctx, int stream, int32_t cap, int32_t* n, int32_t* ids);
 /* Pinned (page-locked) host memory.  Host images handed to vslam_process_host / vslam_frame_begin from ordinary (pageable) memory
  * are staged through a pinned buffer of the context first (one memcpy per image, ~30 us per 467 KB); images that already live in
  * memory from vslam_host_alloc (e.g. the cv::Mat a loader decodes into, constructed on such a buffer) are copied to the device

@@ -8,6 +8,8 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
     python tools/run_kitti.py <EuRoC dir with mav0/cam0 mav0/cam1> --format tum --out traj.txt   (ground truth found in mav0/)
     python tools/run_kitti.py <EuRoC dir> --rectify --format tum --out traj.txt   raw images: rectified on the GPU from mav0/cam{0,1}/sensor.yaml
     python tools/run_kitti.py <sequence dir> --map map.ply   the landmark map as well (binary PLY: x y z id first_frame last_frame updates)
+    python tools/run_kitti.py <sequence dir> --observations bundle.npz   trajectory + landmark map + which landmark was seen in which
+                              frame at which pixels, in one file (io_formats.read_bundle); implies the map; also with --chunks
 
 The sequence runs in exact mode (one stream, whole sequence, bit-for-bit the reference port's arithmetic); images are
 uploaded frame by frame through vslam_process_host.  With --gt (KITTI 3x4 rows) the ATE-RMSE after rigid alignment is
@@ -28,7 +30,7 @@ from vslam_pose_estimation_framework_amd import evaluation, hip, io_formats  # n
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
 
 
-def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False):
+def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -41,6 +43,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
         api.set_rectification(rect)
     if want_map:
         api.enable_map(MAP_ENTRIES_PER_FRAME * steps)
+    if want_obs:
+        api.enable_observations(steps * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
     rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
     Lb = np.zeros((len(plan), rows, cols), np.uint8)
     Rb = np.zeros_like(Lb)
@@ -60,12 +64,14 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
     for c in range(len(plan)):
         flags |= api.frame_info(c).error_flags
     chunks = [api.poses(c, 0, en - st) for c, (st, fi, en) in enumerate(plan)]
-    lm_map = sharding.assemble_map([api.map(c) for c in range(len(plan))], chunks, plan) if want_map else None
-    return np.asarray(sharding.assemble_trajectory(chunks, plan)).reshape(n, 12), flags, lm_map
+    maps = [api.map(c) for c in range(len(plan))] if want_map else None
+    lm_map = sharding.assemble_map(maps, chunks, plan) if want_map else None
+    obs = sharding.assemble_observations(maps, [api.observations(c) for c in range(len(plan))], plan) if want_obs else None
+    return np.asarray(sharding.assemble_trajectory(chunks, plan)).reshape(n, 12), flags, lm_map, obs
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6, rectify=False, map_path=None):
+        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None):
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
     if rectify and not euroc:
         raise SystemExit("--rectify: a KITTI odometry folder is already rectified (it takes raw EuRoC / ASL folders with sensor.yaml)")
@@ -104,15 +110,19 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         io_formats.apply_calib(cfg, seq.K, seq.baseline, left.shape[0], left.shape[1])
     t0 = time.perf_counter()
     flags = 0
+    want_map = bool(map_path or obs_path)        # the log's ids are the map's
+    obs = None
     if chunks > 1:
-        poses, flags, lm_map = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=bool(map_path))
+        poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path))
     else:
         cfg.max_history_frames = 512
         api.create(cfg, device, 1)
         if rect is not None:
             api.set_rectification(rect)
-        if map_path:
+        if want_map:
             api.enable_map(MAP_ENTRIES_PER_FRAME * n)
+        if obs_path:
+            api.enable_observations(n * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
         for k in range(n):
             if k:
                 left, right = seq.pair(k)
@@ -123,8 +133,10 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
                 log("frame %6d  status %s  points %5d  tracked %5d  inliers %5d" % (
                     k, "tracking" if fi.status == 1 else "localizing", fi.n_points, fi.n_tracked, fi.n_inliers))
         poses = api.poses(0, 0, n)
-        lm_map = api.map(0) if map_path else None
+        lm_map = api.map(0) if want_map else None
+        obs = api.observations(0) if obs_path else None
     dt = time.perf_counter() - t0
+    K, baseline_h = np.array(cfg.K, np.float64).reshape(3, 3), np.array(cfg.baseline_h, np.float64)
     api.destroy()
     log("%d frames in %.2f s (%.1f frames/s incl. PNG decode and upload), error flags %d" % (n, dt, n / dt, flags))
     if out_path:
@@ -141,6 +153,25 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
                              updates=lm_map["updates"])
         log("landmark map: %d landmarks -> %s" % (len(lm_map["id"]), map_path))
         result["map"] = lm_map
+    if want_map and not map_path:
+        if flags & 8:
+            log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
+        result["map"] = lm_map
+    if obs_path:
+        io_formats.write_bundle(obs_path, K, baseline_h, poses, lm_map, obs)
+        res, valid = evaluation.reprojection_residuals(K, baseline_h, poses, lm_map["xyz"], obs["id"], obs["frame"], obs["kp"])
+        norm = np.linalg.norm(res[valid], axis=1)
+        empty = n - len(np.unique(obs["frame"]))
+        result["observations"] = obs
+        result["reprojection"] = {"observations": int(len(obs["id"])), "landmarks": int(len(lm_map["id"])), "valid": int(valid.sum()),
+                                  "median_px": float(np.median(norm)) if len(norm) else None,
+                                  "p90_px": float(np.percentile(norm, 90)) if len(norm) else None, "frames_without_observation": int(empty)}
+        log("observations: %d of %d landmarks -> %s%s" % (len(obs["id"]), len(lm_map["id"]), obs_path,
+                                                        "  (%d dropped with warm-up duplicates)" % obs["dropped"] if "dropped" in obs else ""))
+        log("frames without any observation: %d of %d" % (empty, n))
+        if len(norm):
+            log("reprojection residual norm (xL, y, xR) against the map: median %.3f px, 90th percentile %.3f px over %d observations" % (
+                result["reprojection"]["median_px"], result["reprojection"]["p90_px"], len(norm)))
     if gt_path:
         gt = io_formats.read_trajectory_kitti(gt_path)[:n]
         result["ate_rmse_aligned"] = evaluation.ate_rmse(poses[:len(gt)], gt)
@@ -168,9 +199,11 @@ def main():
     ap.add_argument("--asl-gt", default=None, help="ASL ground-truth csv for the trajectory_analyzer step (needs --format tum --out)")
     ap.add_argument("--rectify", action="store_true", help="EuRoC / ASL folder of raw images: undistort and rectify them on the GPU from mav0/cam{0,1}/sensor.yaml")
     ap.add_argument("--map", default=None, help="write the landmark map (every landmark of the run, world frame) to this binary PLY file")
+    ap.add_argument("--observations", default=None, help="write trajectory, landmark map and the landmark observation log (id, frame, xL yL xR yR) "
+                    "to this .npz bundle (io_formats.read_bundle); implies the map")
     a = ap.parse_args()
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
-        rectify=a.rectify, map_path=a.map)
+        rectify=a.rectify, map_path=a.map, obs_path=a.observations)
 
 
 if __name__ == "__main__":

@@ -304,6 +304,35 @@ class CApi(object):
         return dict(id=np.arange(int(first), int(first) + k, dtype=np.int32), xyz=xyz[:k].copy(), first_frame=info[:k, 0].copy(),
                     last_frame=info[:k, 1].copy(), updates=info[:k, 2].copy(), desc=desc[:k].copy())
 
+    # -- landmark observations (vslam_enable_observations; needs the map) ----------------------------------------------
+    def enable_observations(self, capacity_per_stream):
+        """Log (landmark id, frame, keypoints) of every point that carries a map id, capacity_per_stream entries per stream; 0 turns it off."""
+        self.check(self.fn("enable_observations")(self.ctx, C.c_int32(int(capacity_per_stream))))
+
+    def observation_count(self, stream=0):
+        n = C.c_int32()
+        self.check(self.fn("get_observation_count")(self.ctx, C.c_int(stream), C.byref(n)))
+        return n.value
+
+    def observations(self, stream=0, first=0):
+        """Log entries first .. of `stream`: dict of numpy arrays id, frame (0-based per stream), kp [n, 4] (xL, yL, xR, yR)."""
+        cap = max(self.observation_count(stream) - int(first), 0)
+        n = C.c_int32()
+        idf = np.zeros((max(cap, 1), 2), np.int32)
+        kp = np.zeros((max(cap, 1), 4), np.int16)
+        self.check(self.fn("get_observations")(self.ctx, C.c_int(stream), C.c_int32(int(first)), C.c_int32(cap), C.byref(n), _p(idf, C.c_int32),
+                                               _p(kp, C.c_int16)))
+        k = n.value
+        return dict(id=idf[:k, 0].copy(), frame=idf[:k, 1].copy(), kp=kp[:k].copy())
+
+    def point_ids(self, stream=0):
+        """Map id (or -1) of every point of the finished frame, in points() order; needs the map only."""
+        cap = int(self.cfg.max_points)
+        n = C.c_int32()
+        ids = np.zeros(max(cap, 1), np.int32)
+        self.check(self.fn("get_point_ids")(self.ctx, C.c_int(stream), C.c_int32(cap), C.byref(n), _p(ids, C.c_int32)))
+        return ids[:n.value].copy()
+
     def aligner_result(self, stream=0):
         cap = int(self.cfg.max_points)
         n = C.c_int32()

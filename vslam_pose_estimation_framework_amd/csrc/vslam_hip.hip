@@ -16,6 +16,7 @@
 #include "kernels_report.h"
 #include "kernels_rectify.h"
 #include "kernels_map.h"
+#include "kernels_obs.h"
 
 #define VS_API extern "C" __attribute__((visibility("default")))
 
@@ -100,6 +101,9 @@ struct vslam_ctx {
                 std::vector<void*> mem; } rect;
   // the landmark map (vslam_enable_map, kernels_map.h): off while cap == 0; its own allocations, freed by vslam_enable_map(0) and destroy
   struct MapStore { int32_t cap = 0; DevMap d{}; std::vector<void*> mem; } map;
+  // the observation log on top of it (vslam_enable_observations, kernels_obs.h): off while cap == 0; freed by vslam_enable_observations(0),
+  // vslam_enable_map(0) and destroy
+  struct ObsStore { int32_t cap = 0; DevObs d{}; } obs;
   int sticky = VSLAM_OK;
 };
 
@@ -335,6 +339,7 @@ static int init_state(vslam_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->buf.info, 0, sizeof(vslam_frame_info) * c->B, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->buf.n_points, 0, sizeof(int32_t) * c->B * 2, c->stream));
   if (c->map.cap) HIP_TRY(c, hipMemsetAsync(c->map.d.count, 0, sizeof(int32_t) * c->B, c->stream));
+  if (c->obs.cap) HIP_TRY(c, hipMemsetAsync(c->obs.d.count, 0, sizeof(int32_t) * c->B, c->stream));
   sync_all(c);
   for (int q = 0; q < 2; ++q) {
     HIP_TRY(c, hipMemsetAsync(c->sets[q].n_kp, 0, sizeof(int32_t) * c->B * 2, c->stream));
@@ -555,6 +560,8 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   for (void* p : c->rect.mem) (void)hipFree(p);
   for (void* p : c->map.mem) (void)hipFree(p);
+  if (c->obs.d.log) (void)hipFree(c->obs.d.log);
+  if (c->obs.d.count) (void)hipFree(c->obs.d.count);
   tmp_free(c);
   depth_map_free(c);
   if (c->report) (void)hipHostFree(c->report);
@@ -600,6 +607,8 @@ VS_API int vslam_reset_streams(vslam_ctx* c, int32_t n, const int32_t* streams) 
     hipLaunchKernelGGL(k_reset_stream_trk, dim3(1), dim3(64), 0, c->stream, c->cfg, c->buf, l);
     if (c->map.cap)     // the stream's map starts over with its sequence (frame 0 never reads the previous frame's ids)
       for (int i = 0; i < l.n; ++i) HIP_TRY(c, hipMemsetAsync(c->map.d.count + l.ids[i], 0, sizeof(int32_t), c->stream));
+    if (c->obs.cap)     // and its observation log with it
+      for (int i = 0; i < l.n; ++i) HIP_TRY(c, hipMemsetAsync(c->obs.d.count + l.ids[i], 0, sizeof(int32_t), c->stream));
     l.n = 0;
     return VSLAM_OK;
   };
@@ -736,6 +745,8 @@ static int launch_frame(vslam_ctx* c) {
   }
   // the landmark map, behind the frame's last launch (sequence 4: behind the refinement workgroups of k_tail_lm as well)
   if (c->map.cap) hipLaunchKernelGGL(k_map_commit, dim3(n), dim3(VS_MAP_WG), 0, st, c->cfg, bs, c->map.d);
+  // the observation log, behind the ids k_map_commit has just left for this frame
+  if (c->obs.cap) hipLaunchKernelGGL(k_obs_append, dim3(n), dim3(VS_OBS_WG), 0, st, c->cfg, bs, c->map.d, c->obs.d);
   HIP_TRY(c, hipGetLastError());
   return frame_done(c);
 }
@@ -1066,6 +1077,12 @@ VS_API int vslam_get_frame_points(vslam_ctx* c, int s, int in_progress, int32_t 
   return get_points_impl(c, s, in_progress, cap, n, kp, meta, cam, lm, desc);
 }
 // ---- the landmark map (kernels_map.h) -------------------------------------------------------------
+static void obs_free(vslam_ctx* c) {
+  if (c->obs.d.log) (void)hipFree(c->obs.d.log);
+  if (c->obs.d.count) (void)hipFree(c->obs.d.count);
+  c->obs.d = DevObs{};
+  c->obs.cap = 0;
+}
 static void map_free(vslam_ctx* c) {
   for (void* p : c->map.mem) (void)hipFree(p);
   c->map.mem.clear();
@@ -1085,7 +1102,9 @@ VS_API int vslam_enable_map(vslam_ctx* c, int32_t cap) {
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                        // no commit of the old store may still be in flight
   map_free(c);
-  if (cap == 0) return VSLAM_OK;
+  if (cap == 0) { obs_free(c); return VSLAM_OK; }     // no ids, no log
+  // a new store hands out ids from 0 again: the observation log starts over with it
+  if (c->obs.cap) HIP_TRY(c, hipMemsetAsync(c->obs.d.count, 0, sizeof(int32_t) * c->B, c->stream));
   const size_t B = (size_t)c->B, n = B * (size_t)cap;
   DevMap d{};
   d.cap = cap; d.B = c->B;
@@ -1100,7 +1119,7 @@ VS_API int vslam_enable_map(vslam_ctx* c, int32_t cap) {
   if (e == hipSuccess) e = hipMemsetAsync(d.count, 0, B * sizeof(int32_t), c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d.ids, 0xff, 2 * B * (size_t)c->cfg.MAXP * sizeof(int32_t), c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) { map_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_enable_map: ") + hipGetErrorString(e)); }
+  if (e != hipSuccess) { map_free(c); obs_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_enable_map: ") + hipGetErrorString(e)); }
   c->map.d = d;
   c->map.cap = cap;
   return VSLAM_OK;
@@ -1128,6 +1147,80 @@ VS_API int vslam_get_map(vslam_ctx* c, int s, int32_t first_id, int32_t cap, int
   HIP_TRY(c, d2h(c, xyz, c->map.d.xyz + o * 3, (size_t)cnt * 3));
   HIP_TRY(c, d2h(c, info, c->map.d.info + o * 3, (size_t)cnt * 3));
   HIP_TRY(c, d2h(c, desc, c->map.d.desc + o * 32, (size_t)cnt * 32));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VSLAM_OK;
+}
+// ---- the observation log (kernels_obs.h) ------------------------------------------------------------
+VS_API int vslam_enable_observations(vslam_ctx* c, int32_t cap) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (cap < 0) return fail(c, VSLAM_ERR_INVALID, "vslam_enable_observations: negative capacity");
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_enable_observations called inside a frame");
+  if (!c->map.cap) return fail(c, VSLAM_ERR_STATE, "vslam_enable_observations needs the landmark map (vslam_enable_map): ids come from it");
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                        // no append to the old store may still be in flight
+  obs_free(c);
+  if (cap == 0) return VSLAM_OK;
+  const size_t B = (size_t)c->B;
+  DevObs d{};
+  d.cap = cap;
+  hipError_t e = hipMalloc((void**)&d.log, B * (size_t)cap * sizeof(uint4));
+  if (e == hipSuccess) e = hipMalloc((void**)&d.count, B * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemsetAsync(d.log, 0, B * (size_t)cap * sizeof(uint4), c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d.count, 0, B * sizeof(int32_t), c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    if (d.log) (void)hipFree(d.log);
+    if (d.count) (void)hipFree(d.count);
+    return fail(c, VSLAM_ERR_HIP, std::string("vslam_enable_observations: ") + hipGetErrorString(e));
+  }
+  c->obs.d = d;
+  c->obs.cap = cap;
+  return VSLAM_OK;
+}
+static int obs_count(vslam_ctx* c, int s, int32_t* n) {
+  int rc = check_stream(c, s);
+  if (rc) return rc;
+  if (!c->obs.cap) return fail(c, VSLAM_ERR_STATE, "the observation log is not enabled (vslam_enable_observations)");
+  HIP_TRY(c, d2h(c, n, c->obs.d.count + s, 1));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VSLAM_OK;
+}
+VS_API int vslam_get_observation_count(vslam_ctx* c, int s, int32_t* n) {
+  if (c && !n) return fail(c, VSLAM_ERR_INVALID, "vslam_get_observation_count: null output");
+  return obs_count(c, s, n);
+}
+VS_API int vslam_get_observations(vslam_ctx* c, int s, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame, int16_t* kp) {
+  if (c && (!n || first < 0 || cap < 0)) return fail(c, VSLAM_ERR_INVALID, "vslam_get_observations: null count, negative first entry or capacity");
+  int32_t size = 0;
+  int rc = obs_count(c, s, &size);
+  if (rc) return rc;
+  const int32_t cnt = std::max(0, std::min(cap, size - first));
+  *n = cnt;
+  if (!cnt || (!id_frame && !kp)) return VSLAM_OK;
+  std::vector<uint4> e((size_t)cnt);
+  HIP_TRY(c, d2h(c, e.data(), c->obs.d.log + (size_t)s * c->obs.cap + (size_t)first, (size_t)cnt));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int32_t i = 0; i < cnt; ++i) {
+    if (id_frame) { id_frame[2 * i] = (int32_t)e[i].x; id_frame[2 * i + 1] = (int32_t)e[i].y; }
+    if (kp) std::memcpy(kp + 4 * (size_t)i, &e[i].z, 8);
+  }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_point_ids(vslam_ctx* c, int s, int32_t cap, int32_t* n, int32_t* ids) {
+  int rc = check_stream(c, s);
+  if (rc) return rc;
+  if (!n || cap < 0) return fail(c, VSLAM_ERR_INVALID, "vslam_get_point_ids: null count or negative capacity");
+  if (!c->map.cap) return fail(c, VSLAM_ERR_STATE, "the landmark map is not enabled (vslam_enable_map)");
+  StreamState st;
+  HIP_TRY(c, d2h(c, &st, c->buf.st + s, 1));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int32_t cnt = 0;
+  HIP_TRY(c, d2h(c, &cnt, c->buf.n_points + s * 2 + st.cur, 1));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (!st.has_prev) cnt = 0;           // the point list vslam_get_points reports
+  *n = cnt;
+  if (cnt > cap) return fail(c, VSLAM_ERR_CAPACITY, "point id output capacity too small");
+  HIP_TRY(c, d2h(c, ids, c->map.d.ids + ((size_t)st.cur * c->B + s) * c->cfg.MAXP, (size_t)cnt));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VSLAM_OK;
 }

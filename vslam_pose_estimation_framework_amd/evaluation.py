@@ -194,6 +194,30 @@ def trajectory_analyzer(tum_path, asl_path, skip=0):
     return {"correspondences": len(meas), "raw_rmse": raw, "optimal_rmse": rmse(moved, ref), "transform": T, "iterations": log}
 
 
+# ---- reprojection of the landmark map into the frames that observed it -------------------------------------------------------------
+def reprojection_residuals(K, baseline_h, poses, xyz, obs_id, obs_frame, obs_kp):
+    """Residuals of the observation log (vslam_get_observations) against the landmark map (vslam_get_map) and the trajectory
+    (vslam_get_poses).  Landmark xyz[obs_id] goes through world_to_camera = inverse(poses[obs_frame]) into the left camera,
+    (u, v, w) = K p, and into the right camera with vslam_config's baseline_h convention, (u', v', w') = K p + baseline_h.
+    Returns (residuals [n, 3] = observed - projected as (xL - u/w, yL - v/w, xR - u'/w'), valid [n] bool: the point lies in front of
+    both cameras, w > 0 and w' > 0; rows that are not valid hold NaN)."""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    bh = np.asarray(baseline_h, np.float64).reshape(3)
+    P = np.asarray(poses, np.float64).reshape(-1, 3, 4)[np.asarray(obs_frame, np.int64)]
+    X = np.asarray(xyz, np.float64).reshape(-1, 3)[np.asarray(obs_id, np.int64)]
+    kp = np.asarray(obs_kp, np.float64).reshape(-1, 4)
+    pc = np.einsum("nji,nj->ni", P[:, :, :3], X - P[:, :, 3])          # R^T (X - t)
+    hl = pc @ K.T
+    hr = hl + bh
+    valid = (hl[:, 2] > 0) & (hr[:, 2] > 0)
+    res = np.full((len(kp), 3), np.nan)
+    wl, wr = hl[valid, 2], hr[valid, 2]
+    res[valid, 0] = kp[valid, 0] - hl[valid, 0] / wl
+    res[valid, 1] = kp[valid, 1] - hl[valid, 1] / wl
+    res[valid, 2] = kp[valid, 2] - hr[valid, 0] / wr
+    return res, valid
+
+
 # ---- relative errors: metrics that resolve a seam ------------------------------------------------------------------------------
 # ATE of open-loop odometry is a random walk in the measurement noise (DESIGN.md: 29 % run-to-run spread of the sequential
 # pipeline alone), so it cannot carry a 1 % criterion.  The KITTI odometry benchmark's own metric — translation / rotation error of

@@ -471,6 +471,46 @@ def read_ply(path):
     return out
 
 
+# ---- the structure-and-motion bundle: trajectory + landmark map + observation log --------------------------------------------
+BUNDLE_MAP_FIELDS = ("id", "xyz", "first_frame", "last_frame", "updates")      # always there; desc / chunk when the map has them
+
+
+def write_bundle(path, K, baseline_h, poses, lm_map, obs):
+    """One .npz with everything a mapping or bundle-adjustment back end needs: K [3, 3], baseline_h [3] (vslam_config: the right
+    camera projects K p + baseline_h), poses [F, 12] (camera_left_to_world, row-major 3x4), the map arrays of capi.CApi.map /
+    sharding.assemble_map under map_<name>, and the observation log (capi.CApi.observations / sharding.assemble_observations) as
+    obs_id, obs_frame, obs_kp [n, 4] (xL, yL, xR, yR).  obs_id indexes the map arrays, obs_frame the poses.  Written to `path`
+    exactly (no suffix is added); arrays keep their dtypes, so read_bundle returns them bit for bit."""
+    arrays = {"K": np.asarray(K, np.float64).reshape(3, 3), "baseline_h": np.asarray(baseline_h, np.float64).reshape(3),
+              "poses": np.asarray(poses, np.float64).reshape(-1, 12)}
+    for k in BUNDLE_MAP_FIELDS:
+        arrays["map_" + k] = np.asarray(lm_map[k])
+    for k in ("desc", "chunk"):
+        if k in lm_map:
+            arrays["map_" + k] = np.asarray(lm_map[k])
+    arrays["obs_id"] = np.asarray(obs["id"], np.int32)
+    arrays["obs_frame"] = np.asarray(obs["frame"], np.int32)
+    arrays["obs_kp"] = np.asarray(obs["kp"], np.int16).reshape(-1, 4)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def read_bundle(path):
+    """write_bundle's file -> dict: K, baseline_h, poses [F, 12], map (dict of the map arrays), obs_id, obs_frame, obs_kp."""
+    with np.load(path) as z:
+        out = {k: z[k] for k in ("K", "baseline_h", "poses", "obs_id", "obs_frame", "obs_kp")}
+        out["map"] = {k[4:]: z[k] for k in z.files if k.startswith("map_")}
+    return out
+
+
+def write_observations_text(path, obs_id, obs_frame, obs_kp):
+    """One observation per line, `frame id xL yL xR yR`, in the log's order (by frame, then by point order)."""
+    kp = np.asarray(obs_kp).reshape(-1, 4)
+    with open(path, "w") as f:
+        for i, fr, k in zip(np.asarray(obs_id).tolist(), np.asarray(obs_frame).tolist(), kp.tolist()):
+            f.write("%d %d %d %d %d %d\n" % (fr, i, k[0], k[1], k[2], k[3]))
+
+
 def write_trajectory_kitti(path, poses):
     with open(path, "w") as f:
         for T in np.asarray(poses, np.float64).reshape(-1, 12):

@@ -176,6 +176,39 @@ def assemble_map(chunk_maps, chunk_poses, plan, seam_frames=1):
     return out
 
 
+def assemble_observations(chunk_maps, chunk_obs, plan):
+    """Observation logs of the chunks (capi.CApi.observations: id = the chunk map's id, frame counted from the chunk's first processed
+    frame) -> one log that goes with assemble_map's map.  An observation is kept exactly when assemble_map keeps its landmark
+    (first_frame of chunk map entry `id` inside the chunk's own range [first_unique, end)); its id becomes that landmark's id in the
+    assembled map (the same renumbering: kept landmarks 0 .. n-1 in chunk order), its frame the global frame number (+ start).
+    Consequence at seams: a landmark tracked across a seam is re-created in the next chunk's warm-up and dropped there as a duplicate,
+    and its observations inside that chunk's own range go with it, so the frames just after a seam are thinner in observations.
+    Returns dict: id, frame, kp [n, 4], chunk, dropped (observations that went with warm-up duplicates)."""
+    parts = {k: [] for k in ("id", "frame", "kp", "chunk")}
+    base, dropped = 0, 0
+    for c, (start, first, end) in enumerate(plan):
+        if end <= first:                  # an empty chunk: assemble_map skips it as well
+            continue
+        ff = np.asarray(chunk_maps[c]["first_frame"], np.int64) + start
+        keep_lm = (ff >= first) & (ff < end)
+        new_id = np.where(keep_lm, base + np.cumsum(keep_lm) - 1, -1)
+        base += int(keep_lm.sum())
+        o = chunk_obs[c]
+        oid = np.asarray(o["id"], np.int64)
+        if oid.size and (oid.min() < 0 or oid.max() >= len(ff)):
+            raise ValueError("chunk %d: observation of landmark %d, the chunk map has %d entries" % (c, int(oid.max() if oid.min() >= 0 else oid.min()), len(ff)))
+        keep = keep_lm[oid] if oid.size else np.zeros(0, bool)
+        dropped += int(oid.size - keep.sum())
+        parts["id"].append(new_id[oid[keep]] if oid.size else np.zeros(0, np.int64))
+        parts["frame"].append(np.asarray(o["frame"], np.int64)[keep] + start)
+        parts["kp"].append(np.asarray(o["kp"], np.int16).reshape(-1, 4)[keep])
+        parts["chunk"].append(np.full(int(keep.sum()), c, np.int64))
+    out = {k: (np.concatenate(parts[k]) if parts[k] else np.zeros(0, np.int64)).astype(np.int32) for k in ("id", "frame", "chunk")}
+    out["kp"] = np.concatenate(parts["kp"]) if parts["kp"] else np.zeros((0, 4), np.int16)
+    out["dropped"] = dropped
+    return out
+
+
 def gather_poses(local_poses, group=None):
     """All-gather of per-rank pose blocks [chunks_per_rank, frames, 12] (torch tensor, any device) ->
     [world*chunks_per_rank, frames, 12].  One collective per run; RCCL on GPUs, gloo in CPU tests."""
