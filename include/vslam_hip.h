@@ -666,6 +666,28 @@ int vslam_rgbd_get_frame_info_stream(vslam_rgbd* t, int32_t stream, vslam_frame_
 int vslam_rgbd_get_points_stream(vslam_rgbd* t, int32_t stream, int32_t cap, int32_t* n, float* xy, double* cam, int32_t* meta4, uint8_t* desc);
 int vslam_rgbd_get_frame_info(vslam_rgbd* t, vslam_frame_info* out, int32_t* n_temporary);
 int vslam_rgbd_get_points(vslam_rgbd* t, int32_t cap, int32_t* n, float* xy, double* cam, int32_t* meta4, uint8_t* desc);
+/* The landmark map and the observation log of this mode (opt-in; csrc/kernels_rgbd_map.h): the contract of vslam_enable_map /
+ * vslam_enable_observations restated for this tracker's data, one sequence or a batch.  Identity is the track: a point whose predecessor
+ * carries an id takes it, else a point whose landmark was created or updated this frame takes the next id (dense from 0 after enabling or
+ * vslam_rgbd_reset, in point order: id k is the k-th landmark the reference creates), else -1.  Map entry: world coordinates, info3 =
+ * (first_frame, last_frame, updates), the 32 descriptor bytes of the point at the last update; rewritten exactly in the frames that created
+ * or updated the landmark.  Observation entry, one per point with an id, in point order: id_frame2 = (id, frame), xy (the keypoint, float)
+ * and cam (the point's camera coordinates, the measurement Landmark::update consumed), both bit for bit what vslam_rgbd_get_points reports;
+ * a landmark's entries start with the frame that created its map entry.  Frames are 0-based per sequence.  A full map refuses later
+ * landmarks for their track's life and sets bit 8 of that frame's error_flags; a full log keeps the first `capacity` entries and sets bit
+ * 16 in every frame that dropped one; neither stops the tracker.  vslam_rgbd_reset clears both and leaves them enabled; capacity 0 turns
+ * the store off (vslam_rgbd_enable_map(0): map and log); the log needs the map (VSLAM_ERR_STATE otherwise).  Enabling between frames of a
+ * running sequence is allowed: tracks that already carry a landmark get an id at their next update.  With a frame in flight (between
+ * submit and wait) every call here returns VSLAM_ERR_STATE; so does every call on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type
+ * ORB), which does not have the feature.  Any output pointer may be NULL; first_id / first read only what is new;
+ * vslam_rgbd_get_point_ids: the finished frame's ids in vslam_rgbd_get_points order (needs the map only). */
+int vslam_rgbd_enable_map(vslam_rgbd* t, int32_t capacity_per_stream);
+int vslam_rgbd_get_map_size(vslam_rgbd* t, int32_t stream, int32_t* n);
+int vslam_rgbd_get_map(vslam_rgbd* t, int32_t stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz, int32_t* info3, uint8_t* desc);
+int vslam_rgbd_enable_observations(vslam_rgbd* t, int32_t capacity_per_stream);
+int vslam_rgbd_get_observation_count(vslam_rgbd* t, int32_t stream, int32_t* n);
+int vslam_rgbd_get_observations(vslam_rgbd* t, int32_t stream, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame2, float* xy, double* cam);
+int vslam_rgbd_get_point_ids(vslam_rgbd* t, int32_t stream, int32_t cap, int32_t* n, int32_t* ids);
 
 /* ---- OrbDetector components (first half; base_framepoint_generator.cpp:52-70) ----------------------
  * The reference's OrbDetector is cv::ORB::create(5000, 1.2, 8, 31, 0, 2, HARRIS_SCORE, 31, threshold) used as a DETECTOR

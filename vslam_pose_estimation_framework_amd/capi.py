@@ -749,7 +749,63 @@ def _extra_methods():
 _extra_methods()
 
 
-class RgbdTracker(object):
+class _RgbdMapApi(object):
+    """vslam_rgbd_enable_map / _enable_observations and their getters (the device-resident loop only), shared by RgbdTracker and
+    RgbdBatch: the dict keys of CApi.map / CApi.observations, with xy and cam in place of kp."""
+
+    def enable_map(self, capacity_per_stream):
+        """Keep every landmark of every sequence on the device (capacity_per_stream entries each); 0 turns map and log off."""
+        self._check(self.lib.vslam_rgbd_enable_map(self.h, C.c_int32(int(capacity_per_stream))))
+
+    def map_size(self, stream=0):
+        n = C.c_int32()
+        self._check(self.lib.vslam_rgbd_get_map_size(self.h, C.c_int32(stream), C.byref(n)))
+        return n.value
+
+    def map(self, stream=0, first=0):
+        """Landmarks first .. of `stream`: dict of numpy arrays id, xyz [n, 3] (world), first_frame, last_frame, updates, desc [n, 32]."""
+        cap = max(self.map_size(stream) - int(first), 0)
+        n = C.c_int32()
+        xyz = np.zeros((max(cap, 1), 3), np.float64)
+        info = np.zeros((max(cap, 1), 3), np.int32)
+        desc = np.zeros((max(cap, 1), 32), np.uint8)
+        self._check(self.lib.vslam_rgbd_get_map(self.h, C.c_int32(stream), C.c_int32(int(first)), C.c_int32(cap), C.byref(n), _p(xyz, C.c_double),
+                                                _p(info, C.c_int32), _p(desc, C.c_uint8)))
+        k = n.value
+        return dict(id=np.arange(int(first), int(first) + k, dtype=np.int32), xyz=xyz[:k].copy(), first_frame=info[:k, 0].copy(),
+                    last_frame=info[:k, 1].copy(), updates=info[:k, 2].copy(), desc=desc[:k].copy())
+
+    def enable_observations(self, capacity_per_stream):
+        """Log (landmark id, frame, keypoint, camera coordinates) of every point that carries a map id; needs the map; 0 turns it off."""
+        self._check(self.lib.vslam_rgbd_enable_observations(self.h, C.c_int32(int(capacity_per_stream))))
+
+    def observation_count(self, stream=0):
+        n = C.c_int32()
+        self._check(self.lib.vslam_rgbd_get_observation_count(self.h, C.c_int32(stream), C.byref(n)))
+        return n.value
+
+    def observations(self, stream=0, first=0):
+        """Log entries first .. of `stream`: dict of numpy arrays id, frame (0-based per sequence), xy [n, 2] float32, cam [n, 3] float64."""
+        cap = max(self.observation_count(stream) - int(first), 0)
+        n = C.c_int32()
+        idf = np.zeros((max(cap, 1), 2), np.int32)
+        xy = np.zeros((max(cap, 1), 2), np.float32)
+        cam = np.zeros((max(cap, 1), 3), np.float64)
+        self._check(self.lib.vslam_rgbd_get_observations(self.h, C.c_int32(stream), C.c_int32(int(first)), C.c_int32(cap), C.byref(n),
+                                                         _p(idf, C.c_int32), _p(xy, C.c_float), _p(cam, C.c_double)))
+        k = n.value
+        return dict(id=idf[:k, 0].copy(), frame=idf[:k, 1].copy(), xy=xy[:k].copy(), cam=cam[:k].copy())
+
+    def point_ids(self, stream=0):
+        """Map id (or -1) of every point of the finished frame, in points() order; needs the map only."""
+        cap = int(self.cfg.max_points) * 4
+        n = C.c_int32()
+        ids = np.zeros(max(cap, 1), np.int32)
+        self._check(self.lib.vslam_rgbd_get_point_ids(self.h, C.c_int32(stream), C.c_int32(cap), C.byref(n), _p(ids, C.c_int32)))
+        return ids[:n.value].copy()
+
+
+class RgbdTracker(_RgbdMapApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -806,7 +862,7 @@ class RgbdTracker(object):
             self.h = None
 
 
-class RgbdBatch(object):
+class RgbdBatch(_RgbdMapApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

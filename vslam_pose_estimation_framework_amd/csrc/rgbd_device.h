@@ -8,6 +8,7 @@
 // track), the block image pipeline .. aligner .. tail is enqueued again, at most twice.
 #pragma once
 #include "kernels_rgbd.h"
+#include "kernels_rgbd_map.h"
 
 namespace vs_rgbd {
 
@@ -113,6 +114,115 @@ public:
       if (hipStreamSynchronize(q) != hipSuccess) { err = "RGB-D reset: space-map buffers"; return VSLAM_ERR_HIP; }
     }
     failed = false; failed_why.clear(); pending = false;
+    if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
+    return VSLAM_OK;
+  }
+
+  // ---- the landmark map and the observation log (kernels_rgbd_map.h): opt-in, their own allocations, nothing launched while cap == 0 ----
+  int enable_map(int32_t cap) {
+    if (cap < 0) { err = "vslam_rgbd_enable_map: negative capacity"; return VSLAM_ERR_INVALID; }
+    if (pending) { err = "vslam_rgbd_enable_map: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    map_free();                                     // also the log: its ids are the map's
+    drop_graph();                                   // a captured launch sequence holds the old store (or none)
+    if (cap == 0) return VSLAM_OK;
+    const size_t nB = (size_t)B, n = nB * (size_t)cap;
+    RgbdMap d{};
+    d.cap = cap; d.B = B;
+    hipError_t e = map_alloc(&d.rows, n * 4);
+    if (e == hipSuccess) e = map_alloc(&d.first, n);
+    if (e == hipSuccess) e = map_alloc(&d.count, nB);
+    if (e == hipSuccess) e = map_alloc(&d.committed, nB);
+    if (e == hipSuccess) e = map_alloc(&d.ids, 2 * nB * (size_t)rb.MAXP);
+    if (e == hipSuccess) { mp = d; e = map_clear(); }
+    if (e != hipSuccess) { map_free(); err = std::string("vslam_rgbd_enable_map: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    return VSLAM_OK;
+  }
+  int enable_observations(int32_t cap) {
+    if (cap < 0) { err = "vslam_rgbd_enable_observations: negative capacity"; return VSLAM_ERR_INVALID; }
+    if (pending) { err = "vslam_rgbd_enable_observations: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (!mp.cap) { err = "vslam_rgbd_enable_observations needs the landmark map (vslam_rgbd_enable_map): ids come from it"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    obs_free();
+    drop_graph();
+    if (cap == 0) return VSLAM_OK;
+    const size_t nB = (size_t)B;
+    hipError_t e = hipMalloc((void**)&mp.log, nB * (size_t)cap * 3 * sizeof(uint4));
+    if (e == hipSuccess) e = hipMalloc((void**)&mp.ocount, nB * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(mp.log, 0, nB * (size_t)cap * 3 * sizeof(uint4), q);
+    if (e == hipSuccess) e = hipMemsetAsync(mp.ocount, 0, nB * sizeof(int32_t), q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    if (e != hipSuccess) { obs_free(); err = std::string("vslam_rgbd_enable_observations: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    mp.ocap = cap;
+    return VSLAM_OK;
+  }
+  // what every getter below checks first; *size: entries of the store the call reads
+  int map_ready(int stream, bool log, int32_t* size) {
+    if (stream < 0 || stream >= B) { err = "stream index out of range"; return VSLAM_ERR_INVALID; }
+    if (pending) { err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (!mp.cap) { err = "the landmark map is not enabled (vslam_rgbd_enable_map)"; return VSLAM_ERR_STATE; }
+    if (log && !mp.ocap) { err = "the observation log is not enabled (vslam_rgbd_enable_observations)"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    if (size) {
+      const hipError_t e = hipMemcpy(size, (log ? mp.ocount : mp.count) + stream, sizeof(int32_t), hipMemcpyDeviceToHost);
+      if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    }
+    return VSLAM_OK;
+  }
+  int get_map(int stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz, int32_t* info3, uint8_t* desc) {
+    if (!n || first_id < 0 || cap < 0) { err = "vslam_rgbd_get_map: null count, negative first id or capacity"; return VSLAM_ERR_INVALID; }
+    int32_t size = 0;
+    const int rc = map_ready(stream, false, &size);
+    if (rc) return rc;
+    const int32_t cnt = std::max(0, std::min(cap, size - first_id));
+    *n = cnt;
+    if (!cnt || (!xyz && !info3 && !desc)) return VSLAM_OK;
+    const size_t o = (size_t)stream * mp.cap + (size_t)first_id;
+    std::vector<uint4> rows((size_t)cnt * 4);
+    std::vector<int32_t> first((size_t)cnt);
+    hipError_t e = hipMemcpy(rows.data(), mp.rows + o * 4, rows.size() * sizeof(uint4), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(first.data(), mp.first + o, first.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    for (int32_t i = 0; i < cnt; ++i) {
+      const uint4* r4 = rows.data() + 4 * (size_t)i;
+      if (xyz) { std::memcpy(xyz + 3 * (size_t)i, &r4[0], 16); std::memcpy(xyz + 3 * (size_t)i + 2, &r4[1], 8); }
+      if (info3) { info3[3 * i] = first[i]; info3[3 * i + 1] = (int32_t)r4[1].z; info3[3 * i + 2] = (int32_t)r4[1].w; }
+      if (desc) std::memcpy(desc + 32 * (size_t)i, &r4[2], 32);
+    }
+    return VSLAM_OK;
+  }
+  int get_observations(int stream, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame2, float* xy, double* cam) {
+    if (!n || first < 0 || cap < 0) { err = "vslam_rgbd_get_observations: null count, negative first entry or capacity"; return VSLAM_ERR_INVALID; }
+    int32_t size = 0;
+    const int rc = map_ready(stream, true, &size);
+    if (rc) return rc;
+    const int32_t cnt = std::max(0, std::min(cap, size - first));
+    *n = cnt;
+    if (!cnt || (!id_frame2 && !xy && !cam)) return VSLAM_OK;
+    std::vector<uint4> e3((size_t)cnt * 3);
+    const hipError_t e = hipMemcpy(e3.data(), mp.log + ((size_t)stream * mp.ocap + (size_t)first) * 3, e3.size() * sizeof(uint4), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    for (int32_t i = 0; i < cnt; ++i) {
+      const uint4* r3 = e3.data() + 3 * (size_t)i;
+      if (id_frame2) { id_frame2[2 * i] = (int32_t)r3[0].x; id_frame2[2 * i + 1] = (int32_t)r3[0].y; }
+      if (xy) std::memcpy(xy + 2 * (size_t)i, &r3[0].z, 8);
+      if (cam) { std::memcpy(cam + 3 * (size_t)i, &r3[1], 16); std::memcpy(cam + 3 * (size_t)i + 2, &r3[2], 8); }
+    }
+    return VSLAM_OK;
+  }
+  int get_point_ids(int stream, int32_t cap, int32_t* n, int32_t* ids) {
+    if (!n || cap < 0) { err = "vslam_rgbd_get_point_ids: null count or negative capacity"; return VSLAM_ERR_INVALID; }
+    const int rc = map_ready(stream, false, nullptr);
+    if (rc) return rc;
+    const RgbdState& hs = hosts[stream];
+    const int np = hs.frame_count == 0 ? 0 : hs.last_points;     // the point list vslam_rgbd_get_points reports
+    *n = np;
+    if (np > cap) { err = "point id output capacity too small"; return VSLAM_ERR_CAPACITY; }
+    if (!np || !ids) return VSLAM_OK;
+    const hipError_t e = hipMemcpy(ids, mp.ids + ((size_t)((hs.frame_count - 1) & 1) * B + stream) * rb.MAXP, (size_t)np * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
     return VSLAM_OK;
   }
 
@@ -199,6 +309,40 @@ private:
   int32_t graph_stride = -1;
   const uint8_t* graph_img = nullptr;
   hipEvent_t ev_fork = nullptr;
+  // the landmark map and the observation log (kernels_rgbd_map.h): off while cap / ocap == 0.  Allocations of their own, freed when the
+  // store is turned off or replaced (the inner context's allocation list only grows until destroy)
+  RgbdMap mp{};
+  std::vector<void*> map_mem;
+
+  template <typename T>
+  hipError_t map_alloc(T** ptr, size_t count) {
+    const hipError_t e = hipMalloc((void**)ptr, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) map_mem.push_back(*ptr);
+    return e;
+  }
+  void obs_free() {
+    if (mp.log) (void)hipFree(mp.log);
+    if (mp.ocount) (void)hipFree(mp.ocount);
+    mp.log = nullptr; mp.ocount = nullptr; mp.ocap = 0;
+  }
+  void map_free() {
+    obs_free();
+    for (void* ptr : map_mem) (void)hipFree(ptr);
+    map_mem.clear();
+    mp = RgbdMap{};
+  }
+  // ids from 0 again, no point labelled, nothing logged; the rows are cleared too so that a read never returns another run's data
+  hipError_t map_clear() {
+    const size_t nB = (size_t)B, n = nB * (size_t)mp.cap;
+    hipError_t e = hipMemsetAsync(mp.rows, 0, n * 4 * sizeof(uint4), q);
+    if (e == hipSuccess) e = hipMemsetAsync(mp.first, 0, n * sizeof(int32_t), q);
+    if (e == hipSuccess) e = hipMemsetAsync(mp.count, 0, nB * sizeof(int32_t), q);
+    if (e == hipSuccess) e = hipMemsetAsync(mp.committed, 0, nB * sizeof(int32_t), q);
+    if (e == hipSuccess) e = hipMemsetAsync(mp.ids, 0xff, 2 * nB * (size_t)rb.MAXP * sizeof(int32_t), q);
+    if (e == hipSuccess && mp.ocap) e = hipMemsetAsync(mp.ocount, 0, nB * sizeof(int32_t), q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    return e;
+  }
 
   void release() {
     // an un-waited frame may still be copying into `pinned` and running on q / q2: both queues drain before anything is freed
@@ -207,6 +351,7 @@ private:
     pending = false;
     if (pinned) { (void)hipHostFree(pinned); pinned = nullptr; }
     drop_graph();
+    map_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (q2) { (void)hipStreamDestroy(q2); q2 = nullptr; }
     if (ev_depth) { (void)hipEventDestroy(ev_depth); ev_depth = nullptr; }
@@ -254,6 +399,9 @@ private:
     const int lm_gx = std::max(2, std::min((d.MAXP + RGBD_LM_PTS - 1) / RGBD_LM_PTS, 256 / B));
     hipLaunchKernelGGL(k_rgbd_landmarks, dim3(lm_gx, B), dim3(256), 0, q, d, rb);
     hipLaunchKernelGGL(k_rgbd_finish, dim3(B), dim3(wg1), 0, q, d, b, rb);
+    // opt-in: ids, map rows and log entries of the frame k_rgbd_finish has just closed, ahead of the state block's copy out (it raises the
+    // capacity bits in the frame's report); skips itself like the rest of the tail, and serves a frame once however many attempts it took
+    if (mp.cap) hipLaunchKernelGGL(k_rgbd_map_commit, dim3(B), dim3(VS_RGBD_MAP_WG), 0, q, rb, mp);
   }
 
   int submit_frame(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t lss, size_t dss, bool on_device) {

@@ -2775,6 +2775,43 @@ VS_API int vslam_rgbd_get_points(vslam_rgbd* r, int32_t cap, int32_t* n, float* 
   }
   return VSLAM_OK;
 }
+// ---- the RGB-D landmark map and observation log (kernels_rgbd_map.h): the device-resident loop only ----
+static int rgbd_map_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) keeps no landmark map or observation log; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_enable_map(vslam_rgbd* r, int32_t cap) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_enable_map") : r->d.enable_map(cap);
+}
+VS_API int vslam_rgbd_get_map_size(vslam_rgbd* r, int32_t stream, int32_t* n) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (r->on_host) return rgbd_map_host_refusal(r, "vslam_rgbd_get_map_size");
+  if (!n) { r->d.err = "vslam_rgbd_get_map_size: null output"; return VSLAM_ERR_INVALID; }
+  return r->d.map_ready(stream, false, n);
+}
+VS_API int vslam_rgbd_get_map(vslam_rgbd* r, int32_t stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz, int32_t* info3, uint8_t* desc) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_map") : r->d.get_map(stream, first_id, cap, n, xyz, info3, desc);
+}
+VS_API int vslam_rgbd_enable_observations(vslam_rgbd* r, int32_t cap) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_enable_observations") : r->d.enable_observations(cap);
+}
+VS_API int vslam_rgbd_get_observation_count(vslam_rgbd* r, int32_t stream, int32_t* n) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (r->on_host) return rgbd_map_host_refusal(r, "vslam_rgbd_get_observation_count");
+  if (!n) { r->d.err = "vslam_rgbd_get_observation_count: null output"; return VSLAM_ERR_INVALID; }
+  return r->d.map_ready(stream, true, n);
+}
+VS_API int vslam_rgbd_get_observations(vslam_rgbd* r, int32_t stream, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame2, float* xy, double* cam) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_observations") : r->d.get_observations(stream, first, cap, n, id_frame2, xy, cam);
+}
+VS_API int vslam_rgbd_get_point_ids(vslam_rgbd* r, int32_t stream, int32_t cap, int32_t* n, int32_t* ids) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_point_ids") : r->d.get_point_ids(stream, cap, n, ids);
+}
 
 // ---- pose all-gather on RCCL (loaded lazily: the single-GPU path has no dependency on librccl.so) ----------------------------
 #include <dlfcn.h>

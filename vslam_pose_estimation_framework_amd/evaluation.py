@@ -218,6 +218,27 @@ def reprojection_residuals(K, baseline_h, poses, xyz, obs_id, obs_frame, obs_kp)
     return res, valid
 
 
+def reprojection_residuals_uvd(K, poses, xyz, obs_id, obs_frame, obs_xy, obs_cam):
+    """Residuals of the RGB-D observation log (vslam_rgbd_get_observations) against the landmark map (vslam_rgbd_get_map) and the
+    trajectory.  Landmark xyz[obs_id] goes through world_to_camera = inverse(poses[obs_frame]) into the camera, (u, v, w) = K p.
+    Returns (residuals [n, 3] = observed - projected as (x - u/w, y - v/w, cam_z - w): two pixel residuals and one depth residual
+    in metres, valid [n] bool: the point lies in front of the camera, w > 0; rows that are not valid hold NaN)."""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    P = np.asarray(poses, np.float64).reshape(-1, 3, 4)[np.asarray(obs_frame, np.int64)]
+    X = np.asarray(xyz, np.float64).reshape(-1, 3)[np.asarray(obs_id, np.int64)]
+    xy = np.asarray(obs_xy, np.float64).reshape(-1, 2)
+    cam = np.asarray(obs_cam, np.float64).reshape(-1, 3)
+    pc = np.einsum("nji,nj->ni", P[:, :, :3], X - P[:, :, 3])          # R^T (X - t)
+    h = pc @ K.T
+    valid = h[:, 2] > 0
+    res = np.full((len(xy), 3), np.nan)
+    w = h[valid, 2]
+    res[valid, 0] = xy[valid, 0] - h[valid, 0] / w
+    res[valid, 1] = xy[valid, 1] - h[valid, 1] / w
+    res[valid, 2] = cam[valid, 2] - w
+    return res, valid
+
+
 # ---- relative errors: metrics that resolve a seam ------------------------------------------------------------------------------
 # ATE of open-loop odometry is a random walk in the measurement noise (DESIGN.md: 29 % run-to-run spread of the sequential
 # pipeline alone), so it cannot carry a 1 % criterion.  The KITTI odometry benchmark's own metric — translation / rotation error of

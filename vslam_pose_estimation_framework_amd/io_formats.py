@@ -503,6 +503,31 @@ def read_bundle(path):
     return out
 
 
+def write_bundle_rgbd(path, K, poses, lm_map, obs):
+    """The bundle of the RGB-D tracker (capi.RgbdTracker.map / .observations): K [3, 3], poses [F, 12], the map arrays under
+    map_<name>, and the log as obs_id, obs_frame, obs_xy [n, 2] float32 (the keypoint) and obs_cam [n, 3] float64 (the point's camera
+    coordinates: pixel and depth measurement).  One camera, so no baseline_h and no obs_kp: read it with read_bundle_rgbd."""
+    arrays = {"K": np.asarray(K, np.float64).reshape(3, 3), "poses": np.asarray(poses, np.float64).reshape(-1, 12)}
+    for k in BUNDLE_MAP_FIELDS:
+        arrays["map_" + k] = np.asarray(lm_map[k])
+    if "desc" in lm_map:
+        arrays["map_desc"] = np.asarray(lm_map["desc"])
+    arrays["obs_id"] = np.asarray(obs["id"], np.int32)
+    arrays["obs_frame"] = np.asarray(obs["frame"], np.int32)
+    arrays["obs_xy"] = np.asarray(obs["xy"], np.float32).reshape(-1, 2)
+    arrays["obs_cam"] = np.asarray(obs["cam"], np.float64).reshape(-1, 3)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def read_bundle_rgbd(path):
+    """write_bundle_rgbd's file -> dict: K, poses [F, 12], map (dict of the map arrays), obs_id, obs_frame, obs_xy, obs_cam."""
+    with np.load(path) as z:
+        out = {k: z[k] for k in ("K", "poses", "obs_id", "obs_frame", "obs_xy", "obs_cam")}
+        out["map"] = {k[4:]: z[k] for k in z.files if k.startswith("map_")}
+    return out
+
+
 def write_observations_text(path, obs_id, obs_frame, obs_kp):
     """One observation per line, `frame id xL yL xR yR`, in the log's order (by frame, then by point order)."""
     kp = np.asarray(obs_kp).reshape(-1, 4)
