@@ -33,6 +33,21 @@ class Oracle(CApi):
     def __init__(self):
         super().__init__(ensure_built(), "orc_")
 
+    def _on_config(self, method, *a, **k):
+        """orc_track_match / orc_stereo_match take the configuration where the product takes its context."""
+        ctx = self.ctx
+        self.ctx = C.byref(self.cfg)
+        try:
+            return method(*a, **k)
+        finally:
+            self.ctx = ctx
+
+    def track_match(self, *a, **k):
+        return self._on_config(super().track_match, *a, **k)
+
+    def stereo_match(self, *a, **k):
+        return self._on_config(super().stereo_match, *a, **k)
+
     def scene_kitti(self, scale=1.0, seed=7):
         s = SynthScene()
         self.lib.orc_synth_default_kitti(C.byref(s))

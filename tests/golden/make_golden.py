@@ -247,7 +247,12 @@ def v2t(v):
     return T
 
 
-def linearize(T, moving, fixed, omega, weight, ignore_outliers, kernel=4.0, min_depth=0.1, rows=376, cols=1241):
+def linearize(T, moving, fixed, omega, weight, ignore_outliers, kernel=4.0, min_depth=0.1, rows=376, cols=1241, K=None, B=None, abs_sum=None):
+    """K, B: camera matrix and baseline vector (default: KITTI); abs_sum: optional 2 x 6 x 6 numpy.longdouble array that receives
+    [0] the sum of the absolute values of every measurement's contribution to H (the scale of H's summation error) and [1] the sum of the
+    absolute values of the row products those contributions are made of."""
+    K = KITTI_K if K is None else K
+    B = KITTI_B if B is None else B
     H = np.zeros((6, 6)); b = np.zeros(6); E = 0.0; ninl = 0
     n = len(moving)
     chi_out = -np.ones(n); inl = np.zeros(n, np.uint8)
@@ -255,8 +260,8 @@ def linearize(T, moving, fixed, omega, weight, ignore_outliers, kernel=4.0, min_
         p = T[:3, :3] @ moving[u] + T[:3, 3]
         if p[2] < min_depth:
             continue
-        abcL = KITTI_K @ p
-        abcR = abcL + KITTI_B
+        abcL = K @ p
+        abcR = abcL + B
         uvL = abcL[:2] / abcL[2]
         uvR = abcR[:2] / abcR[2]
         if uvL[0] < 0 or uvL[0] > cols or uvL[1] < 0 or uvL[1] > rows:
@@ -276,23 +281,29 @@ def linearize(T, moving, fixed, omega, weight, ignore_outliers, kernel=4.0, min_
             ninl += 1
         E += chi
         Jt = np.hstack([weight[u] * np.eye(3), -2 * skew(p)])
-        KJ = KITTI_K @ Jt
+        KJ = K @ Jt
         JL = np.array([[1 / abcL[2], 0, -abcL[0] / abcL[2] ** 2], [0, 1 / abcL[2], -abcL[1] / abcL[2] ** 2]])
         JR = np.array([[1 / abcR[2], 0, -abcR[0] / abcR[2] ** 2], [0, 1 / abcR[2], -abcR[1] / abcR[2] ** 2]])
         J = np.vstack([JL @ KJ, JR @ KJ])
         H += om * (J.T @ J)
+        if abs_sum is not None:
+            abs_sum[0] += np.abs(om * (J.T @ J)); abs_sum[1] += om * (np.abs(J).T @ np.abs(J))
         b += om * (J.T @ e)
     return H, b, E, ninl, chi_out, inl
 
 
-def converge(T, moving, fixed, omega, weight, damping=5.0, delta=1e-3, max_it=1000, min_inl=100):
+def converge(T, moving, fixed, omega, weight, damping=5.0, delta=1e-3, max_it=1000, min_inl=100, solve=np.linalg.solve, observe=None, **lin):
+    """solve: the 6 x 6 solver; observe(ignore_outliers, chi): called after every linearization; lin: keyword arguments handed on to
+    linearize (kernel, min_depth, rows, cols, K, B)."""
     its = 0
     Eprev = 0.0
 
     def one_round(T, ignore):
-        H, b, E, ninl, chi, inl = linearize(T, moving, fixed, omega, weight, ignore)
+        H, b, E, ninl, chi, inl = linearize(T, moving, fixed, omega, weight, ignore, **lin)
+        if observe is not None:
+            observe(ignore, chi)
         H = H + damping * len(moving) * np.eye(6)
-        dx = np.linalg.solve(H, -b)
+        dx = solve(H, -b)
         T = v2t(dx) @ T
         R = T[:3, :3]
         T[:3, :3] = R - 0.5 * R @ (R.T @ R - np.eye(3))
@@ -349,7 +360,9 @@ def gen_aligner(rng):
 
 
 # ---- UVDAligner (RGB-D mode, uvd_aligner.cpp) ---------------------------------------------------------------------
-def linearize_uvd(T, moving, fixed, w_uv, w_d, weight, ignore_outliers, kernel=4.0, min_depth=0.1, rows=376, cols=1241):
+def linearize_uvd(T, moving, fixed, w_uv, w_d, weight, ignore_outliers, kernel=4.0, min_depth=0.1, rows=376, cols=1241, K=None, abs_sum=None):
+    """K, abs_sum: as in linearize."""
+    K = KITTI_K if K is None else K
     H = np.zeros((6, 6)); b = np.zeros(6); E = 0.0; ninl = 0
     n = len(moving)
     chi_out = -np.ones(n); inl = np.zeros(n, np.uint8)
@@ -357,7 +370,7 @@ def linearize_uvd(T, moving, fixed, w_uv, w_d, weight, ignore_outliers, kernel=4
         p = T[:3, :3] @ moving[u] + T[:3, 3]
         if p[2] <= min_depth:
             continue
-        a = KITTI_K @ p
+        a = K @ p
         uv = a[:2] / a[2]
         if uv[0] < 0 or uv[0] > cols or uv[1] < 0 or uv[1] > rows:
             continue
@@ -376,20 +389,25 @@ def linearize_uvd(T, moving, fixed, w_uv, w_d, weight, ignore_outliers, kernel=4
         Jt = np.hstack([weight[u] * np.eye(3), -2 * skew(p)])
         iz = 1 / p[2]
         Jp = np.array([[iz, 0, -a[0] * iz * iz], [0, iz, -a[1] * iz * iz], [0, 0, 1.0]])
-        J = Jp @ KITTI_K @ Jt
+        J = Jp @ K @ Jt
         H += J.T @ Om @ J
+        if abs_sum is not None:
+            abs_sum[0] += np.abs(J.T @ Om @ J); abs_sum[1] += np.abs(J).T @ Om @ np.abs(J)
         b += J.T @ Om @ e
     return H, b, E, ninl, chi_out, inl
 
 
-def converge_uvd(T, moving, fixed, w_uv, w_d, weight, damping=5.0, delta=1e-3, max_it=1000):
+def converge_uvd(T, moving, fixed, w_uv, w_d, weight, damping=5.0, delta=1e-3, max_it=1000, solve=np.linalg.solve, observe=None, **lin):
+    """solve, observe, lin: as in converge (lin goes to linearize_uvd)."""
     its = 0
     Eprev = 0.0
 
     def one_round(T, ignore):
-        H, b, E, ninl, chi, inl = linearize_uvd(T, moving, fixed, w_uv, w_d, weight, ignore)
+        H, b, E, ninl, chi, inl = linearize_uvd(T, moving, fixed, w_uv, w_d, weight, ignore, **lin)
+        if observe is not None:
+            observe(ignore, chi)
         H = H + damping * len(moving) * np.eye(6)
-        dx = np.linalg.solve(H, -b)
+        dx = solve(H, -b)
         T = v2t(dx) @ T
         R = T[:3, :3]
         T[:3, :3] = R - 0.5 * R @ (R.T @ R - np.eye(3))

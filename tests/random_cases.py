@@ -1,0 +1,904 @@
+"""Seeded random cases for the stand-alone solver and matcher entries, shared by tests/test_oracle_random.py (CPU: oracle against the
+Python restatements of tests/golden/make_golden.py) and tests/test_hip_random_entries.py (GPU: HIP against both).
+
+No fixtures, no GPU use.  Every case comes from numpy.random.default_rng(seed); the seed is part of every failure message.  A draw is
+rejected only for a reason computed from the Python reference alone (`Rejections`), and the CPU test asserts that at most one draw in ten is.
+
+Sizes the pure-Python references can afford (everything else is compared with the oracle only):
+  aligners            n <= PY_ALIGN_MAX
+  track_match         nP <= PY_TRACK_MAX with a window d <= 15, nP <= 65 with d = 50, nP = 1 with the window wider than the image
+  stereo_match        nL, nR <= PY_STEREO_MAX, keypoint binning off (stereo_sweep has no binning)
+  landmark_update     n <= PY_LANDMARK_MAX
+  depth_track         every case (small images)
+  resize / harris     images of at most PY_IMAGE_MAX pixels
+"""
+import numpy as np
+
+from golden import make_golden as mg
+
+KITTI_K, KITTI_B = mg.KITTI_K, mg.KITTI_B
+ROWS, COLS = 376, 1241
+PY_ALIGN_MAX, PY_TRACK_MAX, PY_STEREO_MAX, PY_LANDMARK_MAX, PY_IMAGE_MAX = 1025, 513, 2500, 513, 70000
+
+# kernel geometry the inputs are built to cross (dev_types.h, kernels_frame.h, kernels_depth.h)
+VS_WG, VS_MAXCAND, VS_MAXRCAND, VS_DT_CAP, VS_DT_K = 512, 16, 8, 32, 6
+
+
+class Rejections(object):
+    """draws and rejected draws of one case family"""
+
+    def __init__(self):
+        self.draws, self.rejected = 0, 0
+
+    def check(self, name):
+        print("%s: %d of %d draws rejected" % (name, self.rejected, self.draws))
+        assert self.rejected * 10 <= self.draws, (name, self.rejected, self.draws)
+
+
+def config_with(api, **fields):
+    cfg = api.default_config("kitti")
+    for k, v in fields.items():
+        if k == "K":
+            for i in range(9):
+                cfg.K[i] = float(np.asarray(v).ravel()[i])
+        else:
+            setattr(cfg, k, v)
+    return cfg
+
+
+def near(rng, desc, k):
+    bits = np.unpackbits(desc)
+    bits[rng.choice(256, size=k, replace=False)] ^= 1
+    return np.packbits(bits)
+
+
+# ---- A. aligners -------------------------------------------------------------------------------------------------------------------
+ALIGN_SIZES = [0, 1, 2, 15, 16, 17, 63, 64, 65, 511, 512, 513, 575, 576, 1023, 1024, 1025, 1536, 3000]
+SEAMS = [0, 63, 64, 511, 512, 513]
+SKEW_K = np.array([[718.856, 0.3, 607.1928], [0, 718.856, 185.2157], [0, 0, 1.0]])
+V_TRUE = {False: np.array([0.02, -0.01, -0.9, 0.001, 0.012, -0.0005]), True: np.array([0.01, -0.005, -0.06, 0.002, 0.01, -0.001])}
+V_ROT = np.array([0.0, 0.0, 0.0, 0.004, 0.012, -0.003])
+
+
+def full_piv_solve(H, b):
+    """The rank rule of the aligner's 6 x 6 solver: full pivoting (first maximum in column-major order), an exactly zero remaining
+    corner ends the elimination, the unknowns beyond the rank are 0."""
+    A, y = np.array(H, float), np.array(b, float)
+    n = len(y); perm = list(range(n)); rank = n
+    for k in range(n):
+        sub = np.abs(A[k:, k:])
+        if sub.max() == 0:
+            rank = k
+            break
+        j, i = np.unravel_index(np.argmax(sub.T), sub.T.shape)      # column-major scan
+        pr, pc = k + i, k + j
+        A[[k, pr]] = A[[pr, k]]; y[[k, pr]] = y[[pr, k]]
+        A[:, [k, pc]] = A[:, [pc, k]]; perm[k], perm[pc] = perm[pc], perm[k]
+        for r in range(k + 1, n):
+            f = A[r, k] / A[k, k]
+            A[r, k:] -= f * A[k, k:]; y[r] -= f * y[k]
+    x = np.zeros(n)
+    if rank:
+        x[perm[:rank]] = np.linalg.solve(np.triu(A[:rank, :rank]), y[:rank])
+    return x
+
+
+def gen_align(seed, n, uvd=False, K=KITTI_K, noise=0.25, outlier_frac=0.08, skip_wave=False, certain_inliers=None, v_true=None,
+              zero_translation_weights=False):
+    """Scene of gen_aligner / gen_aligner_uvd at any size: depths, a known motion, pixel noise, gross outliers of up to 30 px, rows behind
+    the camera and rows projecting outside the image.  The skipped rows and outliers sit on the chunk and wave seams (SEAMS, n - 1) besides
+    random places; skip_wave skips 512 .. 575 entirely; certain_inliers = k makes k noise-free rows and gross outliers of the rest."""
+    rng = np.random.default_rng(seed)
+    v_true = V_TRUE[uvd] if v_true is None else v_true
+    Tt = mg.v2t(v_true)
+    z = rng.uniform(0.8, 8.0, n) if uvd else rng.uniform(6, 45, n)
+    # projections well inside both images, before and after the motion: only the rows made for it are skipped
+    u, v = rng.uniform(240, 1040, n), rng.uniform(50, 320, n)
+    Ki = np.linalg.inv(K)
+    X = (Ki @ np.stack([u * z, v * z, z])).T.reshape(n, 3)
+    role = np.zeros(n, np.int8)                                   # 0 plain, 1 outlier, 2 behind the camera, 3 outside the image
+    if certain_inliers is not None:
+        role[rng.permutation(n)[certain_inliers:]] = 1
+        noise = 0.0
+    else:
+        role[rng.random(n) < outlier_frac] = 1
+        role[rng.random(n) < 0.02] = 2
+        role[rng.random(n) < 0.02] = 3
+        first = int(rng.integers(0, 3))
+        for k, i in enumerate(sorted(set(s for s in SEAMS + [n - 1] if 0 <= s < n))):
+            role[i] = 1 + (first + k) % 3
+        if skip_wave:
+            role[512:576] = np.where(np.arange(512, min(576, n)) % 2, 2, 3)[:max(min(576, n) - 512, 0)]
+    X[role == 2] = [0.0, 0.0, -3.0]
+    X[role == 3] = [60.0, 0.0, 6.0] if not uvd else [40.0, 0.0, 3.0]
+    P = (Tt[:3, :3] @ X.T).T + Tt[:3, 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = (K @ P.T).T
+        if uvd:
+            fixed = np.hstack([a[:, :2] / a[:, 2:3], P[:, 2:3]])
+        else:
+            aR = a + KITTI_B
+            fixed = np.hstack([a[:, :2] / a[:, 2:3], aR[:, :2] / aR[:, 2:3]])
+    fixed[role >= 2] = 100.0
+    if noise > 0:
+        fixed[:, :2 if uvd else 4] += rng.normal(0, noise, (n, 2 if uvd else 4))
+        if uvd:
+            fixed[:, 2] += rng.normal(0, 0.02, n)
+    nout = int((role == 1).sum())
+    gross = rng.uniform(10, 30, (nout, 4)) * rng.choice([-1.0, 1.0], (nout, 4))
+    if uvd:
+        fixed[role == 1, :2] += gross[:, :2]
+    else:
+        fixed[role == 1] += gross
+    case = dict(seed=seed, n=n, uvd=uvd, moving=X, fixed=fixed, role=role, skipped=role >= 2, T0=np.eye(4)[:3].copy(), Ttrue=Tt[:3])
+    with np.errstate(divide="ignore"):
+        depth = np.where(P[:, 2] > 0, P[:, 2], 1.0)
+    if uvd:
+        w_uv = np.where(rng.random(n) < 0.5, 1.0, 1.0 + rng.integers(0, 12, n))
+        unreliable = (rng.random(n) < 0.15) & (certain_inliers is None)
+        case.update(w_uv=w_uv, w_d=np.where(unreliable, 0.0, 10.0 * w_uv), weight=np.where(unreliable, 0.0, np.minimum(5.0 / depth, 1.0)))
+    else:
+        case.update(omega=np.where(rng.random(n) < 0.5, 1.0, 1.0 + np.log(rng.integers(2, 30, n))), weight=np.minimum(15.0 / depth, 1.0))
+    if zero_translation_weights:
+        case["weight"] = np.zeros(n)
+    return case
+
+
+def align_args(case):
+    if case["uvd"]:
+        return (case["moving"], case["fixed"], case["w_uv"], case["w_d"], case["weight"])
+    return (case["moving"], case["fixed"], case["omega"], case["weight"])
+
+
+def run_align(api, case):
+    f = api.align_points_uvd if case["uvd"] else api.align_points
+    return f(*(align_args(case) + (case["T0"],)))
+
+
+def ref_align(case, rej=None, damping=5.0, max_it=1000, K=None, solve=np.linalg.solve, kernel=4.0):
+    """converge / converge_uvd on the case; None when the draw is rejected: a chi of some round within 1e-6 relative of the kernel."""
+    rounds = []
+    T0 = np.vstack([case["T0"], [0, 0, 0, 1.0]])
+    f = mg.converge_uvd if case["uvd"] else mg.converge
+    T, H, E, ninl, chi, inl, its = f(T0, *align_args(case), damping=damping, max_it=max_it, solve=solve, K=K,
+                                     observe=lambda ignore, c: rounds.append((ignore, c.copy())))
+    if rej is not None:
+        rej.draws += 1
+        for _, c in rounds:
+            if np.any((c >= 0) & (np.abs(c - kernel) <= 1e-6 * kernel)):
+                rej.rejected += 1
+                return None
+    return dict(T=T[:3], H=H, total_error=E, n_inliers=ninl, chi=chi, inlier=inl, iterations=its, refine_rounds=sum(1 for r in rounds if r[0]))
+
+
+def first_round_H(case, damping, K=None):
+    """First round's damped normal matrix and the derived per-entry bound 4 n 2^-52 S, S = sum of |per-measurement term| in longdouble.
+
+    One entry cannot be held to that S.  H[2][5] (= H[5][2]) of the RGB-D model, translation along z against rotation about z, is zero
+    analytically in every measurement of a pinhole camera with fx = fy: w_uv (J[0][2] J[0][5] + J[1][2] J[1][5]) = 0 and the depth row has
+    J[2][5] = 0.  Each term is the rounding residue of two products that cancel, so S (1e-13 where the products sum to 1e4) measures noise, not
+    scale; with a skewed K the entry is small but not zero and the same holds.  Two correct double evaluations differ there by about
+    0.6 * 2^-52 * P (measured: oracle against linearize_uvd, n = 15 .. 1025), P = the sum of the absolute row products w |J[k][i] J[k][j]|.
+    For these two entries of the RGB-D model alone the bound is 4 * 2^-52 * max(n S, P), four roundings of the products; every other
+    entry, and the whole stereo model, keeps 4 n 2^-52 S."""
+    S = np.zeros((2, 6, 6), np.longdouble)
+    T0 = np.vstack([case["T0"], [0, 0, 0, 1.0]])
+    f = mg.linearize_uvd if case["uvd"] else mg.linearize
+    H = f(T0, *align_args(case), False, K=K, abs_sum=S)[0] + damping * case["n"] * np.eye(6)
+    scale = case["n"] * S[0]
+    if case["uvd"]:
+        scale[2, 5] = scale[5, 2] = max(scale[2, 5], S[1][2, 5])
+    return H, np.asarray(4 * 2.0 ** -52 * scale, np.float64)
+
+
+def assert_align_vs_ref(r, ref, case, tag):
+    msg = "%s seed %d n %d" % (tag, case["seed"], case["n"])
+    rel = np.linalg.norm(r["T"] - ref["T"]) / np.linalg.norm(ref["T"])
+    print("%s: pose rel %.3g, E %.17g vs %.17g, its %d" % (msg, rel, r["total_error"], ref["total_error"], r["iterations"]))
+    assert rel <= 1e-9, (msg, rel)
+    np.testing.assert_array_equal(r["inlier"], ref["inlier"], err_msg=msg)
+    assert r["n_inliers"] == ref["n_inliers"] and r["iterations"] == ref["iterations"], (msg, r["n_inliers"], ref["n_inliers"], r["iterations"], ref["iterations"])
+    np.testing.assert_allclose(r["total_error"], ref["total_error"], rtol=1e-7, atol=1e-9, err_msg=msg)
+    assert_skipped(r, case, msg)
+
+
+def assert_align_vs_oracle(r, ro, case, tag):
+    msg = "%s seed %d n %d (oracle)" % (tag, case["seed"], case["n"])
+    np.testing.assert_array_equal(r["inlier"], ro["inlier"], err_msg=msg)
+    assert r["n_inliers"] == ro["n_inliers"] and r["iterations"] == ro["iterations"], (msg, r["n_inliers"], ro["n_inliers"], r["iterations"], ro["iterations"])
+    np.testing.assert_allclose(r["chi"], ro["chi"], rtol=1e-9, atol=1e-12, err_msg=msg)
+    np.testing.assert_allclose(r["T"], ro["T"], rtol=1e-9, atol=1e-12, err_msg=msg)
+    np.testing.assert_allclose(r["total_error"], ro["total_error"], rtol=1e-9, atol=1e-12, err_msg=msg)
+    assert_skipped(r, case, msg)
+
+
+def assert_skipped(r, case, msg):
+    sk = case["skipped"]
+    assert np.all(r["chi"][sk] == -1) and not r["inlier"][sk].any(), (msg, np.nonzero(sk)[0][:8])
+    if r["iterations"] > 0:
+        assert np.all(r["chi"][~sk] >= 0), msg
+
+
+def assert_H(H, Href, tol, msg):
+    err = np.abs(H - Href)
+    print("%s: max |dH| / bound %.3g" % (msg, float(np.max(np.where(tol > 0, err / np.where(tol > 0, tol, 1), err * 1e300)) if err.size else 0)))
+    assert np.all(err <= tol), (msg, float(err.max()), np.argwhere(err > tol)[:4].tolist())
+
+
+# ---- B. temporal matcher -----------------------------------------------------------------------------------------------------------
+TRACK_NP = [1, 63, 64, 65, 511, 512, 513, 2000]
+WIDE = 1300      # a window wider than the image
+
+
+def gen_track(seed, nP, nF, d):
+    """Previous points by their projection in the current frame (KITTI geometry), current features around them, clutter.  Built in:
+    clusters of more than VS_MAXCAND features in one window (kinds 3, 11: exact rescan), points whose only left candidate sits at the
+    projection with more than VS_MAXRCAND right candidates in its band (kind 15: the right list overflows while the left one does not), exact
+    Hamming ties, features on columns 15 / 16 / 31 / 32, projections on the first and last row and column, points behind the camera,
+    rivals for one feature."""
+    rng = np.random.default_rng(seed)
+    K, bh = KITTI_K, KITTI_B
+    T = np.eye(4)[:3].copy()
+    T[:, 3] = rng.normal(0, 0.05, 3)
+    ang = rng.normal(0, 0.01)
+    T[0, 0], T[0, 2], T[2, 0], T[2, 2] = np.cos(ang), np.sin(ang), -np.sin(ang), np.cos(ang)
+    R, t = T[:, :3], T[:, 3]
+    prev, fL, fR, usedL, usedR = [], [], [], set(), set()
+    dd = min(d, 60)
+
+    def add(side, used, r, c, desc):
+        if 0 <= r < ROWS and 0 <= c < COLS and (r, c) not in used:
+            used.add((r, c)); side.append((int(r), int(c), desc))
+            return True
+        return False
+
+    def add_prev(u, v, z, dl=None, epi=None):
+        q = np.array([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z])
+        dl = rng.integers(0, 256, 32, dtype=np.uint8) if dl is None else dl
+        prev.append((R.T @ (q - t), dl, near(rng, dl, int(rng.integers(0, 20))), int(rng.integers(-1, 2)) if epi is None else epi))
+        return dl
+    edge = [(0.5, 100.5), (COLS + 0.5, 100.5), (300.5, 0.5), (300.5, ROWS + 0.5), (COLS - 0.5, ROWS - 0.5), (15.5, 40.5), (16.5, 41.5), (31.5, 60.5), (32.5, 61.5)]
+    for ip in range(nP):
+        z = float(rng.uniform(4.0, 40.0))
+        kind = ip % 23 if nP >= 23 else -1
+        if kind == 22 and ip // 23 < len(edge):
+            u, v = edge[ip // 23]
+        else:
+            u, v = int(rng.integers(-6, COLS + 6)) + float(rng.uniform(0.1, 0.9)), int(rng.integers(-6, ROWS + 6)) + float(rng.uniform(0.1, 0.9))
+        if kind == 7:
+            z = -z                                                      # behind the camera: neither tracked nor lost
+        if kind == 15:
+            z = float(rng.uniform(4.0, 20.0))                           # disparity > 19 px: the whole band lies left of the left feature
+        if kind in (3, 11, 15):                                         # clusters: well inside, the feature at the projection itself
+            u, v = int(rng.integers(120, COLS - 80)) + 0.5, int(rng.integers(70, ROWS - 70)) + 0.5
+        dl = add_prev(u, v, z, epi=1 if kind == 11 else -1 if kind == 15 and ip % 2 else None)
+        col, row = int(u), int(v)
+        disp = -bh[0] / abs(z)
+        if kind in (3, 11):
+            add(fL, usedL, row, col, dl.copy())
+            tie = near(rng, dl, 6)
+            for _ in range(24):                                         # > VS_MAXCAND in the window, several with one descriptor
+                add(fL, usedL, row + int(rng.integers(-dd, dd + 1)), col + int(rng.integers(-dd, dd + 1)), tie.copy() if rng.random() < 0.4 else near(rng, dl, int(rng.integers(4, 50))))
+            colR = int(u - disp)
+            rtie = near(rng, dl, 5)
+            for _ in range(14):                                         # > VS_MAXRCAND in the band (kind 11: three rows, epipolar offset 1)
+                add(fR, usedR, row + (int(rng.integers(-1, 2)) if kind == 11 else 0), colR + int(rng.integers(-dd, dd + 1)), rtie.copy() if rng.random() < 0.4 else near(rng, dl, int(rng.integers(0, 45))))
+            continue
+        if kind == 15:                                                  # one left candidate, > VS_MAXRCAND right candidates in its band
+            add(fL, usedL, row, col, dl.copy())
+            colR = int(u - disp)
+            for _ in range(22):
+                add(fR, usedR, row + int(rng.integers(-1, 2)) * abs(prev[-1][3]), colR + int(rng.integers(-min(dd, 14), min(dd, 14) + 1)), near(rng, dl, int(rng.integers(0, 44))))
+            continue
+        if kind == 5:                                                   # the point the rival after it competes with: a feature both want
+            add(fL, usedL, row, col, near(rng, dl, 3))
+        for _ in range(int(rng.integers(0, 4))):
+            r, c = row + int(rng.integers(-dd - 1, dd + 2)), col + int(rng.integers(-dd - 1, dd + 2))
+            if rng.random() < 0.15:
+                c = 32 * (c // 32) + int(rng.choice([15, 16, 31, 32]))                 # on both sides of a 16 px cell border
+            df = near(rng, dl, int(rng.integers(0, 45)))
+            if add(fL, usedL, r, c, df):
+                for _ in range(int(rng.integers(0, 3))):
+                    add(fR, usedR, r + int(rng.integers(-1, 2)), int(round(c - disp)) + int(rng.integers(-3, 4)), near(rng, df, int(rng.integers(0, 35))))
+    for ip in range(5, nP - 1, 23):                                     # rivals replace the point after every 23rd + 5
+        cam, dl, dr, epi = prev[ip]
+        prev[ip + 1] = (cam + rng.normal(0, 0.005, 3), near(rng, dl, 2), dr, epi)
+    guard = 0
+    while (len(fL) < nF or len(fR) < nF) and guard < 20 * nF:
+        guard += 1
+        if len(fL) < nF:
+            add(fL, usedL, int(rng.integers(0, ROWS)), int(rng.integers(0, COLS)), rng.integers(0, 256, 32, dtype=np.uint8))
+        if len(fR) < nF:
+            add(fR, usedR, int(rng.integers(0, ROWS)), int(rng.integers(0, COLS)), rng.integers(0, 256, 32, dtype=np.uint8))
+    case = dict(seed=seed, nP=nP, d=d, T=T, prev=prev, fL=fL, fR=fR, tau_track=50.0, tau_tri=45.0,
+                cam=np.array([p[0] for p in prev]).reshape(-1, 3), pdL=np.array([p[1] for p in prev], np.uint8).reshape(-1, 32),
+                pdR=np.array([p[2] for p in prev], np.uint8).reshape(-1, 32), epi=np.array([p[3] for p in prev], np.int32),
+                rcL=np.array([(a[0], a[1]) for a in fL], np.int32).reshape(-1, 2), dL=np.array([a[2] for a in fL], np.uint8).reshape(-1, 32),
+                rcR=np.array([(a[0], a[1]) for a in fR], np.int32).reshape(-1, 2), dR=np.array([a[2] for a in fR], np.uint8).reshape(-1, 32))
+    return case
+
+
+def track_premises(case):
+    """From the inputs alone, with the candidate rules of k_track_candidates restated: per search mode the first left candidate of every
+    previous point (window, descriptor gate, 100 px gate of the distance mode; smallest (primary, row, column)), then
+      max_left        the largest left candidate count of a point (> VS_MAXCAND: exact rescan),
+      max_right[m]    the largest right candidate count (band around the first left candidate, its descriptor against tau_tri) among the
+                      points whose left list did NOT overflow: only those collect right candidates,
+      rivals[m]       features that are the first candidate of two or more points,
+      ties            equal distances among one point's left candidates,
+      edges           projections on column 0 / COLS and row 0 / ROWS, behind: points behind the camera,
+      ambiguous       a projection within 1e-9 px of the truncation (the reason to reject)."""
+    T, d = case["T"], case["d"]
+    q = case["cam"] @ T[:, :3].T + T[:, 3]
+    uvw = q @ KITTI_K.T
+    ok = uvw[:, 2] > 0
+    w = np.where(ok, uvw[:, 2], 1.0)
+    u, v = uvw[:, 0] / w, uvw[:, 1] / w
+    uR = (uvw[:, 0] + KITTI_B[0]) / w
+    near_int = lambda x: np.abs(x - np.rint(x)) < 1e-9
+    ambiguous = bool(np.any(ok & (near_int(u) | near_int(v) | near_int(uR))))
+    col, row = np.trunc(u), np.trunc(v)
+    ok &= (col >= 0) & (col <= COLS) & (row >= 0) & (row <= ROWS)
+    rcL, rcR = case["rcL"].astype(np.int64), case["rcR"].astype(np.int64)
+    maxL = ties = 0
+    maxR, firsts = {0: 0, 1: 0}, {0: [], 1: []}
+    for i in np.nonzero(ok)[0]:
+        inw = np.nonzero((np.abs(rcL[:, 0] - row[i]) <= d) & (np.abs(rcL[:, 1] - col[i]) <= d))[0]
+        dist = np.unpackbits(case["dL"][inw] ^ case["pdL"][i], axis=1).sum(1).astype(np.int64)
+        inw, dist = inw[dist < case["tau_track"]], dist[dist < case["tau_track"]]
+        maxL = max(maxL, len(inw))
+        ties += int(len(dist) - len(np.unique(dist)))
+        pix = (row[i] - rcL[inw, 0]) ** 2 + (col[i] - rcL[inw, 1]) ** 2
+        for by_app in (0, 1):
+            cand, prim = (inw, dist) if by_app else (inw[pix < 10000], pix[pix < 10000])
+            if not 1 <= len(cand) <= VS_MAXCAND:
+                continue
+            f = cand[np.lexsort((rcL[cand, 1], rcL[cand, 0], prim))[0]]
+            firsts[by_app].append(int(f))
+            ex, ey = np.float32(col[i]) - np.float32(rcL[f, 1]), np.float32(row[i]) - np.float32(rcL[f, 0])
+            colR, rowR = np.trunc(uR[i] - float(ex)), np.trunc(v[i] - float(ey))
+            if colR < 0 or colR > COLS or rowR < 0 or rowR > ROWS:
+                continue
+            e = abs(int(case["epi"][i]))
+            band = (np.abs(rcR[:, 0] - rowR) <= e) & (rcR[:, 1] >= colR - d) & (rcR[:, 1] < min(colR + d + 1, rcL[f, 1]))
+            maxR[by_app] = max(maxR[by_app], int((np.unpackbits(case["dR"][band] ^ case["dL"][f], axis=1).sum(1) < case["tau_tri"]).sum()))
+    rivals = {m: int((np.bincount(firsts[m], minlength=1) > 1).sum()) for m in (0, 1)}
+    edges = [int((ok & (col == 0)).sum()), int((ok & (col == COLS)).sum()), int((ok & (row == 0)).sum()), int((ok & (row == ROWS)).sum())]
+    return dict(max_left=maxL, max_right=maxR, rivals=rivals, ties=ties, edges=edges, ambiguous=ambiguous, behind=int((uvw[:, 2] <= 0).sum()))
+
+
+def run_track(api, case, by_app):
+    return api.track_match(case["T"], case["d"], case["tau_track"], case["tau_tri"], by_app, case["cam"], case["pdL"], case["pdR"], case["epi"],
+                           case["rcL"], case["dL"], case["rcR"], case["dR"])
+
+
+def ref_track(case, by_app):
+    tr, lost = mg.track_ref(KITTI_K, KITTI_B, ROWS, COLS, case["T"], case["prev"], case["fL"], case["fR"], case["d"], case["tau_track"], case["tau_tri"], bool(by_app), 1.0)
+    return np.array(tr, np.int32).reshape(-1, 4), np.array(lost, np.int32)
+
+
+def track_python_affordable(nP, d):
+    return (nP <= PY_TRACK_MAX and d <= 15) or (nP <= 65 and d <= 50) or nP == 1
+
+
+# ---- C. stereo matcher -------------------------------------------------------------------------------------------------------------
+STEREO_SIZES = [(0, 0), (0, 64), (64, 0), (1, 1), (64, 64), (513, 64), (513, 513), (2500, 513), (2500, 2500), (6000, 2500), (6000, 6000)]
+
+
+def gen_stereo(seed, nL, nR):
+    """Left features over the KITTI image, right = left shifted by a disparity with bit noise (some a row up or down), clutter; two rows
+    carry more than 64 features each, runs of equal descriptors along a row give ties and the ordering constraint.  One feature per pixel."""
+    rng = np.random.default_rng(seed)
+    usedL, usedR, L, Rr = set(), set(), [], []
+
+    def add(side, used, r, c, desc):
+        if 0 <= r < ROWS and 0 <= c < COLS and (r, c) not in used:
+            used.add((r, c)); side.append((int(r), int(c), desc))
+    dense = [int(x) for x in rng.choice(np.arange(5, ROWS - 5), 2, replace=False)] if nL >= 513 else []
+    guard = 0
+    while len(L) < nL and guard < 50 * (nL + 1):
+        guard += 1
+        r = dense[len(L) % 2] if dense and len(L) < 180 else int(rng.integers(0, ROWS))
+        c = int(rng.integers(0, COLS))
+        desc = rng.integers(0, 256, 32, dtype=np.uint8)
+        if L and rng.random() < 0.1:
+            r, desc = L[-1][0], L[-1][2].copy()                        # the same descriptor further along the row
+        n0 = len(L)
+        add(L, usedL, r, c, desc)
+        if len(L) > n0 and len(Rr) < nR and rng.random() < 0.8:
+            rr = r + (int(rng.integers(-1, 2)) if rng.random() < 0.3 else 0)
+            add(Rr, usedR, rr, c - int(rng.integers(0, 70)), near(rng, desc, int(rng.integers(0, 40))) if rng.random() < 0.7 else desc.copy())
+    guard = 0
+    while len(Rr) < nR and guard < 50 * (nR + 1):
+        guard += 1
+        add(Rr, usedR, int(rng.integers(0, ROWS)), int(rng.integers(0, COLS)), rng.integers(0, 256, 32, dtype=np.uint8))
+    arr = lambda S: (np.array([(a[0], a[1]) for a in S], np.int32).reshape(-1, 2), np.array([a[2] for a in S], np.uint8).reshape(-1, 32))
+    rcL, dL = arr(L); rcR, dR = arr(Rr)
+    per_row = np.bincount(rcL[:, 0], minlength=ROWS).max() if len(L) else 0
+    return dict(seed=seed, rcL=rcL, dL=dL, rcR=rcR, dR=dR, tau=40.0, max_per_row=int(per_row))
+
+
+def ref_stereo(case, epi):
+    offsets = [0] + [s * u for u in range(1, epi + 1) for s in (1, -1)]
+    tl = lambda rc, ds: ([tuple(int(v) for v in p) for p in rc], list(ds))
+    rcL, dL = tl(case["rcL"], case["dL"]); rcR, dR = tl(case["rcR"], case["dR"])
+    return np.array(mg.stereo_sweep(rcL, dL, rcR, dR, case["tau"], 1.0, offsets), np.int32).reshape(-1, 4)
+
+
+# ---- D. landmark refinement --------------------------------------------------------------------------------------------------------
+LANDMARK_N = [1, 511, 512, 513, 3000]
+TRACK_LENGTHS = [1, 2, 8, 9, 10, 31, 32, 33, 60]
+POSE_TABLES = [47, 48, 49, 100]
+
+
+def gen_landmark(seed, n, n_frames):
+    """gen_landmark's scenarios (plain refinement, kernel saturation, reset to the mean, newest-first lists, a kept estimate) at any batch size,
+    track lengths from TRACK_LENGTHS (as far as the pose table reaches)."""
+    rng = np.random.default_rng(seed)
+    w2c, c2w = [], []
+    for f in range(n_frames):
+        v = np.array([0.02 * f + rng.normal(0, 0.01), rng.normal(0, 0.01), 0.9 * f + rng.normal(0, 0.02), rng.normal(0, 0.004), 0.01 * np.sin(f / 5.0), rng.normal(0, 0.004)])
+        Cw = mg.v2t(v)
+        c2w.append(Cw[:3, :]); w2c.append(np.linalg.inv(Cw)[:3, :])
+    lengths = [m for m in TRACK_LENGTHS if m <= n_frames]
+    offsets, frame_of, cam, world, updates, meas_all = [0], [], [], [], [], []
+    for i in range(n):
+        length = lengths[int(rng.integers(0, len(lengths)))]
+        f0 = int(rng.integers(0, n_frames - length + 1))
+        X = c2w[f0][:, :3] @ np.array([rng.uniform(-6, 6), rng.uniform(-2, 2), rng.uniform(4 + 0.9 * length, 40 + 0.9 * length)]) + c2w[f0][:, 3]
+        kind = (i + seed) % 6
+        meas = []
+        for k in range(length):
+            f = f0 + k
+            pc = w2c[f][:, :3] @ X + w2c[f][:, 3]
+            noise = rng.normal(0, 0.02 * max(pc[2], 1.0) / 10, 3)
+            if kind == 3 and k % 2 == 0:
+                noise += rng.normal(0, 8.0, 3)
+            mc = pc + noise
+            mc[2] = max(mc[2], 0.3)
+            meas.append((f, mc))
+        if kind == 4:
+            meas = meas[::-1]
+        w0 = X + rng.normal(0, 0.3, 3)
+        up0 = length - 1 if kind != 5 else length + 5
+        if kind == 2:
+            w0 = X + np.array([0, 0, -200.0 - 0.9 * n_frames])
+        offsets.append(offsets[-1] + len(meas)); frame_of += [m[0] for m in meas]; cam += [m[1] for m in meas]
+        world.append(w0); updates.append(up0); meas_all.append(meas)
+    return dict(seed=seed, n=n, w2c=np.array(w2c), c2w=np.array(c2w), offsets=np.array(offsets, np.int32), frame_of=np.array(frame_of, np.int32),
+                cam=np.array(cam).reshape(-1, 3), world=np.array(world), updates=np.array(updates, np.int32), meas=meas_all)
+
+
+def run_landmark(api, cfg, case):
+    return api.landmark_update(cfg, case["offsets"], case["frame_of"], case["w2c"], case["c2w"], case["cam"], case["world"], case["updates"])
+
+
+def ref_landmark(case):
+    out = [mg.landmark_update_ref(case["w2c"], case["c2w"], case["meas"][i], case["world"][i], int(case["updates"][i])) for i in range(case["n"])]
+    return np.array([o[0] for o in out]).reshape(-1, 3), np.array([o[1] for o in out], np.int32)
+
+
+def assert_landmark(w, u, wr, ur, case, tag):
+    msg = "%s seed %d n %d" % (tag, case["seed"], case["n"])
+    np.testing.assert_array_equal(u, ur, err_msg=msg)
+    np.testing.assert_allclose(w, wr, rtol=1e-9, atol=1e-9, err_msg=msg)
+    kept = np.all(wr == case["world"], axis=1)
+    np.testing.assert_array_equal(w[kept], case["world"][kept], err_msg=msg + " kept")
+    moved = ~kept
+    return int(moved.sum()), int(kept.sum()), int((u != case["updates"]).sum())
+
+
+# ---- E. small entries --------------------------------------------------------------------------------------------------------------
+SHAPES = [(5, 40), (7, 7), (8, 9), (47, 63), (48, 64), (49, 65), (57, 57), (63, 200), (97, 129), (130, 70), (200, 333), (376, 1241), (480, 752)]
+PIC_SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1000, 5000]
+
+
+def gen_point_in_camera(seed, n):
+    """Pixel pairs of points between 2 m (generous parallax) and 2000 m (about a third of a pixel) under a 0.9 m forward + sideways motion."""
+    rng = np.random.default_rng(seed)
+    T = mg.v2t(np.array([0.3, -0.02, -0.9, 0.001, 0.012, -0.0005]))[:3]
+    z = np.exp(rng.uniform(np.log(2.0), np.log(2000.0), n))
+    u, v = rng.uniform(50, COLS - 50, n), rng.uniform(20, ROWS - 20, n)
+    X = np.stack([(u - KITTI_K[0, 2]) * z / KITTI_K[0, 0], (v - KITTI_K[1, 2]) * z / KITTI_K[1, 1], z], 1)
+    Pc = X @ T[:, :3].T + T[:, 3]
+    xc = (Pc @ KITTI_K.T)
+    xc = xc[:, :2] / xc[:, 2:3] + rng.normal(0, 0.2, (n, 2))
+    return dict(seed=seed, xp=np.stack([u, v], 1).astype(np.float32), xc=xc.astype(np.float32), T=T, K=KITTI_K)
+
+
+def ref_point_in_camera(case):
+    return np.array([mg.point_in_camera_ref(case["xp"][i], case["xc"][i], case["T"], case["K"]) for i in range(len(case["xp"]))]).reshape(-1, 3)
+
+
+def image(rng, rows, cols):
+    bs = int(rng.integers(3, 9))
+    base = rng.integers(20, 236, (rows // bs + 2, cols // bs + 2))
+    img = np.kron(base, np.ones((bs, bs), np.int64))[:rows, :cols]
+    return np.clip(img + rng.integers(-6, 7, img.shape), 0, 255).astype(np.uint8)
+
+
+def resize_targets(rows, cols):
+    """down by 1.2 (the ORB pyramid), odd sizes, up"""
+    return [(max(int(round(rows / 1.2)), 1), max(int(round(cols / 1.2)), 1)), ((rows * 2 // 3) | 1, (cols * 2 // 3) | 1), (rows + 3, cols + 5), (rows // 2 + 1, cols)]
+
+
+def harris_points(rng, rows, cols, n):
+    """points at least 16 px inside (the entry's gate), the four extreme corners among them; none for images too small"""
+    if rows < 33 or cols < 33:
+        return np.zeros((0, 2), np.int16)
+    pts = np.stack([rng.integers(16, cols - 16, n), rng.integers(16, rows - 16, n)], 1)
+    pts[:4] = [(16, 16), (cols - 17, 16), (16, rows - 17), (cols - 17, rows - 17)]
+    return pts.astype(np.int16)
+
+
+DT_ROWS, DT_COLS, DT_F = 120, 160, 150.0
+DT_K = np.array([[DT_F, 0, 80.0], [0, DT_F, 60.0], [0, 0, 1.0]])
+DT_SIZES = [1, 64, 513, 1500]
+
+
+def gen_depth_track(seed, nP, d):
+    """gen_depth_track's crowded scene at any size; every tenth point's window holds more than VS_DT_CAP features (d >= 5) and every tenth + 5
+    more than VS_DT_K; a fifth of the pixels have no depth and a tenth are below the minimum."""
+    rng = np.random.default_rng(seed)
+    rows, cols = DT_ROWS, DT_COLS
+    T = np.eye(4)[:3].copy()
+    T[:, 3] = rng.normal(0, 0.02, 3)
+    ang = rng.normal(0, 0.01)
+    T[0, 0], T[0, 2], T[2, 0], T[2, 2] = np.cos(ang), np.sin(ang), -np.sin(ang), np.cos(ang)
+    zmap = rng.uniform(0.5, 6.0, (rows, cols)).astype(np.float32)
+    zmap[rng.random((rows, cols)) < 0.2] = np.float32(10.0)
+    zmap[rng.random((rows, cols)) < 0.1] = np.float32(0.05)
+    space = mg.depth_track_space(zmap, DT_K[0, 2], DT_K[1, 2], DT_F)
+    prev, feats, used = [], [], set()
+    for ip in range(nP):
+        z = float(rng.uniform(0.8, 6.0))
+        u, v = int(rng.integers(-4, cols + 4)) + float(rng.uniform(0.1, 0.9)), int(rng.integers(-4, rows + 4)) + float(rng.uniform(0.1, 0.9))
+        crowd = {0: 3 * VS_DT_CAP, 5: 2 * VS_DT_K}.get(ip % 10, 0)
+        if crowd:
+            u, v = int(rng.integers(20, cols - 20)) + 0.5, int(rng.integers(20, rows - 20)) + 0.5
+        if ip % 17 == 16:
+            z = -z
+        q = np.array([(u - DT_K[0, 2]) * z / DT_F, (v - DT_K[1, 2]) * z / DT_F, z])
+        dp = rng.integers(0, 256, 32, dtype=np.uint8)
+        prev.append((T[:, :3].T @ (q - T[:, 3]), dp, int(rng.random() < 0.5), int(rng.random() < 0.15)))
+        tie = near(rng, dp, 7)
+        for _ in range(crowd if crowd else int(rng.integers(0, 3))):
+            r, c = int(v) + int(rng.integers(-d - (0 if crowd else 1), d + (1 if crowd else 2))), int(u) + int(rng.integers(-d - (0 if crowd else 1), d + (1 if crowd else 2)))
+            if 0 <= r < rows and 0 <= c < cols and (r, c) not in used:
+                used.add((r, c)); feats.append((r, c, tie.copy() if crowd and rng.random() < 0.3 else near(rng, dp, int(rng.integers(0, 45)))))
+        if ip % 5 == 4:
+            prev[-1] = (prev[-2][0] + rng.normal(0, 0.005, 3), near(rng, prev[-2][1], 3), 1, 0)      # a rival of the point before
+    for _ in range(60):
+        r, c = int(rng.integers(0, rows)), int(rng.integers(0, cols))
+        if (r, c) not in used:
+            used.add((r, c)); feats.append((r, c, rng.integers(0, 256, 32, dtype=np.uint8)))
+    rc = np.array([(a[0], a[1]) for a in feats], np.int32).reshape(-1, 2)
+    q = np.array([p[0] for p in prev]).reshape(-1, 3) @ T[:, :3].T + T[:, 3]
+    uvw = q @ DT_K.T
+    ok = uvw[:, 2] > 0
+    w = np.where(ok, uvw[:, 2], 1.0)
+    uu, vv = uvw[:, 0] / w, uvw[:, 1] / w
+    ambiguous = bool(np.any(ok & ((np.abs(uu - np.rint(uu)) < 1e-9) | (np.abs(vv - np.rint(vv)) < 1e-9))))
+    ok &= (uu >= 0) & (np.trunc(uu) <= cols) & (vv >= 0) & (np.trunc(vv) <= rows)
+    counts = [int(((np.abs(rc[:, 0] - np.trunc(vv[i])) <= d) & (np.abs(rc[:, 1] - np.trunc(uu[i])) <= d)).sum()) for i in np.nonzero(ok)[0]]
+    return dict(seed=seed, nP=nP, d=d, T=T, space=space, prev=prev, feats=feats, tau=35.0, ambiguous=ambiguous, max_window=max(counts + [0]),
+                over_k=sum(1 for k in counts if VS_DT_K < k <= VS_DT_CAP), over_cap=sum(1 for k in counts if k > VS_DT_CAP),
+                depthless=int((zmap[rc[:, 0], rc[:, 1]] >= 10.0).sum()),
+                cam=np.array([p[0] for p in prev]).reshape(-1, 3), pd=np.array([p[1] for p in prev], np.uint8).reshape(-1, 32),
+                flags=np.array([p[2] | (p[3] << 1) for p in prev], np.uint8), rc=rc, desc=np.array([a[2] for a in feats], np.uint8).reshape(-1, 32))
+
+
+def depth_params(tri):
+    from vslam_pose_estimation_framework_amd.capi import DepthParams
+    Ki = np.linalg.inv(DT_K)
+    return DepthParams.make(DT_ROWS, DT_COLS, DT_K, Ki, Ki, np.eye(4)[:3], 1e-3, 0.1, 10.0, int(tri), 0, 6)
+
+
+def run_depth_track(api, case, by_app, tri):
+    tr, xyz, tmp, lost, nlm = api.depth_track(depth_params(tri), case["space"], case["T"], case["d"], case["tau"], by_app, case["cam"], case["pd"], case["flags"],
+                                              case["rc"], case["desc"])
+    return tr, tmp, lost, nlm, xyz
+
+
+def ref_depth_track(case, by_app, tri):
+    tr, tmp, lost, nlm = mg.depth_track_ref(DT_K, DT_ROWS, DT_COLS, case["space"], case["T"], case["prev"], case["feats"], case["d"], case["tau"], bool(by_app), 0.1, 10.0, tri)
+    return np.array(tr, np.int32).reshape(-1, 2), np.array(tmp, np.int32).reshape(-1, 2), np.array(lost, np.int32), nlm
+
+
+# ---- sweeps: `api` is the implementation under test, `orc` the oracle (None in the CPU test, where the oracle is under test), `python`
+# switches the comparison with the Python restatement on; make_api / make_orc create the extra contexts a case needs ----------------
+def _contexts(make_api, make_orc, **fields):
+    out = []
+    for make in (make_api, make_orc):
+        if make is None:
+            out.append(None)
+            continue
+        a = make()
+        a.create(config_with(a, **fields), 0, 1)
+        out.append(a)
+    return out
+
+
+def _destroy(pair):
+    for a in pair:
+        if a is not None:
+            a.destroy()
+
+
+def sweep_align_converged(api, orc, rej, uvd, sizes=ALIGN_SIZES, base_seed=5000, K=None, python_max=PY_ALIGN_MAX):
+    """Converged runs at every size; seams carry skipped rows and outliers; 1536 also with the whole wave 512 .. 575 skipped."""
+    total = 0
+    for n in sizes:
+        for skip_wave in ((False, True) if n == 1536 else (False,)):
+            seed = base_seed + 10 * n + int(skip_wave) + (5 if uvd else 0)
+            for attempt in range(4):
+                case = gen_align(seed + 1000000 * attempt, n, uvd, K=KITTI_K if K is None else K, skip_wave=skip_wave)
+                ref = None
+                if 0 < n <= python_max:
+                    ref = ref_align(case, rej, K=K)
+                    if ref is None:
+                        continue
+                break
+            else:
+                raise AssertionError("four rejected draws in a row, seed %d" % seed)
+            if skip_wave:
+                assert case["skipped"][512:576].all()
+            r = run_align(api, case)
+            if orc is not None:
+                assert_align_vs_oracle(r, run_align(orc, case), case, "converged")
+            if ref is not None:
+                assert_align_vs_ref(r, ref, case, "converged")
+            if n == 0:
+                np.testing.assert_array_equal(r["T"], case["T0"])
+                assert r["n_inliers"] == 0
+            total += n * r["iterations"]
+    return total
+
+
+def sweep_align_gate(api, orc, rej, uvd):
+    """Exactly 100 certain inliers: no inlier-only round; 101: they run (aligner_minimum_number_of_inliers = 100, UVD: hard-wired)."""
+    rounds = 0
+    # the inliers must also outnumber everything else (skipped rows count as outliers), so n <= 2 k - 1: the gate cannot sit in a later chunk
+    for k, n in ((100, 140), (101, 141), (100, 199), (101, 201)):
+        case = gen_align(7000 + k + n + (3 if uvd else 0), n, uvd, certain_inliers=k)
+        ref = ref_align(case, rej)
+        assert ref is not None, "rejected gate case, seed %d" % case["seed"]
+        assert ref["n_inliers"] == k, (case["seed"], ref["n_inliers"])
+        assert (ref["refine_rounds"] > 0) == (k == 101), (case["seed"], k, ref["refine_rounds"])
+        r = run_align(api, case)
+        if orc is not None:
+            assert_align_vs_oracle(r, run_align(orc, case), case, "gate %d" % k)
+        assert_align_vs_ref(r, ref, case, "gate %d" % k)
+        rounds += ref["refine_rounds"]
+    return rounds
+
+
+def sweep_align_first_round(make_api, make_orc, uvd, sizes=ALIGN_SIZES, K=None):
+    """aligner_maximum_number_of_iterations = 1: H_out is the first round's damped normal matrix."""
+    fields = dict(aligner_maximum_number_of_iterations=1)
+    if K is not None:
+        fields["K"] = K
+    pair = _contexts(make_api, make_orc, **fields)
+    total = 0
+    try:
+        for n in sizes:
+            case = gen_align(9000 + n + (7 if uvd else 0), n, uvd, K=KITTI_K if K is None else K)
+            Href, tol = first_round_H(case, 5.0, K)
+            r = run_align(pair[0], case)
+            assert r["iterations"] == 1, (n, r["iterations"])
+            assert_H(r["H"], Href, tol, "first round H seed %d n %d uvd %d" % (case["seed"], n, uvd))
+            if pair[1] is not None:
+                ro = run_align(pair[1], case)
+                assert_align_vs_oracle(r, ro, case, "first round")
+            total += n
+    finally:
+        _destroy(pair)
+    return total
+
+
+def sweep_align_fallback(make_api, make_orc, uvd):
+    """aligner_damping = 0 and all translation weights 0: H has exactly zero rows and columns 0 .. 2, the unpivoted elimination must refuse and the
+    full-pivot solver must stop at rank 3 — translation update exactly 0, rotation update = solution of the rotational 3 x 3 block."""
+    total = 0
+    for max_it in (1, 3):
+        pair = _contexts(make_api, make_orc, aligner_damping=0.0, aligner_maximum_number_of_iterations=max_it)
+        try:
+            for n in (0, 64, 513):
+                case = gen_align(11000 + n + max_it + (9 if uvd else 0), n, uvd, v_true=V_ROT, noise=0.1, zero_translation_weights=True)
+                if uvd:
+                    case["w_d"] = np.zeros(n)          # the depth row's Jacobian has translation columns only through the weights: keep it out
+                r = run_align(pair[0], case)
+                msg = "fallback seed %d n %d max_it %d" % (case["seed"], n, max_it)
+                if pair[1] is not None:
+                    assert_align_vs_oracle(r, run_align(pair[1], case), case, msg)
+                if n == 0:
+                    np.testing.assert_array_equal(r["T"], case["T0"], err_msg=msg)
+                    assert np.all(r["H"] == 0), msg
+                    continue
+                assert np.all(r["H"][:3, :] == 0) and np.all(r["H"][:, :3] == 0), msg
+                assert np.all(r["T"][:, 3] == 0), (msg, r["T"][:, 3])
+                ref = ref_align(case, None, damping=0.0, max_it=max_it, solve=full_piv_solve)
+                assert_align_vs_ref(r, ref, case, msg)
+                if max_it == 1:
+                    f = mg.linearize_uvd if uvd else mg.linearize
+                    H, b = f(np.eye(4), *align_args(case), False)[:2]
+                    assert np.linalg.cond(H[3:, 3:]) < 1e6, msg
+                    dx = np.concatenate([np.zeros(3), np.linalg.solve(H[3:, 3:], -b[3:])])
+                    Tn = mg.v2t(dx) @ np.eye(4)
+                    Rn = Tn[:3, :3]
+                    Tn[:3, :3] = Rn - 0.5 * Rn @ (Rn.T @ Rn - np.eye(3))
+                    np.testing.assert_allclose(r["T"], Tn[:3], rtol=1e-9, atol=1e-12, err_msg=msg)
+                    assert np.linalg.norm(r["T"][:, :3] - np.eye(3)) > 1e-4, msg      # the update is not trivially zero
+                total += n
+        finally:
+            _destroy(pair)
+    return total
+
+
+def sweep_track(api, orc, rej, python=True, sizes=TRACK_NP):
+    total = 0
+    for nP in sizes:
+        for d in (1, 15, 50) + ((WIDE,) if nP in (1, 63) else ()):
+            nF = int(np.clip(3 * nP + 500, 500, 6000)) if d != WIDE else 500
+            for attempt in range(4):                                   # a rejected draw is redrawn: no size is lost
+                seed = 13000 + 10 * nP + d + 1000000 * attempt
+                case = gen_track(seed, nP, nF, d)
+                prem = track_premises(case)
+                rej.draws += 1
+                if not prem["ambiguous"]:
+                    break
+                rej.rejected += 1
+            else:
+                raise AssertionError("four rejected draws in a row, seed %d" % seed)
+            assert len(case["rcL"]) >= 500 and len(case["rcR"]) >= 500, seed
+            if nP >= 63 and d >= 15:
+                assert prem["max_left"] > VS_MAXCAND and prem["ties"] > 0 and prem["behind"] > 0, (seed, prem)
+                assert prem["max_right"][0] > VS_MAXRCAND and prem["max_right"][1] > VS_MAXRCAND, (seed, prem)
+                assert prem["rivals"][0] > 0 and prem["rivals"][1] > 0, (seed, prem)
+            if nP >= 511:
+                assert min(prem["edges"]) > 0, (seed, prem)
+            for by_app in (1, 0):
+                tr, lost = run_track(api, case, by_app)
+                msg = "track seed %d nP %d d %d by_appearance %d" % (seed, nP, d, by_app)
+                if orc is not None:
+                    to, lo = run_track(orc, case, by_app)
+                    np.testing.assert_array_equal(tr, to, err_msg=msg + " (oracle)")
+                    np.testing.assert_array_equal(lost, lo, err_msg=msg + " lost (oracle)")
+                if python and track_python_affordable(nP, d):
+                    tp, lp = ref_track(case, by_app)
+                    np.testing.assert_array_equal(tr, tp, err_msg=msg)
+                    np.testing.assert_array_equal(lost, lp, err_msg=msg + " lost")
+                total += len(tr)
+    return total
+
+
+def sweep_stereo(make_api, make_orc, python=True, sizes=STEREO_SIZES):
+    from vslam_pose_estimation_framework_amd.capi import VslamError
+    total = 0
+    for epi in (0, 1):
+        for binning in (0, 1):
+            pair = _contexts(make_api, make_orc, maximum_epipolar_search_offset_pixels=epi, enable_keypoint_binning=binning)
+            try:
+                for nL, nR in sizes:
+                    case = gen_stereo(17000 + nL + 7 * nR + epi, nL, nR)
+                    if nL >= 513:
+                        assert case["max_per_row"] > 64, (case["seed"], case["max_per_row"])
+                    args = (case["tau"], case["rcL"], case["dL"], case["rcR"], case["dR"])
+                    msg = "stereo seed %d %d x %d epi %d binning %d" % (case["seed"], nL, nR, epi, binning)
+                    out = pair[0].stereo_match(*args)
+                    if pair[1] is not None:
+                        np.testing.assert_array_equal(out, pair[1].stereo_match(*args), err_msg=msg + " (oracle)")
+                    if python and not binning and max(nL, nR) <= PY_STEREO_MAX:
+                        np.testing.assert_array_equal(out, ref_stereo(case, epi), err_msg=msg)
+                    if len(out) > 1:
+                        try:
+                            pair[0].stereo_match(*args, cap=len(out) - 1)
+                            raise AssertionError(msg + ": capacity overflow not reported")
+                        except VslamError as e:
+                            assert e.code == -4, msg
+                        np.testing.assert_array_equal(pair[0].stereo_match(*args, cap=len(out)), out, err_msg=msg + " exact capacity")
+                    total += len(out)
+            finally:
+                _destroy(pair)
+    return total
+
+
+def sweep_landmark(api, orc, python=True, sizes=LANDMARK_N):
+    moved = kept = taken = 0
+    for k, n in enumerate(sizes):
+        for n_frames in (POSE_TABLES if n <= 513 else POSE_TABLES[-1:]):
+            case = gen_landmark(19000 + n + n_frames, n, n_frames)
+            w, u = run_landmark(api, api.cfg, case)
+            if orc is not None:
+                wo, uo = run_landmark(orc, orc.default_config("kitti"), case)
+                assert_landmark(w, u, wo, uo, case, "landmark (oracle)")
+            if python and n <= PY_LANDMARK_MAX:
+                wr, ur = ref_landmark(case)
+                a, b, c = assert_landmark(w, u, wr, ur, case, "landmark")
+            else:
+                a, b, c = int((~np.all(w == case["world"], axis=1)).sum()), int(np.all(w == case["world"], axis=1).sum()), int((u != case["updates"]).sum())
+            moved += a; kept += b; taken += c
+    return moved, kept, taken
+
+
+def sweep_point_in_camera(api, orc):
+    total = 0
+    for n in PIC_SIZES:
+        case = gen_point_in_camera(23000 + n, n)
+        out = api.point_in_camera(case["xp"], case["xc"], case["T"], case["K"])
+        np.testing.assert_allclose(out, ref_point_in_camera(case), rtol=1e-9, atol=1e-9, err_msg="point_in_camera seed %d" % case["seed"])
+        if orc is not None:
+            np.testing.assert_allclose(out, orc.point_in_camera(case["xp"], case["xc"], case["T"], case["K"]), rtol=1e-9, atol=1e-9, err_msg="point_in_camera seed %d (oracle)" % case["seed"])
+        deg = api.point_in_camera(case["xp"], case["xp"], np.eye(4)[:3], case["K"])       # exactly no parallax
+        assert np.all(np.isfinite(deg)), case["seed"]
+        total += n
+    return total
+
+
+def sweep_resize_harris(api, orc, python=True):
+    rng = np.random.default_rng(29000)
+    umax = mg.orb_umax_ref(15)
+    pixels = points = 0
+    for rows, cols in SHAPES:
+        img = image(rng, rows, cols)
+        small = rows * cols <= PY_IMAGE_MAX
+        for dr, dc in resize_targets(rows, cols):
+            out = api.resize_linear_u8(img, dr, dc)
+            msg = "resize seed 29000 %dx%d -> %dx%d" % (rows, cols, dr, dc)
+            if orc is not None:
+                np.testing.assert_array_equal(out, orc.resize_linear_u8(img, dr, dc), err_msg=msg + " (oracle)")
+            if python and small:
+                np.testing.assert_array_equal(out, mg.resize_linear_ref(img, dr, dc), err_msg=msg)
+            pixels += dr * dc
+        pts = harris_points(rng, rows, cols, 300 if not small else 60)
+        if len(pts):
+            resp, ang = api.harris_angle(img, pts)
+            msg = "harris_angle seed 29000 %dx%d" % (rows, cols)
+            if orc is not None:
+                ro, ao = orc.harris_angle(img, pts)
+                np.testing.assert_array_equal(resp.view(np.uint32), ro.view(np.uint32), err_msg=msg + " (oracle)")
+                np.testing.assert_array_equal(ang.view(np.uint32), ao.view(np.uint32), err_msg=msg + " angle (oracle)")
+            if python and small:
+                rr = np.array([mg.harris_ref(img, int(x), int(y)) for x, y in pts], np.float32)
+                ar = np.array([mg.ic_angle_ref(img, int(x), int(y), 15, umax) for x, y in pts], np.float32)
+                np.testing.assert_array_equal(resp.view(np.uint32), rr.view(np.uint32), err_msg=msg)
+                np.testing.assert_array_equal(ang.view(np.uint32), ar.view(np.uint32), err_msg=msg + " angle")
+            points += len(pts)
+    return pixels, points
+
+
+def sweep_depth_track(api, orc, rej, python=True):
+    total = temp = 0
+    for nP in DT_SIZES:
+        for d in (2, 7):
+            for attempt in range(4):
+                seed = 31000 + 10 * nP + d + 1000000 * attempt
+                case = gen_depth_track(seed, nP, d)
+                rej.draws += 1
+                if not case["ambiguous"]:
+                    break
+                rej.rejected += 1
+            else:
+                raise AssertionError("four rejected draws in a row, seed %d" % seed)
+            if nP >= 64:
+                assert case["over_k"] > 0 and case["depthless"] > 10, (seed, case["over_k"], case["depthless"])
+                if d >= 5:
+                    assert case["over_cap"] > 0 and case["max_window"] > VS_DT_CAP, (seed, case["max_window"])
+            for by_app in (1, 0):
+                for tri in (1, 0):
+                    tr, tmp, lost, nlm, xyz = run_depth_track(api, case, by_app, tri)
+                    msg = "depth_track seed %d nP %d d %d by_appearance %d triangulation %d" % (seed, nP, d, by_app, tri)
+                    refs = []
+                    if orc is not None:
+                        refs.append((run_depth_track(orc, case, by_app, tri)[:4], " (oracle)"))
+                    if python:
+                        refs.append((ref_depth_track(case, by_app, tri), ""))
+                    for (tr2, tmp2, lost2, nlm2), who in refs:
+                        np.testing.assert_array_equal(tr, tr2, err_msg=msg + who)
+                        np.testing.assert_array_equal(tmp, tmp2, err_msg=msg + " temporary" + who)
+                        np.testing.assert_array_equal(lost, lost2, err_msg=msg + " lost" + who)
+                        assert nlm == nlm2, msg + who
+                    want = np.array([case["space"][case["rc"][f, 0], case["rc"][f, 1]] for _, f in tr], np.float64).reshape(-1, 3)
+                    np.testing.assert_array_equal(xyz, want, err_msg=msg + " xyz")
+                    total += len(tr); temp += len(tmp)
+    return total, temp

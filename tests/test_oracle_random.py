@@ -1,0 +1,77 @@
+"""CPU: the oracle's stand-alone solver and matcher entries against the Python restatements of tests/golden/make_golden.py on the seeded
+random cases of tests/random_cases.py.  This is where the generators, their premises and the tolerances are validated without a GPU; the
+sizes the Python references can afford are listed at the top of random_cases.py.  The volume thresholds are about two thirds of what the
+oracle produces (counts that the case list fixes are asserted exactly)."""
+import pytest
+
+import random_cases as rc
+from _oracle import Oracle
+
+
+@pytest.mark.parametrize("uvd", [False, True], ids=["stereo", "uvd"])
+def test_aligner_converged_random_sizes(oracle, uvd):
+    rej = rc.Rejections()
+    total = rc.sweep_align_converged(oracle, None, rej, uvd, sizes=[n for n in rc.ALIGN_SIZES if n <= rc.PY_ALIGN_MAX])
+    rounds = rc.sweep_align_gate(oracle, None, rej, uvd)
+    rej.check("aligner uvd=%d" % uvd)
+    print("measurement rounds", total, "inlier-only rounds", rounds)
+    assert total > 58000 and rounds >= 4
+
+
+@pytest.mark.parametrize("uvd", [False, True], ids=["stereo", "uvd"])
+def test_aligner_first_round_normal_matrix(uvd):
+    total = rc.sweep_align_first_round(Oracle, None, uvd, sizes=[n for n in rc.ALIGN_SIZES if n <= rc.PY_ALIGN_MAX])
+    assert total == sum(n for n in rc.ALIGN_SIZES if n <= rc.PY_ALIGN_MAX)
+
+
+@pytest.mark.parametrize("uvd", [False, True], ids=["stereo", "uvd"])
+def test_aligner_general_camera_matrix(uvd):
+    rej = rc.Rejections()
+    o = Oracle()
+    o.create(rc.config_with(o, K=rc.SKEW_K), 0, 1)
+    try:
+        total = rc.sweep_align_converged(o, None, rej, uvd, sizes=[64, 513, 1025], base_seed=6000, K=rc.SKEW_K)
+    finally:
+        o.destroy()
+    total += rc.sweep_align_first_round(Oracle, None, uvd, sizes=[64, 513, 1025], K=rc.SKEW_K)
+    rej.check("aligner general K uvd=%d" % uvd)
+    assert total > 16000 + 64 + 513 + 1025
+
+
+@pytest.mark.parametrize("uvd", [False, True], ids=["stereo", "uvd"])
+def test_aligner_rank_deficient_fallback(uvd):
+    assert rc.sweep_align_fallback(Oracle, None, uvd) == 2 * (64 + 513)
+
+
+def test_track_match_random(oracle):
+    rej = rc.Rejections()
+    total = rc.sweep_track(oracle, None, rej)
+    rej.check("track_match")
+    print("tracked", total)
+    assert total > 4300
+
+
+def test_stereo_match_random():
+    total = rc.sweep_stereo(Oracle, None)
+    print("stereo matches", total)
+    assert total > 17500
+
+
+def test_landmark_update_random(oracle):
+    moved, kept, taken = rc.sweep_landmark(oracle, None)
+    print("landmarks moved", moved, "kept", kept, "estimates taken", taken)
+    assert moved > 4800 and kept > 1200 and taken > 3800
+
+
+def test_small_entries_random(oracle):
+    assert rc.sweep_point_in_camera(oracle, None) == sum(rc.PIC_SIZES)
+    pixels, points = rc.sweep_resize_harris(oracle, None)
+    assert pixels > 1650000 and points == 1080
+
+
+def test_depth_track_random(oracle):
+    rej = rc.Rejections()
+    total, temp = rc.sweep_depth_track(oracle, None, rej)
+    rej.check("depth_track")
+    print("tracked", total, "temporary", temp)
+    assert total > 3200 and temp > 380
