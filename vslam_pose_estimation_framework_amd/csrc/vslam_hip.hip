@@ -143,8 +143,6 @@ static hipError_t tmp_get(vslam_ctx* c, void** p, size_t bytes) {
   T.used += bytes;
   return hipSuccess;
 }
-template <typename T>
-static hipError_t tmp_alloc(vslam_ctx* c, T** p, size_t count) { return tmp_get(c, (void**)p, count * sizeof(T)); }
 // start of an entry point: everything handed out before is dead (every entry synchronises before it returns its results); blocks that
 // had to be chained during a call are merged into one, so that a steady caller allocates nothing
 static void tmp_reset(vslam_ctx* c) {
@@ -544,6 +542,22 @@ static void depth_map_free(vslam_ctx* c) {
   (void)hipFree(m.depth); (void)hipFree(m.key); (void)hipFree(m.last); (void)hipFree(m.space);
   (void)hipFree(m.row_map); (void)hipFree(m.col_map);
   m = vslam_ctx::DepthMap();
+}
+// the resident space map at rows x cols: its own allocations (it outlives the call that fills it), kept while the size stays
+static hipError_t depth_map_resize(vslam_ctx* c, int rows, int cols) {
+  vslam_ctx::DepthMap& m = c->dm;
+  if (m.rows == rows && m.cols == cols) return hipSuccess;
+  depth_map_free(c);
+  const size_t n = (size_t)rows * cols;
+  hipError_t e = hipMalloc((void**)&m.depth, n * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m.key, n * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&m.last, n * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m.space, n * 3 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&m.row_map, n * sizeof(int16_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m.col_map, n * sizeof(int16_t));
+  if (e != hipSuccess) { depth_map_free(c); return e; }
+  m.rows = rows; m.cols = cols;
+  return hipSuccess;
 }
 VS_API int vslam_create(const vslam_config* cfg, int device, int n_streams, vslam_ctx** out) {
   // a tracker needs room for a keypoint (descriptor border 28 / 31 px); the scratch contexts of the stand-alone entries accept
@@ -957,8 +971,8 @@ VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_
   int16_t* dxy = nullptr;
   uint16_t* da = nullptr;
   hipError_t e = tmp_get(c, (void**)&ds, (size_t)rows * row_stride);
-  if (e == hipSuccess) e = tmp_alloc(c, &dxy, pxy.size());
-  if (e == hipSuccess) e = tmp_alloc(c, &da, pa.size());
+  if (e == hipSuccess) e = tmp_get(c, (void**)&dxy, pxy.size() * 2);
+  if (e == hipSuccess) e = tmp_get(c, (void**)&da, pa.size() * 2);
   if (e == hipSuccess) e = tmp_get(c, (void**)&dd, (size_t)drows * ms);
   if (e == hipSuccess) e = hipMemcpyAsync(ds, src, (size_t)(rows - 1) * row_stride + cols, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dxy, pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice, c->stream);
@@ -1267,513 +1281,6 @@ VS_API int vslam_get_aligner_weights(vslam_ctx* c, int s, int32_t cap, int32_t* 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VSLAM_OK;
 }
-VS_API int vslam_aligner_weights(vslam_ctx* c, int32_t n_calls, const int32_t* n, const int32_t* inverse_depth, const double* depth, double* out) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (n_calls < 0 || (n_calls && (!n || !inverse_depth))) return fail(c, VSLAM_ERR_INVALID, "aligner_weights: bad argument");
-  size_t total = 0; int nmax = 0;
-  for (int k = 0; k < n_calls; ++k) { if (n[k] < 0) return fail(c, VSLAM_ERR_INVALID, "aligner_weights: negative size"); total += (size_t)n[k]; nmax = std::max(nmax, n[k]); }
-  if (total && (!depth || !out)) return fail(c, VSLAM_ERR_INVALID, "aligner_weights: bad argument");
-  if (!n_calls || !total) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  int32_t *dn = nullptr, *di = nullptr; double *dd = nullptr, *dw = nullptr, *dout = nullptr;
-  hipError_t e = tmp_get(c, (void**)&dn, (size_t)n_calls * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&di, (size_t)n_calls * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dd, total * 8);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dw, (size_t)nmax * 8);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dout, total * 8);
-  if (e == hipSuccess) e = hipMemcpyAsync(dn, n, (size_t)n_calls * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(di, inverse_depth, (size_t)n_calls * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dd, depth, total * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_aligner_weights, dim3(1), dim3(256), 0, c->stream, n_calls, dn, di, dd, c->cfg.c.maximum_reliable_depth_meters, dw, dout);
-    e = hipMemcpyAsync(out, dout, total * 8, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-// ---- RGB-D components (DepthFramePointGenerator pieces, stand-alone) ------------------------------------------------
-static int make_scratch_ctx(vslam_ctx* parent, int rows, int cols, int nmax, int maxp, vslam_ctx** out);
-static int depth_params_ok(vslam_ctx* c, const vslam_depth_params* p) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!p || p->rows <= 0 || p->cols <= 0 || p->rows > 32767 || p->cols > 32767) return fail(c, VSLAM_ERR_INVALID, "depth: image size out of range");
-  if (!(p->maximum_depth_meters > 0) || (p->enable_keypoint_binning && p->bin_size_pixels <= 0)) return fail(c, VSLAM_ERR_INVALID, "depth: bad parameters");
-  return VSLAM_OK;
-}
-VS_API int vslam_depth_space_map(vslam_ctx* c, const vslam_depth_params* p, const uint16_t* depth, int32_t row_stride, float* space,
-                                 int16_t* row_map, int16_t* col_map) {
-  int rc = depth_params_ok(c, p);
-  if (rc != VSLAM_OK) return rc;
-  if (!depth) return fail(c, VSLAM_ERR_INVALID, "depth tracker requires a 16bit mono image to encode depth");   // :411-413
-  if (row_stride < p->cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
-  HIP_TRY(c, hipSetDevice(c->device));
-  vslam_ctx::DepthMap& m = c->dm;
-  const size_t n = (size_t)p->rows * p->cols;
-  if (m.rows != p->rows || m.cols != p->cols) {
-    depth_map_free(c);
-    hipError_t e = hipMalloc((void**)&m.depth, n * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&m.key, n * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&m.last, n * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&m.space, n * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m.row_map, n * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&m.col_map, n * sizeof(int16_t));
-    if (e != hipSuccess) { depth_map_free(c); return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e)); }
-    m.rows = p->rows; m.cols = p->cols;
-  }
-  m.valid = false;
-  // rows re-packed on the device side of the copy (dense device image, stride = cols)
-  if (row_stride == p->cols) HIP_TRY(c, hipMemcpyAsync(m.depth, depth, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-  else HIP_TRY(c, hipMemcpy2DAsync(m.depth, (size_t)p->cols * 2, depth, (size_t)row_stride * 2, (size_t)p->cols * 2, p->rows, hipMemcpyHostToDevice, c->stream));
-  const float f0 = (float)p->maximum_depth_meters;
-  uint32_t f0_bits;
-  std::memcpy(&f0_bits, &f0, 4);
-  const dim3 grid((p->cols + 255) / 256, p->rows);
-  hipLaunchKernelGGL(k_depth_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)n, f0_bits, m.key, m.last);
-  hipLaunchKernelGGL(k_depth_min, grid, dim3(256), 0, c->stream, *p, m.depth, p->cols, m.key, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(k_depth_pick, grid, dim3(256), 0, c->stream, *p, m.depth, p->cols, f0_bits, m.key, m.last, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(k_depth_write, grid, dim3(256), 0, c->stream, *p, m.depth, p->cols, f0_bits, m.key, m.last, m.space, m.row_map, m.col_map, 0, (const int32_t*)nullptr);
-  HIP_TRY(c, hipGetLastError());
-  if (space) HIP_TRY(c, hipMemcpyAsync(space, m.space, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (row_map) HIP_TRY(c, hipMemcpyAsync(row_map, m.row_map, n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-  if (col_map) HIP_TRY(c, hipMemcpyAsync(col_map, m.col_map, n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  m.valid = true;
-  return VSLAM_OK;
-}
-VS_API int vslam_depth_compute(vslam_ctx* c, const vslam_depth_params* p, const float* space, int32_t nF, const int32_t* rcF, int32_t nT,
-                               const int32_t* rcT, int32_t cap, int32_t* n_new, int32_t* new_feat, double* new_xyz, int32_t* n_temp,
-                               int32_t* temp_feat, double* temp_xyz) {
-  tmp_reset(c);
-  int rc = depth_params_ok(c, p);
-  if (rc != VSLAM_OK) return rc;
-  if (nF < 0 || nT < 0 || cap < 0 || !n_new || !n_temp || (nF && !rcF) || (nT && !rcT) || (cap && (!new_feat || !new_xyz || !temp_feat || !temp_xyz)))
-    return fail(c, VSLAM_ERR_INVALID, "depth_compute: bad argument");
-  for (int i = 0; i < nF; ++i) if (rcF[2 * i] < 0 || rcF[2 * i] >= p->rows || rcF[2 * i + 1] < 0 || rcF[2 * i + 1] >= p->cols) return fail(c, VSLAM_ERR_INVALID, "depth_compute: feature outside the image");
-  for (int i = 0; i < nT; ++i) if (rcT[2 * i] < 0 || rcT[2 * i] >= p->rows || rcT[2 * i + 1] < 0 || rcT[2 * i + 1] >= p->cols) return fail(c, VSLAM_ERR_INVALID, "depth_compute: point outside the image");
-  if (!space && !(c->dm.valid && c->dm.rows == p->rows && c->dm.cols == p->cols)) return fail(c, VSLAM_ERR_STATE, "depth_compute: no resident space map of this size");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = (size_t)p->rows * p->cols;
-  const int rows_bin = p->enable_keypoint_binning ? p->rows / p->bin_size_pixels + 1 : 0;   // base_framepoint_generator.cpp:304-305
-  const int cols_bin = p->enable_keypoint_binning ? p->cols / p->bin_size_pixels + 1 : 0;
-  const int n_bins = (rows_bin + 1) * (cols_bin + 1);
-  float* dspace = nullptr; int32_t *dF = nullptr, *dT = nullptr, *dcnt = nullptr, *dnf = nullptr, *dtf = nullptr;
-  double *dnx = nullptr, *dtx = nullptr; unsigned long long* dbins = nullptr; uint8_t* dcls = nullptr;
-  const size_t capa = std::max(cap, 1);
-  hipError_t e = hipSuccess;
-  if (space) { e = tmp_get(c, (void**)&dspace, n * 3 * sizeof(float)); if (e == hipSuccess) e = hipMemcpyAsync(dspace, space, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream); }
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dF, std::max(nF, 1) * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dT, std::max(nT, 1) * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dcnt, 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dnf, capa * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dtf, capa * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dnx, capa * 3 * sizeof(double));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dtx, capa * 3 * sizeof(double));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dbins, (size_t)n_bins * sizeof(unsigned long long));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dcls, std::max(nF, 1));
-  if (e == hipSuccess && nF) e = hipMemcpyAsync(dF, rcF, (size_t)nF * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nT) e = hipMemcpyAsync(dT, rcT, (size_t)nT * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  int32_t cnt[2] = {0, 0};
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_depth_compute, dim3(1), dim3(1024), 0, c->stream, *p, space ? dspace : c->dm.space, nF, dF, nT, dT, dbins, n_bins,
-                       rows_bin, cols_bin, cap, dcnt, dnf, dnx, dtf, dtx, dcls);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(cnt, dcnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) {
-    *n_new = cnt[0]; *n_temp = cnt[1];
-    const int a = std::min(cnt[0], cap), b = std::min(cnt[1], cap);
-    if (a) { e = hipMemcpy(new_feat, dnf, (size_t)a * sizeof(int32_t), hipMemcpyDeviceToHost); if (e == hipSuccess) e = hipMemcpy(new_xyz, dnx, (size_t)a * 3 * sizeof(double), hipMemcpyDeviceToHost); }
-    if (e == hipSuccess && b) { e = hipMemcpy(temp_feat, dtf, (size_t)b * sizeof(int32_t), hipMemcpyDeviceToHost); if (e == hipSuccess) e = hipMemcpy(temp_xyz, dtx, (size_t)b * 3 * sizeof(double), hipMemcpyDeviceToHost); }
-  }
-
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  if (cnt[0] > cap || cnt[1] > cap) return fail(c, VSLAM_ERR_CAPACITY, "depth_compute: output capacity too small");
-  return VSLAM_OK;
-}
-VS_API int vslam_depth_track(vslam_ctx* c, const vslam_depth_params* p, const float* space, const double T[12], int32_t d, double tau,
-                             int32_t by_appearance, int32_t nP, const double* cam, const uint8_t* pdesc, const uint8_t* pflags, int32_t nL,
-                             const int32_t* rcL, const uint8_t* dL, int32_t* n_tracked, int32_t* out2, double* xyz, int32_t* n_temp,
-                             int32_t* temp2, int32_t* n_lost, int32_t* lost, int32_t* n_tracked_landmarks) {
-  tmp_reset(c);
-  int rc = depth_params_ok(c, p);
-  if (rc != VSLAM_OK) return rc;
-  if (!T || d < 0 || nP < 0 || nL < 0 || !n_tracked || !n_temp || !n_lost || !n_tracked_landmarks || (nP && (!cam || !pdesc || !pflags || !out2 || !xyz || !temp2 || !lost)) ||
-      (nL && (!rcL || !dL)))
-    return fail(c, VSLAM_ERR_INVALID, "depth_track: bad argument");
-  if (!space && !(c->dm.valid && c->dm.rows == p->rows && c->dm.cols == p->cols)) return fail(c, VSLAM_ERR_STATE, "depth_track: no resident space map of this size");
-  const int rows = p->rows, cols = p->cols, CW = (cols + 15) / 16, CW1 = CW + 1;
-  // features row-major + (row, 16-px cell) CSR, as the image pipeline leaves them (k_emit).  Several features on ONE pixel (an OrbDetector
-  // finds a corner on more than one pyramid level): setFeatures (intensity_feature_matcher.cpp:48-70) writes them into the lattice in list
-  // order, so only the LAST one can ever be found through the lattice — the others stay in the feature vector (compute() still sees them) but
-  // are invisible to track(), also after the last one has been taken.
-  std::vector<int> ord(nL);
-  for (int i = 0; i < nL; ++i) {
-    ord[i] = i;
-    if (rcL[2 * i] < 0 || rcL[2 * i] >= rows || rcL[2 * i + 1] < 0 || rcL[2 * i + 1] >= cols) return fail(c, VSLAM_ERR_INVALID, "feature outside the image");
-  }
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return rcL[2 * a] != rcL[2 * b] ? rcL[2 * a] < rcL[2 * b] : (rcL[2 * a + 1] != rcL[2 * b + 1] ? rcL[2 * a + 1] < rcL[2 * b + 1] : a < b); });
-  std::vector<int16_t> xy((size_t)std::max(nL, 1) * 2);
-  std::vector<uint8_t> ds((size_t)std::max(nL, 1) * 32);
-  std::vector<uint8_t> vis(std::max(nL, 1), 1);
-  bool duplicates = false;
-  std::vector<int32_t> rowcell((size_t)rows * CW1);
-  for (int k = 0; k < nL; ++k) {
-    xy[2 * k] = (int16_t)rcL[2 * ord[k] + 1]; xy[2 * k + 1] = (int16_t)rcL[2 * ord[k]];
-    std::memcpy(&ds[(size_t)32 * k], dL + (size_t)32 * ord[k], 32);
-    if (k + 1 < nL && rcL[2 * ord[k]] == rcL[2 * ord[k + 1]] && rcL[2 * ord[k] + 1] == rcL[2 * ord[k + 1] + 1]) { vis[k] = 0; duplicates = true; }
-  }
-  for (int r = 0, k = 0; r < rows; ++r)
-    for (int cc = 0; cc < CW1; ++cc) {
-      while (k < nL && (xy[2 * k + 1] < r || (xy[2 * k + 1] == r && xy[2 * k] < 16 * cc))) ++k;
-      rowcell[(size_t)r * CW1 + cc] = k;
-    }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = (size_t)rows * cols, P1 = std::max(nP, 1), L1 = std::max(nL, 1);
-  DepthTrack a;
-  std::memset(&a, 0, sizeof a);
-  a.p = *p; std::memcpy(a.T, T, sizeof a.T); a.d = d; a.by_app = by_appearance ? 1 : 0; a.tau = tau; a.nP = nP; a.nL = nL; a.CW = CW;
-  float* dspace = nullptr; double *dcam = nullptr, *dxyz = nullptr; uint8_t *dpd = nullptr, *dpf = nullptr, *dds = nullptr; int16_t* dxy = nullptr;
-  int32_t *drc = nullptr, *dhold = nullptr, *dpick = nullptr, *dcnt = nullptr, *dout2 = nullptr, *dtmp2 = nullptr, *dlost = nullptr;
-  unsigned long long* dcand = nullptr;
-  uint8_t* dvis = nullptr;
-  hipError_t e = hipSuccess;
-  if (space) { e = tmp_get(c, (void**)&dspace, n * 3 * sizeof(float)); if (e == hipSuccess) e = hipMemcpyAsync(dspace, space, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream); }
-  if (e == hipSuccess && duplicates) { e = tmp_get(c, (void**)&dvis, L1); if (e == hipSuccess) e = hipMemcpyAsync(dvis, vis.data(), (size_t)nL, hipMemcpyHostToDevice, c->stream); }
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dcand, P1 * (VS_DT_K + 1) * sizeof(unsigned long long));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dcam, P1 * 3 * sizeof(double));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dxyz, P1 * 3 * sizeof(double));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dpd, P1 * 32);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dpf, P1);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dds, L1 * 32);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dxy, L1 * 2 * sizeof(int16_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&drc, rowcell.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dhold, L1 * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dpick, P1 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dcnt, 4 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dout2, P1 * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dtmp2, P1 * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dlost, P1 * sizeof(int32_t));
-  if (e == hipSuccess && nP) e = hipMemcpyAsync(dcam, cam, (size_t)nP * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nP) e = hipMemcpyAsync(dpd, pdesc, (size_t)nP * 32, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nP) e = hipMemcpyAsync(dpf, pflags, (size_t)nP, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nL) e = hipMemcpyAsync(dds, ds.data(), (size_t)nL * 32, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nL) e = hipMemcpyAsync(dxy, xy.data(), (size_t)nL * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(drc, rowcell.data(), rowcell.size() * 4, hipMemcpyHostToDevice, c->stream);
-  int32_t cnt[4] = {0, 0, 0, 0};
-  if (e == hipSuccess) {
-    a.cam = dcam; a.pdesc = dpd; a.pflags = dpf; a.kxy = dxy; a.desc = dds; a.rowcell = drc; a.space = space ? dspace : c->dm.space; a.fvis = dvis;
-    a.hold = dhold; a.pick = dpick; a.cand = dcand; a.counts = dcnt; a.out2 = dout2; a.xyz = dxyz; a.temp2 = dtmp2; a.lost = dlost;
-    if (nP) hipLaunchKernelGGL(k_depth_track_candidates, dim3(std::min(1024, (nP + 15) / 16)), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(k_depth_track, dim3(1), dim3(1024), 0, c->stream, a);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(cnt, dcnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // also: the host staging vectors may go out of scope now
-  if (e == hipSuccess) {
-    *n_tracked = cnt[0]; *n_temp = cnt[1]; *n_lost = cnt[2]; *n_tracked_landmarks = cnt[3];
-    if (cnt[0]) { e = hipMemcpy(out2, dout2, (size_t)cnt[0] * 8, hipMemcpyDeviceToHost); if (e == hipSuccess) e = hipMemcpy(xyz, dxyz, (size_t)cnt[0] * 24, hipMemcpyDeviceToHost); }
-    if (e == hipSuccess && cnt[1]) e = hipMemcpy(temp2, dtmp2, (size_t)cnt[1] * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && cnt[2]) e = hipMemcpy(lost, dlost, (size_t)cnt[2] * 4, hipMemcpyDeviceToHost);
-    for (int u = 0; u < cnt[0]; ++u) out2[2 * u + 1] = ord[out2[2 * u + 1]];     // back to the caller's feature numbering
-    for (int u = 0; u < cnt[1]; ++u) temp2[2 * u + 1] = ord[temp2[2 * u + 1]];
-  }
-
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-VS_API int vslam_depth_recover(vslam_ctx* c, const vslam_depth_params* p, const float* space, const uint8_t* img, int32_t row_stride,
-                               const double w2c[12], int32_t n, const uint8_t* has_lm, const double* lm, const uint8_t* pdesc, float kp_size,
-                               double tau, int32_t* n_rec, int32_t* rec_index, float* rec_xy, uint8_t* rec_desc, double* rec_xyz) {
-  tmp_reset(c);
-  int rc = depth_params_ok(c, p);
-  if (rc != VSLAM_OK) return rc;
-  if (!img || !w2c || n < 0 || !n_rec || (n && (!has_lm || !lm || !pdesc || !rec_index || !rec_xy || !rec_desc || !rec_xyz)))
-    return fail(c, VSLAM_ERR_INVALID, "depth_recover: bad argument");
-  if (row_stride < p->cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
-  if (!space && !(c->dm.valid && c->dm.rows == p->rows && c->dm.cols == p->cols)) return fail(c, VSLAM_ERR_STATE, "depth_recover: no resident space map of this size");
-  *n_rec = 0;
-  if (n == 0) return VSLAM_OK;
-  // box image of the left image through the image pipeline's own kernel (scratch context of the image size)
-  vslam_ctx* t = nullptr;
-  rc = make_scratch_ctx(c, p->rows, p->cols, 64, 64, &t);
-  if (rc != VSLAM_OK) return rc;
-  const size_t npx = (size_t)p->rows * p->cols;
-  DepthRecover a;
-  std::memset(&a, 0, sizeof a);
-  a.p = *p; std::memcpy(a.w2c, w2c, sizeof a.w2c); a.kp_size = kp_size; a.tau = tau; a.n = n;
-  float *dspace = nullptr, *dkxy = nullptr, *drxy = nullptr; double *dlm = nullptr, *drxyz = nullptr; uint8_t *dhl = nullptr, *dpd = nullptr, *dkeep = nullptr, *ddesc = nullptr, *drdesc = nullptr;
-  int16_t* dbxy = nullptr; int32_t *dcell = nullptr, *dcnt = nullptr, *dridx = nullptr;
-  hipError_t e = hipSuccess;
-  if (space) { e = tmp_alloc(c, &dspace, npx * 3); if (e == hipSuccess) e = hipMemcpyAsync(dspace, space, npx * 3 * sizeof(float), hipMemcpyHostToDevice, t->stream_img); }
-  if (e == hipSuccess) e = tmp_alloc(c, &dkxy, (size_t)n * 2);
-  if (e == hipSuccess) e = tmp_alloc(c, &drxy, (size_t)n * 2);
-  if (e == hipSuccess) e = tmp_alloc(c, &dlm, (size_t)n * 3);
-  if (e == hipSuccess) e = tmp_alloc(c, &drxyz, (size_t)n * 3);
-  if (e == hipSuccess) e = tmp_alloc(c, &dhl, (size_t)n);
-  if (e == hipSuccess) e = tmp_alloc(c, &dpd, (size_t)n * 32);
-  if (e == hipSuccess) e = tmp_alloc(c, &dkeep, (size_t)n);
-  if (e == hipSuccess) e = tmp_alloc(c, &ddesc, (size_t)n * 32);
-  if (e == hipSuccess) e = tmp_alloc(c, &drdesc, (size_t)n * 32);
-  if (e == hipSuccess) e = tmp_alloc(c, &dbxy, (size_t)n * 2);
-  if (e == hipSuccess) e = tmp_alloc(c, &dcell, (size_t)n);
-  if (e == hipSuccess) e = tmp_alloc(c, &dcnt, 1);
-  if (e == hipSuccess) e = tmp_alloc(c, &dridx, (size_t)n);
-  if (e == hipSuccess) e = hipMemcpyAsync(dhl, has_lm, (size_t)n, hipMemcpyHostToDevice, t->stream_img);
-  if (e == hipSuccess) e = hipMemcpyAsync(dlm, lm, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, t->stream_img);
-  if (e == hipSuccess) e = hipMemcpyAsync(dpd, pdesc, (size_t)n * 32, hipMemcpyHostToDevice, t->stream_img);
-  rc = e == hipSuccess ? upload_images(t, img, img, row_stride, 0) : fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  if (rc == VSLAM_OK) {
-    if (!space) (void)hipStreamSynchronize(c->stream);   // the resident map was written on the parent's stream
-    a.has_lm = dhl; a.lm = dlm; a.pdesc = dpd; a.space = space ? dspace : c->dm.space; a.bxy = dbxy; a.kxy = dkxy; a.cell = dcell;
-    a.keep = dkeep; a.desc = ddesc; a.count = dcnt; a.rec_index = dridx; a.rec_xy = drxy; a.rec_desc = drdesc; a.rec_xyz = drxyz;
-    hipLaunchKernelGGL(k_depth_recover_project, dim3((n + 255) / 256), dim3(256), 0, t->stream_img, a);
-    if (p->descriptor_type == VSLAM_DESCRIPTOR_ORB) {
-      // cv::ORB::create() as extractor: Gaussian image (in the scratch context's box memory), steered tests at the rounded pixels
-      uint8_t* dblur = reinterpret_cast<uint8_t*>(t->buf.box);
-      Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = t->cfg.gauss7[i];
-      hipLaunchKernelGGL(k_gauss7_plain, dim3((p->cols + VS_TILE_W - 1) / VS_TILE_W, (p->rows + VS_TILE_H - 1) / VS_TILE_H), dim3(256), 0, t->stream_img,
-                         t->buf.img[0], t->buf.img_row_stride, p->rows, p->cols, gk, dblur, t->cfg.bstride);
-      hipLaunchKernelGGL(k_orb_at, dim3(std::min(64, (n + 3) / 4)), dim3(256), 0, t->stream_img, dblur, t->cfg.bstride, p->rows, p->cols, n, dbxy, t->cfg.orb_cos, t->cfg.orb_sin, dkeep, ddesc);
-    } else {
-      dim3 g1(t->cfg.TX, (p->rows + VS_TILE_H - 1) / VS_TILE_H, 2);
-      hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, t->stream_img, t->cfg, t->buf);
-      hipLaunchKernelGGL(k_brief_at, dim3(std::min(64, (n + 3) / 4)), dim3(256), 0, t->stream_img, t->buf.box, t->cfg.bstride, p->rows, p->cols, n, dbxy, dkeep, ddesc);
-    }
-    hipLaunchKernelGGL(k_depth_recover_finish, dim3(1), dim3(1024), 0, t->stream_img, a);
-    e = hipGetLastError();
-    int32_t cnt = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, dcnt, 4, hipMemcpyDeviceToHost, t->stream_img);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream_img);
-    if (e == hipSuccess && cnt) {
-      e = hipMemcpy(rec_index, dridx, (size_t)cnt * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(rec_xy, drxy, (size_t)cnt * 8, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(rec_desc, drdesc, (size_t)cnt * 32, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(rec_xyz, drxyz, (size_t)cnt * 24, hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) *n_rec = cnt;
-    else rc = fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  }
-  scratch_put(c, t);
-  return rc;
-}
-VS_API int vslam_point_in_camera(vslam_ctx* c, int32_t n, const float* xp, const float* xc, const double T[12], const double K[9], double* out) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (n < 0 || !T || !K || (n && (!xp || !xc || !out))) return fail(c, VSLAM_ERR_INVALID, "point_in_camera: bad argument");
-  if (n == 0) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  float *dp = nullptr, *dc = nullptr; double *dT = nullptr, *dK = nullptr, *dout = nullptr;
-  hipError_t e = tmp_get(c, (void**)&dp, (size_t)n * 2 * sizeof(float));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dc, (size_t)n * 2 * sizeof(float));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dT, 12 * sizeof(double));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dK, 9 * sizeof(double));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dout, (size_t)n * 3 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(dp, xp, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dc, xc, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dT, T, 12 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dK, K, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_point_in_camera, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dp, dc, dT, dK, dout);
-    e = hipMemcpyAsync(out, dout, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-
-VS_API int vslam_landmark_update(vslam_ctx* c, int32_t n, const int32_t* offsets, const int32_t* frame_of, int32_t n_frames, const double* w2c,
-                                 const double* c2w, const double* cam, double* world, int32_t* updates) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (n < 0 || n_frames < 0 || (n && (!offsets || !world || !updates))) return fail(c, VSLAM_ERR_INVALID, "landmark_update: bad argument");
-  if (n == 0) return VSLAM_OK;
-  const int M = offsets[n];
-  if (M < 0 || (M && (!frame_of || !w2c || !c2w || !cam))) return fail(c, VSLAM_ERR_INVALID, "landmark_update: bad argument");
-  for (int i = 0; i < n; ++i) if (offsets[i] > offsets[i + 1] || offsets[i] < 0) return fail(c, VSLAM_ERR_INVALID, "landmark_update: offsets not ascending");
-  for (int m = 0; m < M; ++m) if (frame_of[m] < 0 || frame_of[m] >= n_frames) return fail(c, VSLAM_ERR_INVALID, "landmark_update: frame index out of range");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int32_t *doff = nullptr, *dfo = nullptr, *dup = nullptr; double *dw2c = nullptr, *dc2w = nullptr, *dcam = nullptr, *dworld = nullptr;
-  hipError_t e = tmp_get(c, (void**)&doff, (size_t)(n + 1) * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dfo, std::max<size_t>(M, 1) * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dup, (size_t)n * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dw2c, std::max<size_t>(n_frames, 1) * 96);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dc2w, std::max<size_t>(n_frames, 1) * 96);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dcam, std::max<size_t>(M, 1) * 24);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dworld, (size_t)n * 24);
-  if (e == hipSuccess) e = hipMemcpyAsync(doff, offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && M) e = hipMemcpyAsync(dfo, frame_of, (size_t)M * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dup, updates, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && n_frames) e = hipMemcpyAsync(dw2c, w2c, (size_t)n_frames * 96, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && n_frames) e = hipMemcpyAsync(dc2w, c2w, (size_t)n_frames * 96, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && M) e = hipMemcpyAsync(dcam, cam, (size_t)M * 24, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dworld, world, (size_t)n * 24, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_landmark_update, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, doff, dfo, dw2c, dc2w, dcam, dworld, dup,
-                       c->cfg.c.landmark_maximum_number_of_iterations, c->cfg.c.landmark_maximum_error_squared_meters);
-    e = hipMemcpyAsync(world, dworld, (size_t)n * 24, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(updates, dup, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-
-// ---- OrbDetector components ---------------------------------------------------------------------------------------
-VS_API int vslam_resize_linear_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, uint8_t* dst, int32_t drows,
-                                  int32_t dcols) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!src || !dst || rows < 2 || cols < 2 || drows < 1 || dcols < 1 || row_stride < cols) return fail(c, VSLAM_ERR_INVALID, "resize: bad argument");
-  HIP_TRY(c, hipSetDevice(c->device));
-  uint8_t *ds = nullptr, *dd = nullptr;
-  hipError_t e = tmp_get(c, (void**)&ds, (size_t)rows * row_stride);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dd, (size_t)drows * dcols);
-  if (e == hipSuccess) e = hipMemcpyAsync(ds, src, (size_t)(rows - 1) * row_stride + cols, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_resize_linear_u8, dim3((dcols + 255) / 256, drows), dim3(256), 0, c->stream, ds, rows, cols, row_stride, dd, drows, dcols, dcols);
-    e = hipMemcpyAsync(dst, dd, (size_t)drows * dcols, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-static OrbUmax orb_umax_table(int half) {   // orb.cpp computeKeyPoints: row half-widths of the circular patch
-  OrbUmax t;
-  std::memset(&t, 0, sizeof t);
-  const int vmax = (int)std::floor(half * std::sqrt(2.f) / 2 + 1), vmin = (int)std::ceil(half * std::sqrt(2.f) / 2);
-  for (int v = 0; v <= vmax; ++v) t.v[v] = (int)std::lrint(std::sqrt((double)half * half - v * v));
-  for (int v = half, v0 = 0; v >= vmin; --v) { while (t.v[v0] == t.v[v0 + 1]) ++v0; t.v[v] = v0; ++v0; }
-  return t;
-}
-VS_API int vslam_harris_angle(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t row_stride, int32_t n, const int16_t* xy,
-                              float* response, float* angle) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!img || n < 0 || rows < 33 || cols < 33 || row_stride < cols || (n && (!xy || !response || !angle))) return fail(c, VSLAM_ERR_INVALID, "harris_angle: bad argument");
-  for (int i = 0; i < n; ++i)
-    if (xy[2 * i] < 16 || xy[2 * i + 1] < 16 || xy[2 * i] >= cols - 16 || xy[2 * i + 1] >= rows - 16) return fail(c, VSLAM_ERR_INVALID, "harris_angle: keypoint closer than 16 px to the border");
-  if (n == 0) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  uint8_t* di = nullptr; int16_t* dxy = nullptr; float *dr = nullptr, *da = nullptr; int32_t* dn = nullptr;
-  hipError_t e = tmp_get(c, (void**)&di, (size_t)rows * row_stride);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dxy, (size_t)n * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dr, (size_t)n * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&da, (size_t)n * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dn, 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(di, img, (size_t)(rows - 1) * row_stride + cols, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dxy, xy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dn, &n, 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    const int blocks = std::min(256, (n + 3) / 4);
-    hipLaunchKernelGGL(k_orb_harris, dim3(blocks), dim3(256), 0, c->stream, di, row_stride, dn, dxy, dr);
-    hipLaunchKernelGGL(k_orb_angle, dim3(blocks), dim3(256), 0, c->stream, di, row_stride, dn, dxy, dr, 15, orb_umax_table(15), da, (float*)nullptr,
-                       (const int32_t*)nullptr, 0, 1.f, 0, 31);
-    e = hipMemcpyAsync(response, dr, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(angle, da, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-VS_API int vslam_orb_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t row_stride, int32_t nfeatures, float scale_factor,
-                            int32_t nlevels, int32_t edge, int32_t patch, int32_t fast_threshold, int32_t cap, int32_t* n, float* keypoints) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!img || !n || nlevels < 1 || nlevels > 16 || nfeatures < 0 || patch < 3 || patch > 63 || cap < 0 || (cap && !keypoints) || row_stride < cols ||
-      !(scale_factor > 1.f) || edge < patch / 2 + 1 || edge < 4 || rows < 2 * edge + 8 || cols < 2 * edge + 8 || rows > 32767 || cols > 32767)
-    return fail(c, VSLAM_ERR_INVALID, "orb_detect: bad argument");
-  HIP_TRY(c, hipSetDevice(c->device));
-  // features per level (orb.cpp computeKeyPoints), float arithmetic as upstream
-  std::vector<int> per(nlevels);
-  {
-    const float factor = (float)(1.0 / scale_factor);
-    float nd = nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
-    int sum = 0;
-    for (int l = 0; l < nlevels - 1; ++l) { per[l] = (int)std::lrint(nd); sum += per[l]; nd *= factor; }
-    per[nlevels - 1] = std::max(nfeatures - sum, 0);
-  }
-  const int half = patch / 2;
-  const OrbUmax um = orb_umax_table(half);
-  hipStream_t st = c->stream;
-  std::vector<void*> tmp;
-  auto dmal = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, std::max<size_t>(bytes, 4)) != hipSuccess) return nullptr; tmp.push_back(q); return q; };
-  float* dout = (float*)dmal((size_t)std::max(cap, 1) * 6 * sizeof(float));
-  int32_t* dtotal = (int32_t*)dmal(4);
-  int rc = VSLAM_OK;
-  hipError_t e = (dout && dtotal) ? hipMemsetAsync(dtotal, 0, 4, st) : hipErrorOutOfMemory;
-  const uint8_t* lev = nullptr;
-  int lrows = rows, lcols = cols, lstride = (cols + 63) & ~63;
-  std::vector<vslam_ctx*> scratch;
-  if (e == hipSuccess) {
-    uint8_t* d0 = (uint8_t*)dmal((size_t)rows * lstride);
-    if (!d0) e = hipErrorOutOfMemory;
-    else e = hipMemcpy2DAsync(d0, lstride, img, row_stride, cols, rows, hipMemcpyHostToDevice, st);
-    lev = d0;
-  }
-  for (int l = 0; l < nlevels && e == hipSuccess && rc == VSLAM_OK; ++l) {
-    const float sc = (float)std::pow((double)scale_factor, (double)l);
-    if (l > 0) {
-      const int nr = (int)std::lrint(rows / sc), nc = (int)std::lrint(cols / sc);
-      if (nr < 2 * edge + 8 || nc < 2 * edge + 8) break;
-      const int ns = (nc + 63) & ~63;
-      uint8_t* dl = (uint8_t*)dmal((size_t)nr * ns);
-      if (!dl) { e = hipErrorOutOfMemory; break; }
-      hipLaunchKernelGGL(k_resize_linear_u8, dim3((nc + 255) / 256, nr), dim3(256), 0, st, lev, lrows, lcols, lstride, dl, nr, nc, ns);
-      lev = dl; lrows = nr; lcols = nc; lstride = ns;
-    }
-    // FAST-9/16 + NMS + border filter through the image pipeline's own kernels on a scratch context of the level's size
-    vslam_ctx* t = nullptr;
-    rc = make_scratch_ctx(c, lrows, lcols, 65535, 64, &t);
-    if (rc != VSLAM_OK) break;
-    scratch.push_back(t);
-    t->cfg.n_regions = 1;
-    t->cfg.regions[0].x = 0; t->cfg.regions[0].y = 0; t->cfg.regions[0].w = lcols; t->cfg.regions[0].h = lrows;
-    StreamState sst;
-    e = hipMemcpy(&sst, t->buf.st, sizeof sst, hipMemcpyDeviceToHost);
-    sst.thr[0] = fast_threshold;
-    if (e == hipSuccess) e = hipMemcpy(t->buf.st, &sst, sizeof sst, hipMemcpyHostToDevice);
-    if (e != hipSuccess) break;
-    rc = set_images_device(t, lev, lev, lstride, 0);
-    if (rc != VSLAM_OK) break;
-    const int N = t->cfg.NMAX;
-    int16_t* xy1 = (int16_t*)dmal((size_t)N * 4); int16_t* xy2 = (int16_t*)dmal((size_t)N * 4);
-    float* r1 = (float*)dmal((size_t)N * 4); float* r2 = (float*)dmal((size_t)N * 4); float* rh = (float*)dmal((size_t)N * 4);
-    int32_t* n1 = (int32_t*)dmal(4); int32_t* n2 = (int32_t*)dmal(4);
-    if (!xy1 || !xy2 || !r1 || !r2 || !rh || !n1 || !n2) { e = hipErrorOutOfMemory; break; }
-    dim3 g1(t->cfg.TX, (lrows + VS_TILE_H - 1) / VS_TILE_H, 1);
-    hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, st, t->cfg, t->buf);
-    hipLaunchKernelGGL(k_emit, dim3(1, 1), dim3(512), 0, st, t->cfg, t->buf, edge, 0);                                  // runByImageBorder(edgeThreshold)
-    hipLaunchKernelGGL(k_orb_select<uint8_t>, dim3(1), dim3(1024), 0, st, t->buf.n_kp, t->buf.kp_xy, t->buf.kp_score, 2 * per[l], n1, xy1, r1, N);   // retainBest(2 n) on the FAST score
-    hipLaunchKernelGGL(k_orb_harris, dim3(256), dim3(256), 0, st, lev, lstride, n1, xy1, rh);
-    hipLaunchKernelGGL(k_orb_select<float>, dim3(1), dim3(1024), 0, st, n1, xy1, rh, per[l], n2, xy2, r2, N);            // retainBest(n) on the Harris response
-    hipLaunchKernelGGL(k_orb_angle, dim3(256), dim3(256), 0, st, lev, lstride, n2, xy2, r2, half, um, (float*)nullptr, dout, dtotal, cap, sc, l, patch);
-    hipLaunchKernelGGL(k_orb_advance, dim3(1), dim3(1), 0, st, dtotal, n2);
-    e = hipGetLastError();
-  }
-  int32_t total = 0;
-  if (e == hipSuccess && rc == VSLAM_OK) e = hipMemcpyAsync(&total, dtotal, 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess && rc == VSLAM_OK) {
-    *n = total;
-    const int m = std::min(total, cap);
-    if (m) e = hipMemcpy(keypoints, dout, (size_t)m * 6 * sizeof(float), hipMemcpyDeviceToHost);
-    for (vslam_ctx* t : scratch) { int32_t cnt = 0; if (hipMemcpy(&cnt, t->buf.n_kp, 4, hipMemcpyDeviceToHost) == hipSuccess && cnt >= t->cfg.NMAX) rc = fail(c, VSLAM_ERR_CAPACITY, "orb_detect: more than 65535 FAST corners on a level"); }
-    if (rc == VSLAM_OK && total > cap) rc = fail(c, VSLAM_ERR_CAPACITY, "orb_detect: output capacity too small");
-  }
-  for (vslam_ctx* t : scratch) scratch_put(c, t);
-  for (void* q : tmp) (void)hipFree(q);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return rc;
-}
-
 VS_API int vslam_get_poses(vslam_ctx* c, int s, int32_t first, int32_t nf, double* out) {
   int rc = check_stream(c, s);
   if (rc) return rc;
@@ -1821,519 +1328,8 @@ VS_API int vslam_enable_timers(vslam_ctx* c, int on) {
   return VSLAM_OK;
 }
 
-// ---- stand-alone kernels ---------------------------------------------------------------------------
-static int make_scratch_ctx(vslam_ctx* parent, int rows, int cols, int nmax, int maxp, vslam_ctx** out) {
-  vslam_config cfg = parent->cfg.c;
-  cfg.rows = rows; cfg.cols = cols; cfg.det_rows = 1; cfg.det_cols = 1;
-  cfg.descriptor_type = VSLAM_DESCRIPTOR_BRIEF;   // the stand-alone FAST / BRIEF entries need the box image whatever the parent uses
-  cfg.max_keypoints = std::max(64, nmax); cfg.max_points = std::max(64, maxp); cfg.max_history_frames = 2;
-  return scratch_get(parent, cfg, out);
-}
-VS_API int vslam_fast_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, int32_t rx, int32_t ry,
-                             int32_t rw, int32_t rh, int32_t threshold, int32_t cap, int32_t* n, int16_t* xy, int32_t* score) {
-  if (!c || !img || !n) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (rx < 0 || ry < 0 || rw < 1 || rh < 1 || rx + rw > cols || ry + rh > rows || cap < 0 || (cap && (!xy))) return fail(c, VSLAM_ERR_INVALID, "ROI outside the image");
-  HIP_TRY(c, hipSetDevice(c->device));
-  vslam_ctx* t = nullptr;
-  int rc = make_scratch_ctx(c, rows, cols, std::min(rows * cols, 65535), 64, &t);   // 16-bit feature indices; independent of `cap`: one pooled scratch context serves every call
-  if (rc != VSLAM_OK) return rc;
-  t->cfg.n_regions = 1;
-  t->cfg.regions[0].x = rx; t->cfg.regions[0].y = ry; t->cfg.regions[0].w = rw; t->cfg.regions[0].h = rh;
-  StreamState st;
-  hipError_t e = hipMemcpy(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost);
-  st.thr[0] = threshold;
-  if (e == hipSuccess) e = hipMemcpy(t->buf.st, &st, sizeof st, hipMemcpyHostToDevice);
-  rc = e == hipSuccess ? upload_images(t, img, img, stride, 0) : fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  if (rc == VSLAM_OK) {
-    dim3 g1(t->cfg.TX, (rows + VS_TILE_H - 1) / VS_TILE_H, 2);
-    hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, t->stream_img, t->cfg, t->buf);
-    hipLaunchKernelGGL(k_emit, dim3(1, 2), dim3(512), 0, t->stream_img, t->cfg, t->buf, 0, 0);
-    int32_t cnt = 0;
-    rc = vslam_get_keypoints(t, 0, 0, cap, &cnt, xy, score, nullptr);
-    *n = cnt;
-    if (rc == VSLAM_OK) {
-      // more corners in the ROI than the scratch buffers hold (k_emit clamps and raises error bit 0): not a silent truncation
-      ImgInfo ii;
-      if (hipMemcpy(&ii, t->sets[t->last_set].iinfo, sizeof ii, hipMemcpyDeviceToHost) == hipSuccess && ii.raw_count[0][0] > cnt) {
-        *n = ii.raw_count[0][0];
-        rc = fail(c, VSLAM_ERR_CAPACITY, "fast_detect: more corners than the output capacity (65535 at most)");
-      }
-    }
-    if (rc == VSLAM_OK) for (int i = 0; i < cnt; ++i) { xy[2 * i] = (int16_t)(xy[2 * i] - rx); xy[2 * i + 1] = (int16_t)(xy[2 * i + 1] - ry); }
-    else if (rc != VSLAM_ERR_CAPACITY || c->err.empty()) c->err = t->err;
-  }
-  scratch_put(c, t);
-  return rc;
-}
-VS_API int vslam_brief_describe(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, int32_t n,
-                                const int16_t* xy, uint8_t* keep, uint8_t* desc) {
-  tmp_reset(c);
-  if (!c || !img || !xy || !keep || !desc || n < 0) return VSLAM_ERR_INVALID;
-  vslam_ctx* t = nullptr;
-  int rc = make_scratch_ctx(c, rows, cols, 64, 64, &t);
-  if (rc != VSLAM_OK) return rc;
-  int16_t* dxy = nullptr; uint8_t* dkeep = nullptr; uint8_t* ddesc = nullptr;
-  hipError_t e = tmp_alloc(c, &dxy, (size_t)n * 2);
-  if (e == hipSuccess) e = tmp_alloc(c, &dkeep, (size_t)n);
-  if (e == hipSuccess) e = tmp_alloc(c, &ddesc, (size_t)n * 32);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(dxy, xy, (size_t)n * 2 * sizeof(int16_t), hipMemcpyHostToDevice, t->stream_img);
-  rc = e == hipSuccess ? upload_images(t, img, img, stride, 0) : fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  if (rc == VSLAM_OK && n) {
-    dim3 g1(t->cfg.TX, (rows + VS_TILE_H - 1) / VS_TILE_H, 2);
-    hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, t->stream_img, t->cfg, t->buf);
-    hipLaunchKernelGGL(k_brief_at, dim3(std::min(64, (n + 3) / 4)), dim3(256), 0, t->stream_img, t->buf.box, t->cfg.bstride, rows, cols,
-                       n, dxy, dkeep, ddesc);
-    e = hipMemcpyAsync(keep, dkeep, (size_t)n, hipMemcpyDeviceToHost, t->stream_img);
-    if (e == hipSuccess) e = hipMemcpyAsync(desc, ddesc, (size_t)n * 32, hipMemcpyDeviceToHost, t->stream_img);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream_img);
-    if (e != hipSuccess) rc = fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  }
-  scratch_put(c, t);
-  return rc;
-}
-// cv::ORB::create()->compute() pieces, stand-alone (known-answer tests)
-static int orb_blur_device(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, uint8_t** dimg, uint8_t** dblur) {
-  hipError_t e = tmp_get(c, (void**)dimg, (size_t)rows * stride);     // per-call scratch: the caller has reset the arena
-  if (e == hipSuccess) e = tmp_get(c, (void**)dblur, (size_t)rows * cols);
-  if (e == hipSuccess) e = hipMemcpyAsync(*dimg, img, (size_t)(rows - 1) * stride + cols, hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = c->cfg.gauss7[i];
-  hipLaunchKernelGGL(k_gauss7_plain, dim3((cols + VS_TILE_W - 1) / VS_TILE_W, (rows + VS_TILE_H - 1) / VS_TILE_H), dim3(256), 0, c->stream, *dimg, stride, rows, cols, gk, *dblur, cols);
-  return VSLAM_OK;
-}
-VS_API int vslam_gaussian_blur7_u8(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, uint8_t* out) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!img || !out || rows < 4 || cols < 4 || stride < cols) return fail(c, VSLAM_ERR_INVALID, "gaussian_blur7: bad argument");   // one reflection per border
-  HIP_TRY(c, hipSetDevice(c->device));
-  tmp_reset(c);
-  uint8_t *dimg = nullptr, *dblur = nullptr;
-  int rc = orb_blur_device(c, img, rows, cols, stride, &dimg, &dblur);
-  hipError_t e = hipSuccess;
-  if (rc == VSLAM_OK) e = hipMemcpyAsync(out, dblur, (size_t)rows * cols, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (rc != VSLAM_OK) return rc;
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-VS_API int vslam_orb_describe(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, int32_t n, const int16_t* xy,
-                              float angle_degrees, uint8_t* keep, uint8_t* desc) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!img || n < 0 || rows < 4 || cols < 4 || stride < cols || (n && (!xy || !keep || !desc))) return fail(c, VSLAM_ERR_INVALID, "orb_describe: bad argument");
-  if (n == 0) return VSLAM_OK;
-  if (rows < 2 * VSLAM_ORB_BORDER + 1 || cols < 2 * VSLAM_ORB_BORDER + 1) {   // no pixel is 31 px away from every border: all keypoints removed
-    std::memset(keep, 0, (size_t)n);
-    std::memset(desc, 0, (size_t)n * 32);
-    return VSLAM_OK;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  uint8_t *dimg = nullptr, *dblur = nullptr, *dkeep = nullptr, *ddesc = nullptr; int16_t* dxy = nullptr;
-  int rc = orb_blur_device(c, img, rows, cols, stride, &dimg, &dblur);
-  hipError_t e = hipSuccess;
-  if (rc == VSLAM_OK) {
-    e = tmp_get(c, (void**)&dxy, (size_t)n * 4);
-    if (e == hipSuccess) e = tmp_get(c, (void**)&dkeep, (size_t)n);
-    if (e == hipSuccess) e = tmp_get(c, (void**)&ddesc, (size_t)n * 32);
-    if (e == hipSuccess) e = hipMemcpyAsync(dxy, xy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-      float a, b;
-      orb_rotation_host(angle_degrees, &a, &b);
-      hipLaunchKernelGGL(k_orb_at, dim3(std::min(64, (n + 3) / 4)), dim3(256), 0, c->stream, dblur, cols, rows, cols, n, dxy, a, b, dkeep, ddesc);
-      e = hipMemcpyAsync(keep, dkeep, (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(desc, ddesc, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  }
-  if (rc != VSLAM_OK) return rc;
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-// cv::ORB::create()->compute() on an OrbDetector's keypoints: a pyramid up to the highest octave present (level l from level l-1, as the detector
-// builds it), the 7x7 Gaussian per level, the steered tests per keypoint at its level.  Positions, border filter and rotations are host arithmetic
-// (float products rounded half-to-even, cos / sin through the host libm as OpenCV evaluates them).
-VS_API int vslam_orb_describe_keypoints(vslam_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, int32_t n, const float* kp6,
-                                        float scale_factor, uint8_t* keep, uint8_t* desc) {
-  tmp_reset(c);
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!img || n < 0 || rows < 4 || cols < 4 || stride < cols || !(scale_factor > 1.f) || (n && (!kp6 || !keep || !desc))) return fail(c, VSLAM_ERR_INVALID, "orb_describe_keypoints: bad argument");
-  if (n == 0) return VSLAM_OK;
-  int top = 0;
-  for (int i = 0; i < n; ++i) { const int o = (int)kp6[6 * (size_t)i + 5]; if (o < 0 || o > 15) return fail(c, VSLAM_ERR_INVALID, "orb_describe_keypoints: octave out of range"); top = std::max(top, o); }
-  HIP_TRY(c, hipSetDevice(c->device));
-  OrbLevels L;
-  std::memset(&L, 0, sizeof L);
-  float scale[16];
-  uint8_t* raw[16];
-  hipError_t e = hipSuccess;
-  for (int l = 0; l <= top; ++l) {      // every level is validated BEFORE the first launch: an error return must not leave kernels running on the arena
-    scale[l] = (float)std::pow((double)scale_factor, (double)l);
-    L.rows[l] = l ? (int)std::lrint(rows / scale[l]) : rows; L.cols[l] = l ? (int)std::lrint(cols / scale[l]) : cols;
-    if (L.rows[l] < 8 || L.cols[l] < 8) return fail(c, VSLAM_ERR_INVALID, "orb_describe_keypoints: pyramid level smaller than 8 pixels");
-  }
-  for (int l = 0; l <= top && e == hipSuccess; ++l) {
-    L.stride[l] = L.cols[l];
-    uint8_t* blur = nullptr;
-    e = tmp_get(c, (void**)&raw[l], l ? (size_t)L.rows[l] * L.cols[l] : (size_t)rows * stride);
-    if (e == hipSuccess) e = tmp_get(c, (void**)&blur, (size_t)L.rows[l] * L.cols[l]);
-    L.blur[l] = blur;
-    if (e != hipSuccess) break;
-    const int lstride = l ? L.cols[l] : stride;
-    if (l == 0) e = hipMemcpyAsync(raw[0], img, (size_t)(rows - 1) * stride + cols, hipMemcpyHostToDevice, c->stream);
-    else hipLaunchKernelGGL(k_resize_linear_u8, dim3((L.cols[l] + 255) / 256, L.rows[l]), dim3(256), 0, c->stream, raw[l - 1], L.rows[l - 1], L.cols[l - 1],
-                            l == 1 ? stride : L.cols[l - 1], raw[l], L.rows[l], L.cols[l], L.cols[l]);
-    Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = c->cfg.gauss7[i];
-    hipLaunchKernelGGL(k_gauss7_plain, dim3((L.cols[l] + VS_TILE_W - 1) / VS_TILE_W, (L.rows[l] + VS_TILE_H - 1) / VS_TILE_H), dim3(256), 0, c->stream, raw[l], lstride,
-                       L.rows[l], L.cols[l], gk, blur, L.cols[l]);
-  }
-  std::vector<int32_t> pos((size_t)n * 3);
-  std::vector<float> ab((size_t)n * 2);
-  const int reach = 23;   // the rotated 31 x 31 pattern reaches cvRound(15 sqrt 2) = 21 pixels
-  for (int i = 0; i < n; ++i) {
-    const float* k = kp6 + 6 * (size_t)i;
-    const int lv = (int)k[5];
-    const float inv = 1.f / scale[lv];
-    const int cx = (int)std::lrint(k[0] * inv), cy = (int)std::lrint(k[1] * inv);
-    const int x0 = (int)std::lrint(k[0]), y0 = (int)std::lrint(k[1]);
-    const bool in = x0 >= VSLAM_ORB_BORDER && x0 < cols - VSLAM_ORB_BORDER && y0 >= VSLAM_ORB_BORDER && y0 < rows - VSLAM_ORB_BORDER &&   // runByImageBorder(31) at level 0
-                    cx >= reach && cy >= reach && cx < L.cols[lv] - reach && cy < L.rows[lv] - reach;
-    pos[3 * (size_t)i] = cx; pos[3 * (size_t)i + 1] = cy; pos[3 * (size_t)i + 2] = in ? lv : -1;
-    orb_rotation_host(k[3], &ab[2 * (size_t)i], &ab[2 * (size_t)i + 1]);
-  }
-  int32_t* dpos = nullptr; float* dab = nullptr; uint8_t *dkeep = nullptr, *ddesc = nullptr;
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dpos, pos.size() * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dab, ab.size() * 4);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dkeep, (size_t)n);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&ddesc, (size_t)n * 32);
-  if (e == hipSuccess) e = hipMemcpyAsync(dpos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_orb_at_levels, dim3(std::min(64, (n + 3) / 4)), dim3(256), 0, c->stream, L, n, dpos, dab, dkeep, ddesc);
-    e = hipMemcpyAsync(keep, dkeep, (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(desc, ddesc, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);    // also: the host staging vectors may go out of scope now
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-// ---- descriptor test pairs as run-time data (the tables are __constant__ arrays of this module: one copy per device) ------
-static int pattern_io(int device, int which, const int8_t* in, int8_t* out) {
-  if ((!in && !out) || device < 0) { g_create_error = "pattern: bad argument"; return VSLAM_ERR_INVALID; }
-  if (in) {
-    for (int i = 0; i < 256; ++i) {
-      const int8_t* q = in + 4 * i;
-      if (which == 0) {
-        for (int k = 0; k < 4; ++k) if (q[k] < -VSLAM_BRIEF_PATCH_HALF || q[k] > VSLAM_BRIEF_PATCH_HALF) { g_create_error = "brief pattern: offset beyond the 48 px patch"; return VSLAM_ERR_INVALID; }
-      } else {
-        // a 31 x 31 patch: |x|, |y| <= 15 (OpenCV's bit_pattern_31_ reaches (12, -13), radius 17.7).  Where the reach matters: the
-        // tiled extractor (k_orb_describe) stages a 16 px margin and rotates by the FAST keypoints' fixed -1 degree, so a rotated,
-        // rounded offset is at most rint(15 cos 1 + 15 sin 1) = 15; the kernels that rotate by arbitrary angles gather from the
-        // whole image behind the 31 px border, and 15 sqrt 2 < 22.
-        for (int k = 0; k < 4; ++k) if (q[k] < -15 || q[k] > 15) { g_create_error = "orb pattern: offset beyond the 31 px patch (|x|, |y| <= 15)"; return VSLAM_ERR_INVALID; }
-      }
-    }
-  }
-  if (hipSetDevice(device) != hipSuccess) { g_create_error = "pattern: no such HIP device"; return VSLAM_ERR_NO_DEVICE; }
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess && in) e = which == 0 ? hipMemcpyToSymbol(HIP_SYMBOL(c_brief), in, 1024) : hipMemcpyToSymbol(HIP_SYMBOL(c_orb), in, 1024);
-  if (e == hipSuccess && out) e = which == 0 ? hipMemcpyFromSymbol(out, HIP_SYMBOL(c_brief), 1024) : hipMemcpyFromSymbol(out, HIP_SYMBOL(c_orb), 1024);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { g_create_error = std::string("pattern: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
-  return VSLAM_OK;
-}
-VS_API int vslam_set_brief_pattern(int device, const int8_t* pairs) { return pattern_io(device, 0, pairs, nullptr); }
-VS_API int vslam_set_orb_pattern(int device, const int8_t* pairs) { return pattern_io(device, 1, pairs, nullptr); }
-VS_API int vslam_get_brief_pattern(int device, int8_t* out) { return pattern_io(device, 0, nullptr, out); }
-VS_API int vslam_get_orb_pattern(int device, int8_t* out) { return pattern_io(device, 1, nullptr, out); }
-
-VS_API int vslam_knn2(vslam_ctx* c, int norm, int32_t nq, const uint8_t* q, int32_t nt, const uint8_t* t, int32_t* idx, float* dist) {
-  tmp_reset(c);
-  if (!c || !q || !t || !idx || !dist || nq < 0 || nt < 0 || norm < 0 || norm > 3) return VSLAM_ERR_INVALID;
-  if (nq == 0) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  uint8_t *dq = nullptr, *dt = nullptr; int32_t* di = nullptr; float* dd = nullptr;
-  hipError_t e = tmp_get(c, (void**)&dq, (size_t)nq * 32);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dt, std::max<size_t>((size_t)nt * 32, 32));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&di, (size_t)nq * 2 * sizeof(int32_t));
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dd, (size_t)nq * 2 * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nt) e = hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_knn2, dim3((nq + 15) / 16), dim3(256), 0, c->stream, norm, nq, dq, nt, dt, di, dd);
-    e = hipMemcpyAsync(idx, di, (size_t)nq * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(dist, dd, (size_t)nq * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-static int align_points_impl(vslam_ctx* c, bool uvd, int32_t n, const double* moving, const double* fixed4, const double* omega,
-                             const double* weight, const double T_init[12], double T_out[12], double* chi, uint8_t* inlier,
-                             int32_t* n_inliers, double* total_error, int32_t* iterations, double H_out[36]) {
-  tmp_reset(c);
-  vslam_ctx* t = nullptr;
-  vslam_config cfg = c->cfg.c;
-  cfg.max_points = (std::max(64, n) + 1023) / 1024 * 1024; cfg.max_keypoints = 64; cfg.max_history_frames = 2;   // rounded: one pooled scratch context serves every call
-  int rc = scratch_get(c, cfg, &t);
-  if (rc != VSLAM_OK) return rc;
-  double* dT = nullptr;
-  hipError_t e = tmp_alloc(c, &dT, 12);
-  if (e == hipSuccess) e = hipMemcpyAsync(dT, T_init, 12 * sizeof(double), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(t->buf.al_moving, moving, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(t->buf.al_fixed, fixed4, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(t->buf.al_omega, omega, (size_t)n * sizeof(double), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(t->buf.al_weight, weight, (size_t)n * sizeof(double), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) {
-    if (uvd) hipLaunchKernelGGL(k_align_points<true>, dim3(1), dim3(VS_WG), 0, t->stream, t->cfg, t->buf, n, dT);
-    else hipLaunchKernelGGL(k_align_points<false>, dim3(1), dim3(VS_WG), 0, t->stream, t->cfg, t->buf, n, dT);
-    StreamState st;
-    e = hipMemcpyAsync(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost, t->stream);
-    if (e == hipSuccess && chi && n) e = hipMemcpyAsync(chi, t->buf.al_chi, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, t->stream);
-    if (e == hipSuccess && inlier && n) e = hipMemcpyAsync(inlier, t->buf.al_inl, (size_t)n, hipMemcpyDeviceToHost, t->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e == hipSuccess) {
-      if (T_out) std::memcpy(T_out, st.al_T, sizeof(double) * 12);
-      if (H_out) std::memcpy(H_out, st.al_H, sizeof(double) * 36);
-      if (n_inliers) *n_inliers = st.al_inliers;
-      if (total_error) *total_error = st.al_total_error;
-      if (iterations) *iterations = st.al_iterations;
-    }
-  }
-  if (e != hipSuccess) rc = fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  scratch_put(c, t);
-  return rc;
-}
-VS_API int vslam_align_points(vslam_ctx* c, int32_t n, const double* moving, const double* fixed, const double* omega,
-                              const double* weight, const double T_init[12], double T_out[12], double* chi, uint8_t* inlier,
-                              int32_t* n_inliers, double* total_error, int32_t* iterations, double H_out[36]) {
-  if (!c || n < 0 || !moving || !fixed || !omega || !weight || !T_init) return VSLAM_ERR_INVALID;
-  return align_points_impl(c, false, n, moving, fixed, omega, weight, T_init, T_out, chi, inlier, n_inliers, total_error, iterations, H_out);
-}
-VS_API int vslam_align_points_uvd(vslam_ctx* c, int32_t n, const double* moving, const double* fixed_uvd, const double* omega_uv,
-                                  const double* omega_depth, const double* weight, const double T_init[12], double T_out[12],
-                                  double* chi, uint8_t* inlier, int32_t* n_inliers, double* total_error, int32_t* iterations,
-                                  double H_out[36]) {
-  if (!c || n < 0 || !moving || !fixed_uvd || !omega_uv || !omega_depth || !weight || !T_init) return VSLAM_ERR_INVALID;
-  std::vector<double> f4((size_t)std::max(n, 1) * 4);   // (u, v, depth, depth information) per measurement
-  for (int i = 0; i < n; ++i) { f4[4 * (size_t)i] = fixed_uvd[3 * (size_t)i]; f4[4 * (size_t)i + 1] = fixed_uvd[3 * (size_t)i + 1]; f4[4 * (size_t)i + 2] = fixed_uvd[3 * (size_t)i + 2]; f4[4 * (size_t)i + 3] = omega_depth[i]; }
-  return align_points_impl(c, true, n, moving, f4.data(), omega_uv, weight, T_init, T_out, chi, inlier, n_inliers, total_error, iterations, H_out);
-}
-
-// features of one image of scratch context t as the image pipeline would leave them: row-major order, coordinates,
-// descriptors, cleared used flags, the row / 16-px-cell CSR.  order[k] = caller index of sorted feature k.
-static int upload_features(vslam_ctx* c, vslam_ctx* t, int side, int n, const int32_t* rcx, const uint8_t* dx, std::vector<int>& ord) {
-  const DevCfg& dc = t->cfg;
-  const int rows = dc.c.rows, cols = dc.c.cols, CW1 = dc.CW + 1;
-  ord.resize(n);
-  for (int i = 0; i < n; ++i) {
-    ord[i] = i;
-    if (rcx[2 * i] < 0 || rcx[2 * i] >= rows || rcx[2 * i + 1] < 0 || rcx[2 * i + 1] >= cols) return fail(c, VSLAM_ERR_INVALID, "feature outside the image");
-  }
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return rcx[2 * a] != rcx[2 * b] ? rcx[2 * a] < rcx[2 * b] : rcx[2 * a + 1] < rcx[2 * b + 1]; });
-  std::vector<int16_t> xy((size_t)std::max(n, 1) * 2);
-  std::vector<uint8_t> ds((size_t)std::max(n, 1) * 32), used((size_t)std::max(n, 1), 0);
-  std::vector<int32_t> rowcell((size_t)rows * CW1);
-  for (int k = 0; k < n; ++k) {
-    xy[2 * k] = (int16_t)rcx[2 * ord[k] + 1]; xy[2 * k + 1] = (int16_t)rcx[2 * ord[k]];
-    std::memcpy(&ds[(size_t)32 * k], dx + (size_t)32 * ord[k], 32);
-  }
-  int k = 0;
-  for (int r = 0; r < rows; ++r)
-    for (int cc = 0; cc < CW1; ++cc) {
-      while (k < n && (xy[2 * k + 1] < r || (xy[2 * k + 1] == r && xy[2 * k] < 16 * cc))) ++k;
-      rowcell[(size_t)r * CW1 + cc] = k;
-    }
-  const size_t N = dc.NMAX;
-  hipError_t e = hipSuccess;
-  if (n) e = hipMemcpyAsync(t->buf.kp_xy + side * N * 2, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(t->buf.desc + side * N * 32, ds.data(), (size_t)n * 32, hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(t->buf.used + side * N, used.data(), (size_t)n, hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->buf.rowcell + (size_t)side * rows * CW1, rowcell.data(), rowcell.size() * 4, hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->buf.n_kp + side, &n, 4, hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);   // the host vectors go out of scope
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-
-VS_API int vslam_track_match(vslam_ctx* c, const double T[12], int32_t d, double tau_track, double tau_tri, int32_t by_appearance,
-                             int32_t nP, const double* cam, const uint8_t* pdL, const uint8_t* pdR, const int32_t* epi,
-                             int32_t nL, const int32_t* rcL, const uint8_t* dL, int32_t nR, const int32_t* rcR, const uint8_t* dR,
-                             int32_t* n_tracked, int32_t* out4, int32_t* n_lost, int32_t* lost) {
-  if (!c || !T || nP < 0 || nL < 0 || nR < 0 || !n_tracked || !out4 || !n_lost || !lost) return VSLAM_ERR_INVALID;
-  if ((nP && (!cam || !pdL || !pdR || !epi)) || (nL && (!rcL || !dL)) || (nR && (!rcR || !dR))) return VSLAM_ERR_INVALID;
-  vslam_ctx* t = nullptr;
-  vslam_config cfg = c->cfg.c;
-  cfg.max_points = std::max(64, nP); cfg.max_keypoints = std::max(64, std::max(nL, nR)); cfg.max_history_frames = 2;
-  int rc = scratch_get(c, cfg, &t);
-  if (rc != VSLAM_OK) return rc;
-  std::vector<int> order[2];
-  rc = upload_features(c, t, 0, nL, rcL, dL, order[0]);
-  if (rc == VSLAM_OK) rc = upload_features(c, t, 1, nR, rcR, dR, order[1]);
-  hipError_t e = hipSuccess;
-  if (rc == VSLAM_OK) {
-    // previous points in point buffer 0
-    std::vector<uint8_t> pdesc((size_t)std::max(nP, 1) * 64);
-    std::vector<int32_t> meta((size_t)std::max(nP, 1) * META, 0);
-    for (int i = 0; i < nP; ++i) {
-      std::memcpy(&pdesc[(size_t)64 * i], pdL + (size_t)32 * i, 32); std::memcpy(&pdesc[(size_t)64 * i + 32], pdR + (size_t)32 * i, 32);
-      meta[(size_t)i * META + M_EPI] = epi[i]; meta[(size_t)i * META + M_PREV] = -1;
-    }
-    if (nP) e = hipMemcpyAsync(t->buf.p_cam, cam, (size_t)nP * 3 * sizeof(double), hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess && nP) e = hipMemcpyAsync(t->buf.p_desc, pdesc.data(), (size_t)nP * 64, hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess && nP) e = hipMemcpyAsync(t->buf.p_meta, meta.data(), (size_t)nP * META * 4, hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t->buf.n_points, &nP, 4, hipMemcpyHostToDevice, t->stream);
-    StreamState st;
-    if (e == hipSuccess) e = hipMemcpyAsync(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost, t->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e == hipSuccess) {
-      st.has_prev = 1; st.cur = 0; st.win = d; st.tau_track = tau_track; st.tau_tri = tau_tri;
-      st.status = by_appearance ? VSLAM_LOCALIZING : VSLAM_TRACKING;
-      std::memcpy(st.prior, T, sizeof(double) * 12);
-      e = hipMemcpyAsync(t->buf.st, &st, sizeof st, hipMemcpyHostToDevice, t->stream);
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_track_candidates, dim3(16, 1), dim3(256), 0, t->stream, t->cfg, t->buf, by_appearance ? 1 : 0);
-      hipLaunchKernelGGL(k_stage, dim3(1), dim3(VS_WG), 0, t->stream, t->cfg, t->buf, (int)VS_STAGE_TRACK, by_appearance ? 1 : 0, StageIo{});
-      e = hipMemcpyAsync(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost, t->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    }
-    if (e == hipSuccess) {
-      std::vector<int32_t> trk((size_t)std::max(st.n_trk, 1) * 4), ls((size_t)std::max(st.n_lost, 1));
-      if (st.n_trk) e = hipMemcpy(trk.data(), t->buf.trk, (size_t)st.n_trk * 16, hipMemcpyDeviceToHost);
-      if (e == hipSuccess && st.n_lost) e = hipMemcpy(ls.data(), t->buf.lost, (size_t)st.n_lost * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) {
-        *n_tracked = st.n_trk; *n_lost = st.n_lost;
-        for (int u = 0; u < st.n_trk; ++u) {
-          out4[4 * u] = trk[4 * u]; out4[4 * u + 1] = order[0][trk[4 * u + 1]]; out4[4 * u + 2] = order[1][trk[4 * u + 2]]; out4[4 * u + 3] = trk[4 * u + 3];
-        }
-        for (int u = 0; u < st.n_lost; ++u) lost[u] = ls[u];
-      }
-    }
-    if (e != hipSuccess) rc = fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  }
-  scratch_put(c, t);
-  return rc;
-}
-
-VS_API int vslam_stereo_match(vslam_ctx* c, double tau_tri, int32_t nL, const int32_t* rcL, const uint8_t* dL, int32_t nR,
-                              const int32_t* rcR, const uint8_t* dR, int32_t cap, int32_t* n_out, int32_t* out4) {
-  if (!c || nL < 0 || nR < 0 || cap < 0 || !n_out || (cap && !out4) || (nL && (!rcL || !dL)) || (nR && (!rcR || !dR))) return VSLAM_ERR_INVALID;
-  vslam_ctx* t = nullptr;
-  vslam_config cfg = c->cfg.c;
-  cfg.max_keypoints = std::max(64, std::max(nL, nR)); cfg.max_points = std::max(64, nL); cfg.max_history_frames = 2;
-  int rc = scratch_get(c, cfg, &t);
-  if (rc != VSLAM_OK) return rc;
-  std::vector<int> order[2];
-  rc = upload_features(c, t, 0, nL, rcL, dL, order[0]);
-  if (rc == VSLAM_OK) rc = upload_features(c, t, 1, nR, rcR, dR, order[1]);
-  if (rc == VSLAM_OK) {
-    StreamState st;
-    hipError_t e = hipMemcpyAsync(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost, t->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e == hipSuccess) {
-      st.tau_tri = tau_tri; st.n_cur = 0; st.cur = 0;
-      e = hipMemcpyAsync(t->buf.st, &st, sizeof st, hipMemcpyHostToDevice, t->stream);
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_stereo_dist, dim3((t->cfg.NMAX + 255) / 256, 1), dim3(256), 0, t->stream, t->cfg, t->buf);
-      hipLaunchKernelGGL(k_stage, dim3(1), dim3(VS_WG), 0, t->stream, t->cfg, t->buf, (int)VS_STAGE_STEREO, 0, StageIo{});
-      e = hipMemcpyAsync(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost, t->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    }
-    if (e == hipSuccess) {
-      const int n = st.n_new;
-      *n_out = n;
-      if (n > cap) rc = fail(c, VSLAM_ERR_CAPACITY, "stereo_match: output capacity too small");
-      else if (n) {
-        // the new points were written to point buffer 1 (current = previous ^ 1)
-        const size_t P = t->cfg.MAXP;
-        std::vector<int16_t> kp((size_t)n * 4);
-        std::vector<int32_t> meta((size_t)n * META);
-        e = hipMemcpy(kp.data(), t->buf.p_kp + P * 4, (size_t)n * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(meta.data(), t->buf.p_meta + P * META, (size_t)n * META * 4, hipMemcpyDeviceToHost);
-        for (int i = 0; i < n && e == hipSuccess; ++i) {
-          int il = -1, ir = -1;   // ids by coordinates (one feature per pixel)
-          for (int k = 0; k < nL; ++k) if (rcL[2 * k] == kp[4 * i + 1] && rcL[2 * k + 1] == kp[4 * i]) il = k;
-          for (int k = 0; k < nR; ++k) if (rcR[2 * k] == kp[4 * i + 3] && rcR[2 * k + 1] == kp[4 * i + 2]) ir = k;
-          out4[4 * i] = il; out4[4 * i + 1] = ir; out4[4 * i + 2] = meta[(size_t)i * META + M_DIST]; out4[4 * i + 3] = meta[(size_t)i * META + M_EPI];
-        }
-      }
-    }
-    if (e != hipSuccess) rc = fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  }
-  scratch_put(c, t);
-  return rc;
-}
-
-VS_API int vslam_stereo_recover(vslam_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int32_t row_stride, const double w2c[12], int32_t n,
-                                const uint8_t* has_lm, const double* lm, const uint8_t* pdL, const uint8_t* pdR, double tau_track, double tau_tri,
-                                int32_t* n_rec, int32_t* rec_index, int32_t* rec_xy4, int32_t* rec_dist, uint8_t* rec_desc, double* rec_xyz) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!imgL || !imgR || !w2c || n < 0 || !n_rec || (n && (!has_lm || !lm || !pdL || !pdR || !rec_index || !rec_xy4 || !rec_dist || !rec_desc || !rec_xyz)))
-    return fail(c, VSLAM_ERR_INVALID, "stereo_recover: bad argument");
-  if (row_stride < c->cfg.c.cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
-  *n_rec = 0;
-  if (n == 0) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  vslam_ctx* t = nullptr;
-  vslam_config cfg = c->cfg.c;
-  cfg.det_rows = 1; cfg.det_cols = 1; cfg.max_keypoints = 64; cfg.max_points = (std::max(64, n) + 1023) & ~1023; cfg.max_history_frames = 2;
-  int rc = scratch_get(c, cfg, &t);
-  if (rc != VSLAM_OK) return rc;
-  const size_t P = t->cfg.MAXP;
-  std::vector<uint8_t> desc((size_t)n * 64);
-  std::vector<int32_t> meta((size_t)n * META, 0), lost((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    std::memcpy(&desc[(size_t)64 * i], pdL + (size_t)32 * i, 32);
-    std::memcpy(&desc[(size_t)64 * i + 32], pdR + (size_t)32 * i, 32);
-    meta[(size_t)i * META + M_LMUP] = has_lm[i] ? 1 : 0;
-    meta[(size_t)i * META + M_PREV] = -1;
-    lost[i] = i;
-  }
-  hipStream_t q = t->stream_img;
-  hipError_t e = hipMemcpyAsync(t->buf.p_desc, desc.data(), desc.size(), hipMemcpyHostToDevice, q);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->buf.p_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, q);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->buf.p_lm, lm, (size_t)n * 24, hipMemcpyHostToDevice, q);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->buf.lost, lost.data(), (size_t)n * 4, hipMemcpyHostToDevice, q);
-  rc = e == hipSuccess ? upload_images(t, imgL, imgR, row_stride, 0) : fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  if (rc == VSLAM_OK) {
-    const int rows = t->cfg.c.rows;
-    if (t->cfg.c.descriptor_type == VSLAM_DESCRIPTOR_ORB) {
-      Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = t->cfg.gauss7[i];
-      hipLaunchKernelGGL(k_gauss7, dim3(t->cfg.TX, (rows + VS_TILE_H - 1) / VS_TILE_H, 2), dim3(256), 0, q, t->cfg, t->buf, gk);
-    } else {
-      hipLaunchKernelGGL(k_fast_box, dim3(t->cfg.TX, (rows + VS_TILE_H - 1) / VS_TILE_H, 2), dim3(256), VS_FB_DYN_LDS, q, t->cfg, t->buf);
-    }
-    RecoverAlone a;
-    std::memcpy(a.w2c, w2c, sizeof a.w2c); a.tau_track = tau_track; a.tau_tri = tau_tri; a.n = n;
-    hipLaunchKernelGGL(k_recover_alone, dim3(1), dim3(VS_WG), 0, q, t->cfg, t->buf, a);
-    e = hipGetLastError();
-    StreamState st;
-    if (e == hipSuccess) e = hipMemcpyAsync(&st, t->buf.st, sizeof st, hipMemcpyDeviceToHost, q);
-    if (e == hipSuccess) e = hipStreamSynchronize(q);
-    if (e == hipSuccess && st.n_cur > 0) {
-      const int k = st.n_cur;
-      std::vector<int16_t> kp((size_t)k * 4);
-      std::vector<int32_t> m((size_t)k * META);
-      e = hipMemcpy(kp.data(), t->buf.p_kp + P * 4, (size_t)k * 8, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(m.data(), t->buf.p_meta + P * META, (size_t)k * META * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(rec_desc, t->buf.p_desc + P * 64, (size_t)k * 64, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(rec_xyz, t->buf.p_cam + P * 3, (size_t)k * 24, hipMemcpyDeviceToHost);
-      for (int i = 0; i < k && e == hipSuccess; ++i) {
-        rec_index[i] = m[(size_t)i * META + M_PREV]; rec_dist[i] = m[(size_t)i * META + M_DIST];
-        for (int j = 0; j < 4; ++j) rec_xy4[4 * i + j] = kp[4 * (size_t)i + j];
-      }
-      if (e == hipSuccess) *n_rec = k;
-    }
-    if (e != hipSuccess) rc = fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  } else if (c->err.empty()) c->err = t->err;
-  scratch_put(c, t);
-  return rc;
-}
+// ---- stand-alone component entries (one piece of the pipeline on caller data) and their helpers ----
+#include "host_entries.h"
 
 // ---- stage entry points (the reference's plug-in virtuals; control flow stays with the caller) ----------
 static StageIo stage_io(vslam_ctx* c, int report, int in_progress) {
