@@ -386,6 +386,9 @@ __global__ __launch_bounds__(256) void k_recover_brief(const DevCfg c, const Dev
 #define VS_LM_CN 6
 #endif
 #define VS_LM_NP 48   // world_to_camera of the last VS_LM_NP frames staged in LDS (one copy for all points of the frame)
+// The trail addresses measurements 0 .. VS_TRAIL of a track directly; everything older goes through the ring's `prev` links and reads the ring.
+// The directly addressed part therefore never leaves the staged window (nor, in a team, the lanes' measurement slots: see landmark_team).
+static_assert(VS_TRAIL + 1 <= VS_LM_NP, "the directly addressed measurements must lie inside the staged pose window");
 struct LmCache { double w2c[VS_LM_NP][12]; double rtr[VS_LM_NP][9]; double cam[VS_WG][VS_LM_CN][4]; };
 // R^T R of world_to_camera k (J^T J of every measurement taken in that frame: a property of the frame, symmetric to the bit) next to the staged poses
 __device__ __forceinline__ void lm_stage_rtr(LmCache* lc, int f, int hcap) {
@@ -520,8 +523,7 @@ __device__ __forceinline__ bool landmark_point(const DevCfg& c, const DevBuf& b,
             for (int u = 0; u < NB; ++u) {
               const int k = k0 + u;
               if (k < n_direct) {
-                if (k < VS_LM_NP) accumulate(lc->w2c[k], lc->rtr[k], mc[u], H, bv, err, n_out);
-                else accumulate(hpose_of(c, b, s, f - k) + 12, nullptr, mc[u], H, bv, err, n_out);
+                accumulate(lc->w2c[k], lc->rtr[k], mc[u], H, bv, err, n_out);   // k < n_direct <= VS_TRAIL + 1: inside the staged window
               }
             }
           }
@@ -587,6 +589,20 @@ struct LmTerm { double e2, h[6], b[3]; int kind, pad; };   // kind 0: behind the
 __device__ __forceinline__ bool landmark_is_long(const DevCfg& c, const int32_t* m) {
   return m[M_LMUP] != 0 && min(m[M_TLEN] + 1, c.HCAP) >= VS_LM_TEAM_MIN && c.trail;
 }
+// The active landmarks of a frame counted without refining them, for the callers whose refinement runs BESIDE them in the same launch (k_tail_lm,
+// k_stage_lm): a point is active iff its track is long enough for a landmark.  Called by the whole workgroup; returns this thread's share.
+// A track that outgrew the history ring raises error bit 4 here as well: the refinement's own atomicOr (landmark_point / landmark_team) is not
+// ordered against the report its neighbour workgroup writes, and the frame that truncates first must show the bit under every launch sequence.
+__device__ __forceinline__ int lm_count_active(const DevCfg& c, const DevBuf& b, int s, const PtView& cvc, int n_cur) {
+  int active = 0, cut = 0;
+  for (int i = threadIdx.x; i < n_cur; i += VS_WG) {
+    const int tlen = cvc.meta[(size_t)i * META + M_TLEN];
+    if (tlen >= c.c.minimum_track_length_for_landmark_creation) { ++active; cut |= tlen + 1 > c.HCAP ? 1 : 0; }
+  }
+  cut = __syncthreads_or(cut);
+  if (cut && threadIdx.x == 0) atomicOr(&b.st[s].error_flags, 4);
+  return active;
+}
 __device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, int s, const PtView& cv, int f, int i, LmCache* lc, LmTerm* terms, int gl) {
   const double* w2c_cur = hpose_of(c, b, s, f) + 12;
   int32_t* m = cv.meta + (size_t)i * META;
@@ -616,6 +632,7 @@ __device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, 
   }
   // this lane's measurements of the directly addressed part (k = gl, gl + 8, ...) into its LDS slots, all loads in flight, once
   constexpr int NG = VS_LM_CN;                       // groups whose measurements have a slot (k < 8 * NG)
+  static_assert(VS_TRAIL + 1 <= VS_LM_TEAM_G * NG, "every directly addressed measurement needs a slot");
   double (*slot)[4] = lc->cam[threadIdx.x];
   {
     double mv[NG][4];
@@ -647,17 +664,9 @@ __device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, 
       if (k < n_direct) {
         double mc[4];
         const int g = k0 / VS_LM_TEAM_G;
-        if (g < NG) { mc[0] = slot[g][0]; mc[1] = slot[g][1]; mc[2] = slot[g][2]; mc[3] = slot[g][3]; }
-        else { const double* src = hcam_of(c, b, s, f - k) + 4 * (size_t)tr[k - 1]; mc[0] = src[0]; mc[1] = src[1]; mc[2] = src[2]; mc[3] = src[3]; }
-        const double* W;
-        double rtr_far[9];
-        const double* RtR;
-        if (k < VS_LM_NP) { W = lc->w2c[k]; RtR = lc->rtr[k]; }
-        else {
-          W = hpose_of(c, b, s, f - k) + 12;
-          for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) rtr_far[3 * r + cc] = (W[r] * W[cc] + W[4 + r] * W[4 + cc]) + W[8 + r] * W[8 + cc];
-          RtR = rtr_far;
-        }
+        mc[0] = slot[g][0]; mc[1] = slot[g][1]; mc[2] = slot[g][2]; mc[3] = slot[g][3];      // k < n_direct: every directly addressed measurement has a slot
+        const double* W = lc->w2c[k];                                                         // ... and its frame lies inside the staged window
+        const double* RtR = lc->rtr[k];
         double sp[3];
         tf_apply(W, wv, sp);
         if (sp[2] <= 0) { t.kind = 0; }
@@ -1577,7 +1586,7 @@ __device__ __forceinline__ void frame_phase2(const DevCfg& c, const DevBuf& b, i
     info.track_attempts = fc.attempts; info.n_after_prune = fc.n_after_prune; info.n_recovered = fc.n_recovered;
     info.n_active_landmarks = n_active; info.n_new_stereo = sh.n_cand; info.n_points = sh.n_cur;
     info.track_broken = fc.broken; info.fallback = fc.fallback; info.window_pixels = fc.win;
-    info.error_flags = st.error_flags; info.tau_track = fc.tau_track; info.tau_triangulation = tau_tri2;
+    info.error_flags = ld_relaxed(&st.error_flags); info.tau_track = fc.tau_track; info.tau_triangulation = tau_tri2;
     for (int k = 0; k < 12; ++k) { info.camera_left_to_world[k] = c2w[k]; info.previous_to_current[k] = fc.prior[k]; }
     if (f < VS_POSE_LOG) { double* pl = b.pose_log + ((size_t)s * VS_POSE_LOG + f) * 12; for (int k = 0; k < 12; ++k) pl[k] = c2w[k]; }
     st.dbg[8] += wall_clock64() - fc.t0;
@@ -1799,9 +1808,7 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
     if (phase == 4) {
       // the landmark kernel will run BESIDE phase 2: the number of active landmarks — what the status switch needs — is the number of points
       // whose track is long enough for a landmark (landmark_point returns false for nothing else)
-      const PtView cvc = pts_of(c, b, s, pb_cur);
-      int active = 0;
-      for (int i = tid; i < sh.n_cur; i += VS_WG) active += cvc.meta[(size_t)i * META + M_TLEN] >= c.c.minimum_track_length_for_landmark_creation ? 1 : 0;
+      const int active = lm_count_active(c, b, s, pts_of(c, b, s, pb_cur), sh.n_cur);
       int total;
       block_exclusive_scan(active, sh.scan, &total);
       if (tid == 0) fc.n_active = total;
@@ -1993,9 +2000,7 @@ __device__ __forceinline__ void stage_body(const DevCfg& c, const DevBuf& b, int
   } else if (stage == VS_STAGE_UPDATE || stage == VS_STAGE_STEREO || stage == VS_STAGE_COMPUTE || stage == VS_STAGE_STEREO_COUNT) {
     if (stage == VS_STAGE_STEREO_COUNT) {
       // _number_of_active_landmarks without the refinement: a point is active iff its track is long enough for a landmark
-      const PtView cvc = pts_of(c, b, s, pb_cur);
-      int active = 0;
-      for (int i = tid; i < sh.n_cur; i += VS_WG) active += cvc.meta[(size_t)i * META + M_TLEN] >= c.c.minimum_track_length_for_landmark_creation ? 1 : 0;
+      const int active = lm_count_active(c, b, s, pts_of(c, b, s, pb_cur), sh.n_cur);
       int total;
       block_exclusive_scan(active, sh.scan, &total);
       if (tid == 0) { st.n_active = total; info.n_active_landmarks = total; }
@@ -2026,7 +2031,7 @@ __device__ __forceinline__ void stage_body(const DevCfg& c, const DevBuf& b, int
         int rl = 0, rr = 0;
         for (int r = 0; r < c.n_regions; ++r) { rl += b.iinfo[s].raw_count[0][r]; rr += b.iinfo[s].raw_count[1][r]; info.thresholds[r] = b.iinfo[s].thr_after[r]; }
         info.n_detected_left = rl; info.n_detected_right = rr;
-        info.n_new_stereo = sh.n_cand; info.n_points = sh.n_cur; info.window_pixels = st.win; info.error_flags = st.error_flags;
+        info.n_new_stereo = sh.n_cand; info.n_points = sh.n_cur; info.window_pixels = st.win; info.error_flags = ld_relaxed(&st.error_flags);
         info.tau_track = st.tau_track; info.tau_triangulation = st.tau_tri;
         for (int k = 0; k < 12; ++k) { info.camera_left_to_world[k] = c2w[k]; info.previous_to_current[k] = st.prior[k]; }
         if (f < VS_POSE_LOG) { double* pl = b.pose_log + ((size_t)s * VS_POSE_LOG + f) * 12; for (int k = 0; k < 12; ++k) pl[k] = c2w[k]; }

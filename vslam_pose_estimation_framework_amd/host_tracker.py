@@ -55,9 +55,12 @@ def _div(a, b):
 class PoseTracker3D(object):
     """pose_tracker_3d.h:14-134 — state and methods named as in the reference."""
 
-    def __init__(self, api):
+    def __init__(self, api, one_launch_compute=False):
+        """one_launch_compute: _updatePoints and the generator's compute() as ONE call (vslam_compute, what the shim issues) instead of
+        vslam_update_points + vslam_stereo_new."""
         self.api = api
         self.cfg = api.cfg
+        self.one_launch_compute = bool(one_launch_compute)
         self.configure()
 
     def _target_number_of_keypoints(self):
@@ -124,12 +127,20 @@ class PoseTracker3D(object):
         self._set_frame_pose(self._frame_pose)
         if has_previous:
             api.check(api.fn("prune_recover")(api.ctx))     # _prunePoints + recoverPoints
-        api.check(api.fn("update_points")(api.ctx))          # _updatePoints
-        self._number_of_active_landmarks = api.frame_info(0).n_active_landmarks
-        if self._number_of_active_landmarks > c.minimum_number_of_landmarks_to_track:
-            self._status = TRACKING
-        self._push_state()
-        api.check(api.fn("stereo_new")(api.ctx))             # _framepoint_generator->compute(current_frame)
+        if self.one_launch_compute:
+            # _updatePoints + compute(current_frame) in one launch; the frame's report carries the status the frame began with, the
+            # tracker's own status switches here as below
+            api.check(api.fn("compute")(api.ctx))
+            self._number_of_active_landmarks = api.frame_info(0).n_active_landmarks
+            if self._number_of_active_landmarks > c.minimum_number_of_landmarks_to_track:
+                self._status = TRACKING
+        else:
+            api.check(api.fn("update_points")(api.ctx))          # _updatePoints
+            self._number_of_active_landmarks = api.frame_info(0).n_active_landmarks
+            if self._number_of_active_landmarks > c.minimum_number_of_landmarks_to_track:
+                self._status = TRACKING
+            self._push_state()
+            api.check(api.fn("stereo_new")(api.ctx))             # _framepoint_generator->compute(current_frame)
         self._number_of_tracked_landmarks_previous = self._number_of_active_landmarks
         fi = api.frame_info(0)
         self._previous_pose = list(self._frame_pose)
