@@ -1,5 +1,5 @@
-"""The fused landmark refinement (landmark_point / landmark_team / wg_landmarks_lds / lm_teams_body, csrc/kernels_frame2.h) against the
-numpy rebuild of tests/landmark_rebuild.py — itself proved against the CPU oracle in tests/test_landmark_refinement_host.py — on the slow
+"""The fused landmark refinement (landmark_point / landmark_team / wg_landmarks_lds / lm_teams_body, csrc/kernels_frame_lm.h, on the
+arithmetic of csrc/landmark_math.h) against the numpy rebuild of tests/landmark_rebuild.py — itself proved against the CPU oracle in tests/test_landmark_refinement_host.py — on the slow
 street scene, whose tracks outgrow every seam of that code: one lane / a team of eight (9 measurements), the end of the 16-bit
 predecessor trail (33, from where the ring's `prev` links are walked) and the history ring itself (truncation, error bit 4).  With the
 default kernel every truncated update is kept, so only test_truncated_updates_whose_result_is_exported sees values computed over a cut list.

@@ -1,8 +1,9 @@
-// kernels_frame2.h — second half of the frame kernel: prune, recovery, landmark refinement,
+// kernels_frame2.h — second half of the frame kernel: prune, recovery, landmark refinement (kernels_frame_lm.h),
 // stereo sweep + binning, and the PoseTracker3D control flow that strings the stages together.
 #pragma once
 #include "kernels_frame.h"
 #include "kernels_report.h"
+#include "kernels_frame_lm.h"
 #include <type_traits>
 
 // write one framepoint (Frame::createFramepoint, types/frame.cpp:61-84) from a left/right feature pair
@@ -375,548 +376,6 @@ __global__ __launch_bounds__(256) void k_recover_brief(const DevCfg c, const Dev
   for (int q = wave; q < nl; q += nwaves) recover_brief_wave(c, b, s, st.cur, q, lane, st.fc.tau_gen, st.fc.tau_tri);
 }
 
-// _updatePoints' landmark part (pose_tracker_3d.cpp:475-520) for framepoint i of the current frame: creation = mean of the track's world
-// coordinates (Landmark::Landmark, landmark.cpp:19-31), otherwise Gauss-Newton refinement over all measurements of the track (Landmark::update,
-// :66-167).  Measurements are reached by walking the per-frame `prev` links of the history ring (frame f, index i) -> (f-1, prev[i]).  Returns
-// true when the point carries an active landmark afterwards.
-// The poses of the last VS_LM_NP frames are staged in LDS once per workgroup and the first VS_LM_CN measurements of the point's track once per
-// point (the chain walk is a chase of dependent HBM loads, and the Gauss-Newton rounds would repeat it); longer tracks continue in HBM from where
-// the cache ends.  Same order of accumulation, same bits.
-#ifndef VS_LM_CN
-#define VS_LM_CN 6
-#endif
-#define VS_LM_NP 48   // world_to_camera of the last VS_LM_NP frames staged in LDS (one copy for all points of the frame)
-// The trail addresses measurements 0 .. VS_TRAIL of a track directly; everything older goes through the ring's `prev` links and reads the ring.
-// The directly addressed part therefore never leaves the staged window (nor, in a team, the lanes' measurement slots: see landmark_team).
-static_assert(VS_TRAIL + 1 <= VS_LM_NP, "the directly addressed measurements must lie inside the staged pose window");
-struct LmCache { double w2c[VS_LM_NP][12]; double rtr[VS_LM_NP][9]; double cam[VS_WG][VS_LM_CN][4]; };
-// R^T R of world_to_camera k (J^T J of every measurement taken in that frame: a property of the frame, symmetric to the bit) next to the staged poses
-__device__ __forceinline__ void lm_stage_rtr(LmCache* lc, int f, int hcap) {
-  for (int t = threadIdx.x; t < VS_LM_NP * 9; t += VS_WG) {
-    const int k = t / 9, e = t - 9 * k, rr = e / 3, cc = e - 3 * rr;
-    if (f - k >= 0 && k < hcap) { const double* W = lc->w2c[k]; lc->rtr[k][e] = (W[rr] * W[cc] + W[4 + rr] * W[4 + cc]) + W[8 + rr] * W[8 + cc]; }
-  }
-}
-__device__ __forceinline__ bool landmark_point(const DevCfg& c, const DevBuf& b, int s, const PtView& cv, int f, int i, LmCache* lc) {
-  const double* w2c_cur = hpose_of(c, b, s, f) + 12;
-  {
-    int32_t* m = cv.meta + (size_t)i * META;
-    const int tlen = m[M_TLEN];
-    if (tlen < c.c.minimum_track_length_for_landmark_creation) return false;
-    int len = tlen + 1;
-    if (len > c.HCAP) { len = c.HCAP; atomicOr(&b.st[s].error_flags, 4); }
-    double wpos[3];
-    if (m[M_LMUP] == 0) {
-      // Landmark::Landmark: average of the world coordinates along the track
-      double acc[3] = {0, 0, 0};
-      int ff = f, ii = i;
-      for (int k = 0; k < len; ++k) {
-        double wp[3];
-        tf_apply(hpose_of(c, b, s, ff), hcam_of(c, b, s, ff) + 4 * (size_t)ii, wp);
-        for (int q = 0; q < 3; ++q) acc[q] += wp[q];
-        ii = hprev_of(c, b, s, ff)[ii];
-        --ff;
-        if (ii < 0 && k + 1 < len) { len = k + 1; break; }
-      }
-      for (int q = 0; q < 3; ++q) wpos[q] = acc[q] / (double)len;
-      m[M_LMUP] = len;
-    } else {
-      // Landmark::update
-      double wv[3] = {cv.lm[3 * (size_t)i], cv.lm[3 * (size_t)i + 1], cv.lm[3 * (size_t)i + 2]};
-      for (int q = 0; q < 3; ++q) wpos[q] = wv[q];
-      double err_prev = 0;
-      const double kern = c.c.landmark_maximum_error_squared_meters;
-      // one measurement of the track: residual, saturated kernel, H += R^T om R, b += R^T om e
-      // mc = x, y, z, 1 / z of the measurement (the history ring keeps the inverse depth: one division per measurement, not one per round);
-      // RtR = the staged R^T R of the measurement's frame, or null (computed here)
-      auto accumulate = [&](const double* W, const double* RtR, const double* mc, double* H, double* bv, double& err, int& n_out) {
-        double sp[3];
-        tf_apply(W, wv, sp);
-        if (sp[2] <= 0) {
-          ++n_out;
-        } else {
-          const double e[3] = {sp[0] - mc[0], sp[1] - mc[1], sp[2] - mc[2]};
-          double om = mc[3];
-          const double e2 = om * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-          err += e2;
-          if (e2 > kern) { om *= kern / e2; ++n_out; }
-          if (RtR) {
-            const double h01 = om * RtR[1], h02 = om * RtR[2], h12 = om * RtR[5];
-            H[0] += om * RtR[0]; H[4] += om * RtR[4]; H[8] += om * RtR[8];
-            H[1] += h01; H[3] += h01; H[2] += h02; H[6] += h02; H[5] += h12; H[7] += h12;
-          } else {
-            for (int r = 0; r < 3; ++r)
-              for (int cc = 0; cc < 3; ++cc) H[3 * r + cc] += om * ((W[r] * W[cc] + W[4 + r] * W[4 + cc]) + W[8 + r] * W[8 + cc]);
-          }
-          for (int r = 0; r < 3; ++r) bv[r] += om * ((W[r] * e[0] + W[4 + r] * e[1]) + W[8 + r] * e[2]);
-        }
-      };
-      // Measurement k of the track (frame f - k): index i for k = 0, the trail's entry k - 1 up to k = VS_TRAIL, then the
-      // `prev` links of the history ring.  n_direct = measurements addressed without a link walk; a 0xFFFF entry (the track
-      // starts there) ends the list like a negative `prev` link does.
-      const uint16_t* tr = cv.trail + (size_t)i * VS_TRAIL;
-      int n_direct = 1;
-      bool ended = false;
-      if (c.trail) {
-        const int want = min(len, VS_TRAIL + 1);
-        for (int q0 = 0; q0 < VS_TRAIL && n_direct < want && !ended; q0 += 8) {
-          const uint4 v = *reinterpret_cast<const uint4*>(tr + q0);
-          const uint32_t wv4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const uint32_t ent = (wv4[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
-            if (!ended && n_direct < want) { if (ent == 0xFFFFu) ended = true; else ++n_direct; }
-          }
-        }
-      }
-      auto index_at = [&](int k) -> int { return k == 0 ? i : (int)tr[k - 1]; };   // k < n_direct
-      // the first VS_LM_CN measurements into the thread's LDS slots, once
-      int ncache = 0, ffc = f, iic = i;
-      {
-        double (*slot)[4] = lc->cam[threadIdx.x];
-        if (c.trail) {
-          const int nc = min(min(len, VS_LM_CN), n_direct);
-          double mv[VS_LM_CN][4];
-#pragma unroll
-          for (int k = 0; k < VS_LM_CN; ++k)
-            if (k < nc) { const double* mc = hcam_of(c, b, s, f - k) + 4 * (size_t)index_at(k); mv[k][0] = mc[0]; mv[k][1] = mc[1]; mv[k][2] = mc[2]; mv[k][3] = mc[3]; }
-#pragma unroll
-          for (int k = 0; k < VS_LM_CN; ++k)
-            if (k < nc) { slot[k][0] = mv[k][0]; slot[k][1] = mv[k][1]; slot[k][2] = mv[k][2]; slot[k][3] = mv[k][3]; }
-          ncache = nc;
-        } else {
-          for (int k = 0; k < len && k < VS_LM_CN; ++k) {
-            const double* mc = hcam_of(c, b, s, ffc) + 4 * (size_t)iic;
-            slot[k][0] = mc[0]; slot[k][1] = mc[1]; slot[k][2] = mc[2]; slot[k][3] = mc[3];
-            ++ncache;
-            iic = hprev_of(c, b, s, ffc)[iic];
-            --ffc;
-            if (iic < 0) { ended = true; break; }
-          }
-        }
-      }
-      if (c.trail) {
-        // where the link walk continues after the directly addressed measurements (only tracks longer than VS_TRAIL + 1)
-        if (!ended && n_direct < len) { ffc = f - (n_direct - 1); iic = hprev_of(c, b, s, ffc)[index_at(n_direct - 1)]; --ffc; if (iic < 0) ended = true; }
-        else ended = true;
-      }
-      for (int it = 0; it < c.c.landmark_maximum_number_of_iterations; ++it) {
-        double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bv[3] = {0, 0, 0};
-        double err = 0;
-        int n_out = 0;
-        {
-          const double (*slot)[4] = lc->cam[threadIdx.x];
-          for (int k = 0; k < ncache; ++k) accumulate(lc->w2c[k], lc->rtr[k], slot[k], H, bv, err, n_out);   // frame f - k
-        }
-        if (c.trail) {
-          // directly addressed measurements, four at a time: their (independent) loads are in flight together
-          constexpr int NB = 4;     // loads in flight together
-          for (int k0 = ncache; k0 < n_direct; k0 += NB) {
-            double mc[NB][4];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-              const int k = min(k0 + u, n_direct - 1);
-              const double* src = hcam_of(c, b, s, f - k) + 4 * (size_t)index_at(k);
-              mc[u][0] = src[0]; mc[u][1] = src[1]; mc[u][2] = src[2]; mc[u][3] = src[3];
-            }
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-              const int k = k0 + u;
-              if (k < n_direct) {
-                accumulate(lc->w2c[k], lc->rtr[k], mc[u], H, bv, err, n_out);   // k < n_direct <= VS_TRAIL + 1: inside the staged window
-              }
-            }
-          }
-        }
-        if (!ended) {
-          int ff = ffc, ii = iic;
-          for (int k = c.trail ? n_direct : ncache; k < len; ++k) {
-            accumulate(hpose_of(c, b, s, ff) + 12, nullptr, hcam_of(c, b, s, ff) + 4 * (size_t)ii, H, bv, err, n_out);
-            ii = hprev_of(c, b, s, ff)[ii];
-            --ff;
-            if (ii < 0) break;
-          }
-        }
-        double nb[3] = {-bv[0], -bv[1], -bv[2]}, dx[3];
-        full_piv_solve_regs<3>(H, nb, dx);
-        for (int q = 0; q < 3; ++q) wv[q] += dx[q];
-        if (fabs(err - err_prev) < 1e-5 || it == 999) {
-          const int n_in = len - n_out;
-          if (n_in > m[M_LMUP]) {
-            for (int q = 0; q < 3; ++q) wpos[q] = wv[q];
-            m[M_LMUP] = n_in;
-          } else if (n_in < n_out) {
-            double acc[3] = {0, 0, 0};
-            int f2 = f, i2 = i;
-            for (int k = 0; k < len; ++k) {
-              double wp[3];
-              tf_apply(hpose_of(c, b, s, f2), hcam_of(c, b, s, f2) + 4 * (size_t)i2, wp);
-              for (int q = 0; q < 3; ++q) acc[q] += wp[q];
-              i2 = hprev_of(c, b, s, f2)[i2];
-              --f2;
-              if (i2 < 0) break;
-            }
-            for (int q = 0; q < 3; ++q) wpos[q] = acc[q] / (double)len;
-          }
-          break;
-        }
-        err_prev = err;
-      }
-    }
-    for (int q = 0; q < 3; ++q) cv.lm[3 * (size_t)i + q] = wpos[q];
-    tf_apply(w2c_cur, wpos, cv.camlm + 3 * (size_t)i);
-  }
-  return true;
-}
-
-// Landmark::update of a LONG track by a team of eight lanes (fused frame kernel).  One lane per landmark walks a chain of ~65
-// dependent fp64 operations per measurement and round; the longest track of the frame (dozens of measurements, three rounds)
-// kept the phase waiting for one wavefront.  Only the thirteen ADDITIONS into H, b and the error have to happen in the list's
-// order: the eight lanes evaluate eight consecutive measurements at once (projection, residual, kernel, om * R^T R, om * R^T e),
-// park the terms in LDS, and every lane adds the eight terms in list order into its own copy of the sums — the same operations on
-// the same operands in the same order as landmark_point's serial loop, an eighth of the multiplications on the critical path.
-// Measurements beyond the trail (k >= n_direct: only reachable through the `prev` links) follow serially on every lane alike.
-#define VS_LM_TEAM_G 8          // lanes per team
-#ifndef VS_LM_TEAM_WAVES
-#define VS_LM_TEAM_WAVES 2      // wavefronts of the workgroup that run teams when the frame has long tracks (16 teams at a time)
-#endif
-#ifndef VS_LM_TEAM_MIN
-#define VS_LM_TEAM_MIN 9        // measurements from which a track goes to a team
-#endif
-struct LmTerm { double e2, h[6], b[3]; int kind, pad; };   // kind 0: behind the camera (outlier, nothing added), 1: inlier, 2: outlier with the saturated kernel
-#define VS_LM_TEAM_LDS (VS_LM_TEAM_WAVES * (64 / VS_LM_TEAM_G) * VS_LM_TEAM_G * (int)sizeof(LmTerm))
-// classification used by the work lists: an update (not a creation) of a track with VS_LM_TEAM_MIN or more measurements
-__device__ __forceinline__ bool landmark_is_long(const DevCfg& c, const int32_t* m) {
-  return m[M_LMUP] != 0 && min(m[M_TLEN] + 1, c.HCAP) >= VS_LM_TEAM_MIN && c.trail;
-}
-// The active landmarks of a frame counted without refining them, for the callers whose refinement runs BESIDE them in the same launch (k_tail_lm,
-// k_stage_lm): a point is active iff its track is long enough for a landmark.  Called by the whole workgroup; returns this thread's share.
-// A track that outgrew the history ring raises error bit 4 here as well: the refinement's own atomicOr (landmark_point / landmark_team) is not
-// ordered against the report its neighbour workgroup writes, and the frame that truncates first must show the bit under every launch sequence.
-__device__ __forceinline__ int lm_count_active(const DevCfg& c, const DevBuf& b, int s, const PtView& cvc, int n_cur) {
-  int active = 0, cut = 0;
-  for (int i = threadIdx.x; i < n_cur; i += VS_WG) {
-    const int tlen = cvc.meta[(size_t)i * META + M_TLEN];
-    if (tlen >= c.c.minimum_track_length_for_landmark_creation) { ++active; cut |= tlen + 1 > c.HCAP ? 1 : 0; }
-  }
-  cut = __syncthreads_or(cut);
-  if (cut && threadIdx.x == 0) atomicOr(&b.st[s].error_flags, 4);
-  return active;
-}
-__device__ __forceinline__ bool landmark_team(const DevCfg& c, const DevBuf& b, int s, const PtView& cv, int f, int i, LmCache* lc, LmTerm* terms, int gl) {
-  const double* w2c_cur = hpose_of(c, b, s, f) + 12;
-  int32_t* m = cv.meta + (size_t)i * META;
-  const int tlen = m[M_TLEN];
-  const int lmup0 = m[M_LMUP];
-  int len = tlen + 1;
-  if (len > c.HCAP) { len = c.HCAP; if (gl == 0) atomicOr(&b.st[s].error_flags, 4); }
-  double wpos[3];
-  double wv[3] = {cv.lm[3 * (size_t)i], cv.lm[3 * (size_t)i + 1], cv.lm[3 * (size_t)i + 2]};
-  for (int q = 0; q < 3; ++q) wpos[q] = wv[q];
-  const double kern = c.c.landmark_maximum_error_squared_meters;
-  // directly addressed measurements (landmark_point's n_direct)
-  const uint16_t* tr = cv.trail + (size_t)i * VS_TRAIL;
-  int n_direct = 1;
-  bool ended = false;
-  {
-    const int want = min(len, VS_TRAIL + 1);
-    for (int q0 = 0; q0 < VS_TRAIL && n_direct < want && !ended; q0 += 8) {
-      const uint4 v = *reinterpret_cast<const uint4*>(tr + q0);
-      const uint32_t wv4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const uint32_t ent = (wv4[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
-        if (!ended && n_direct < want) { if (ent == 0xFFFFu) ended = true; else ++n_direct; }
-      }
-    }
-  }
-  // this lane's measurements of the directly addressed part (k = gl, gl + 8, ...) into its LDS slots, all loads in flight, once
-  constexpr int NG = VS_LM_CN;                       // groups whose measurements have a slot (k < 8 * NG)
-  static_assert(VS_TRAIL + 1 <= VS_LM_TEAM_G * NG, "every directly addressed measurement needs a slot");
-  double (*slot)[4] = lc->cam[threadIdx.x];
-  {
-    double mv[NG][4];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int k = VS_LM_TEAM_G * g + gl;
-      if (k < n_direct) {
-        const double* mc = hcam_of(c, b, s, f - k) + 4 * (size_t)(k == 0 ? i : (int)tr[k - 1]);
-        mv[g][0] = mc[0]; mv[g][1] = mc[1]; mv[g][2] = mc[2]; mv[g][3] = mc[3];
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-      if (VS_LM_TEAM_G * g + gl < n_direct) { slot[g][0] = mv[g][0]; slot[g][1] = mv[g][1]; slot[g][2] = mv[g][2]; slot[g][3] = mv[g][3]; }
-  }
-  // where the link walk continues after the directly addressed measurements
-  int ffc = f, iic = i;
-  if (!ended && n_direct < len) { ffc = f - (n_direct - 1); iic = hprev_of(c, b, s, ffc)[n_direct == 1 ? i : (int)tr[n_direct - 2]]; --ffc; if (iic < 0) ended = true; }
-  else ended = true;
-  double err_prev = 0;
-  for (int it = 0; it < c.c.landmark_maximum_number_of_iterations; ++it) {
-    double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bv[3] = {0, 0, 0};
-    double err = 0;
-    int n_out = 0;
-    for (int k0 = 0; k0 < n_direct; k0 += VS_LM_TEAM_G) {
-      const int k = k0 + gl;
-      LmTerm t;
-      t.kind = -1;
-      if (k < n_direct) {
-        double mc[4];
-        const int g = k0 / VS_LM_TEAM_G;
-        mc[0] = slot[g][0]; mc[1] = slot[g][1]; mc[2] = slot[g][2]; mc[3] = slot[g][3];      // k < n_direct: every directly addressed measurement has a slot
-        const double* W = lc->w2c[k];                                                         // ... and its frame lies inside the staged window
-        const double* RtR = lc->rtr[k];
-        double sp[3];
-        tf_apply(W, wv, sp);
-        if (sp[2] <= 0) { t.kind = 0; }
-        else {
-          const double e[3] = {sp[0] - mc[0], sp[1] - mc[1], sp[2] - mc[2]};
-          double om = mc[3];
-          t.e2 = om * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-          t.kind = 1;
-          if (t.e2 > kern) { om *= kern / t.e2; t.kind = 2; }
-          t.h[0] = om * RtR[0]; t.h[1] = om * RtR[1]; t.h[2] = om * RtR[2]; t.h[3] = om * RtR[4]; t.h[4] = om * RtR[5]; t.h[5] = om * RtR[8];
-          for (int r = 0; r < 3; ++r) t.b[r] = om * ((W[r] * e[0] + W[4 + r] * e[1]) + W[8 + r] * e[2]);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();     // the previous batch's terms have been read by every lane of the team
-      terms[gl] = t;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const int nb_ = min(VS_LM_TEAM_G, n_direct - k0);
-#pragma unroll
-      for (int u = 0; u < VS_LM_TEAM_G; ++u) {
-        if (u < nb_) {
-          const LmTerm q = terms[u];
-          if (q.kind == 0) { ++n_out; }
-          else {
-            err += q.e2;
-            if (q.kind == 2) ++n_out;
-            H[0] += q.h[0]; H[4] += q.h[3]; H[8] += q.h[5];
-            { const double h01 = q.h[1], h02 = q.h[2], h12 = q.h[4]; H[1] += h01; H[3] += h01; H[2] += h02; H[6] += h02; H[5] += h12; H[7] += h12; }
-            bv[0] += q.b[0]; bv[1] += q.b[1]; bv[2] += q.b[2];
-          }
-        }
-      }
-    }
-    if (!ended) {
-      // beyond the trail: the serial loop of landmark_point, on every lane of the team alike
-      int ff = ffc, ii = iic;
-      for (int k = n_direct; k < len; ++k) {
-        const double* W = hpose_of(c, b, s, ff) + 12;
-        const double* mc = hcam_of(c, b, s, ff) + 4 * (size_t)ii;
-        double sp[3];
-        tf_apply(W, wv, sp);
-        if (sp[2] <= 0) {
-          ++n_out;
-        } else {
-          const double e[3] = {sp[0] - mc[0], sp[1] - mc[1], sp[2] - mc[2]};
-          double om = mc[3];
-          const double e2 = om * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-          err += e2;
-          if (e2 > kern) { om *= kern / e2; ++n_out; }
-          for (int r = 0; r < 3; ++r)
-            for (int cc = 0; cc < 3; ++cc) H[3 * r + cc] += om * ((W[r] * W[cc] + W[4 + r] * W[4 + cc]) + W[8 + r] * W[8 + cc]);
-          for (int r = 0; r < 3; ++r) bv[r] += om * ((W[r] * e[0] + W[4 + r] * e[1]) + W[8 + r] * e[2]);
-        }
-        ii = hprev_of(c, b, s, ff)[ii];
-        --ff;
-        if (ii < 0) break;
-      }
-    }
-    double nb[3] = {-bv[0], -bv[1], -bv[2]}, dx[3];
-    full_piv_solve_regs<3>(H, nb, dx);
-    for (int q = 0; q < 3; ++q) wv[q] += dx[q];
-    if (fabs(err - err_prev) < 1e-5 || it == 999) {
-      const int n_in = len - n_out;
-      if (n_in > lmup0) {
-        for (int q = 0; q < 3; ++q) wpos[q] = wv[q];
-        if (gl == 0) m[M_LMUP] = n_in;
-      } else if (n_in < n_out) {
-        double acc[3] = {0, 0, 0};
-        int f2 = f, i2 = i;
-        for (int k = 0; k < len; ++k) {
-          double wp[3];
-          tf_apply(hpose_of(c, b, s, f2), hcam_of(c, b, s, f2) + 4 * (size_t)i2, wp);
-          for (int q = 0; q < 3; ++q) acc[q] += wp[q];
-          i2 = hprev_of(c, b, s, f2)[i2];
-          --f2;
-          if (i2 < 0) break;
-        }
-        for (int q = 0; q < 3; ++q) wpos[q] = acc[q] / (double)len;
-      }
-      break;
-    }
-    err_prev = err;
-  }
-  if (gl == 0) {
-    for (int q = 0; q < 3; ++q) cv.lm[3 * (size_t)i + q] = wpos[q];
-    tf_apply(w2c_cur, wpos, cv.camlm + 3 * (size_t)i);
-  }
-  return true;
-}
-
-// Besides the history ring (camera coordinates and `prev` link of every point of frame f), every point gets its trail: the
-// indices of its track's points in frames f-1 .. f-VS_TRAIL (its predecessor, then the predecessor's own trail shifted by one;
-// 0xFFFF where the track starts before that).  The landmark refinement then addresses its measurements directly instead of
-// walking the links, a chain of dependent HBM loads per measurement.
-__device__ __forceinline__ void wg_publish_history(const DevCfg& c, const DevBuf& b, int s, int n, int pb_cur, int f) {
-  const PtView cv = pts_of(c, b, s, pb_cur);
-  const PtView pv = pts_of(c, b, s, pb_cur ^ 1);
-  double* hc = hcam_of(c, b, s, f);
-  int32_t* hp = hprev_of(c, b, s, f);
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    { const double x = cv.cam[3 * (size_t)i], y = cv.cam[3 * (size_t)i + 1], z = cv.cam[3 * (size_t)i + 2];
-      reinterpret_cast<double2*>(hc + 4 * (size_t)i)[0] = make_double2(x, y); reinterpret_cast<double2*>(hc + 4 * (size_t)i)[1] = make_double2(z, 1 / z); }   // Measurement::inverse_depth_meters
-    const int ip = cv.meta[(size_t)i * META + M_PREV];
-    hp[i] = ip;
-    if (c.trail) {
-      uint4* dst = reinterpret_cast<uint4*>(cv.trail + (size_t)i * VS_TRAIL);
-      if (ip < 0) {
-        dst[0] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);   // only entry 0 is ever reached: len = 1
-      } else {
-        const uint4* src = reinterpret_cast<const uint4*>(pv.trail + (size_t)ip * VS_TRAIL);
-        uint32_t w[VS_TRAIL / 2];
-#pragma unroll
-        for (int q = 0; q < VS_TRAIL / 8; ++q) { const uint4 v = src[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-        uint32_t o[VS_TRAIL / 2];
-        o[0] = (uint32_t)ip | (w[0] << 16);
-#pragma unroll
-        for (int q = 1; q < VS_TRAIL / 2; ++q) o[q] = (w[q - 1] >> 16) | (w[q] << 16);
-#pragma unroll
-        for (int q = 0; q < VS_TRAIL / 8; ++q) dst[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-      }
-    }
-  }
-}
-
-// Landmark creation / refinement of the frame's points inside the stream's workgroup (PoseTracker3D::_updatePoints' landmark part): the poses of the
-// last VS_LM_NP frames and every lane's first measurements staged in the LDS arena, short tracks one lane each, long tracks a team of eight lanes
-// (landmark_point / landmark_team).  Returns the number of active landmarks (block-uniform).  Used by k_frame's fused launches and by the
-// stage path's UPDATE / COMPUTE stages; history of frame f must have been published (wg_publish_history).
-__device__ __forceinline__ int wg_landmarks_lds(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_cur, int f, unsigned char* arena) {
-  const int tid = threadIdx.x;
-  const PtView cvu = pts_of(c, b, s, pb_cur);
-  int active = 0;
-  static_assert(sizeof(LmCache) <= VS_ARENA, "landmark measurement cache must fit the LDS arena");
-  LmCache* lc = reinterpret_cast<LmCache*>(arena);
-  for (int t = tid; t < VS_LM_NP * 12; t += VS_WG) { const int k = t / 12; if (f - k >= 0 && k < c.HCAP) lc->w2c[k][t - 12 * k] = hpose_of(c, b, s, f - k)[12 + t - 12 * k]; }
-  __syncthreads();
-  lm_stage_rtr(lc, f, c.HCAP);
-  // The points that carry a landmark (track long enough: creation or refinement) are compacted into a work list first: ~40 % of
-  // the frame's points, one per thread in a single round instead of two half-empty ones (a thread's refinement is a serial chain).
-  static_assert(sizeof(LmCache) + VS_LM_TEAM_LDS + 4096 <= VS_ARENA, "landmark cache + team terms must leave room for the work lists");
-  constexpr int LIST_CAP = (VS_ARENA - (int)sizeof(LmCache) - VS_LM_TEAM_LDS) / 2;
-  LmTerm* team_terms = reinterpret_cast<LmTerm*>(arena + VS_ARENA - VS_LM_TEAM_LDS);
-  uint16_t* work = reinterpret_cast<uint16_t*>(arena + sizeof(LmCache));
-  const bool listed = sh.n_cur <= LIST_CAP && sh.n_cur <= 65535;
-  if (tid == 0) { sh.flag = 0; sh.n_proj = 0; }       // n_proj (recovery is over): the count of long tracks
-  __syncthreads();
-  if (listed) {
-    // short tracks (one lane each) from the front of the list, long ones (a team of eight lanes each) from its end
-    for (int i0 = 0; i0 < sh.n_cur; i0 += VS_WG) {
-      const int i = i0 + tid;
-      const int32_t* mi = cvu.meta + (size_t)min(i, sh.n_cur - 1) * META;
-      const bool need = i < sh.n_cur && mi[M_TLEN] >= c.c.minimum_track_length_for_landmark_creation;
-      const bool lng = need && landmark_is_long(c, mi);
-      const unsigned long long m = __ballot(need && !lng), ml = __ballot(lng);
-      int base = 0, basel = 0;
-      if ((tid & 63) == 0 && m) base = atomicAdd(&sh.flag, __popcll(m));
-      if ((tid & 63) == 0 && ml) basel = atomicAdd(&sh.n_proj, __popcll(ml));
-      base = __builtin_amdgcn_readfirstlane(base); basel = __builtin_amdgcn_readfirstlane(basel);
-      if (need && !lng) work[base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)i;
-      if (lng) work[LIST_CAP - 1 - (basel + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ml >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ml, 0u)))] = (uint16_t)i;
-    }
-    __syncthreads();
-    const int n_work = sh.flag;
-    const int n_long = sh.n_proj;
-    const int team_waves = min(VS_LM_TEAM_WAVES, (n_long + 64 / VS_LM_TEAM_G - 1) / (64 / VS_LM_TEAM_G));
-    const int wv_ = tid >> 6;
-    if (wv_ < team_waves) {
-      const int team = tid / VS_LM_TEAM_G, gl = tid % VS_LM_TEAM_G;
-      for (int q = team; q < n_long; q += team_waves * (64 / VS_LM_TEAM_G))
-        active += (landmark_team(c, b, s, cvu, f, work[LIST_CAP - 1 - q], lc, team_terms + team * VS_LM_TEAM_G, gl) && gl == 0) ? 1 : 0;
-    } else {
-      for (int q = tid - 64 * team_waves; q < n_work; q += VS_WG - 64 * team_waves) active += landmark_point(c, b, s, cvu, f, work[q], lc) ? 1 : 0;
-    }
-  } else {
-    for (int i = tid; i < sh.n_cur; i += VS_WG) active += landmark_point(c, b, s, cvu, f, i, lc) ? 1 : 0;
-  }
-  int total;
-  block_exclusive_scan(active, sh.scan, &total);
-  __syncthreads();
-  if (tid == 0) sh.flag = 0;
-  __syncthreads();
-  return total;
-}
-
-__device__ __forceinline__ void wg_update_points(const DevCfg& c, const DevBuf& b, int s, FrameShared& sh, int pb_cur, int f, unsigned char* arena) {
-  const int tid = threadIdx.x;
-  // publish the current frame's cam/prev to the history ring first (chains start here)
-  wg_publish_history(c, b, s, sh.n_cur, pb_cur, f);
-  __syncthreads();
-  const int total = wg_landmarks_lds(c, b, s, sh, pb_cur, f, arena);     // the fused launch's refinement (LDS-cached, teams): 31 us per KITTI-sized frame where one thread per track took 80
-  if (tid == 0) sh.n_lm = total;  // _number_of_active_landmarks
-  __syncthreads();
-}
-
-// The same refinement spread over `gridDim.x` workgroups per stream, each with the frame workgroup's own machinery (poses of the last VS_LM_NP frames
-// and every lane's first measurements in LDS, teams of eight lanes for long tracks: landmark_team / landmark_point, i.e. the operations of
-// k_frame's landmark phase in the same order): launch sequence 4 (k_tail_lm) and the stage path of a one-stream context (k_stage_lm) run it beside the
-// frame's last phase / stage, inside the same launch, where a wide one-thread-per-track kernel (56 us for one KITTI-sized stream) would be longer
-// than what it hides behind.
-// share g of G of stream s; n_short / n_long_sh: workgroup-shared counters.  The share-0 workgroup adds its duration to the stream's landmark
-// chronometer (neither caller is timed by HIP events).
-__device__ __forceinline__ void lm_teams_body(const DevCfg& c, const DevBuf& b, int s, int g, int G, unsigned char* arena, int& n_short, int& n_long_sh) {
-  const int tid = threadIdx.x;
-  const unsigned long long t_begin = wall_clock64();
-  StreamState& st = b.st[s];
-  const int n_cur = st.fc.n_cur, f = st.fc.lm_f;
-  const PtView cvu = pts_of(c, b, s, st.fc.lm_pb);
-  LmCache* lc = reinterpret_cast<LmCache*>(arena);
-  for (int t = tid; t < VS_LM_NP * 12; t += VS_WG) { const int k = t / 12; if (f - k >= 0 && k < c.HCAP) lc->w2c[k][t - 12 * k] = hpose_of(c, b, s, f - k)[12 + t - 12 * k]; }
-  if (tid == 0) { n_short = 0; n_long_sh = 0; }
-  __syncthreads();
-  lm_stage_rtr(lc, f, c.HCAP);
-  constexpr int LIST_CAP = (VS_ARENA - (int)sizeof(LmCache) - VS_LM_TEAM_LDS) / 2;
-  LmTerm* team_terms = reinterpret_cast<LmTerm*>(arena + VS_ARENA - VS_LM_TEAM_LDS);
-  uint16_t* work = reinterpret_cast<uint16_t*>(arena + sizeof(LmCache));
-  const bool listed = n_cur <= LIST_CAP && n_cur <= 65535;
-  __syncthreads();
-  if (listed) {
-    // a workgroup's share: the points i with i % G == g (the lists' order depends on the order of the atomics: a share must not be defined through it);
-    // its two work lists: short tracks from the front, long ones from the end
-    for (int i0 = 0; i0 < n_cur; i0 += VS_WG) {
-      const int i = i0 + tid;
-      const int32_t* mi = cvu.meta + (size_t)min(i, n_cur - 1) * META;
-      const bool need = i < n_cur && (i % G) == g && mi[M_TLEN] >= c.c.minimum_track_length_for_landmark_creation;
-      const bool lng = need && landmark_is_long(c, mi);
-      const unsigned long long m = __ballot(need && !lng), ml = __ballot(lng);
-      int base = 0, basel = 0;
-      if ((tid & 63) == 0 && m) base = atomicAdd(&n_short, __popcll(m));
-      if ((tid & 63) == 0 && ml) basel = atomicAdd(&n_long_sh, __popcll(ml));
-      base = __builtin_amdgcn_readfirstlane(base); basel = __builtin_amdgcn_readfirstlane(basel);
-      if (need && !lng) work[base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)i;
-      if (lng) work[LIST_CAP - 1 - (basel + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ml >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ml, 0u)))] = (uint16_t)i;
-    }
-    __syncthreads();
-    const int n_work = n_short;
-    const int n_long = n_long_sh;
-    constexpr int TEAMS = VS_LM_TEAM_WAVES * (64 / VS_LM_TEAM_G);      // teams of a workgroup
-    if ((tid >> 6) < VS_LM_TEAM_WAVES) {
-      const int team = tid / VS_LM_TEAM_G, gl = tid % VS_LM_TEAM_G;
-      for (int q = team; q < n_long; q += TEAMS) landmark_team(c, b, s, cvu, f, work[LIST_CAP - 1 - q], lc, team_terms + team * VS_LM_TEAM_G, gl);
-    } else {
-      constexpr int SH = VS_WG - 64 * VS_LM_TEAM_WAVES;
-      for (int q = tid - 64 * VS_LM_TEAM_WAVES; q < n_work; q += SH) landmark_point(c, b, s, cvu, f, work[q], lc);
-    }
-  } else {
-    for (int i = g * VS_WG + tid; i < n_cur; i += G * VS_WG) landmark_point(c, b, s, cvu, f, i, lc);
-  }
-  if (g == 0 && tid == 0) st.ticks[3] += wall_clock64() - t_begin;
-}
 // sdist[i][k], k < 16: Hamming distance of left feature i to right feature g0 + w0 + k of its row [g0, g1), where the
 // window [w0, m) holds the (up to 16) nearest right features at or left of the left feature: m = number of right
 // features of the row with x <= xl, w0 = max(m - 16, 0).  Nothing is written for m = 0 or m >= 255.

@@ -28,6 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_depth.h"
+#include "landmark_math.h"
 
 #define RGBD_F_LM 1      // FramePoint::landmark() is set (the point went through Landmark::Landmark or Landmark::update)
 #define RGBD_F_UNREL 2   // hasUnreliableDepth (inherited along a track)
@@ -623,19 +624,18 @@ __global__ __launch_bounds__(1024) void k_rgbd_recover_finish(const DevCfg c, co
 //
 // Eight lanes per framepoint.  A Gauss-Newton round over a long track is a chain of ~65 dependent fp64 operations per measurement on one lane
 // (measured: 72 us per frame for 60-frame tracks with one lane per point) — but only the thirteen ADDITIONS into H, b and the error have to
-// happen in the list's order.  So the eight lanes evaluate eight consecutive measurements at once (projection, residual, kernel, the products
-// om * R^T R and om * R^T e), park the results in LDS, and every lane then adds the eight contributions in list order: same operations on the
-// same operands in the same order as the serial loop, an eighth of its multiplications on the critical path.
+// happen in the list's order.  So the eight lanes evaluate eight consecutive measurements at once (lm_term), park the results in LDS, and every
+// lane then adds the eight contributions in list order (lm_team_add): same operations on the same operands in the same order as the serial
+// loop, an eighth of its multiplications on the critical path.
 #define RGBD_LM_NP 64     // world_to_camera (and R^T R) of the newest RGBD_LM_NP frames staged in LDS, one copy for the workgroup
-#define RGBD_LM_G 8       // lanes per framepoint
+#define RGBD_LM_G LM_TEAM_G   // lanes per framepoint
 #define RGBD_LM_PTS (256 / RGBD_LM_G)
 #define RGBD_LM_PRE 64    // measurements of a track kept in LDS across the rounds (each is two dependent HBM loads: trail entry, then the ring)
 struct RgbdPoseLds { double w2c[12]; double rtr[9]; };
-struct RgbdLmTerm { double e2, h[6], b[3]; int kind, pad; };   // kind 0: behind the camera (an outlier, nothing added), 1: inlier, 2: outlier with a saturated kernel
 __global__ __launch_bounds__(256) void k_rgbd_landmarks(const DevCfg c, const RgbdBuf all) {
   const RgbdBuf r = rgbd_stream(all, blockIdx.y);
   __shared__ RgbdPoseLds s_pose[RGBD_LM_NP];
-  __shared__ RgbdLmTerm s_term[RGBD_LM_PTS][RGBD_LM_G];
+  __shared__ LmTerm s_term[RGBD_LM_PTS][RGBD_LM_G];
   __shared__ double s_meas[RGBD_LM_PTS][RGBD_LM_PRE][4];     // the track's newest measurements, fetched once for all Gauss-Newton rounds
   RgbdState& st = *r.st;
   if (!rgbd_tail_on(st)) return;
@@ -649,8 +649,8 @@ __global__ __launch_bounds__(256) void k_rgbd_landmarks(const DevCfg c, const Rg
   __syncthreads();
   // J^T J of a measurement (J = the rotation of world_to_camera) depends on the frame only: once per frame instead of once per measurement and round
   for (int t = threadIdx.x; t < RGBD_LM_NP * 9; t += 256) {
-    const int k = t / 9, e = t - 9 * k, rr = e / 3, cc = e - 3 * rr;
-    if (k <= f && k < H) { const double* W = s_pose[k].w2c; s_pose[k].rtr[e] = (W[rr] * W[cc] + W[4 + rr] * W[4 + cc]) + W[8 + rr] * W[8 + cc]; }
+    const int k = t / 9, e = t - 9 * k;
+    if (k <= f && k < H) s_pose[k].rtr[e] = lm_rtr_entry(s_pose[k].w2c, e);
   }
   __syncthreads();
   const int g = threadIdx.x / RGBD_LM_G, gl = threadIdx.x % RGBD_LM_G;
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(256) void k_rgbd_landmarks(const DevCfg c, const Rg
         for (int q = 0; q < 3; ++q) world[q] = wv[q];
         const double kern = c.c.landmark_maximum_error_squared_meters;
         double err_prev = 0;
-        RgbdLmTerm* terms = s_term[g];
+        LmTerm* terms = s_term[g];
         // every lane fetches the measurements it will evaluate (list positions gl, gl + 8, ...), all loads in flight together, once
         double (*meas)[4] = s_meas[g];
         for (int j = gl; j < len && j < RGBD_LM_PRE; j += RGBD_LM_G) {
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(256) void k_rgbd_landmarks(const DevCfg c, const Rg
           for (int j0 = 0; j0 < len; j0 += RGBD_LM_G) {
             // this lane's measurement of the batch
             const int j = j0 + gl;
-            RgbdLmTerm t;
+            LmTerm t;
             t.kind = -1;
             if (j < len) {
               const int k = k_at(j);
@@ -725,67 +725,30 @@ __global__ __launch_bounds__(256) void k_rgbd_landmarks(const DevCfg c, const Rg
               if (k < RGBD_LM_NP) { W = s_pose[k].w2c; RtR = s_pose[k].rtr; }
               else {     // a track older than the staged poses: the same expressions from HBM
                 W = r.h_pose + (size_t)((f - k) % H) * 24 + 12;
-                for (int e = 0; e < 9; ++e) { const int rr = e / 3, cc = e - 3 * rr; rtr_far[e] = (W[rr] * W[cc] + W[4 + rr] * W[4 + cc]) + W[8 + rr] * W[8 + cc]; }
+                lm_rtr(W, rtr_far);
                 RtR = rtr_far;
               }
-              double sp[3];
-              tf_apply(W, wv, sp);
-              if (sp[2] <= 0) { t.kind = 0; }
-              else {
-                const double er[3] = {sp[0] - mc[0], sp[1] - mc[1], sp[2] - mc[2]};
-                double om = mc[3];
-                t.e2 = om * ((er[0] * er[0] + er[1] * er[1]) + er[2] * er[2]);
-                t.kind = 1;
-                if (t.e2 > kern) { om *= kern / t.e2; t.kind = 2; }
-                // R^T R is symmetric to the bit (its entries are sums of commuting products): six products instead of nine
-                t.h[0] = om * RtR[0]; t.h[1] = om * RtR[1]; t.h[2] = om * RtR[2]; t.h[3] = om * RtR[4]; t.h[4] = om * RtR[5]; t.h[5] = om * RtR[8];
-                for (int rr = 0; rr < 3; ++rr) t.b[rr] = om * ((W[rr] * er[0] + W[4 + rr] * er[1]) + W[8 + rr] * er[2]);
-              }
+              t = lm_term(W, RtR, mc, wv, kern);
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();     // the previous batch's terms have been read by every lane of the group
-            terms[gl] = t;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // every lane adds the batch in list order (its own copy of the accumulators: no broadcast afterwards); plain LDS loads, so that
-            // the next terms are on their way while one is being added (volatile reads cost one LDS round trip EACH: 88 per batch)
-            const int nb_ = min(RGBD_LM_G, len - j0);
-#pragma unroll
-            for (int u = 0; u < RGBD_LM_G; ++u) {
-              if (u < nb_) {
-                const RgbdLmTerm q = terms[u];
-                if (q.kind == 0) { ++n_out; }
-                else {
-                  err += q.e2;
-                  if (q.kind == 2) ++n_out;
-                  Hm[0] += q.h[0]; Hm[4] += q.h[3]; Hm[8] += q.h[5];
-                  { const double h01 = q.h[1], h02 = q.h[2], h12 = q.h[4]; Hm[1] += h01; Hm[3] += h01; Hm[2] += h02; Hm[6] += h02; Hm[5] += h12; Hm[7] += h12; }
-                  bv[0] += q.b[0]; bv[1] += q.b[1]; bv[2] += q.b[2];
-                }
-              }
-            }
+            lm_team_add(terms, gl, t, min(RGBD_LM_G, len - j0), Hm, bv, err, n_out);
           }
-          double nb[3] = {-bv[0], -bv[1], -bv[2]}, dx[3];
-          full_piv_solve_regs<3>(Hm, nb, dx);
-          for (int q = 0; q < 3; ++q) wv[q] += dx[q];
-          if (fabs(err - err_prev) < 1e-5 || it == 999) {
-            const int n_in = len - n_out;
-            if ((unsigned)n_in > (unsigned)updates) {
-              for (int q = 0; q < 3; ++q) world[q] = wv[q];
-              updates = n_in;
-            } else if (n_in < n_out) {
-              double acc[3] = {0, 0, 0};
-              for (int j = 0; j < len; ++j) {
-                const int k = k_at(j);
-                double mc[4], wp[3];
-                cam_of(k, mc);
-                tf_apply(pose_of(k), mc, wp);
-                for (int q = 0; q < 3; ++q) acc[q] += wp[q];
-              }
-              for (int q = 0; q < 3; ++q) world[q] = acc[q] / (double)len;
+          int n_in;
+          const LmRound end = lm_round_end(Hm, bv, wv, err, err_prev, it, len, n_out, updates, n_in);
+          if (end == LM_ACCEPT) {
+            for (int q = 0; q < 3; ++q) world[q] = wv[q];
+            updates = n_in;
+          } else if (end == LM_RESET) {
+            double acc[3] = {0, 0, 0};
+            for (int j = 0; j < len; ++j) {
+              const int k = k_at(j);
+              double mc[4], wp[3];
+              cam_of(k, mc);
+              tf_apply(pose_of(k), mc, wp);
+              for (int q = 0; q < 3; ++q) acc[q] += wp[q];
             }
-            break;
+            for (int q = 0; q < 3; ++q) world[q] = acc[q] / (double)len;
           }
+          if (end != LM_NEXT_ROUND) break;
           err_prev = err;
         }
       }
