@@ -3,7 +3,9 @@
   - the SHIM (shim/proslam_hip_plugin.h: HipStereoFramePointGenerator / HipStereoUVAligner deriving from the reference's
     classes) against minimal declaration stubs of the reference interfaces it touches (tests/shim_stubs/, test-only): it
     must compile (signature drift against base_framepoint_generator.h / base_aligner.h / frame.h fails here), link, and —
-    on the GPU box — reproduce the fused device path frame by frame, host objects included."""
+    on the GPU box — reproduce the fused device path frame by frame, host objects included;
+  - csrc/device_store.h (the memory a switchable feature owns on the device) on counting malloc / free stand-ins, under
+    AddressSanitizer and UndefinedBehaviorSanitizer: host code only, no GPU."""
 import os
 import subprocess
 
@@ -41,6 +43,14 @@ def test_shim_compiles_links_and_fails_loudly_without_a_gpu():
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "fails loudly without a GPU" in out.stdout
+
+
+def test_device_store_frees_every_allocation_exactly_once():
+    """Enable / replace / disable, a failure at every allocation of a store, a double release and destroy with stores live."""
+    exe = _build("test_device_store")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "every allocation freed exactly once" in out.stdout
 
 
 @pytest.mark.gpu

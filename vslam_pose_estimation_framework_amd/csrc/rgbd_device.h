@@ -1,5 +1,5 @@
 // rgbd_device.h — host side of the device-resident RGB-D loop (kernels_rgbd.h): buffers, the per-frame launch sequence on one HIP stream,
-// one small read-back per frame.  Included by vslam_hip.hip after the context code (it uses create_internal / buf_set / fail of that file).
+// one small read-back per frame.  Included by host_rgbd.h after the context code (it uses create_internal / buf_set / fail of host_ctx.h).
 //
 // A frame is: two host-to-device copies (image, depth), ~17 kernel launches on two streams (the space map runs beside the image pipeline), one 1.2 KB device-to-host copy, one stream synchronisation.
 // A context tracks n_streams independent sequences side by side (vslam_rgbd_create_batch): the same ~17 launches serve all of them — one
@@ -130,11 +130,11 @@ public:
     const size_t nB = (size_t)B, n = nB * (size_t)cap;
     RgbdMap d{};
     d.cap = cap; d.B = B;
-    hipError_t e = map_alloc(&d.rows, n * 4);
-    if (e == hipSuccess) e = map_alloc(&d.first, n);
-    if (e == hipSuccess) e = map_alloc(&d.count, nB);
-    if (e == hipSuccess) e = map_alloc(&d.committed, nB);
-    if (e == hipSuccess) e = map_alloc(&d.ids, 2 * nB * (size_t)rb.MAXP);
+    hipError_t e = map_mem.alloc(&d.rows, n * 4);
+    if (e == hipSuccess) e = map_mem.alloc(&d.first, n);
+    if (e == hipSuccess) e = map_mem.alloc(&d.count, nB);
+    if (e == hipSuccess) e = map_mem.alloc(&d.committed, nB);
+    if (e == hipSuccess) e = map_mem.alloc(&d.ids, 2 * nB * (size_t)rb.MAXP);
     if (e == hipSuccess) { mp = d; e = map_clear(); }
     if (e != hipSuccess) { map_free(); err = std::string("vslam_rgbd_enable_map: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
     return VSLAM_OK;
@@ -149,10 +149,8 @@ public:
     drop_graph();
     if (cap == 0) return VSLAM_OK;
     const size_t nB = (size_t)B;
-    hipError_t e = hipMalloc((void**)&mp.log, nB * (size_t)cap * 3 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void**)&mp.ocount, nB * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(mp.log, 0, nB * (size_t)cap * 3 * sizeof(uint4), q);
-    if (e == hipSuccess) e = hipMemsetAsync(mp.ocount, 0, nB * sizeof(int32_t), q);
+    hipError_t e = obs_mem.alloc_fill(&mp.log, nB * (size_t)cap * 3, 0, q);
+    if (e == hipSuccess) e = obs_mem.alloc_fill(&mp.ocount, nB, 0, q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
     if (e != hipSuccess) { obs_free(); err = std::string("vslam_rgbd_enable_observations: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
     mp.ocap = cap;
@@ -160,8 +158,7 @@ public:
   }
   // what every getter below checks first; *size: entries of the store the call reads
   int map_ready(int stream, bool log, int32_t* size) {
-    if (stream < 0 || stream >= B) { err = "stream index out of range"; return VSLAM_ERR_INVALID; }
-    if (pending) { err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (int rc = readable(stream)) return rc;
     if (!mp.cap) { err = "the landmark map is not enabled (vslam_rgbd_enable_map)"; return VSLAM_ERR_STATE; }
     if (log && !mp.ocap) { err = "the observation log is not enabled (vslam_rgbd_enable_observations)"; return VSLAM_ERR_STATE; }
     (void)hipSetDevice(ic->device);
@@ -255,11 +252,15 @@ public:
     return rc;
   }
 
-  bool frame_in_flight() const { return pending; }
-  int get_points(int stream, int32_t cap, int32_t* n, float* xy, double* cam, int32_t* meta4, uint8_t* desc) {
+  // what every getter of sequence `stream` checks first; a frame between submit() and wait() is rewriting the lists the getters read (and
+  // flags of the previous list): not readable
+  int readable(int stream) {
     if (stream < 0 || stream >= B) { err = "stream index out of range"; return VSLAM_ERR_INVALID; }
-    // a frame between submit() and wait() is rewriting the lists these copies read (and flags of the previous list): not readable
     if (pending) { err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    return VSLAM_OK;
+  }
+  int get_points(int stream, int32_t cap, int32_t* n, float* xy, double* cam, int32_t* meta4, uint8_t* desc) {
+    if (int rc = readable(stream)) return rc;
     const RgbdState& hs = hosts[stream];
     if (hs.frame_count == 0) { *n = 0; return VSLAM_OK; }
     const int np = hs.last_points;
@@ -312,23 +313,15 @@ private:
   // the landmark map and the observation log (kernels_rgbd_map.h): off while cap / ocap == 0.  Allocations of their own, freed when the
   // store is turned off or replaced (the inner context's allocation list only grows until destroy)
   RgbdMap mp{};
-  std::vector<void*> map_mem;
+  DeviceStore map_mem, obs_mem;
 
-  template <typename T>
-  hipError_t map_alloc(T** ptr, size_t count) {
-    const hipError_t e = hipMalloc((void**)ptr, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) map_mem.push_back(*ptr);
-    return e;
-  }
   void obs_free() {
-    if (mp.log) (void)hipFree(mp.log);
-    if (mp.ocount) (void)hipFree(mp.ocount);
+    obs_mem.release();
     mp.log = nullptr; mp.ocount = nullptr; mp.ocap = 0;
   }
   void map_free() {
     obs_free();
-    for (void* ptr : map_mem) (void)hipFree(ptr);
-    map_mem.clear();
+    map_mem.release();
     mp = RgbdMap{};
   }
   // ids from 0 again, no point labelled, nothing logged; the rows are cleared too so that a read never returns another run's data
