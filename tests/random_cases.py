@@ -385,15 +385,30 @@ def track_python_affordable(nP, d):
 STEREO_SIZES = [(0, 0), (0, 64), (64, 0), (1, 1), (64, 64), (513, 64), (513, 513), (2500, 513), (2500, 2500), (6000, 2500), (6000, 6000)]
 
 
-def gen_stereo(seed, nL, nR):
+def gen_stereo(seed, nL, nR, row_features=0, rows=ROWS, cols=COLS):
     """Left features over the KITTI image, right = left shifted by a disparity with bit noise (some a row up or down), clutter; two rows
-    carry more than 64 features each, runs of equal descriptors along a row give ties and the ordering constraint.  One feature per pixel."""
+    carry more than 64 features each, runs of equal descriptors along a row give ties and the ordering constraint.  One feature per pixel.
+    row_features = k > 255 first puts k left and k right features on ONE row of the last quarter of the image (so a banded sweep meets it in a band
+    with non-zero index bases), matched like the rest: more than 255 right features lie at or left of its last left features."""
     rng = np.random.default_rng(seed)
     usedL, usedR, L, Rr = set(), set(), [], []
+    ROWS, COLS = rows, cols
 
     def add(side, used, r, c, desc):
         if 0 <= r < ROWS and 0 <= c < COLS and (r, c) not in used:
             used.add((r, c)); side.append((int(r), int(c), desc))
+    if row_features:
+        r = int(rng.integers(3 * ROWS // 4, ROWS - 1))
+        for c in rng.choice(COLS, row_features, replace=False):
+            desc = rng.integers(0, 256, 32, dtype=np.uint8)
+            add(L, usedL, r, int(c), desc)
+            if rng.random() < 0.8:
+                add(Rr, usedR, r, int(c) - int(rng.integers(0, 70)), near(rng, desc, int(rng.integers(0, 40))) if rng.random() < 0.7 else desc.copy())
+        while len(Rr) < row_features:
+            add(Rr, usedR, r, int(rng.integers(0, COLS)), rng.integers(0, 256, 32, dtype=np.uint8))
+        xR = np.sort([a[1] for a in Rr])
+        behind = max(int(np.searchsorted(xR, a[1], side="right")) for a in L)
+        assert len(L) == row_features and behind > 255, (seed, len(L), behind)
     dense = [int(x) for x in rng.choice(np.arange(5, ROWS - 5), 2, replace=False)] if nL >= 513 else []
     guard = 0
     while len(L) < nL and guard < 50 * (nL + 1):
@@ -416,6 +431,59 @@ def gen_stereo(seed, nL, nR):
     rcL, dL = arr(L); rcR, dR = arr(Rr)
     per_row = np.bincount(rcL[:, 0], minlength=ROWS).max() if len(L) else 0
     return dict(seed=seed, rcL=rcL, dL=dL, rcR=rcR, dR=dR, tau=40.0, max_per_row=int(per_row))
+
+
+# Which form of the sweep and of the bin tables a case reaches, from its sizes alone (kernels_stereo.h, VS_ARENA of dev_types.h).  The tests assert
+# these as preconditions: a change of VS_ARENA or of the staging layout fails them instead of silently moving a case to another path.
+VS_ARENA = 131072
+
+
+def stereo_stage_bytes(rows, nL, nR):
+    """LDS bytes the sweep stages for `rows` image rows with nL left and nR right features: 8 per row start pair, 20 per left, 3 per right feature"""
+    return 8 * ((rows + 8) & ~7) + 20 * ((nL + 7) & ~7) + 3 * ((nR + 7) & ~7)
+
+
+def stereo_sweep_form(case, rows):
+    """'staged' (whole image; '+ distances' when the 16-byte distance rows ride along), 'banded', or 'single row' when some row's own slices exceed
+    the arena at epipolar offset 0"""
+    nL, nR = len(case["rcL"]), len(case["rcR"])
+    whole = stereo_stage_bytes(rows, nL, nR)
+    if whole <= VS_ARENA:
+        return "staged + distances" if ((whole + 15) & ~15) + 16 * nL <= VS_ARENA else "staged"
+    perL, perR = np.bincount(case["rcL"][:, 0], minlength=rows), np.bincount(case["rcR"][:, 0], minlength=rows)
+    return "single row" if max(stereo_stage_bytes(1, int(a), int(b)) for a, b in zip(perL, perR)) > VS_ARENA else "banded"
+
+
+def bin_table_form(rows, cols, bin_size, n):
+    """tables of the bin competition for n candidates: 32-bit in LDS, else 16-bit in LDS, else 32-bit in HBM"""
+    nb = (rows // bin_size + 1) * (cols // bin_size + 1)
+    if (3 * (nb + 1) + 4 * n) * 4 <= VS_ARENA:
+        return "i32 lds"
+    if n < 32767 and (2 * ((nb + 2) // 2) + n) * 4 + 4 * n + 16 <= VS_ARENA:
+        return "u16 lds"
+    return "i32 hbm"
+
+
+# (name, rows, cols, bin size (None: the configuration's 15), nL, nR, row_features, sweep form, bin-table form)
+STEREO_BIN_CASES = [("bin %d" % b, ROWS, COLS, b, n, n, 0, "staged + distances", form) for b, form in ((5, "u16 lds"), (3, "i32 hbm")) for n in (513, 2500)]
+STEREO_DENSE_ROW_CASES = [("dense row", ROWS, COLS, None, 513, 513, 300, "staged + distances", "i32 lds"),
+                          ("dense row", ROWS, COLS, None, 6400, 513, 300, "banded", "i32 lds")]
+STEREO_WIDE_CASES = [("wide", 32, 8192, None, 6000, 6000, 5800, "single row", "i32 lds")]
+
+
+def ref_stereo_binned(case, epi, rows, cols, bin_size):
+    """The bin competition (stereo_framepoint_generator.cpp:371-394, :435-456) on the sweep's matches in sweep order, no tracked points: a candidate
+    takes its bin when the bin is empty or when its disparity is larger and its distance not larger than the holder's; emission in bin order."""
+    m = ref_stereo(case, epi)
+    rows_bin, cols_bin = rows // bin_size + 1, cols // bin_size + 1
+    grid = {}
+    for q, (il, ir, dist, _) in enumerate(m):
+        r, c = case["rcL"][il]
+        k = min(int(np.rint(r / float(bin_size))), rows_bin - 1) * cols_bin + min(int(np.rint(c / float(bin_size))), cols_bin - 1)
+        disp = int(c - case["rcR"][ir][1])
+        if k not in grid or (disp > grid[k][0] and dist <= grid[k][1]):
+            grid[k] = (disp, int(dist), q)
+    return m[[grid[k][2] for k in sorted(grid)]].reshape(-1, 4), len(m) - len(grid)
 
 
 def ref_stereo(case, epi):
@@ -801,6 +869,51 @@ def sweep_stereo(make_api, make_orc, python=True, sizes=STEREO_SIZES):
             finally:
                 _destroy(pair)
     return total
+
+
+def _stereo_contexts(make_api, make_orc, **fields):
+    """_contexts for stereo_match alone: the oracle's entry reads the configuration, not a context (and orc_create wants 64 image rows)"""
+    out = []
+    for make in (make_api, make_orc):
+        a = make() if make is not None else None
+        if a is not None and a.prefix == "orc_":
+            a.cfg = config_with(a, **fields).copy()
+        elif a is not None:
+            a.create(config_with(a, **fields), 0, 1)
+        out.append(a)
+    return out
+
+
+def sweep_stereo_forms(make_api, make_orc, cases, python_max=PY_STEREO_MAX):
+    """Binning on, both epipolar settings: every case asserts from its sizes which sweep form and which bin tables it reaches, then compares with the
+    oracle exactly (and with the Python restatement while the right side is small enough for it).  Returns (matches, candidates that lost their bin)."""
+    total = lost = 0
+    for epi in (0, 1):
+        for name, rows, cols, bin_size, nL, nR, row_features, sweep_form, table_form in cases:
+            fields = dict(maximum_epipolar_search_offset_pixels=epi, enable_keypoint_binning=1, rows=rows, cols=cols)
+            if bin_size is not None:
+                fields["bin_size_pixels"] = bin_size
+            pair = _stereo_contexts(make_api, make_orc, **fields)
+            try:
+                case = gen_stereo(41000 + nL + 7 * nR + 13 * row_features + 100 * (bin_size or 0) + epi, nL, nR, row_features=row_features, rows=rows, cols=cols)
+                msg = "stereo %s seed %d %d x %d epi %d" % (name, case["seed"], nL, nR, epi)
+                assert (len(case["rcL"]), len(case["rcR"])) == (nL, nR), msg
+                bs = int(pair[0].cfg.bin_size_pixels)
+                assert stereo_sweep_form(case, rows) == sweep_form, (msg, stereo_sweep_form(case, rows))
+                assert bin_table_form(rows, cols, bs, 0) == table_form and bin_table_form(rows, cols, bs, nL) == table_form, (msg, bs)
+                args = (case["tau"], case["rcL"], case["dL"], case["rcR"], case["dR"])
+                out = pair[0].stereo_match(*args)
+                if pair[1] is not None:
+                    np.testing.assert_array_equal(out, pair[1].stereo_match(*args), err_msg=msg + " (oracle)")
+                if nR <= python_max:
+                    ref, n_lost = ref_stereo_binned(case, epi, rows, cols, bs)
+                    np.testing.assert_array_equal(out, ref, err_msg=msg)
+                    lost += n_lost
+                print("%s: %d matches" % (msg, len(out)))
+                total += len(out)
+            finally:
+                _destroy(pair)
+    return total, lost
 
 
 def sweep_landmark(api, orc, python=True, sizes=LANDMARK_N):

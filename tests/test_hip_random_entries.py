@@ -68,6 +68,23 @@ def test_stereo_match_random():
     assert rc.sweep_stereo(hip.load, Oracle) > 17500
 
 
+def test_stereo_bin_table_forms():
+    """The bin competition on its 16-bit LDS tables (bin 5) and on its HBM tables (bin 3); bin 15 of every other test takes the 32-bit LDS tables."""
+    assert rc.sweep_stereo_forms(hip.load, Oracle, rc.STEREO_BIN_CASES, python_max=0)[0] > 7000
+
+
+def test_stereo_dense_row():
+    """More than 255 right features behind a left feature: step B's explicit scan from the cursor, in the whole-image sweep and in a band.
+    (Step B once skipped such a left feature when the cursor stood past the row's 255th right feature: 194 of the oracle's 199 matches at
+    513 x 513, epipolar offset 0.  The count of right features saturates at 255, and 255 now means "scan".)"""
+    assert rc.sweep_stereo_forms(hip.load, Oracle, rc.STEREO_DENSE_ROW_CASES, python_max=0)[0] > 800
+
+
+def test_stereo_single_row_overflow():
+    """One row whose slices alone exceed the arena: the reference loop on HBM."""
+    assert rc.sweep_stereo_forms(hip.load, Oracle, rc.STEREO_WIDE_CASES, python_max=0)[0] > 1000
+
+
 def test_landmark_update_random(gpu, oracle):
     moved, kept, taken = rc.sweep_landmark(gpu, oracle)
     assert moved > 4800 and kept > 1200 and taken > 3800

@@ -57,6 +57,27 @@ def test_stereo_match_random():
     assert total > 17500
 
 
+def test_stereo_bin_table_forms():
+    """bin 5 (16-bit tables) and bin 3 (tables in HBM) on the KITTI geometry; `lost` = candidates that lost their bin, so bins are contested"""
+    total, lost = rc.sweep_stereo_forms(Oracle, None, rc.STEREO_BIN_CASES)
+    print("stereo matches", total, "lost their bin", lost)
+    assert total > 7000 and lost > 150
+
+
+def test_stereo_dense_row():
+    """300 + 300 features on one row: more than 255 right features behind a left feature, whole image and banded"""
+    total, lost = rc.sweep_stereo_forms(Oracle, None, rc.STEREO_DENSE_ROW_CASES)
+    print("stereo matches", total, "lost their bin", lost)
+    assert total > 800 and lost > 50
+
+
+def test_stereo_single_row_overflow():
+    """8192 x 32 image, 5800 + 5800 features on one row: the row's slices alone exceed the arena"""
+    total, lost = rc.sweep_stereo_forms(Oracle, None, rc.STEREO_WIDE_CASES, python_max=6000)
+    print("stereo matches", total, "lost their bin", lost)
+    assert total > 1000 and lost > 500
+
+
 def test_landmark_update_random(oracle):
     moved, kept, taken = rc.sweep_landmark(oracle, None)
     print("landmarks moved", moved, "kept", kept, "estimates taken", taken)

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "kernels_frame2.h"
+#include "kernels_stage.h"     // -> kernels_frame2.h -> kernels_stereo.h -> kernels_recover.h -> kernels_frame.h
 #include "kernels_depth.h"
 #include "kernels_orb.h"
 #include "kernels_landmark.h"
