@@ -688,6 +688,26 @@ int vslam_rgbd_enable_observations(vslam_rgbd* t, int32_t capacity_per_stream);
 int vslam_rgbd_get_observation_count(vslam_rgbd* t, int32_t stream, int32_t* n);
 int vslam_rgbd_get_observations(vslam_rgbd* t, int32_t stream, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame2, float* xy, double* cam);
 int vslam_rgbd_get_point_ids(vslam_rgbd* t, int32_t stream, int32_t cap, int32_t* n, int32_t* ids);
+/* Undistortion of raw frames in this mode (opt-in; csrc/kernels_undistort.h): the counterpart of vslam_set_rectification for
+ * one camera with a depth image registered to it (TUM, Kinect / RealSense streams).  One map pair in vslam_set_rectification's format at
+ * the tracker's rows x cols serves image and depth.  The image is remapped like vslam_remap_u8 (bilinear, the same kernel); the depth
+ * image takes the NEAREST raw pixel of the 1/32-px coordinate, ties up — depth is never blended across an edge:
+ *   x = x0 + ((a & 31) >> 4), y = y0 + (((a >> 5) & 31) >> 4), out = raw[y][x] inside the raw image, else 0 (0 = no measurement).
+ * While set, vslam_rgbd_process_host, _submit_host, _submit_batch_host and _submit_batch_device take RAW frames of raw_rows x raw_cols (row
+ * strides >= raw_cols; device depth images of a batch need not be dense); two kernels undistort every sequence's frame ahead of the
+ * detector and of the space map, each on the queue of its consumer.  Device images are read by those two kernels only.  Everything
+ * downstream reports undistorted coordinates.  The maps survive vslam_rgbd_reset.
+ * vslam_rgbd_set_undistortion: host pointers, copied before the call returns; both NULL turns it off and frees the storage.
+ *   VSLAM_ERR_INVALID: one map only, map_a >= 1024, raw size outside 1 .. 32767.  VSLAM_ERR_STATE: a frame in flight, or the host-driven
+ *   loop (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature.
+ * vslam_rgbd_get_undistorted: the image (rows*cols bytes) and depth image (rows*cols uint16) the last finished frame of `stream` was
+ *   processed on, dense; either pointer may be NULL.  VSLAM_ERR_STATE when off, before a frame, or with a frame in flight.
+ * vslam_remap_nearest_u16: the depth remap stand-alone on a host image, the counterpart of vslam_remap_u8 (src rows x cols <= 32767 with
+ *   row_stride elements per row, dst and the maps dst_rows x dst_cols, dense). */
+int vslam_rgbd_set_undistortion(vslam_rgbd* t, int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a);
+int vslam_rgbd_get_undistorted(vslam_rgbd* t, int32_t stream, uint8_t* image, uint16_t* depth);
+int vslam_remap_nearest_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride,
+                            const int16_t* map_xy, const uint16_t* map_a, int32_t dst_rows, int32_t dst_cols, uint16_t* dst);
 
 /* ---- OrbDetector components (first half; base_framepoint_generator.cpp:52-70) ----------------------
  * The reference's OrbDetector is cv::ORB::create(5000, 1.2, 8, 31, 0, 2, HARRIS_SCORE, 31, threshold) used as a DETECTOR

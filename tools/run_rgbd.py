@@ -5,7 +5,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
 
     python tools/run_rgbd.py <folder> [--config icl|tum|xtion] [--intrinsics freiburg1|freiburg2|freiburg3|icl|fx,fy,cx,cy]
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
-                             [--map map.ply] [--observations bundle.npz]
+                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -14,7 +14,11 @@ Colour images are converted like cv::imread(IMREAD_GRAYSCALE).  With a groundtru
 trajectory_analyzer (executables/trajectory_analyzer.cpp, restated in evaluation.py) reports the RMSE after its alignment.
 --map writes every landmark of the run (world frame) as a binary PLY (x y z id first_frame last_frame updates); --observations writes
 trajectory + landmark map + which landmark was seen in which frame at which pixel and depth into one .npz (io_formats.read_bundle_rgbd;
-implies the map) and reports the residuals of the log against map and trajectory.  Both need the device-resident loop (FAST detector)."""
+implies the map) and reports the residuals of the log against map and trajectory.  Both need the device-resident loop (FAST detector).
+--undistort takes the folder's frames as RAW ones of a camera with radial-tangential lens distortion and undoes it on the GPU ahead of the
+detector (vslam_rgbd_set_undistortion: image bilinear, depth nearest, one map for both — the depth images are registered to the colour
+camera); without a value the coefficients are io_formats.TUM_DISTORTION[--intrinsics].  The output camera is --intrinsics' pinhole
+camera at the raw size; trajectory, map and observations are then in undistorted coordinates.  Device-resident loop only."""
 import argparse
 import os
 import sys
@@ -72,8 +76,28 @@ def configure(api, which, rows, cols, K, depth_unit, descriptor=1, detector=0, d
     return cfg, p
 
 
+def distortion_of(undistort, intrinsics):
+    """--undistort's value -> the five coefficients (k1, k2, p1, p2, k3), or None without the flag.  "" (the flag alone): the table's
+    coefficients of a named --intrinsics.  A string "k1,k2,p1,p2[,k3]" or a sequence of 4 or 5 numbers: those."""
+    if undistort is None:
+        return None
+    if isinstance(undistort, str):
+        if undistort.strip() == "":
+            if intrinsics not in io_formats.TUM_DISTORTION:
+                raise SystemExit("--undistort without coefficients needs a named --intrinsics (%s); give k1,k2,p1,p2[,k3]" % ", ".join(sorted(io_formats.TUM_DISTORTION)))
+            return tuple(io_formats.TUM_DISTORTION[intrinsics])
+        try:
+            undistort = [float(v) for v in undistort.split(",")]
+        except ValueError:
+            raise SystemExit("--undistort: expected k1,k2,p1,p2[,k3], got %r" % (undistort,))
+    d = [float(v) for v in undistort]
+    if len(d) not in (4, 5):
+        raise SystemExit("--undistort: 4 or 5 coefficients (k1,k2,p1,p2[,k3]), got %d" % len(d))
+    return tuple(d + [0.0] * (5 - len(d)))
+
+
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
-        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None):
+        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None):
     seq = io_formats.TumRgbdSequence(folder)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
@@ -83,12 +107,25 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     gray, depth = seq.frame(0)
     api = hip.load()
     cfg, p = configure(api, which, gray.shape[0], gray.shape[1], K, depth_unit, descriptor, detector, depth_scale)
+    dist = distortion_of(undistort, intrinsics)
+    if dist is None and any(io_formats.TUM_DISTORTION.get(intrinsics, ())):
+        log("note: the %s camera has lens distortion (k1 %g, k2 %g, ...) and the frames are used as they are; --undistort undoes it on the GPU" % (
+            intrinsics, io_formats.TUM_DISTORTION[intrinsics][0], io_formats.TUM_DISTORTION[intrinsics][1]))
+    if dist is not None and not any(dist):
+        log("--undistort: all distortion coefficients are zero, there is nothing to undo")
+        dist = None
     tr = RgbdTracker(api, cfg, p, device)
     poses, flags = [], 0
     want_map = bool(map_path or obs_path)        # the log's ids are the map's
     lm_map = obs = None
     t0 = time.perf_counter()
     try:
+        if dist is not None:
+            from vslam_pose_estimation_framework_amd import rectify
+            und = rectify.undistortion(rectify.CameraModel(K, dist, gray.shape[0], gray.shape[1]))
+            tr.set_undistortion(und)
+            log("undistorting on the GPU: %dx%d, k1 %g k2 %g p1 %g p2 %g k3 %g, %.1f %% of the pixels have a source inside the raw frame" % (
+                (und.rows, und.cols) + tuple(dist) + (100.0 * float(np.mean(rectify.remap_nearest_u16(np.ones((und.raw_rows, und.raw_cols), np.uint16), und.map_xy, und.map_a))),)))
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
         if obs_path:
@@ -154,7 +191,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     return result
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("folder")
     ap.add_argument("--config", choices=sorted(YAML), default="tum")
@@ -169,9 +206,20 @@ def main():
     ap.add_argument("--map", default=None, help="write the landmark map (every landmark of the run, world frame) to this binary PLY file")
     ap.add_argument("--observations", default=None, help="write trajectory, landmark map and the landmark observation log (id, frame, x y, camera "
                     "coordinates) to this .npz bundle (io_formats.read_bundle_rgbd); implies the map")
-    a = ap.parse_args()
+    ap.add_argument("--undistort", nargs="?", const="", default=None, metavar="k1,k2,p1,p2[,k3]", help="the frames are raw: undo this radial-tangential "
+                    "lens distortion on the GPU ahead of the detector; without a value: the coefficients that belong to a named --intrinsics")
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):          # "--undistort -0.28,0.07,0,0": argparse would read the negative list as an option
+        if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
+            argv[i:i + 2] = ["--undistort=" + argv[i + 1]]
+            break
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
-        map_path=a.map, obs_path=a.observations)
+        map_path=a.map, obs_path=a.observations, undistort=a.undistort)
 
 
 if __name__ == "__main__":

@@ -654,6 +654,18 @@ class CApi(object):
                                        _p(mxy, C.c_int16), _p(ma, C.c_uint16), C.c_int32(ma.shape[0]), C.c_int32(ma.shape[1]), _p(dst, C.c_uint8)))
         return dst
 
+    def remap_nearest_u16(self, image, map_xy, map_a, cols=None):
+        """vslam_remap_nearest_u16: image is rows x stride uint16 (cols <= stride elements used), the maps give the output size."""
+        img = np.ascontiguousarray(image, np.uint16)
+        mxy = np.ascontiguousarray(map_xy, np.int16)
+        ma = np.ascontiguousarray(map_a, np.uint16)
+        assert mxy.shape[:2] == ma.shape and mxy.shape[2] == 2
+        cols = img.shape[1] if cols is None else int(cols)
+        dst = np.zeros(ma.shape, np.uint16)
+        self.check(self.fn("remap_nearest_u16")(*self._ctx_args(), _p(img, C.c_uint16), C.c_int32(img.shape[0]), C.c_int32(cols), C.c_int32(img.shape[1]),
+                                                _p(mxy, C.c_int16), _p(ma, C.c_uint16), C.c_int32(ma.shape[0]), C.c_int32(ma.shape[1]), _p(dst, C.c_uint16)))
+        return dst
+
     def harris_angle(self, image, xy):
         img = np.ascontiguousarray(image, np.uint8)
         pts = np.ascontiguousarray(xy, np.int16).reshape(-1, 2)
@@ -805,7 +817,30 @@ class _RgbdMapApi(object):
         return ids[:n.value].copy()
 
 
-class RgbdTracker(_RgbdMapApi):
+class _RgbdUndistortApi(object):
+    """vslam_rgbd_set_undistortion / _get_undistorted (the device-resident loop only), shared by RgbdTracker and RgbdBatch."""
+
+    def set_undistortion(self, und):
+        """und: rectify.Undistortion (its maps at the tracker's rows x cols), or None to switch it off.  While set, process / submit take
+        raw frames of und.raw_rows x und.raw_cols."""
+        if und is None:
+            self._check(self.lib.vslam_rgbd_set_undistortion(self.h, C.c_int32(0), C.c_int32(0), None, None))
+            return
+        if (und.rows, und.cols) != (self.cfg.rows, self.cfg.cols):
+            raise ValueError("set_undistortion: maps are %dx%d, the tracker is %dx%d" % (und.rows, und.cols, self.cfg.rows, self.cfg.cols))
+        mxy, ma = np.ascontiguousarray(und.map_xy, np.int16), np.ascontiguousarray(und.map_a, np.uint16)
+        self._check(self.lib.vslam_rgbd_set_undistortion(self.h, C.c_int32(und.raw_rows), C.c_int32(und.raw_cols), _p(mxy, C.c_int16), _p(ma, C.c_uint16)))
+
+    def undistorted(self, stream=0):
+        """(image, depth) the last finished frame of `stream` was processed on."""
+        rows, cols = int(self.cfg.rows), int(self.cfg.cols)
+        img = np.zeros((rows, cols), np.uint8)
+        dep = np.zeros((rows, cols), np.uint16)
+        self._check(self.lib.vslam_rgbd_get_undistorted(self.h, C.c_int32(stream), _p(img, C.c_uint8), _p(dep, C.c_uint16)))
+        return img, dep
+
+
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -862,7 +897,7 @@ class RgbdTracker(_RgbdMapApi):
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

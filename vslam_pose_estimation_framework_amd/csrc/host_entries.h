@@ -331,6 +331,29 @@ VS_API int vslam_resize_linear_u8(vslam_ctx* c, const uint8_t* src, int32_t rows
   k.down(dst, dd, (size_t)drows * dcols);
   return k.finish();
 }
+// k_undistort_depth stand-alone on a host image (beside vslam_remap_u8, the image's remap): nearest neighbour on the fixed-point maps
+VS_API int vslam_remap_nearest_u16(vslam_ctx* c, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride, const int16_t* map_xy,
+                                   const uint16_t* map_a, int32_t drows, int32_t dcols, uint16_t* dst) {
+  if (int rc = entry_begin(c)) return rc;
+  if (!src || !dst || !map_xy || !map_a || rows < 1 || cols < 1 || rows > 32767 || cols > 32767 || row_stride < cols || drows < 1 || dcols < 1 ||
+      (size_t)rows * (size_t)row_stride > 0x7fffffffu)
+    return fail(c, VSLAM_ERR_INVALID, "remap: bad argument");
+  if (!rect_maps_ok(map_a, (size_t)drows * dcols)) return fail(c, VSLAM_ERR_INVALID, "remap: interpolation table index >= 1024");
+  const int ms = (dcols + 3) & ~3;
+  std::vector<int16_t> pxy;
+  std::vector<uint16_t> pa;
+  rect_pad_maps(map_xy, map_a, drows, dcols, ms, pxy, pa);
+  Call k(c, c->stream);
+  uint16_t* ds = k.dev<uint16_t>((size_t)rows * row_stride); uint16_t* dd = k.dev<uint16_t>((size_t)drows * dcols);
+  k.up_to(ds, src, (size_t)(rows - 1) * row_stride + cols);
+  UndistortDepthArgs ua{};
+  ua.src = ds; ua.src_row_stride = row_stride; ua.src_rows = rows; ua.src_cols = cols;
+  ua.map_xy = k.up(pxy.data(), pxy.size()); ua.map_a = k.up(pa.data(), pa.size()); ua.map_stride = ms;
+  ua.dst = dd; ua.dst_row_stride = dcols; ua.rows = drows; ua.cols = dcols; ua.n = 1;
+  if (k.ok()) hipLaunchKernelGGL(k_undistort_depth, undistort_grid(drows, dcols, 1), dim3(256), 0, c->stream, ua);
+  k.down(dst, dd, (size_t)drows * dcols);
+  return k.finish();
+}
 static OrbUmax orb_umax_table(int half) {   // orb.cpp computeKeyPoints: row half-widths of the circular patch
   OrbUmax t;
   std::memset(&t, 0, sizeof t);

@@ -41,7 +41,7 @@ VS_API int vslam_rgbd_reset(vslam_rgbd* r) {
 // what every entry that takes a frame checks first; the message lands in the loop's own error string
 static int rgbd_frame_args_ok(vslam_rgbd* r, const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride) {
   if (!left || !depth) { r->err() = "called with empty frame"; return VSLAM_ERR_INVALID; }   // depth_framepoint_generator.cpp:48-50
-  const int cols = r->on_host ? r->t.cfg.cols : r->d.cfg.cols;
+  const int cols = r->on_host ? r->t.cfg.cols : r->d.in_cols();     // the raw width while undistortion maps are set
   if (lstride < cols || dstride < cols) { r->err() = "row stride smaller than image width"; return VSLAM_ERR_INVALID; }
   return VSLAM_OK;
 }
@@ -157,4 +157,17 @@ VS_API int vslam_rgbd_get_observations(vslam_rgbd* r, int32_t stream, int32_t fi
 VS_API int vslam_rgbd_get_point_ids(vslam_rgbd* r, int32_t stream, int32_t cap, int32_t* n, int32_t* ids) {
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_point_ids") : r->d.get_point_ids(stream, cap, n, ids);
+}
+// ---- undistortion of raw frames (kernels_undistort.h): the device-resident loop only ----
+static int rgbd_undistort_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes undistorted frames only; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_undistortion(vslam_rgbd* r, int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_undistort_host_refusal(r, "vslam_rgbd_set_undistortion") : r->d.set_undistortion(raw_rows, raw_cols, map_xy, map_a);
+}
+VS_API int vslam_rgbd_get_undistorted(vslam_rgbd* r, int32_t stream, uint8_t* image, uint16_t* depth) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_undistort_host_refusal(r, "vslam_rgbd_get_undistorted") : r->d.get_undistorted(stream, image, depth);
 }

@@ -9,6 +9,7 @@
 #pragma once
 #include "kernels_rgbd.h"
 #include "kernels_rgbd_map.h"
+#include "kernels_undistort.h"
 
 namespace vs_rgbd {
 
@@ -114,6 +115,7 @@ public:
       if (hipStreamSynchronize(q) != hipSuccess) { err = "RGB-D reset: space-map buffers"; return VSLAM_ERR_HIP; }
     }
     failed = false; failed_why.clear(); pending = false;
+    und.have_frame = false;                                                  // the maps stay (like the rig of a rectifying context)
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
     return VSLAM_OK;
   }
@@ -223,6 +225,53 @@ public:
     return VSLAM_OK;
   }
 
+  // ---- undistortion of raw frames (kernels_undistort.h): opt-in, its own allocations, nothing launched while und.on is false ----
+  // size of the frames the submit entries take: the raw camera's while the maps are set
+  int in_rows() const { return und.on ? und.raw_rows : p.rows; }
+  int in_cols() const { return und.on ? und.raw_cols : p.cols; }
+  int set_undistortion(int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a) {
+    const bool off = !map_xy && !map_a;
+    if (!off && (!map_xy || !map_a)) { err = "vslam_rgbd_set_undistortion: both maps or none"; return VSLAM_ERR_INVALID; }
+    if (!off && (raw_rows < 1 || raw_cols < 1 || raw_rows > 32767 || raw_cols > 32767)) { err = "vslam_rgbd_set_undistortion: invalid raw image dimensions"; return VSLAM_ERR_INVALID; }
+    if (!off && !rect_maps_ok(map_a, (size_t)p.rows * p.cols)) { err = "vslam_rgbd_set_undistortion: interpolation table index >= 1024"; return VSLAM_ERR_INVALID; }
+    if (pending) { err = "vslam_rgbd_set_undistortion: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    (void)hipStreamSynchronize(q2);
+    und_free();
+    drop_graph();                                   // a captured launch sequence holds the old maps and buffers (or none)
+    if (off) return VSLAM_OK;
+    Undist u{};
+    u.raw_rows = raw_rows; u.raw_cols = raw_cols;
+    u.map_stride = (p.cols + 3) & ~3;
+    u.img_stride = u.map_stride;                    // k_rectify stores words: rows 4-byte aligned
+    u.img_stream = ((size_t)p.rows * u.img_stride + 255) & ~(size_t)255;
+    std::vector<int16_t> pxy;
+    std::vector<uint16_t> pa;
+    rect_pad_maps(map_xy, map_a, p.rows, p.cols, u.map_stride, pxy, pa);
+    hipError_t e = und_mem.alloc(&u.map_xy, pxy.size());
+    if (e == hipSuccess) e = und_mem.alloc(&u.map_a, pa.size());
+    if (e == hipSuccess) e = und_mem.alloc(&u.img, u.img_stream * (size_t)B + 64);
+    if (e == hipSuccess) e = und_mem.alloc(&u.raw_depth, (size_t)B * raw_rows * raw_cols);
+    if (e == hipSuccess) e = hipMemcpy(u.map_xy, pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(u.map_a, pa.data(), pa.size() * 2, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { und_free(); err = std::string("vslam_rgbd_set_undistortion: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    u.on = true;
+    und = u;
+    return VSLAM_OK;
+  }
+  // the undistorted image and depth image the last finished frame of `stream` was processed on (dense; either may be null)
+  int get_undistorted(int stream, uint8_t* image, uint16_t* depth) {
+    if (int rc = readable(stream)) return rc;
+    if (!und.on || !und.have_frame) { err = "vslam_rgbd_get_undistorted: no frame has been undistorted since vslam_rgbd_set_undistortion / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    hipError_t e = hipSuccess;
+    if (image) e = hipMemcpy2D(image, (size_t)p.cols, und.img + (size_t)stream * und.img_stream, (size_t)und.img_stride, (size_t)p.cols, (size_t)p.rows, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && depth) e = hipMemcpy(depth, d_depth + (size_t)stream * p.rows * p.cols, (size_t)p.rows * p.cols * 2, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    return VSLAM_OK;
+  }
+
   int process(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t left_stream_stride = 0, size_t depth_stream_stride = 0) {
     const int rc = submit(left, lstride, depth, dstride, left_stream_stride, depth_stream_stride);
     return rc != VSLAM_OK ? rc : wait();
@@ -233,10 +282,11 @@ public:
   // read them where they are; the depth images must then be dense per sequence (depth_stream_stride == rows * depth_row_stride)
   int submit(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t left_stream_stride = 0, size_t depth_stream_stride = 0, bool on_device = false) {
     if (!left || !depth) { err = "called with empty frame"; return VSLAM_ERR_INVALID; }
-    if (on_device && B > 1 && depth_stream_stride != (size_t)p.rows * dstride) { err = "RGB-D batch on device images: depth images must be dense per sequence"; return VSLAM_ERR_INVALID; }
+    if (on_device && !und.on && B > 1 && depth_stream_stride != (size_t)p.rows * dstride) { err = "RGB-D batch on device images: depth images must be dense per sequence"; return VSLAM_ERR_INVALID; }
     if (failed) { err = "RGB-D tracker: an earlier frame failed (" + failed_why + "); reset() before the next frame"; return VSLAM_ERR_STATE; }
     if (pending) { err = "RGB-D tracker: the previous frame has not been waited for"; return VSLAM_ERR_STATE; }
-    if (B > 1 && (left_stream_stride < (size_t)(p.rows - 1) * lstride + p.cols || depth_stream_stride < (size_t)(p.rows - 1) * dstride + p.cols)) {
+    if (und.on && (size_t)und.raw_rows * (size_t)dstride > 0x7fffffffu) { err = "RGB-D frame: raw depth row stride too large"; return VSLAM_ERR_INVALID; }   // k_undistort_depth's 32-bit tap offsets
+    if (B > 1 && (left_stream_stride < (size_t)(in_rows() - 1) * lstride + in_cols() || depth_stream_stride < (size_t)(in_rows() - 1) * dstride + in_cols())) {
       err = "RGB-D batch: stream strides smaller than an image"; return VSLAM_ERR_INVALID;
     }
     const int rc = submit_frame(left, lstride, depth, dstride, left_stream_stride, depth_stream_stride, on_device);
@@ -249,6 +299,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
+    else und.have_frame = und.on;
     return rc;
   }
 
@@ -314,10 +365,27 @@ private:
   // store is turned off or replaced (the inner context's allocation list only grows until destroy)
   RgbdMap mp{};
   DeviceStore map_mem, obs_mem;
+  // undistortion of raw frames: off while und.on is false.  The maps at the tracker's size (rows padded to map_stride entries), the
+  // undistorted images the image pipeline reads, and the raw depth images of a host frame (raw images go through d_img; the
+  // undistorted depth images are d_depth).  raw_*: where this frame's raw images are — the staging buffers or the caller's device memory
+  struct Undist {
+    bool on, have_frame;
+    int32_t raw_rows, raw_cols, map_stride, img_stride;
+    size_t img_stream;
+    int16_t* map_xy; uint16_t* map_a; uint8_t* img; uint16_t* raw_depth;
+  } und{};
+  DeviceStore und_mem;
+  const uint8_t* raw_img = nullptr; int32_t raw_img_stride = 0; size_t raw_img_stream = 0;
+  const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
+  bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
 
   void obs_free() {
     obs_mem.release();
     mp.log = nullptr; mp.ocount = nullptr; mp.ocap = 0;
+  }
+  void und_free() {
+    und_mem.release();
+    und = Undist{};
   }
   void map_free() {
     obs_free();
@@ -345,6 +413,7 @@ private:
     if (pinned) { (void)hipHostFree(pinned); pinned = nullptr; }
     drop_graph();
     map_free();
+    und_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (q2) { (void)hipStreamDestroy(q2); q2 = nullptr; }
     if (ev_depth) { (void)hipEventDestroy(ev_depth); ev_depth = nullptr; }
@@ -399,20 +468,29 @@ private:
 
   int submit_frame(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t lss, size_t dss, bool on_device) {
     (void)hipSetDevice(ic->device);
-    const int rows = p.rows, cols = p.cols;
+    const int rows = in_rows(), cols = in_cols();      // of the frames that come in: raw ones while the undistortion maps are set
+    src_on_device = on_device;
     if (on_device) {
       use_graph = false;                       // the captured graph holds the staging buffers' addresses
       bs = buf_set(ic, 0, 0);
-      bs.img[0] = left; bs.img[1] = left; bs.img_row_stride = lstride; bs.img_stream_stride = lss;
+      if (und.on) {                            // the two undistortion kernels are the only readers of the caller's memory
+        raw_img = left; raw_img_stride = lstride; raw_img_stream = lss;
+        raw_dep = depth; raw_dep_stride = dstride; raw_dep_stream = dss;
+        bs.img[0] = und.img; bs.img[1] = und.img; bs.img_row_stride = und.img_stride; bs.img_stream_stride = und.img_stream;
+        depth_src = d_depth; depth_src_stride = p.cols;
+      } else {
+        bs.img[0] = left; bs.img[1] = left; bs.img_row_stride = lstride; bs.img_stream_stride = lss;
+        depth_src = depth; depth_src_stride = dstride;
+      }
       all_active(bs);
-      depth_src = depth; depth_src_stride = dstride;
       enqueue_first_attempt(false);
       hipError_t e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(pinned, rb.st, sizeof(RgbdState) * (size_t)B, hipMemcpyDeviceToHost, q);
       if (e != hipSuccess) { ic->sticky = VSLAM_ERR_HIP; return hip_fail(e, "RGB-D frame"); }
       return VSLAM_OK;
     }
-    depth_src = d_depth; depth_src_stride = cols;
+    depth_src = d_depth; depth_src_stride = p.cols;
+    uint16_t* const depth_up = und.on ? und.raw_depth : d_depth;     // where the depth images are copied to, re-packed
     // inputs: the caller's row stride kept on the device for the image, the depth image re-packed
     const size_t ib = (size_t)(rows - 1) * lstride + cols;                 // bytes of one image the caller owns
     // device bytes per sequence: the caller's own stream stride when the images lie in one (nearly) dense block — then ONE copy brings all of
@@ -423,6 +501,7 @@ private:
       (void)hipStreamSynchronize(q);
       if (d_img) (void)hipFree(d_img);
       d_img = nullptr; img_stream = 0;
+      drop_graph();                            // it holds the old buffer and its stream stride
       const hipError_t e = hipMalloc((void**)&d_img, need * (size_t)B + 64);
       if (e != hipSuccess) return hip_fail(e, "image buffer");
       img_stream = need;
@@ -433,17 +512,23 @@ private:
     if (dense) e = hipMemcpyAsync(d_img, left, (size_t)(B - 1) * lss + ib, hipMemcpyHostToDevice, q);
     else for (int s = 0; s < B && e == hipSuccess; ++s) e = hipMemcpyAsync(d_img + (size_t)s * img_stream, left + (size_t)s * lss, ib, hipMemcpyHostToDevice, q);
     if (e == hipSuccess) {
-      if (dstride == cols && (B == 1 || dss == (size_t)rows * cols)) e = hipMemcpyAsync(d_depth, depth, (size_t)B * rows * cols * 2, hipMemcpyHostToDevice, qd);
+      if (dstride == cols && (B == 1 || dss == (size_t)rows * cols)) e = hipMemcpyAsync(depth_up, depth, (size_t)B * rows * cols * 2, hipMemcpyHostToDevice, qd);
       else for (int s = 0; s < B && e == hipSuccess; ++s) {
         const uint16_t* dsrc = depth + (size_t)s * dss;
-        uint16_t* ddst = d_depth + (size_t)s * rows * cols;
+        uint16_t* ddst = depth_up + (size_t)s * rows * cols;
         if (dstride == cols) e = hipMemcpyAsync(ddst, dsrc, (size_t)rows * cols * 2, hipMemcpyHostToDevice, qd);
         else e = hipMemcpy2DAsync(ddst, (size_t)cols * 2, dsrc, (size_t)dstride * 2, (size_t)cols * 2, rows, hipMemcpyHostToDevice, qd);
       }
     }
     if (e != hipSuccess) return hip_fail(e, "image / depth upload");
     bs = buf_set(ic, 0, 0);
-    bs.img[0] = d_img; bs.img[1] = d_img; bs.img_row_stride = lstride; bs.img_stream_stride = img_stream;
+    if (und.on) {
+      raw_img = d_img; raw_img_stride = lstride; raw_img_stream = img_stream;
+      raw_dep = und.raw_depth; raw_dep_stride = cols; raw_dep_stream = (size_t)rows * cols;
+      bs.img[0] = und.img; bs.img[1] = und.img; bs.img_row_stride = und.img_stride; bs.img_stream_stride = und.img_stream;
+    } else {
+      bs.img[0] = d_img; bs.img[1] = d_img; bs.img_row_stride = lstride; bs.img_stream_stride = img_stream;
+    }
     all_active(bs);
     if (use_graph && (!graph_exec || graph_stride != lstride || graph_img != d_img)) capture_graph(lstride);
     if (use_graph && graph_exec) {
@@ -469,7 +554,15 @@ private:
     uint32_t f0_bits;
     std::memcpy(&f0_bits, &f0, 4);
     const dim3 grid((cols + 255) / 256, rows, B);
-    if (depth_src != d_depth) { (void)hipEventRecord(ev_fork, q); (void)hipStreamWaitEvent(q2, ev_fork, 0); }   // device images: whatever wrote them was ordered before q
+    if (src_on_device) { (void)hipEventRecord(ev_fork, q); (void)hipStreamWaitEvent(q2, ev_fork, 0); }   // device images: whatever wrote them was ordered before q
+    // raw depth -> undistorted depth on the space map's queue, behind the depth upload and ahead of the map's first kernel
+    if (und.on) {
+      UndistortDepthArgs ua{};
+      ua.src = raw_dep; ua.src_stream_stride = raw_dep_stream; ua.src_row_stride = raw_dep_stride; ua.src_rows = und.raw_rows; ua.src_cols = und.raw_cols;
+      ua.map_xy = und.map_xy; ua.map_a = und.map_a; ua.map_stride = und.map_stride;
+      ua.dst = d_depth; ua.dst_stream_stride = (size_t)rows * cols; ua.dst_row_stride = cols; ua.rows = rows; ua.cols = cols; ua.n = B;
+      hipLaunchKernelGGL(k_undistort_depth, undistort_grid(rows, cols, B), dim3(256), 0, q2, ua);
+    }
     // pinhole matrices, identity offset: one direct pass; the general three passes stay enqueued behind it and skip every image whose depth
     // pixels all landed on themselves (k_depth_direct checks that and raises rb.cross[image] otherwise)
     const int32_t* gate = nullptr;
@@ -485,6 +578,12 @@ private:
     hipLaunchKernelGGL(k_depth_write, ggrid, dim3(256), 0, q2, p, depth_src, depth_src_stride, f0_bits, rb.dkey, rb.dlast, rb.space, rb.row_map, rb.col_map, 1, gate);   // leaves the z-buffer initialised for the next frame
     (void)hipEventRecord(ev_depth, q2);
     depth_pending = true;
+    // raw image -> undistorted image on the image pipeline's queue, ahead of the detector and behind the fork, so that the space map's
+    // queue does not wait for it (once per frame: further attempts read the undistorted image again)
+    if (und.on)
+      hipLaunchKernelGGL(k_rectify, undistort_grid(rows, cols, B), dim3(256), 0, q,
+                         undistort_image_args(raw_img, raw_img_stream, raw_img_stride, und.raw_rows, und.raw_cols, und.map_xy, und.map_a, und.map_stride, und.img,
+                                              und.img_stream, und.img_stride, rows, cols, B));
     enqueue_attempt(bs);
     enqueue_tail(bs);
   }

@@ -16,6 +16,7 @@
 #include "kernels_landmark.h"
 #include "kernels_report.h"
 #include "kernels_rectify.h"
+#include "kernels_undistort.h"
 #include "kernels_map.h"
 #include "kernels_obs.h"
 

@@ -205,6 +205,10 @@ def rgb_to_gray_opencv(rgb):
 # The RGB-D benchmark's camera intrinsics (fx, fy, cx, cy) and its 16-bit depth unit (1 / 5000 m); ICL-NUIM is distributed in the same layout.
 TUM_INTRINSICS = {"freiburg1": (517.3, 516.5, 318.6, 255.3), "freiburg2": (520.9, 521.0, 325.1, 249.7), "freiburg3": (535.4, 539.2, 320.1, 247.6),
                   "icl": (481.2, 480.0, 319.5, 239.5)}
+# the lens distortion (k1, k2, p1, p2, k3) that belongs to these camera matrices, as the benchmark's calibration page lists it [recalled];
+# freiburg3's images and ICL-NUIM's renderings come undistorted.  rectify.undistortion() / tools/run_rgbd.py --undistort apply it.
+TUM_DISTORTION = {"freiburg1": (0.2624, -0.9531, -0.0054, 0.0026, 1.1633), "freiburg2": (0.2312, -0.7849, -0.0033, -0.0001, 0.9172),
+                  "freiburg3": (0.0, 0.0, 0.0, 0.0, 0.0), "icl": (0.0, 0.0, 0.0, 0.0, 0.0)}
 TUM_DEPTH_UNIT_M = 1.0 / 5000.0
 
 

@@ -9,6 +9,8 @@ The product path is `k_rectify` (csrc/kernels_rectify.h) behind `vslam_set_recti
   (initUndistortRectifyMap / convertMaps [recalled]).
 - `remap_u8`: a numpy restatement of the kernel's arithmetic, the tests' checker (not a product path).
 - `Rectification` / `rectification()`: everything a context needs; `apply_to_config` sets the rectified camera.
+- `Undistortion` / `undistortion()`: the one-camera case of the RGB-D tracker (`vslam_rgbd_set_undistortion`): one map pair for the image
+  and the depth image registered to it; `remap_nearest_u16` restates the depth kernel (`k_undistort_depth`, csrc/kernels_undistort.h).
 """
 import numpy as np
 
@@ -197,6 +199,19 @@ def remap_u8(src, map_xy, map_a):
     return ((s + 16384) >> 15).astype(np.uint8)
 
 
+def remap_nearest_u16(src, map_xy, map_a):
+    """The depth kernel's arithmetic on 16-bit single-channel images: the nearest raw pixel of the 1/32-px source coordinate, ties up
+    (this repository's own rule; depth is not interpolated): x = x0 + (ax >> 4), y = y0 + (ay >> 4), out = src[y][x] inside the raw image,
+    else 0 (depth 0 = no measurement).  The tests' checker."""
+    src = np.asarray(src, np.uint16)
+    H, W = src.shape
+    a = np.asarray(map_a).astype(np.int64)
+    x = map_xy[..., 0].astype(np.int64) + ((a & 31) >> 4)
+    y = map_xy[..., 1].astype(np.int64) + (((a >> 5) & 31) >> 4)
+    inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+    return np.where(inside, src[np.clip(y, 0, H - 1), np.clip(x, 0, W - 1)], 0).astype(np.uint16)
+
+
 class Rectification(object):
     """A raw rig made rectifiable: both cameras, (R1, R2, P1, P2) and the fixed-point maps at the rectified size rows x cols."""
 
@@ -225,6 +240,30 @@ def rectification(left, right, R, T, rows=None, cols=None):
     """stereo_rectify + both maps (rectified size = raw size unless rows / cols are given)."""
     R1, R2, P1, P2 = stereo_rectify(left, right, R, T)
     return Rectification(left, right, R1, R2, P1, P2, rows, cols)
+
+
+class Undistortion(object):
+    """One raw camera made undistortable: the camera, the output camera K and the fixed-point maps at the output size rows x cols
+    (default: the raw size and the raw camera's own K)."""
+
+    def __init__(self, cam, K_new=None, rows=None, cols=None):
+        self.cam = cam
+        self.K = (cam.K if K_new is None else np.asarray(K_new, np.float64).reshape(3, 3)).copy()
+        self.raw_rows, self.raw_cols = cam.rows, cam.cols
+        self.rows = int(rows) if rows else cam.rows
+        self.cols = int(cols) if cols else cam.cols
+        P = np.concatenate([self.K, np.zeros((3, 1))], axis=1)
+        self.map_xy, self.map_a = undistort_rectify_maps(cam, np.eye(3), P, self.rows, self.cols)
+
+    def apply(self, image, depth):
+        """The undistorted frame in numpy (remap_u8 of the image, remap_nearest_u16 of the depth image registered to it): the checker
+        of the device path."""
+        return remap_u8(image, self.map_xy, self.map_a), remap_nearest_u16(depth, self.map_xy, self.map_a)
+
+
+def undistortion(cam, K_new=None, rows=None, cols=None):
+    """The maps that undo cam's lens distortion: output camera K_new (default cam.K) at rows x cols (default the raw size)."""
+    return Undistortion(cam, K_new, rows, cols)
 
 
 def apply_to_config(cfg, rect):
