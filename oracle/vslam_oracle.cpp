@@ -646,6 +646,7 @@ struct Stream {
   std::vector<FrameRec> frames;
   std::vector<Landmark> landmarks;
   std::vector<int> lost;       /* _lost_points: indices into the previous frame's points */
+  std::vector<int16_t> tracked_kp; /* (xL, yL, xR, yR) of every point the frame's last track() matched, the ones _prunePoints removes included */
   AlignerIO al;
   bool aligner_valid = false;  /* aligner ran on the current frame->points() (quirk B.3) */
   /* the 8 chronometers SLAMAssembly::printReport prints (slam_assembly.cpp:703-742; CREATE_CHRONOMETER in
@@ -704,6 +705,7 @@ struct Stream {
     frames.clear();
     landmarks.clear();
     lost.clear();
+    tracked_kp.clear();
     poses.clear();
     aligner_valid = false;
     al.weight.clear();           /* a new StereoUVAligner: empty _weights_translation */
@@ -882,6 +884,8 @@ struct Stream {
     /* ids == positions here (fresh stores) */
     storeL.prune_positions(matchedL);
     storeR.prune_positions(matchedR);
+    tracked_kp.clear();
+    for (const Point& p : pts) for (int v : {p.xL, p.yL, p.xR, p.yR}) tracked_kp.push_back((int16_t)v);
   }
 
   /* StereoFramePointGenerator::compute (:135-462) */
@@ -1276,6 +1280,7 @@ struct Stream {
     info.status_at_start = status;
     cur_status_at_start = status;
     n_tracked_points = 0;
+    tracked_kp.clear();
     frames.emplace_back();
     FrameRec& cur = frames[findex];
     set_pose(cur, world_pose);
@@ -1462,6 +1467,17 @@ ORC_API int orc_get_aligner_result(orc_ctx* c, int s, int32_t cap, int32_t* n, d
   for (int i = 0; i < a.n; ++i) { if (chi) chi[i] = a.errors[i]; if (inlier) inlier[i] = a.inliers[i]; }
   if (T) std::memcpy(T, a.T.m, sizeof(double) * 12);
   if (H) std::memcpy(H, a.H, sizeof(double) * 36);
+  return VSLAM_OK;
+}
+/* Checker only (the product's fused path keeps no such list): the keypoints (xL, yL, xR, yR) of every point the frame's last track() matched, in
+ * the order of the previous points.  Those the prune removed afterwards are not among orc_get_points, but their keypoints are gone from the
+ * stores the frame's stereo sweep runs on. */
+ORC_API int orc_get_tracked_keypoints(orc_ctx* c, int s, int32_t cap, int32_t* n, int16_t* kp) {
+  if (!c || s < 0 || s >= (int)c->streams.size() || !n) return VSLAM_ERR_INVALID;
+  const std::vector<int16_t>& t = c->streams[s].tracked_kp;
+  *n = (int32_t)(t.size() / 4);
+  if (*n > cap) return VSLAM_ERR_CAPACITY;
+  if (kp) std::memcpy(kp, t.data(), t.size() * sizeof(int16_t));
   return VSLAM_OK;
 }
 /* _weights_translation as the last StereoUVAligner::initialize of the stream left it */

@@ -48,6 +48,14 @@ class Oracle(CApi):
     def stereo_match(self, *a, **k):
         return self._on_config(super().stereo_match, *a, **k)
 
+    def tracked_keypoints(self, stream=0):
+        """(xL, yL, xR, yR) of every point the frame's last track() matched, the ones the prune removed afterwards included."""
+        cap = int(self.cfg.max_points)
+        n = C.c_int32()
+        kp = np.zeros((cap, 4), np.int16)
+        self.check(self.fn("get_tracked_keypoints")(self.ctx, C.c_int(stream), C.c_int32(cap), C.byref(n), kp.ctypes.data_as(C.c_void_p)))
+        return kp[:n.value].copy()
+
     def scene_kitti(self, scale=1.0, seed=7):
         s = SynthScene()
         self.lib.orc_synth_default_kitti(C.byref(s))

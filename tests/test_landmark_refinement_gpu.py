@@ -9,7 +9,8 @@ same exports (updates to 1e-9 — what numpy.linalg.solve is granted against the
 update counts exactly, kept estimates bit for bit), error bit 4 must be up from the first frame that truncates a track (it is sticky:
 only a reset clears it), and every variant asserts from the run's own `meta` that it reached what it is there for.
 
-Not reached: the unlisted branch of wg_landmarks_lds / lm_teams_body needs more than 6720 points in a frame (LIST_CAP)."""
+Not reached here: the unlisted branch of wg_landmarks_lds / lm_teams_body needs more than 6720 points in a frame's landmark pass (LIST_CAP);
+tests/test_hip_dense_frames.py runs it under oracle parity."""
 import numpy as np
 import pytest
 
