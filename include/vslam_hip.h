@@ -219,6 +219,32 @@ int vslam_set_rectification(vslam_ctx* ctx, int32_t raw_rows, int32_t raw_cols,
 int vslam_get_rectified_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
 int vslam_remap_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride,
                    const int16_t* map_xy, const uint16_t* map_a, int32_t dst_rows, int32_t dst_cols, uint8_t* dst);
+/* ---- histogram equalisation of the input pair (opt-in; csrc/kernels_equalize.h) --------------------------------
+ * The reference's -equalize-histogram / -eh switch (option_equalize_histogram): cv::equalizeHist on each 8-bit image [recalled]:
+ *   h[256] = counts of the rows x cols pixels (row padding is never counted);  i0 = the first v with h[v] != 0;
+ *   a constant image (h[i0] == rows*cols) stays as it is;  scale = 255.f / float(rows*cols - h[i0])  (one IEEE single division);
+ *   lut[v] = 0 for v <= i0, else min(255, rint(float(h[i0+1] + ... + h[v]) * scale))  (one single multiply, ties to even);  out = lut[in].
+ * Images of up to 2^24 pixels (the counts are then exact in float), else VSLAM_ERR_INVALID.
+ * Order: rectify (when set), then equalise, then detect — the rectified pair is equalised, as in the reference's node.  Two kernels
+ * (k_hist_u8, k_equalize_apply) per frame on the queue of the image pipeline, under the fused entries and the stage path alike.  The
+ * equalised pair lives in the context's own input slabs: host images are equalised in place there, device images are READ by the two
+ * kernels only and never written.  A switched-off stream is neither read nor written.
+ * vslam_set_equalization: on != 0 turns it on (its own allocations), 0 turns it off and frees them; nothing is launched while off.
+ *   Synchronises the context.  VSLAM_ERR_STATE between vslam_frame_begin and the end of that frame.  The switch survives vslam_reset and
+ *   vslam_reset_stream(s).
+ * vslam_get_equalized_images: the equalised pair the last submitted frame of `stream` was processed on (rows*cols bytes each, dense);
+ *   VSLAM_ERR_STATE when equalisation is off or no frame has been submitted since it was set.  Synchronises.  With rectification on as
+ *   well, vslam_get_rectified_images still returns the rectified (not yet equalised) pair: it is kept in slabs of its own.
+ * vslam_get_equalization_histograms: uint32 [2][256], the counts of that frame's left and right image; the same errors.  The table is
+ *   zeroed whole every frame, so the rows of a switched-off stream read zero.
+ * vslam_equalize_hist_u8: the same two kernels stand-alone on one host image: src is rows x cols with row_stride bytes per row (any
+ *   alignment), dst is dense, hist256 (may be NULL) receives the counts.  rows or cols 0: VSLAM_OK, nothing written.  VSLAM_ERR_INVALID:
+ *   null src / dst, negative size, row_stride < cols, more than 2^24 pixels; the context stays usable. */
+int vslam_set_equalization(vslam_ctx* ctx, int on);
+int vslam_get_equalized_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
+int vslam_get_equalization_histograms(vslam_ctx* ctx, int stream, uint32_t* hist512);
+int vslam_equalize_hist_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride,
+                           uint8_t* dst /* dense */, uint32_t* hist256 /* may be NULL */);
 /* Block until all queued work of the context is done; returns the sticky HIP error state (VSLAM_ERR_HIP once a runtime
  * call has failed, else VSLAM_OK; capacity overflows are reported in vslam_frame_info.error_flags, see VSLAM_ERR_CAPACITY). */
 int vslam_synchronize(vslam_ctx* ctx);
@@ -706,6 +732,16 @@ int vslam_rgbd_get_point_ids(vslam_rgbd* t, int32_t stream, int32_t cap, int32_t
  *   row_stride elements per row, dst and the maps dst_rows x dst_cols, dense). */
 int vslam_rgbd_set_undistortion(vslam_rgbd* t, int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a);
 int vslam_rgbd_get_undistorted(vslam_rgbd* t, int32_t stream, uint8_t* image, uint16_t* depth);
+/* Histogram equalisation in this mode (opt-in; the definition above vslam_set_equalization): the intensity image only, the depth image is
+ * untouched (slam_assembly.cpp:406-409).  On the image queue, behind the undistortion of the image when that is on and ahead of the
+ * detector, once per frame (further registration attempts read the equalised image again), inside the captured launch sequence as well.
+ * A caller's device image is read only: it is equalised into an image of the tracker's own.  The switch survives vslam_rgbd_reset.
+ * vslam_rgbd_set_equalization: VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type
+ *   ORB), which does not have the feature; VSLAM_ERR_INVALID above 2^24 pixels.
+ * vslam_rgbd_get_equalized: the image (rows*cols bytes, dense) the last finished frame of `stream` was processed on; VSLAM_ERR_STATE
+ *   when off, before a frame, or with a frame in flight. */
+int vslam_rgbd_set_equalization(vslam_rgbd* t, int on);
+int vslam_rgbd_get_equalized(vslam_rgbd* t, int32_t stream, uint8_t* image);
 int vslam_remap_nearest_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride,
                             const int16_t* map_xy, const uint16_t* map_a, int32_t dst_rows, int32_t dst_cols, uint16_t* dst);
 

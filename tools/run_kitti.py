@@ -7,6 +7,8 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
                               [--chunks B [--overlap 6]]   frame-sharded mode: B chunks side by side (approximate at the seams)
     python tools/run_kitti.py <EuRoC dir with mav0/cam0 mav0/cam1> --format tum --out traj.txt   (ground truth found in mav0/)
     python tools/run_kitti.py <EuRoC dir> --rectify --format tum --out traj.txt   raw images: rectified on the GPU from mav0/cam{0,1}/sensor.yaml
+    python tools/run_kitti.py <sequence dir> --equalize   (or -eh, the reference's spelling) cv::equalizeHist on every image, on the GPU,
+                              behind --rectify and ahead of the detector: dim, low-contrast sequences; also with --chunks, --map, --observations
     python tools/run_kitti.py <sequence dir> --map map.ply   the landmark map as well (binary PLY: x y z id first_frame last_frame updates)
     python tools/run_kitti.py <sequence dir> --observations bundle.npz   trajectory + landmark map + which landmark was seen in which
                               frame at which pixels, in one file (io_formats.read_bundle); implies the map; also with --chunks
@@ -30,7 +32,7 @@ from vslam_pose_estimation_framework_amd import evaluation, hip, io_formats  # n
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
 
 
-def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False):
+def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -41,6 +43,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
     api.create(cfg, device, len(plan))
     if rect is not None:
         api.set_rectification(rect)
+    if equalize:
+        api.set_equalization(True)
     if want_map:
         api.enable_map(MAP_ENTRIES_PER_FRAME * steps)
     if want_obs:
@@ -71,7 +75,7 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None):
+        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False):
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
     if rectify and not euroc:
         raise SystemExit("--rectify: a KITTI odometry folder is already rectified (it takes raw EuRoC / ASL folders with sensor.yaml)")
@@ -108,17 +112,24 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
                 log("note: sensor.yaml describes distorted raw cameras and there is no calib.txt; --rectify rectifies them on the GPU")
     else:
         io_formats.apply_calib(cfg, seq.K, seq.baseline, left.shape[0], left.shape[1])
+    if equalize:
+        log("equalising histograms on the GPU (cv::equalizeHist on every image%s)" % (", behind the rectification" if rect is not None else ""))
     t0 = time.perf_counter()
     flags = 0
+    tracking = 0
     want_map = bool(map_path or obs_path)        # the log's ids are the map's
     obs = None
     if chunks > 1:
-        poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path))
+        poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
+                                                equalize=equalize)
+        tracking = None
     else:
         cfg.max_history_frames = 512
         api.create(cfg, device, 1)
         if rect is not None:
             api.set_rectification(rect)
+        if equalize:
+            api.set_equalization(True)
         if want_map:
             api.enable_map(MAP_ENTRIES_PER_FRAME * n)
         if obs_path:
@@ -127,9 +138,10 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             if k:
                 left, right = seq.pair(k)
             api.process_host(left, right)
+            fi = api.frame_info(0)
+            flags |= fi.error_flags
+            tracking += int(fi.status == 1)
             if k % 100 == 99 or k == n - 1:
-                fi = api.frame_info(0)
-                flags |= fi.error_flags
                 log("frame %6d  status %s  points %5d  tracked %5d  inliers %5d" % (
                     k, "tracking" if fi.status == 1 else "localizing", fi.n_points, fi.n_tracked, fi.n_inliers))
         poses = api.poses(0, 0, n)
@@ -145,7 +157,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         else:
             io_formats.write_trajectory_kitti(out_path, poses)
         log("trajectory (%s) -> %s" % (fmt, out_path))
-    result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses}
+    result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses, "tracking_frames": tracking}     # tracking_frames: exact mode only
     if map_path:
         if flags & 8:
             log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
@@ -184,7 +196,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     return result
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("sequence")
     ap.add_argument("--out", default=None)
@@ -201,9 +213,15 @@ def main():
     ap.add_argument("--map", default=None, help="write the landmark map (every landmark of the run, world frame) to this binary PLY file")
     ap.add_argument("--observations", default=None, help="write trajectory, landmark map and the landmark observation log (id, frame, xL yL xR yR) "
                     "to this .npz bundle (io_formats.read_bundle); implies the map")
-    a = ap.parse_args()
+    ap.add_argument("--equalize", "-eh", action="store_true", help="equalise every image's histogram on the GPU ahead of the detector "
+                    "(the reference's -equalize-histogram / -eh): dim or low-contrast sequences")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
-        rectify=a.rectify, map_path=a.map, obs_path=a.observations)
+        rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
 
     python tools/run_rgbd.py <folder> [--config icl|tum|xtion] [--intrinsics freiburg1|freiburg2|freiburg3|icl|fx,fy,cx,cy]
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
-                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]]
+                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -18,7 +18,9 @@ implies the map) and reports the residuals of the log against map and trajectory
 --undistort takes the folder's frames as RAW ones of a camera with radial-tangential lens distortion and undoes it on the GPU ahead of the
 detector (vslam_rgbd_set_undistortion: image bilinear, depth nearest, one map for both — the depth images are registered to the colour
 camera); without a value the coefficients are io_formats.TUM_DISTORTION[--intrinsics].  The output camera is --intrinsics' pinhole
-camera at the raw size; trajectory, map and observations are then in undistorted coordinates.  Device-resident loop only."""
+camera at the raw size; trajectory, map and observations are then in undistorted coordinates.  Device-resident loop only.
+--equalize (or -eh, the reference's spelling) equalises the intensity image's histogram on the GPU (cv::equalizeHist; the depth image is
+untouched), behind --undistort and ahead of the detector: dim or low-contrast sequences.  Device-resident loop only."""
 import argparse
 import os
 import sys
@@ -97,7 +99,7 @@ def distortion_of(undistort, intrinsics):
 
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
-        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None):
+        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False):
     seq = io_formats.TumRgbdSequence(folder)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
@@ -115,7 +117,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
         log("--undistort: all distortion coefficients are zero, there is nothing to undo")
         dist = None
     tr = RgbdTracker(api, cfg, p, device)
-    poses, flags = [], 0
+    poses, flags, tracking = [], 0, 0
     want_map = bool(map_path or obs_path)        # the log's ids are the map's
     lm_map = obs = None
     t0 = time.perf_counter()
@@ -126,6 +128,9 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             tr.set_undistortion(und)
             log("undistorting on the GPU: %dx%d, k1 %g k2 %g p1 %g p2 %g k3 %g, %.1f %% of the pixels have a source inside the raw frame" % (
                 (und.rows, und.cols) + tuple(dist) + (100.0 * float(np.mean(rectify.remap_nearest_u16(np.ones((und.raw_rows, und.raw_cols), np.uint16), und.map_xy, und.map_a))),)))
+        if equalize:
+            tr.set_equalization(True)
+            log("equalising histograms on the GPU (cv::equalizeHist on every intensity image%s)" % (", behind the undistortion" if dist is not None else ""))
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
         if obs_path:
@@ -136,6 +141,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             fi, n_temp = tr.process(gray, depth)
             poses.append(np.array(fi.camera_left_to_world))
             flags |= fi.error_flags
+            tracking += int(fi.status == 1)
             if k % 100 == 99 or k == n - 1:
                 log("frame %6d  status %s  points %5d (+%d temporary)  tracked %5d  inliers %5d  landmarks %5d" % (
                     k, "tracking" if fi.status == 1 else "localizing", fi.n_points, n_temp, fi.n_tracked, fi.n_inliers, fi.n_active_landmarks))
@@ -148,7 +154,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     dt = time.perf_counter() - t0
     poses = np.array(poses).reshape(-1, 3, 4)
     log("%d frames in %.2f s (%.1f frames/s incl. PNG decode and upload), error flags %d" % (n, dt, n / dt, flags))
-    result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses, "times": seq.times[:n]}
+    result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses, "times": seq.times[:n], "tracking_frames": tracking}
     if want_map:
         if flags & 8:
             log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
@@ -208,6 +214,8 @@ def parse_args(argv=None):
                     "coordinates) to this .npz bundle (io_formats.read_bundle_rgbd); implies the map")
     ap.add_argument("--undistort", nargs="?", const="", default=None, metavar="k1,k2,p1,p2[,k3]", help="the frames are raw: undo this radial-tangential "
                     "lens distortion on the GPU ahead of the detector; without a value: the coefficients that belong to a named --intrinsics")
+    ap.add_argument("--equalize", "-eh", action="store_true", help="equalise every intensity image's histogram on the GPU ahead of the detector "
+                    "(the reference's -equalize-histogram / -eh): dim or low-contrast sequences")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):          # "--undistort -0.28,0.07,0,0": argparse would read the negative list as an option
         if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
@@ -219,7 +227,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
-        map_path=a.map, obs_path=a.observations, undistort=a.undistort)
+        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize)
 
 
 if __name__ == "__main__":

@@ -252,6 +252,24 @@ class CApi(object):
         self.check(self.fn("get_rectified_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
         return L, R
 
+    # -- histogram equalisation of the input pair (vslam_set_equalization) ------------------------------------------------
+    def set_equalization(self, on=True):
+        self.check(self.fn("set_equalization")(self.ctx, C.c_int(1 if on else 0)))
+
+    def equalized_images(self, stream=0):
+        """The equalised pair the last submitted frame of `stream` was processed on."""
+        rows, cols = int(self.cfg.rows), int(self.cfg.cols)
+        L = np.zeros((rows, cols), np.uint8)
+        R = np.zeros((rows, cols), np.uint8)
+        self.check(self.fn("get_equalized_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
+        return L, R
+
+    def equalization_histograms(self, stream=0):
+        """uint32 [2, 256]: the counts of the left and right image of the last submitted frame of `stream`."""
+        h = np.zeros((2, 256), np.uint32)
+        self.check(self.fn("get_equalization_histograms")(self.ctx, C.c_int(stream), _p(h, C.c_uint32)))
+        return h
+
     # -- readback -----------------------------------------------------------------------------
     def frame_info(self, stream=0):
         fi = FrameInfo()
@@ -642,6 +660,20 @@ class CApi(object):
                                                C.c_int32(img.shape[1]), _p(dst, C.c_uint8), C.c_int32(dst.shape[0]), C.c_int32(dst.shape[1])))
         return dst
 
+    def equalize_hist_u8(self, image):
+        """vslam_equalize_hist_u8: image is a 2-D uint8 array or view with unit column stride (its row stride and alignment are passed
+        on as they are) -> (dst, hist256)."""
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 2 or (img.shape[1] > 1 and img.strides[1] != 1) or (img.shape[0] > 1 and img.strides[0] < img.shape[1]):
+            img = np.ascontiguousarray(image, np.uint8)
+        rows, cols = img.shape
+        stride = img.strides[0] if rows > 1 else max(cols, 1)
+        dst = np.zeros((rows, cols), np.uint8)
+        hist = np.zeros(256, np.uint32)
+        self.check(self.fn("equalize_hist_u8")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(cols), C.c_int32(stride),
+                                               _p(dst, C.c_uint8), _p(hist, C.c_uint32)))
+        return dst, hist
+
     def remap_u8(self, image, map_xy, map_a, cols=None):
         """vslam_remap_u8: image is rows x stride (cols <= stride bytes used), the maps give the output size."""
         img = np.ascontiguousarray(image, np.uint8)
@@ -840,7 +872,20 @@ class _RgbdUndistortApi(object):
         return img, dep
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi):
+class _RgbdEqualizeApi(object):
+    """vslam_rgbd_set_equalization / _get_equalized (the device-resident loop only), shared by RgbdTracker and RgbdBatch."""
+
+    def set_equalization(self, on=True):
+        self._check(self.lib.vslam_rgbd_set_equalization(self.h, C.c_int(1 if on else 0)))
+
+    def equalized(self, stream=0):
+        """The equalised intensity image the last finished frame of `stream` was processed on."""
+        img = np.zeros((int(self.cfg.rows), int(self.cfg.cols)), np.uint8)
+        self._check(self.lib.vslam_rgbd_get_equalized(self.h, C.c_int32(stream), _p(img, C.c_uint8)))
+        return img
+
+
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -897,7 +942,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi):
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

@@ -80,6 +80,13 @@ struct vslam_ctx {
                 uint8_t* raw[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
                 const uint8_t* src[2] = {nullptr, nullptr}; int32_t src_row_stride = 0; size_t src_stream_stride = 0;   // this step's raw input
                 DeviceStore mem; } rect;
+  // histogram equalisation of the input pair (vslam_set_equalization, kernels_equalize.h): the count table [stream][side][256], zeroed and
+  // refilled every frame, and where the pair the last frame was processed on lies (out*: inside upload[last_set]).  keep[left/right]: with
+  // rectification on as well, k_rectify writes here and the equalised pair goes to upload[parity], so that vslam_get_rectified_images
+  // still returns the rectified pair; one pair suffices, its only readers are the same frame's two kernels on the same queue and a getter.
+  struct Eq { bool on = false, have_frame = false; uint32_t* hist = nullptr; uint8_t* keep[2] = {nullptr, nullptr};
+              const uint8_t* out[2] = {nullptr, nullptr}; int32_t out_row_stride = 0; size_t out_stream_stride = 0;
+              DeviceStore mem, keep_mem; } eq;
   // the landmark map (vslam_enable_map, kernels_map.h): off while cap == 0; its own allocations, freed by vslam_enable_map(0) and destroy
   struct MapStore { int32_t cap = 0; DevMap d{}; DeviceStore mem; } map;
   // the observation log on top of it (vslam_enable_observations, kernels_obs.h): off while cap == 0; freed by vslam_enable_observations(0),
@@ -490,6 +497,23 @@ static void rect_free(vslam_ctx* c) {
   c->rect.mem.release();
   c->rect = vslam_ctx::Rect();
 }
+static void eq_free(vslam_ctx* c) {
+  c->eq.mem.release();
+  c->eq.keep_mem.release();
+  c->eq = vslam_ctx::Eq();
+}
+// the rectified pair's own slabs exist exactly while rectification and equalisation are both on (called by both setters, queues idle)
+static hipError_t eq_keep_sync(vslam_ctx* c) {
+  vslam_ctx::Eq& q = c->eq;
+  const bool want = q.on && c->rect.on;
+  if (want == (q.keep[0] != nullptr)) return hipSuccess;
+  q.keep_mem.release();
+  q.keep[0] = q.keep[1] = nullptr;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && want && e == hipSuccess; ++k) e = q.keep_mem.alloc(&q.keep[k], (size_t)c->B * c->up_stream_stride);
+  if (e != hipSuccess) { q.keep_mem.release(); q.keep[0] = q.keep[1] = nullptr; }
+  return e;
+}
 static void obs_free(vslam_ctx* c) {
   c->obs.mem.release();
   c->obs.d = DevObs{};
@@ -514,6 +538,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
   rect_free(c);
+  eq_free(c);
   map_free(c);
   obs_free(c);
   tmp_free(c);

@@ -890,3 +890,27 @@ VS_API int vslam_stereo_recover(vslam_ctx* c, const uint8_t* imgL, const uint8_t
   scratch_put(c, t);
   return rc;
 }
+
+// ---- cv::equalizeHist on one host image (kernels_equalize.h) --------------------------------------------------------
+VS_API int vslam_equalize_hist_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, uint8_t* dst, uint32_t* hist256) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 0 || cols < 0) return fail(c, VSLAM_ERR_INVALID, "equalize_hist: negative size");
+  if (rows == 0 || cols == 0) return VSLAM_OK;
+  if (!src || !dst || row_stride < cols) return fail(c, VSLAM_ERR_INVALID, "equalize_hist: bad argument");
+  if ((size_t)rows * (size_t)cols > (size_t)VS_EQ_MAX_PIXELS) return fail(c, VSLAM_ERR_INVALID, "equalize_hist: more than 2^24 pixels");
+  Call k(c, c->stream);
+  const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
+  const size_t off = (size_t)((uintptr_t)src & 15u);       // the device copy keeps the caller's alignment: rows start where they would in place
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16);
+  k.up_to(ds + off, src, bytes);
+  const int ostride = (cols + 15) & ~15;
+  uint8_t* dd = k.dev<uint8_t>((size_t)rows * ostride);
+  EqArgs ea;
+  std::memset(&ea, 0, sizeof ea);
+  ea.src[0] = ds + off; ea.src_row_stride = row_stride; ea.dst[0] = dd; ea.dst_row_stride = ostride;
+  ea.hist = k.dev<uint32_t>(256); ea.rows = rows; ea.cols = cols; ea.n = 1; ea.sides = 1; ea.active[0] = 1u;
+  if (k.ok()) k.note(equalize_enqueue(c->stream, ea));
+  if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)cols, dd, (size_t)ostride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  if (hist256) k.down(hist256, ea.hist, 256);
+  return k.finish();
+}

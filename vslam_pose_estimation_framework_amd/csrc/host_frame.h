@@ -1,6 +1,6 @@
 // host_frame.h — one frame on a context: where its input images come from (device pointers, host uploads through pinned staging, raw
 // pairs of a rectifying context), the image pipeline and the frame's launch sequence, the fused entries vslam_process_*, and the
-// rectification switch.  Host code, included by vslam_hip.hip after host_ctx.h.
+// rectification and equalisation switches.  Host code, included by vslam_hip.hip after host_ctx.h.
 #pragma once
 
 // ---- launches ------------------------------------------------------------------------------------
@@ -19,7 +19,6 @@ static int launch_image_pipeline(vslam_ctx* c) {
   const int set = c->parity;
   const int n = c->B;
   hipStream_t st = c->img_override ? c->img_override : c->stream_img;
-  const DevBuf bs = buf_set(c, set, c->img_override ? c->q0_frm : c->q0_img);
   if (!c->img_override && c->img_on_frm_queue) {
     // the last frame's image pipeline ran on the frame queue (stage path) and left no event behind: a caller that switches to
     // the fused path mid-sequence pays one synchronisation here, once
@@ -35,13 +34,32 @@ static int launch_image_pipeline(vslam_ctx* c) {
     // raw pair -> rectified pair in upload[set] (the slab the wait above has freed), ahead of the detector
     const vslam_ctx::Rect& q = c->rect;
     RectArgs ra;
-    for (int k = 0; k < 2; ++k) { ra.src[k] = q.src[k]; ra.map_xy[k] = q.map_xy[k]; ra.map_a[k] = q.map_a[k]; ra.dst[k] = c->upload[set][k]; }
+    // (with equalisation on as well: in slabs of its own, the equalised pair goes to upload[set])
+    for (int k = 0; k < 2; ++k) { ra.src[k] = q.src[k]; ra.map_xy[k] = q.map_xy[k]; ra.map_a[k] = q.map_a[k]; ra.dst[k] = c->eq.keep[0] ? c->eq.keep[k] : c->upload[set][k]; }
     ra.src_stream_stride = q.src_stream_stride; ra.src_row_stride = q.src_row_stride; ra.src_rows = q.raw_rows; ra.src_cols = q.raw_cols;
     ra.map_stride = q.map_stride; ra.dst_stream_stride = c->up_stream_stride; ra.dst_row_stride = c->up_stride;
     ra.rows = d.c.rows; ra.cols = d.c.cols; ra.s0 = 0; ra.n = n; ra.sides = 2;
     std::memcpy(ra.active, c->buf.active, sizeof ra.active);
     hipLaunchKernelGGL(k_rectify, dim3((d.c.cols + 255) / 256, (d.c.rows + 3) / 4, 2 * ((n + VS_RECT_SB - 1) / VS_RECT_SB)), dim3(256), 0, st, ra);
   }
+  if (c->eq.on) {
+    // equalised pair in upload[set]: in place when the input is already there (host upload), written there from the rectified pair's own
+    // slabs or from the caller's device images, which these two kernels alone read; everything downstream reads upload[set]
+    vslam_ctx::Eq& q = c->eq;
+    const bool in_place = !c->rect.on && c->buf.img[0] == c->upload[set][0];
+    EqArgs ea;
+    for (int k = 0; k < 2; ++k) { ea.src[k] = c->rect.on ? q.keep[k] : c->buf.img[k]; ea.dst[k] = c->upload[set][k]; }
+    ea.src_row_stride = c->rect.on ? c->up_stride : c->buf.img_row_stride;
+    ea.src_stream_stride = c->rect.on ? c->up_stream_stride : c->buf.img_stream_stride;
+    ea.dst_row_stride = in_place ? c->buf.img_row_stride : c->up_stride;
+    ea.dst_stream_stride = in_place ? c->buf.img_stream_stride : c->up_stream_stride;
+    ea.hist = q.hist; ea.rows = d.c.rows; ea.cols = d.c.cols; ea.n = n; ea.sides = 2;
+    std::memcpy(ea.active, c->buf.active, sizeof ea.active);
+    HIP_TRY(c, equalize_enqueue(st, ea));
+    c->buf.img[0] = ea.dst[0]; c->buf.img[1] = ea.dst[1]; c->buf.img_row_stride = ea.dst_row_stride; c->buf.img_stream_stride = ea.dst_stream_stride;
+    q.out[0] = ea.dst[0]; q.out[1] = ea.dst[1]; q.out_row_stride = ea.dst_row_stride; q.out_stream_stride = ea.dst_stream_stride;
+  }
+  const DevBuf bs = buf_set(c, set, c->img_override ? c->q0_frm : c->q0_img);
   dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * n);
   const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -72,6 +90,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
   if (st != c->stream) { HIP_TRY(c, hipEventRecord(c->ev_img[set], st)); HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_img[set], 0)); }
   c->last_set = set;
   if (c->rect.on) c->rect.have_frame = true;
+  if (c->eq.on) c->eq.have_frame = true;
   return VSLAM_OK;
 }
 static int frame_done(vslam_ctx* c) {
@@ -269,7 +288,7 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the old maps and raw slabs
   rect_free(c);
-  if (off) return VSLAM_OK;
+  if (off) { (void)eq_keep_sync(c); return VSLAM_OK; }
   vslam_ctx::Rect& q = c->rect;
   q.raw_rows = raw_rows; q.raw_cols = raw_cols;
   q.raw_stride = (raw_cols + 63) & ~63;
@@ -290,6 +309,8 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   }
   if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
   q.on = true;
+  e = eq_keep_sync(c);
+  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
   return VSLAM_OK;
 }
 VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, const int16_t* map_xy,
@@ -337,8 +358,26 @@ VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_
   if (!c->rect.on || !c->rect.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_rectified_images: no frame has been rectified since vslam_set_rectification");
   const int rows = c->cfg.c.rows, cols = c->cfg.c.cols;
   for (int k = 0; k < 2; ++k)
-    HIP_TRY(c, hipMemcpy2D(k ? right : left, cols, c->upload[c->last_set][k] + (size_t)s * c->up_stream_stride, c->up_stride, cols, rows,
-                           hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy2D(k ? right : left, cols, (c->eq.keep[0] ? c->eq.keep[k] : c->upload[c->last_set][k]) + (size_t)s * c->up_stream_stride,
+                           c->up_stride, cols, rows, hipMemcpyDeviceToHost));
+  return VSLAM_OK;
+}
+
+// ---- histogram equalisation of the input pair (kernels_equalize.h) -------------------------------
+VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_equalization called inside a frame");
+  if ((size_t)c->cfg.c.rows * c->cfg.c.cols > (size_t)VS_EQ_MAX_PIXELS) return fail(c, VSLAM_ERR_INVALID, "vslam_set_equalization: more than 2^24 pixels per image");
+  if ((on != 0) == c->eq.on) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the table and the slabs
+  eq_free(c);
+  if (!on) return VSLAM_OK;
+  hipError_t e = c->eq.mem.alloc(&c->eq.hist, (size_t)c->B * 2 * 256);
+  if (e == hipSuccess) e = hipMemset(c->eq.hist, 0, (size_t)c->B * 2 * 256 * sizeof(uint32_t));
+  c->eq.on = e == hipSuccess;
+  if (e == hipSuccess) e = eq_keep_sync(c);
+  if (e != hipSuccess) { eq_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_equalization: ") + hipGetErrorString(e)); }
   return VSLAM_OK;
 }
 

@@ -171,3 +171,16 @@ VS_API int vslam_rgbd_get_undistorted(vslam_rgbd* r, int32_t stream, uint8_t* im
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_undistort_host_refusal(r, "vslam_rgbd_get_undistorted") : r->d.get_undistorted(stream, image, depth);
 }
+// ---- histogram equalisation of the intensity image (kernels_equalize.h): the device-resident loop only ----
+static int rgbd_equalize_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) does not equalise; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_equalization(vslam_rgbd* r, int on) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_set_equalization") : r->d.set_equalization(on);
+}
+VS_API int vslam_rgbd_get_equalized(vslam_rgbd* r, int32_t stream, uint8_t* image) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_equalized") : r->d.get_equalized(stream, image);
+}

@@ -116,6 +116,7 @@ public:
     }
     failed = false; failed_why.clear(); pending = false;
     und.have_frame = false;                                                  // the maps stay (like the rig of a rectifying context)
+    eq.have_frame = false;                                                   // and so does the equalisation switch
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
     return VSLAM_OK;
   }
@@ -272,6 +273,41 @@ public:
     return VSLAM_OK;
   }
 
+  // ---- histogram equalisation of the intensity image (kernels_equalize.h): opt-in, its own allocations, nothing launched while eq.on is
+  // false.  The depth image is untouched.  In place in the image the detector reads (the staged copy of a host frame, the undistorted
+  // image); a caller's device image without undistortion is equalised into eq.img, so that caller memory is never written.
+  int set_equalization(int on) {
+    if (pending) { err = "vslam_rgbd_set_equalization: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if ((size_t)p.rows * p.cols > (size_t)VS_EQ_MAX_PIXELS) { err = "vslam_rgbd_set_equalization: more than 2^24 pixels per image"; return VSLAM_ERR_INVALID; }
+    if ((on != 0) == eq.on) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    (void)hipStreamSynchronize(q2);
+    eq_free();
+    drop_graph();                                   // a captured launch sequence holds the two kernels (or lacks them)
+    if (!on) return VSLAM_OK;
+    Equal u{};
+    u.img_stride = (p.cols + 15) & ~15;
+    u.img_stream = (size_t)p.rows * u.img_stride;
+    hipError_t e = eq_mem.alloc(&u.hist, (size_t)B * 256);
+    if (e == hipSuccess) e = eq_mem.alloc(&u.img, u.img_stream * (size_t)B);
+    if (e == hipSuccess) e = hipMemset(u.hist, 0, (size_t)B * 256 * sizeof(uint32_t));
+    if (e != hipSuccess) { eq_free(); err = std::string("vslam_rgbd_set_equalization: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    u.on = true;
+    eq = u;
+    return VSLAM_OK;
+  }
+  // the equalised image the last finished frame of `stream` was processed on (dense)
+  int get_equalized(int stream, uint8_t* image) {
+    if (int rc = readable(stream)) return rc;
+    if (!eq.on || !eq.have_frame) { err = "vslam_rgbd_get_equalized: no frame has been equalised since vslam_rgbd_set_equalization / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    if (!image) { err = "vslam_rgbd_get_equalized: null output"; return VSLAM_ERR_INVALID; }
+    (void)hipSetDevice(ic->device);
+    const hipError_t e = hipMemcpy2D(image, (size_t)p.cols, eq.out + (size_t)stream * eq.out_stream, (size_t)eq.out_stride, (size_t)p.cols, (size_t)p.rows, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    return VSLAM_OK;
+  }
+
   int process(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t left_stream_stride = 0, size_t depth_stream_stride = 0) {
     const int rc = submit(left, lstride, depth, dstride, left_stream_stride, depth_stream_stride);
     return rc != VSLAM_OK ? rc : wait();
@@ -299,7 +335,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else und.have_frame = und.on;
+    else { und.have_frame = und.on; eq.have_frame = eq.on; }
     return rc;
   }
 
@@ -375,6 +411,15 @@ private:
     int16_t* map_xy; uint16_t* map_a; uint8_t* img; uint16_t* raw_depth;
   } und{};
   DeviceStore und_mem;
+  // equalisation of the intensity image: off while eq.on is false.  The count table [B][256], the image a caller's device frame is
+  // equalised into, and this frame's source (src*) and result (out*: what the image pipeline reads)
+  struct Equal {
+    bool on, have_frame;
+    uint32_t* hist; uint8_t* img; int32_t img_stride; size_t img_stream;
+    const uint8_t* src; int32_t src_stride; size_t src_stream;
+    uint8_t* out; int32_t out_stride; size_t out_stream;
+  } eq{};
+  DeviceStore eq_mem;
   const uint8_t* raw_img = nullptr; int32_t raw_img_stride = 0; size_t raw_img_stream = 0;
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
@@ -382,6 +427,18 @@ private:
   void obs_free() {
     obs_mem.release();
     mp.log = nullptr; mp.ocount = nullptr; mp.ocap = 0;
+  }
+  void eq_free() {
+    eq_mem.release();
+    eq = Equal{};
+  }
+  // this frame's image bs points at becomes the equalisation's source; bs is pointed at its result.  own: the image is ours to overwrite
+  void eq_route(bool own) {
+    if (!eq.on) return;
+    eq.src = bs.img[0]; eq.src_stride = bs.img_row_stride; eq.src_stream = bs.img_stream_stride;
+    if (own) { eq.out = const_cast<uint8_t*>(eq.src); eq.out_stride = eq.src_stride; eq.out_stream = eq.src_stream; }
+    else { eq.out = eq.img; eq.out_stride = eq.img_stride; eq.out_stream = eq.img_stream; }
+    bs.img[0] = eq.out; bs.img[1] = eq.out; bs.img_row_stride = eq.out_stride; bs.img_stream_stride = eq.out_stream;
   }
   void und_free() {
     und_mem.release();
@@ -414,6 +471,7 @@ private:
     drop_graph();
     map_free();
     und_free();
+    eq_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (q2) { (void)hipStreamDestroy(q2); q2 = nullptr; }
     if (ev_depth) { (void)hipEventDestroy(ev_depth); ev_depth = nullptr; }
@@ -482,6 +540,7 @@ private:
         bs.img[0] = left; bs.img[1] = left; bs.img_row_stride = lstride; bs.img_stream_stride = lss;
         depth_src = depth; depth_src_stride = dstride;
       }
+      eq_route(und.on);
       all_active(bs);
       enqueue_first_attempt(false);
       hipError_t e = hipGetLastError();
@@ -529,6 +588,7 @@ private:
     } else {
       bs.img[0] = d_img; bs.img[1] = d_img; bs.img_row_stride = lstride; bs.img_stream_stride = img_stream;
     }
+    eq_route(true);
     all_active(bs);
     if (use_graph && (!graph_exec || graph_stride != lstride || graph_img != d_img)) capture_graph(lstride);
     if (use_graph && graph_exec) {
@@ -584,6 +644,15 @@ private:
       hipLaunchKernelGGL(k_rectify, undistort_grid(rows, cols, B), dim3(256), 0, q,
                          undistort_image_args(raw_img, raw_img_stream, raw_img_stride, und.raw_rows, und.raw_cols, und.map_xy, und.map_a, und.map_stride, und.img,
                                               und.img_stream, und.img_stride, rows, cols, B));
+    // the image equalised, behind the undistortion and ahead of the detector, once per frame like it
+    if (eq.on) {
+      EqArgs ea{};
+      ea.src[0] = eq.src; ea.src_row_stride = eq.src_stride; ea.src_stream_stride = eq.src_stream;
+      ea.dst[0] = eq.out; ea.dst_row_stride = eq.out_stride; ea.dst_stream_stride = eq.out_stream;
+      ea.hist = eq.hist; ea.rows = rows; ea.cols = cols; ea.n = B; ea.sides = 1;
+      std::memcpy(ea.active, bs.active, sizeof ea.active);
+      (void)equalize_enqueue(q, ea);
+    }
     enqueue_attempt(bs);
     enqueue_tail(bs);
   }

@@ -17,6 +17,7 @@
 #include "kernels_report.h"
 #include "kernels_rectify.h"
 #include "kernels_undistort.h"
+#include "kernels_equalize.h"
 #include "kernels_map.h"
 #include "kernels_obs.h"
 
