@@ -245,6 +245,36 @@ int vslam_get_equalized_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_
 int vslam_get_equalization_histograms(vslam_ctx* ctx, int stream, uint32_t* hist512);
 int vslam_equalize_hist_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride,
                            uint8_t* dst /* dense */, uint32_t* hist256 /* may be NULL */);
+/* ---- colour input: interleaved 8-bit colour to grey ahead of everything else (opt-in; csrc/kernels_gray.h) -------------
+ * The reference converts a colour frame itself before anything else happens to it (slam_assembly.cpp:392-399, cvtColor CV_BGR2GRAY).
+ * One definition, cvtColor on 8-bit images with 14 fractional bits [recalled], all integer:
+ *   gray = (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14;  alpha is ignored.
+ * (Newer OpenCV uses 15 bits, 9798 / 19235 / 3735, and differs on 0.26 % of all colour triples: not built.)
+ * Order: colour -> grey -> rectify (when set) -> equalise (when set) -> detect.  One kernel (k_gray_u8) per frame at the head of the image
+ * pipeline, on its queue, under the fused entries and the stage path alike.
+ * vslam_set_color_input: while format is not VSLAM_PIXEL_GRAY8, vslam_process_host, vslam_process_device and vslam_frame_begin take
+ *   interleaved colour images of the size the context otherwise expects (raw_rows x raw_cols while rectification is set, else rows x
+ *   cols); row_stride and image_stride are in BYTES, row_stride >= channels * cols (else VSLAM_ERR_INVALID).  Host images are copied to
+ *   colour slabs of the context's own; device images are READ by this kernel only and never written.  The grey pair is written where the
+ *   next stage reads.  A switched-off stream is neither read nor written.  Synchronises the context; VSLAM_ERR_STATE between
+ *   vslam_frame_begin and the end of that frame; VSLAM_ERR_INVALID for a format outside 0 .. 4.  The switch survives vslam_reset and
+ *   vslam_reset_stream(s).  GRAY8 turns it off and frees its allocations; nothing is launched while off.
+ * vslam_get_gray_images: the grey pair of the last submitted frame of `stream` at the input size (raw_rows x raw_cols while rectification
+ *   is set, else rows x cols; dense); VSLAM_ERR_STATE when the switch is off or no frame has been submitted since it was set.
+ *   Synchronises.  With equalisation on and rectification off the pair is equalised in place afterwards: this getter then returns the
+ *   equalised pair, like vslam_get_equalized_images.
+ * vslam_gray_u8: the kernel stand-alone on one host image: src is rows x cols pixels with row_stride BYTES per row (any alignment), dst is
+ *   dense.  rows or cols 0: VSLAM_OK, nothing written.  VSLAM_ERR_INVALID: null src / dst, negative size, row_stride < channels * cols,
+ *   format outside 1 .. 4; the context stays usable. */
+#define VSLAM_PIXEL_GRAY8 0
+#define VSLAM_PIXEL_BGR8 1   /* a cv::Mat CV_8UC3 */
+#define VSLAM_PIXEL_RGB8 2   /* a decoded PNG, ROS rgb8 */
+#define VSLAM_PIXEL_BGRA8 3
+#define VSLAM_PIXEL_RGBA8 4
+int vslam_set_color_input(vslam_ctx* ctx, int format);
+int vslam_get_gray_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
+int vslam_gray_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride_bytes, int format,
+                  uint8_t* dst /* dense */);
 /* Block until all queued work of the context is done; returns the sticky HIP error state (VSLAM_ERR_HIP once a runtime
  * call has failed, else VSLAM_OK; capacity overflows are reported in vslam_frame_info.error_flags, see VSLAM_ERR_CAPACITY). */
 int vslam_synchronize(vslam_ctx* ctx);
@@ -742,6 +772,19 @@ int vslam_rgbd_get_undistorted(vslam_rgbd* t, int32_t stream, uint8_t* image, ui
  *   when off, before a frame, or with a frame in flight. */
 int vslam_rgbd_set_equalization(vslam_rgbd* t, int on);
 int vslam_rgbd_get_equalized(vslam_rgbd* t, int32_t stream, uint8_t* image);
+/* Colour input in this mode (opt-in; the definition and the VSLAM_PIXEL_* formats above vslam_set_color_input): while the format is not
+ * VSLAM_PIXEL_GRAY8 the intensity image of every process / submit / batch entry, host or device, is interleaved colour at the size the
+ * tracker otherwise expects; its row and stream strides are in BYTES (row stride >= channels * cols).  The depth image is untouched.
+ * k_gray_u8 runs on the image queue ahead of the undistortion, the equalisation and the detector, once per frame (further registration
+ * attempts read the grey image again), inside the captured launch sequence as well.  A caller's device image is read only.  The switch
+ * survives vslam_rgbd_reset.
+ * vslam_rgbd_set_color_input: VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB),
+ *   which does not have the feature; VSLAM_ERR_INVALID for a format outside 0 .. 4.
+ * vslam_rgbd_get_gray: the grey image (dense, at the input size: the raw size while undistortion maps are set) of the last finished
+ *   frame of `stream`; VSLAM_ERR_STATE when off, before a frame, after vslam_rgbd_reset, or with a frame in flight.  With equalisation on
+ *   and undistortion off the image is equalised in place afterwards, and this getter returns it so. */
+int vslam_rgbd_set_color_input(vslam_rgbd* t, int format);
+int vslam_rgbd_get_gray(vslam_rgbd* t, int32_t stream, uint8_t* image);
 int vslam_remap_nearest_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride,
                             const int16_t* map_xy, const uint16_t* map_a, int32_t dst_rows, int32_t dst_cols, uint16_t* dst);
 

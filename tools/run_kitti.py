@@ -9,6 +9,8 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
     python tools/run_kitti.py <EuRoC dir> --rectify --format tum --out traj.txt   raw images: rectified on the GPU from mav0/cam{0,1}/sensor.yaml
     python tools/run_kitti.py <sequence dir> --equalize   (or -eh, the reference's spelling) cv::equalizeHist on every image, on the GPU,
                               behind --rectify and ahead of the detector: dim, low-contrast sequences; also with --chunks, --map, --observations
+    python tools/run_kitti.py <sequence dir with image_2/ image_3/> --color   the odometry benchmark's colour cameras with their own calibration
+                              (P2 / P3 of calib.txt); the RGB frames are converted to grey on the GPU; also with --chunks, --equalize, --map, --observations
     python tools/run_kitti.py <sequence dir> --map map.ply   the landmark map as well (binary PLY: x y z id first_frame last_frame updates)
     python tools/run_kitti.py <sequence dir> --observations bundle.npz   trajectory + landmark map + which landmark was seen in which
                               frame at which pixels, in one file (io_formats.read_bundle); implies the map; also with --chunks
@@ -26,13 +28,13 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from vslam_pose_estimation_framework_amd import evaluation, hip, io_formats  # noqa: E402
+from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, hip, io_formats  # noqa: E402
 
 
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
 
 
-def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False):
+def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -45,12 +47,14 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
         api.set_rectification(rect)
     if equalize:
         api.set_equalization(True)
+    if color:
+        api.set_color_input(color_mod.RGB8)
     if want_map:
         api.enable_map(MAP_ENTRIES_PER_FRAME * steps)
     if want_obs:
         api.enable_observations(steps * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
     rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
-    Lb = np.zeros((len(plan), rows, cols), np.uint8)
+    Lb = np.zeros((len(plan), rows, cols) + ((3,) if color else ()), np.uint8)
     Rb = np.zeros_like(Lb)
     live = [True] * len(plan)
     for k in range(steps):
@@ -75,11 +79,15 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False):
+        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False):
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
+    if color and euroc:
+        raise SystemExit("--color: an ASL / EuRoC folder holds grey images (it takes a KITTI odometry folder with image_2/ and image_3/)")
+    if color and not os.path.isdir(os.path.join(seq_dir, "image_2")):
+        raise SystemExit("--color: no image_2/ and image_3/ under %s" % seq_dir)
     if rectify and not euroc:
         raise SystemExit("--rectify: a KITTI odometry folder is already rectified (it takes raw EuRoC / ASL folders with sensor.yaml)")
-    seq = io_formats.EurocSequence(seq_dir) if euroc else io_formats.KittiSequence(seq_dir)
+    seq = io_formats.EurocSequence(seq_dir) if euroc else io_formats.KittiSequence(seq_dir, color=color)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
         raise SystemExit("no images under %s" % seq_dir)
@@ -112,6 +120,8 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
                 log("note: sensor.yaml describes distorted raw cameras and there is no calib.txt; --rectify rectifies them on the GPU")
     else:
         io_formats.apply_calib(cfg, seq.K, seq.baseline, left.shape[0], left.shape[1])
+    if color:
+        log("colour cameras (image_2 / image_3, calibration P2 / P3): RGB -> grey on the GPU, ahead of %s" % ("the equalisation" if equalize else "the detector"))
     if equalize:
         log("equalising histograms on the GPU (cv::equalizeHist on every image%s)" % (", behind the rectification" if rect is not None else ""))
     t0 = time.perf_counter()
@@ -121,7 +131,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     obs = None
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
-                                                equalize=equalize)
+                                                equalize=equalize, color=color)
         tracking = None
     else:
         cfg.max_history_frames = 512
@@ -130,6 +140,8 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             api.set_rectification(rect)
         if equalize:
             api.set_equalization(True)
+        if color:
+            api.set_color_input(color_mod.RGB8)
         if want_map:
             api.enable_map(MAP_ENTRIES_PER_FRAME * n)
         if obs_path:
@@ -215,13 +227,15 @@ def parse_args(argv=None):
                     "to this .npz bundle (io_formats.read_bundle); implies the map")
     ap.add_argument("--equalize", "-eh", action="store_true", help="equalise every image's histogram on the GPU ahead of the detector "
                     "(the reference's -equalize-histogram / -eh): dim or low-contrast sequences")
+    ap.add_argument("--color", action="store_true", help="a KITTI odometry folder's colour cameras (image_2 / image_3 with the calibration of P2 / P3); "
+                    "the frames are converted to grey on the GPU")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     a = parse_args(argv)
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
-        rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize)
+        rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
 
     python tools/run_rgbd.py <folder> [--config icl|tum|xtion] [--intrinsics freiburg1|freiburg2|freiburg3|icl|fx,fy,cx,cy]
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
-                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh]
+                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -20,7 +20,9 @@ detector (vslam_rgbd_set_undistortion: image bilinear, depth nearest, one map fo
 camera); without a value the coefficients are io_formats.TUM_DISTORTION[--intrinsics].  The output camera is --intrinsics' pinhole
 camera at the raw size; trajectory, map and observations are then in undistorted coordinates.  Device-resident loop only.
 --equalize (or -eh, the reference's spelling) equalises the intensity image's histogram on the GPU (cv::equalizeHist; the depth image is
-untouched), behind --undistort and ahead of the detector: dim or low-contrast sequences.  Device-resident loop only."""
+untouched), behind --undistort and ahead of the detector: dim or low-contrast sequences.  Device-resident loop only.
+--color hands the colour frames over as decoded and converts them to grey on the GPU (vslam_rgbd_set_color_input: the same integers as the
+host conversion without the flag), ahead of --undistort and --equalize.  Device-resident loop only."""
 import argparse
 import os
 import sys
@@ -31,7 +33,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from vslam_pose_estimation_framework_amd import evaluation, hip, io_formats  # noqa: E402
+from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, hip, io_formats  # noqa: E402
 from vslam_pose_estimation_framework_amd.capi import DepthParams, RgbdTracker  # noqa: E402
 
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per processed frame, as tools/run_kitti.py chooses it
@@ -99,14 +101,18 @@ def distortion_of(undistort, intrinsics):
 
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
-        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False):
+        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False):
     seq = io_formats.TumRgbdSequence(folder)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
         raise SystemExit("no associated rgb / depth pairs under %s" % folder)
     fx, fy, cx, cy = io_formats.TUM_INTRINSICS[intrinsics] if intrinsics in io_formats.TUM_INTRINSICS else [float(v) for v in intrinsics.split(",")]
     K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
-    gray, depth = seq.frame(0)
+    fmt = color_mod.GRAY8
+    if color:
+        gray, fmt, depth = seq.frame_color(0)        # `gray`: the intensity image as it is handed over, [rows, cols, 3 | 4] here
+    else:
+        gray, depth = seq.frame(0)
     api = hip.load()
     cfg, p = configure(api, which, gray.shape[0], gray.shape[1], K, depth_unit, descriptor, detector, depth_scale)
     dist = distortion_of(undistort, intrinsics)
@@ -128,6 +134,11 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             tr.set_undistortion(und)
             log("undistorting on the GPU: %dx%d, k1 %g k2 %g p1 %g p2 %g k3 %g, %.1f %% of the pixels have a source inside the raw frame" % (
                 (und.rows, und.cols) + tuple(dist) + (100.0 * float(np.mean(rectify.remap_nearest_u16(np.ones((und.raw_rows, und.raw_cols), np.uint16), und.map_xy, und.map_a))),)))
+        if fmt != color_mod.GRAY8:
+            tr.set_color_input(fmt)
+            log("colour frames (%s): converted to grey on the GPU, ahead of %s" % (color_mod.NAMES[fmt], "the undistortion" if dist is not None else "the detector"))
+        elif color:
+            log("--color: the folder's images are grey already, nothing to convert")
         if equalize:
             tr.set_equalization(True)
             log("equalising histograms on the GPU (cv::equalizeHist on every intensity image%s)" % (", behind the undistortion" if dist is not None else ""))
@@ -137,7 +148,12 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             tr.enable_observations(n * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
         for k in range(n):
             if k:
-                gray, depth = seq.frame(k)
+                if color:
+                    gray, fmt_k, depth = seq.frame_color(k)
+                    if fmt_k != fmt:
+                        raise SystemExit("--color: frame %d is %s, the sequence began as %s" % (k, color_mod.NAMES[fmt_k], color_mod.NAMES[fmt]))
+                else:
+                    gray, depth = seq.frame(k)
             fi, n_temp = tr.process(gray, depth)
             poses.append(np.array(fi.camera_left_to_world))
             flags |= fi.error_flags
@@ -216,6 +232,8 @@ def parse_args(argv=None):
                     "lens distortion on the GPU ahead of the detector; without a value: the coefficients that belong to a named --intrinsics")
     ap.add_argument("--equalize", "-eh", action="store_true", help="equalise every intensity image's histogram on the GPU ahead of the detector "
                     "(the reference's -equalize-histogram / -eh): dim or low-contrast sequences")
+    ap.add_argument("--color", action="store_true", help="hand the colour frames over as decoded and convert them to grey on the GPU, ahead of "
+                    "--undistort and --equalize (without it: converted on the host, frame by frame)")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):          # "--undistort -0.28,0.07,0,0": argparse would read the negative list as an option
         if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
@@ -227,7 +245,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
-        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize)
+        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,8 @@ package loads the oracle.
 import ctypes as C
 import numpy as np
 
+from . import color as _color
+
 MAX_REGIONS = 16
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_STATE = 0, -1, -2, -3, -4, -5
@@ -173,6 +175,7 @@ class CApi(object):
         self.cfg = cfg.copy()
         self.n_streams = n_streams
         self.rect = None
+        self.color = 0
         return self
 
     def destroy(self):
@@ -208,9 +211,20 @@ class CApi(object):
 
     # -- whole frame --------------------------------------------------------------------------
     def process_host(self, left, right):
-        """left/right: uint8 arrays [n_streams, rows, stride] (C-contiguous)."""
+        """left/right: uint8 arrays [n_streams, rows, stride] (C-contiguous); while a colour format is set (set_color_input):
+        [n_streams, rows, cols, channels]."""
         left = np.ascontiguousarray(left, dtype=np.uint8)
         right = np.ascontiguousarray(right, dtype=np.uint8)
+        ch = _color.channels(getattr(self, "color", 0))
+        if ch > 1:
+            if left.ndim == 3:
+                left, right = left[None], right[None]
+            assert left.ndim == 4 and left.shape[3] == ch, (left.shape, ch)
+            n, rows, cols = left.shape[:3]
+            want = (self.rect.raw_rows, self.rect.raw_cols) if getattr(self, "rect", None) is not None else (self.cfg.rows, self.cfg.cols)
+            assert left.shape == right.shape and n == self.n_streams and (rows, cols) == want, (left.shape, right.shape, want)
+            self.check(self.fn("process_host")(self.ctx, _p(left, C.c_uint8), _p(right, C.c_uint8), C.c_int32(cols * ch), C.c_size_t(rows * cols * ch)))
+            return
         if left.ndim == 2:
             left, right = left[None], right[None]
         assert left.shape == right.shape and left.shape[0] == self.n_streams
@@ -269,6 +283,22 @@ class CApi(object):
         h = np.zeros((2, 256), np.uint32)
         self.check(self.fn("get_equalization_histograms")(self.ctx, C.c_int(stream), _p(h, C.c_uint32)))
         return h
+
+    # -- colour input (vslam_set_color_input) ---------------------------------------------------------------------------
+    def set_color_input(self, fmt):
+        """fmt: color.BGR8 / RGB8 / BGRA8 / RGBA8, or color.GRAY8 to switch it off.  While set, the frame entries take interleaved colour
+        images (process_host: [n_streams, rows, cols, channels]; device entries: strides in bytes)."""
+        self.check(self.fn("set_color_input")(self.ctx, C.c_int(int(fmt))))
+        self.color = int(fmt)
+
+    def gray_images(self, stream=0):
+        """The grey pair the last submitted frame of `stream` was converted to, at the input size (the raw size of a rectifying context)."""
+        rect = getattr(self, "rect", None)
+        rows, cols = (int(rect.raw_rows), int(rect.raw_cols)) if rect is not None else (int(self.cfg.rows), int(self.cfg.cols))
+        L = np.zeros((rows, cols), np.uint8)
+        R = np.zeros((rows, cols), np.uint8)
+        self.check(self.fn("get_gray_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
+        return L, R
 
     # -- readback -----------------------------------------------------------------------------
     def frame_info(self, stream=0):
@@ -674,6 +704,25 @@ class CApi(object):
                                                _p(dst, C.c_uint8), _p(hist, C.c_uint32)))
         return dst, hist
 
+    def gray_u8(self, image, fmt, cols=None):
+        """vslam_gray_u8: image is a uint8 array [rows, cols, channels], or a 2-D array or view [rows, >= channels * cols bytes] with unit
+        column stride whose row stride and alignment are passed on as they are (cols is then required) -> grey [rows, cols]."""
+        img = np.asarray(image)
+        if img.ndim == 3:
+            img = np.ascontiguousarray(img, np.uint8)
+            cols = img.shape[1]
+            img = img.reshape(img.shape[0], -1)
+        elif img.dtype != np.uint8 or img.ndim != 2 or (img.shape[1] > 1 and img.strides[1] != 1) or (img.shape[0] > 1 and img.strides[0] < img.shape[1]):
+            img = np.ascontiguousarray(image, np.uint8)
+        if img.ndim != 2 or cols is None:
+            raise ValueError("gray_u8: a [rows, cols, channels] array, or a [rows, bytes] array together with cols")
+        rows = img.shape[0]
+        stride = img.strides[0] if rows > 1 else max(img.shape[1], 1)
+        dst = np.zeros((max(rows, 0), max(int(cols), 0)), np.uint8)
+        self.check(self.fn("gray_u8")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(int(cols)), C.c_int32(stride), C.c_int(int(fmt)),
+                                      _p(dst, C.c_uint8)))
+        return dst
+
     def remap_u8(self, image, map_xy, map_a, cols=None):
         """vslam_remap_u8: image is rows x stride (cols <= stride bytes used), the maps give the output size."""
         img = np.ascontiguousarray(image, np.uint8)
@@ -857,11 +906,13 @@ class _RgbdUndistortApi(object):
         raw frames of und.raw_rows x und.raw_cols."""
         if und is None:
             self._check(self.lib.vslam_rgbd_set_undistortion(self.h, C.c_int32(0), C.c_int32(0), None, None))
+            self._raw_size = None
             return
         if (und.rows, und.cols) != (self.cfg.rows, self.cfg.cols):
             raise ValueError("set_undistortion: maps are %dx%d, the tracker is %dx%d" % (und.rows, und.cols, self.cfg.rows, self.cfg.cols))
         mxy, ma = np.ascontiguousarray(und.map_xy, np.int16), np.ascontiguousarray(und.map_a, np.uint16)
         self._check(self.lib.vslam_rgbd_set_undistortion(self.h, C.c_int32(und.raw_rows), C.c_int32(und.raw_cols), _p(mxy, C.c_int16), _p(ma, C.c_uint16)))
+        self._raw_size = (int(und.raw_rows), int(und.raw_cols))
 
     def undistorted(self, stream=0):
         """(image, depth) the last finished frame of `stream` was processed on."""
@@ -885,7 +936,27 @@ class _RgbdEqualizeApi(object):
         return img
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
+class _RgbdColorApi(object):
+    """vslam_rgbd_set_color_input / _get_gray (the device-resident loop only), shared by RgbdTracker and RgbdBatch.  While a colour format
+    is set, process / submit take the intensity image as [rows, cols, channels] (a batch: [n_streams, rows, cols, channels])."""
+
+    def set_color_input(self, fmt):
+        self._check(self.lib.vslam_rgbd_set_color_input(self.h, C.c_int(int(fmt))))
+
+    def gray(self, stream=0):
+        """The grey image the last finished frame of `stream` was converted to, at the input size (the raw size while undistorting)."""
+        rows, cols = getattr(self, "_raw_size", None) or (int(self.cfg.rows), int(self.cfg.cols))
+        img = np.zeros((rows, cols), np.uint8)
+        self._check(self.lib.vslam_rgbd_get_gray(self.h, C.c_int32(stream), _p(img, C.c_uint8)))
+        return img
+
+
+def _row_bytes(left, image_ndim):
+    """Row stride in bytes of a C-contiguous image array or batch: its trailing channel axis, when it has one, belongs to the row."""
+    return int(left.shape[-1]) if left.ndim == image_ndim else int(left.shape[-2] * left.shape[-1])
+
+
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -908,7 +979,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
     def process(self, left, depth, cols=None):
         """left / depth: 2-D arrays; cols: image width when the arrays carry padding columns (row stride = array width)."""
         left = np.ascontiguousarray(left, np.uint8); depth = np.ascontiguousarray(depth, np.uint16)
-        self._check(self.lib.vslam_rgbd_process_host(self.h, _p(left, C.c_uint8), C.c_int32(left.shape[1]), _p(depth, C.c_uint16), C.c_int32(depth.shape[1])))
+        self._check(self.lib.vslam_rgbd_process_host(self.h, _p(left, C.c_uint8), C.c_int32(_row_bytes(left, 2)), _p(depth, C.c_uint16), C.c_int32(depth.shape[1])))
         fi = FrameInfo()
         nt = C.c_int32()
         self._check(self.lib.vslam_rgbd_get_frame_info(self.h, C.byref(fi), C.byref(nt)))
@@ -918,7 +989,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
         """First half of process(): copies the frame in and enqueues it.  The arrays are kept alive until wait()."""
         left = np.ascontiguousarray(left, np.uint8); depth = np.ascontiguousarray(depth, np.uint16)
         self._inflight = (left, depth)
-        self._check(self.lib.vslam_rgbd_submit_host(self.h, _p(left, C.c_uint8), C.c_int32(left.shape[1]), _p(depth, C.c_uint16), C.c_int32(depth.shape[1])))
+        self._check(self.lib.vslam_rgbd_submit_host(self.h, _p(left, C.c_uint8), C.c_int32(_row_bytes(left, 2)), _p(depth, C.c_uint16), C.c_int32(depth.shape[1])))
 
     def wait(self):
         self._check(self.lib.vslam_rgbd_wait(self.h))
@@ -942,7 +1013,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):
@@ -967,7 +1038,7 @@ class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi):
         left = np.ascontiguousarray(left, np.uint8); depth = np.ascontiguousarray(depth, np.uint16)
         assert left.shape[0] == self.n and depth.shape[0] == self.n
         self._inflight = (left, depth)
-        self._check(self.lib.vslam_rgbd_submit_batch_host(self.h, _p(left, C.c_uint8), C.c_int32(left.shape[2]), C.c_size_t(left.shape[1] * left.shape[2]),
+        self._check(self.lib.vslam_rgbd_submit_batch_host(self.h, _p(left, C.c_uint8), C.c_int32(_row_bytes(left, 3)), C.c_size_t(left.shape[1] * _row_bytes(left, 3)),
                                                           _p(depth, C.c_uint16), C.c_int32(depth.shape[2]), C.c_size_t(depth.shape[1] * depth.shape[2])))
 
     def submit_device(self, left_ptr, left_row_stride, left_stream_stride, depth_ptr, depth_row_stride, depth_stream_stride):

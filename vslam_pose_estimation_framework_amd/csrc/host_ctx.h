@@ -87,6 +87,15 @@ struct vslam_ctx {
   struct Eq { bool on = false, have_frame = false; uint32_t* hist = nullptr; uint8_t* keep[2] = {nullptr, nullptr};
               const uint8_t* out[2] = {nullptr, nullptr}; int32_t out_row_stride = 0; size_t out_stream_stride = 0;
               DeviceStore mem, keep_mem; } eq;
+  // colour input (vslam_set_color_input, kernels_gray.h): off while format == VSLAM_PIXEL_GRAY8.  slab[step parity][left/right]: what host
+  // colour images are copied into (B x in_rows x stride bytes each, allocated on the first host frame at that input size); src*: this step's
+  // colour pair (a slab or the caller's device memory); out*: where k_gray_u8 writes the grey pair — the rectifier's raw slabs when
+  // rectifying, else upload[parity] — and so where vslam_get_gray_images reads it.
+  struct Col { int format = 0; bool have_frame = false; int slab_rows = 0, slab_cols = 0, stride = 0; size_t stream_stride = 0;
+               uint8_t* slab[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+               const uint8_t* src[2] = {nullptr, nullptr}; int32_t src_row_stride = 0; size_t src_stream_stride = 0;
+               uint8_t* out[2] = {nullptr, nullptr}; int32_t out_row_stride = 0; size_t out_stream_stride = 0; int out_rows = 0, out_cols = 0;
+               DeviceStore mem; } col;
   // the landmark map (vslam_enable_map, kernels_map.h): off while cap == 0; its own allocations, freed by vslam_enable_map(0) and destroy
   struct MapStore { int32_t cap = 0; DevMap d{}; DeviceStore mem; } map;
   // the observation log on top of it (vslam_enable_observations, kernels_obs.h): off while cap == 0; freed by vslam_enable_observations(0),
@@ -514,6 +523,29 @@ static hipError_t eq_keep_sync(vslam_ctx* c) {
   if (e != hipSuccess) { q.keep_mem.release(); q.keep[0] = q.keep[1] = nullptr; }
   return e;
 }
+static void col_free(vslam_ctx* c) {
+  c->col.mem.release();
+  c->col = vslam_ctx::Col();
+}
+// the colour slabs exist while the switch is on, at the size of the frames that come in: the raw size while rectification is set (called by
+// both setters, queues idle)
+static hipError_t col_slab_sync(vslam_ctx* c) {
+  vslam_ctx::Col& q = c->col;
+  const int fmt = q.format;
+  const int rows = c->rect.on ? c->rect.raw_rows : c->cfg.c.rows, cols = c->rect.on ? c->rect.raw_cols : c->cfg.c.cols;
+  const int wb = fmt == 0 ? 0 : (fmt <= 2 ? 3 : 4) * cols;
+  if (fmt != 0 && q.slab[0][0] && q.slab_rows == rows && q.slab_cols == wb) return hipSuccess;
+  col_free(c);
+  q.format = fmt;
+  if (fmt == 0) return hipSuccess;
+  q.slab_rows = rows; q.slab_cols = wb;
+  q.stride = (wb + 63) & ~63;
+  q.stream_stride = (size_t)rows * q.stride;
+  hipError_t e = hipSuccess;
+  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = q.mem.alloc(&q.slab[p][k], (size_t)c->B * q.stream_stride);
+  if (e != hipSuccess) col_free(c);
+  return e;
+}
 static void obs_free(vslam_ctx* c) {
   c->obs.mem.release();
   c->obs.d = DevObs{};
@@ -539,6 +571,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   rect_free(c);
   eq_free(c);
+  col_free(c);
   map_free(c);
   obs_free(c);
   tmp_free(c);

@@ -914,3 +914,27 @@ VS_API int vslam_equalize_hist_u8(vslam_ctx* c, const uint8_t* src, int32_t rows
   if (hist256) k.down(hist256, ea.hist, 256);
   return k.finish();
 }
+
+// ---- interleaved 8-bit colour to grey on one host image (kernels_gray.h) --------------------------------------------
+VS_API int vslam_gray_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int format, uint8_t* dst) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 0 || cols < 0) return fail(c, VSLAM_ERR_INVALID, "gray_u8: negative size");
+  if (format < VSLAM_PIXEL_BGR8 || format > VSLAM_PIXEL_RGBA8) return fail(c, VSLAM_ERR_INVALID, "gray_u8: unknown pixel format");
+  if (rows == 0 || cols == 0) return VSLAM_OK;
+  const int64_t wb = (int64_t)gray_channels(format) * cols;
+  if (!src || !dst || (int64_t)row_stride < wb) return fail(c, VSLAM_ERR_INVALID, "gray_u8: bad argument");
+  Call k(c, c->stream);
+  const size_t bytes = (size_t)(rows - 1) * row_stride + (size_t)wb;
+  const size_t off = (size_t)((uintptr_t)src & 15u);       // the device copy keeps the caller's alignment: rows start where they would in place
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16);
+  k.up_to(ds + off, src, bytes);
+  const int ostride = (cols + 15) & ~15;
+  uint8_t* dd = k.dev<uint8_t>((size_t)rows * ostride);
+  GrayArgs ga;
+  std::memset(&ga, 0, sizeof ga);
+  ga.src[0] = ds + off; ga.src_row_stride = row_stride; ga.dst[0] = dd; ga.dst_row_stride = ostride;
+  ga.rows = rows; ga.cols = cols; ga.n = 1; ga.sides = 1; ga.format = format; ga.active[0] = 1u;
+  if (k.ok()) k.note(gray_enqueue(c->stream, ga));
+  if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)cols, dd, (size_t)ostride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  return k.finish();
+}

@@ -1,6 +1,6 @@
 // host_frame.h — one frame on a context: where its input images come from (device pointers, host uploads through pinned staging, raw
 // pairs of a rectifying context), the image pipeline and the frame's launch sequence, the fused entries vslam_process_*, and the
-// rectification and equalisation switches.  Host code, included by vslam_hip.hip after host_ctx.h.
+// rectification, equalisation and colour-input switches.  Host code, included by vslam_hip.hip after host_ctx.h.
 #pragma once
 
 // ---- launches ------------------------------------------------------------------------------------
@@ -30,6 +30,17 @@ static int launch_image_pipeline(vslam_ctx* c) {
   // the image products of this set were last read by the frame kernel two steps ago; the detector thresholds come
   // from the controller in k_emit of the previous step (same queue)
   if (c->frm_pending[set] && st != c->stream) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_frm[set], 0));
+  if (c->col.format != VSLAM_PIXEL_GRAY8) {
+    // colour pair -> grey pair where the next stage reads (set_color_inputs has chosen: the rectifier's raw slabs or upload[set])
+    const vslam_ctx::Col& q = c->col;
+    GrayArgs ga;
+    for (int k = 0; k < 2; ++k) { ga.src[k] = q.src[k]; ga.dst[k] = q.out[k]; }
+    ga.src_row_stride = q.src_row_stride; ga.src_stream_stride = q.src_stream_stride;
+    ga.dst_row_stride = q.out_row_stride; ga.dst_stream_stride = q.out_stream_stride;
+    ga.rows = q.out_rows; ga.cols = q.out_cols; ga.n = n; ga.sides = 2; ga.format = q.format;
+    std::memcpy(ga.active, c->buf.active, sizeof ga.active);
+    HIP_TRY(c, gray_enqueue(st, ga));
+  }
   if (c->rect.on) {
     // raw pair -> rectified pair in upload[set] (the slab the wait above has freed), ahead of the detector
     const vslam_ctx::Rect& q = c->rect;
@@ -91,6 +102,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
   c->last_set = set;
   if (c->rect.on) c->rect.have_frame = true;
   if (c->eq.on) c->eq.have_frame = true;
+  if (c->col.format != VSLAM_PIXEL_GRAY8) c->col.have_frame = true;
   return VSLAM_OK;
 }
 static int frame_done(vslam_ctx* c) {
@@ -233,7 +245,31 @@ static int set_raw_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int3
   q.src[0] = o.p[0]; q.src[1] = o.p[1]; q.src_row_stride = o.row_stride; q.src_stream_stride = o.stream_stride;
   return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], c->up_stride, c->up_stream_stride);
 }
+// Colour input: host pairs go to the colour slabs of this step's parity (upload_to with the byte width as cols), device pairs are read in
+// place (by k_gray_u8 only).  The grey pair is written where the next stage reads: the rectifier's raw slabs when rectifying, else
+// upload[parity]; DevBuf::img points at upload[parity] either way, as it does for a grey host frame.
+static int set_color_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
+  vslam_ctx::Col& q = c->col;
+  vslam_ctx::Rect& rq = c->rect;
+  const int rows = rq.on ? rq.raw_rows : c->cfg.c.rows, cols = rq.on ? rq.raw_cols : c->cfg.c.cols;
+  const int wb = gray_channels(q.format) * cols;
+  if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");
+  if (row_stride < wb) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than channels * image width");
+  ImgLoc o = {{L, R}, row_stride, image_stride};
+  if (!on_device) {
+    const int rc = upload_to(c, L, R, row_stride, image_stride, rows, wb, q.slab[c->parity], q.stride, q.stream_stride, &o);
+    if (rc != VSLAM_OK) return rc;
+  }
+  q.src[0] = o.p[0]; q.src[1] = o.p[1]; q.src_row_stride = o.row_stride; q.src_stream_stride = o.stream_stride;
+  q.out_rows = rows; q.out_cols = cols;
+  for (int k = 0; k < 2; ++k) q.out[k] = rq.on ? rq.raw[c->parity][k] : c->upload[c->parity][k];
+  q.out_row_stride = rq.on ? rq.raw_stride : c->up_stride;
+  q.out_stream_stride = rq.on ? rq.raw_stream_stride : c->up_stream_stride;
+  if (rq.on) { rq.src[0] = q.out[0]; rq.src[1] = q.out[1]; rq.src_row_stride = q.out_row_stride; rq.src_stream_stride = q.out_stream_stride; }
+  return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], c->up_stride, c->up_stream_stride);
+}
 static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
+  if (c->col.format != VSLAM_PIXEL_GRAY8) return set_color_inputs(c, L, R, row_stride, image_stride, on_device);
   if (c->rect.on) return set_raw_inputs(c, L, R, row_stride, image_stride, on_device);
   return on_device ? set_images_device(c, L, R, row_stride, image_stride) : upload_images(c, L, R, row_stride, image_stride);
 }
@@ -288,7 +324,7 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the old maps and raw slabs
   rect_free(c);
-  if (off) { (void)eq_keep_sync(c); return VSLAM_OK; }
+  if (off) { (void)eq_keep_sync(c); return col_slab_sync(c) == hipSuccess ? VSLAM_OK : fail(c, VSLAM_ERR_HIP, "vslam_set_rectification: colour slabs"); }
   vslam_ctx::Rect& q = c->rect;
   q.raw_rows = raw_rows; q.raw_cols = raw_cols;
   q.raw_stride = (raw_cols + 63) & ~63;
@@ -310,6 +346,7 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
   q.on = true;
   e = eq_keep_sync(c);
+  if (e == hipSuccess) e = col_slab_sync(c);
   if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
   return VSLAM_OK;
 }
@@ -378,6 +415,32 @@ VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
   c->eq.on = e == hipSuccess;
   if (e == hipSuccess) e = eq_keep_sync(c);
   if (e != hipSuccess) { eq_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_equalization: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+
+// ---- colour input (kernels_gray.h) ---------------------------------------------------------------
+VS_API int vslam_set_color_input(vslam_ctx* c, int format) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_color_input called inside a frame");
+  if (format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8) return fail(c, VSLAM_ERR_INVALID, "vslam_set_color_input: unknown pixel format");
+  if (format == c->col.format) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the slabs
+  col_free(c);
+  c->col.format = format;
+  const hipError_t e = col_slab_sync(c);
+  if (e != hipSuccess) { col_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_color_input: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  const vslam_ctx::Col& q = c->col;
+  if (q.format == VSLAM_PIXEL_GRAY8 || !q.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_gray_images: no frame has been converted since vslam_set_color_input");
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_gray_images: null output");
+  for (int k = 0; k < 2; ++k)
+    HIP_TRY(c, hipMemcpy2D(k ? right : left, q.out_cols, q.out[k] + (size_t)s * q.out_stream_stride, q.out_row_stride, q.out_cols, q.out_rows,
+                           hipMemcpyDeviceToHost));
   return VSLAM_OK;
 }
 

@@ -42,7 +42,8 @@ VS_API int vslam_rgbd_reset(vslam_rgbd* r) {
 static int rgbd_frame_args_ok(vslam_rgbd* r, const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride) {
   if (!left || !depth) { r->err() = "called with empty frame"; return VSLAM_ERR_INVALID; }   // depth_framepoint_generator.cpp:48-50
   const int cols = r->on_host ? r->t.cfg.cols : r->d.in_cols();     // the raw width while undistortion maps are set
-  if (lstride < cols || dstride < cols) { r->err() = "row stride smaller than image width"; return VSLAM_ERR_INVALID; }
+  const int wb = r->on_host ? cols : r->d.in_bytes();               // channels * width of a colour frame (vslam_rgbd_set_color_input)
+  if (lstride < wb || dstride < cols) { r->err() = "row stride smaller than image width"; return VSLAM_ERR_INVALID; }
   return VSLAM_OK;
 }
 VS_API int vslam_rgbd_process_host(vslam_rgbd* r, const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride) {
@@ -183,4 +184,17 @@ VS_API int vslam_rgbd_set_equalization(vslam_rgbd* r, int on) {
 VS_API int vslam_rgbd_get_equalized(vslam_rgbd* r, int32_t stream, uint8_t* image) {
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_equalized") : r->d.get_equalized(stream, image);
+}
+// ---- colour input (kernels_gray.h): the device-resident loop only ----
+static int rgbd_color_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes grey frames only; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_color_input(vslam_rgbd* r, int format) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_color_host_refusal(r, "vslam_rgbd_set_color_input") : r->d.set_color_input(format);
+}
+VS_API int vslam_rgbd_get_gray(vslam_rgbd* r, int32_t stream, uint8_t* image) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_color_host_refusal(r, "vslam_rgbd_get_gray") : r->d.get_gray(stream, image);
 }

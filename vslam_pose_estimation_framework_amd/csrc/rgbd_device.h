@@ -117,6 +117,7 @@ public:
     failed = false; failed_why.clear(); pending = false;
     und.have_frame = false;                                                  // the maps stay (like the rig of a rectifying context)
     eq.have_frame = false;                                                   // and so does the equalisation switch
+    col.have_frame = false;                                                  // and the colour format
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
     return VSLAM_OK;
   }
@@ -308,6 +309,34 @@ public:
     return VSLAM_OK;
   }
 
+  // ---- colour input (kernels_gray.h): opt-in, its own allocation, nothing launched while col.format is VSLAM_PIXEL_GRAY8.  The intensity
+  // image of every entry is interleaved colour then (strides in bytes); k_gray_u8 converts it into col.gray, an image of the tracker's own at
+  // the input size, which everything behind it reads — the undistortion, else the equalisation (in place) and the detector.  The caller's
+  // image, host copy or device memory, is only read.  The depth image is untouched.
+  int in_bytes() const { return (col.format ? gray_channels(col.format) : 1) * in_cols(); }      // of one row of the intensity image that comes in
+  int set_color_input(int format) {
+    if (pending) { err = "vslam_rgbd_set_color_input: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8) { err = "vslam_rgbd_set_color_input: unknown pixel format"; return VSLAM_ERR_INVALID; }
+    if (format == col.format) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    (void)hipStreamSynchronize(q2);
+    col_free();
+    drop_graph();                                   // a captured launch sequence holds the kernel (or lacks it)
+    col.format = format;
+    return VSLAM_OK;
+  }
+  // the grey image the last finished frame of `stream` was converted to (dense, at the input size)
+  int get_gray(int stream, uint8_t* image) {
+    if (int rc = readable(stream)) return rc;
+    if (!col.format || !col.have_frame) { err = "vslam_rgbd_get_gray: no frame has been converted since vslam_rgbd_set_color_input / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    if (!image) { err = "vslam_rgbd_get_gray: null output"; return VSLAM_ERR_INVALID; }
+    (void)hipSetDevice(ic->device);
+    const hipError_t e = hipMemcpy2D(image, (size_t)col.cols, col.gray + (size_t)stream * col.gray_stream, (size_t)col.gray_stride, (size_t)col.cols, (size_t)col.rows, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    return VSLAM_OK;
+  }
+
   int process(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t left_stream_stride = 0, size_t depth_stream_stride = 0) {
     const int rc = submit(left, lstride, depth, dstride, left_stream_stride, depth_stream_stride);
     return rc != VSLAM_OK ? rc : wait();
@@ -322,7 +351,7 @@ public:
     if (failed) { err = "RGB-D tracker: an earlier frame failed (" + failed_why + "); reset() before the next frame"; return VSLAM_ERR_STATE; }
     if (pending) { err = "RGB-D tracker: the previous frame has not been waited for"; return VSLAM_ERR_STATE; }
     if (und.on && (size_t)und.raw_rows * (size_t)dstride > 0x7fffffffu) { err = "RGB-D frame: raw depth row stride too large"; return VSLAM_ERR_INVALID; }   // k_undistort_depth's 32-bit tap offsets
-    if (B > 1 && (left_stream_stride < (size_t)(in_rows() - 1) * lstride + in_cols() || depth_stream_stride < (size_t)(in_rows() - 1) * dstride + in_cols())) {
+    if (B > 1 && (left_stream_stride < (size_t)(in_rows() - 1) * lstride + in_bytes() || depth_stream_stride < (size_t)(in_rows() - 1) * dstride + in_cols())) {
       err = "RGB-D batch: stream strides smaller than an image"; return VSLAM_ERR_INVALID;
     }
     const int rc = submit_frame(left, lstride, depth, dstride, left_stream_stride, depth_stream_stride, on_device);
@@ -335,7 +364,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else { und.have_frame = und.on; eq.have_frame = eq.on; }
+    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; }
     return rc;
   }
 
@@ -420,6 +449,14 @@ private:
     uint8_t* out; int32_t out_stride; size_t out_stream;
   } eq{};
   DeviceStore eq_mem;
+  // colour input: off while col.format is VSLAM_PIXEL_GRAY8.  The grey image [B] at the input size rows x cols (allocated with the first frame
+  // at that size) and this frame's colour source
+  struct Colour {
+    int format; bool have_frame;
+    uint8_t* gray; int32_t gray_stride; size_t gray_stream; int32_t rows, cols;
+    const uint8_t* src; int32_t src_stride; size_t src_stream;
+  } col{};
+  DeviceStore col_mem;
   const uint8_t* raw_img = nullptr; int32_t raw_img_stride = 0; size_t raw_img_stream = 0;
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
@@ -431,6 +468,30 @@ private:
   void eq_free() {
     eq_mem.release();
     eq = Equal{};
+  }
+  void col_free() {
+    col_mem.release();
+    col = Colour{};
+  }
+  // this frame's intensity image (*img: the staged copy or the caller's device memory) becomes the conversion's source; *img is pointed at
+  // the grey image everything downstream reads
+  hipError_t col_route(const uint8_t** img, int32_t* stride, size_t* stream) {
+    if (!col.format) return hipSuccess;
+    const int rows = in_rows(), cols = in_cols();
+    if (!col.gray || col.rows != rows || col.cols != cols) {
+      (void)hipStreamSynchronize(q);
+      col_mem.release();
+      col.gray = nullptr;
+      drop_graph();                              // it holds the old image
+      col.rows = rows; col.cols = cols;
+      col.gray_stride = (cols + 15) & ~15;
+      col.gray_stream = (size_t)rows * col.gray_stride;
+      const hipError_t e = col_mem.alloc(&col.gray, col.gray_stream * (size_t)B);
+      if (e != hipSuccess) { col.gray = nullptr; return e; }
+    }
+    col.src = *img; col.src_stride = *stride; col.src_stream = *stream;
+    *img = col.gray; *stride = col.gray_stride; *stream = col.gray_stream;
+    return hipSuccess;
   }
   // this frame's image bs points at becomes the equalisation's source; bs is pointed at its result.  own: the image is ours to overwrite
   void eq_route(bool own) {
@@ -472,6 +533,7 @@ private:
     map_free();
     und_free();
     eq_free();
+    col_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (q2) { (void)hipStreamDestroy(q2); q2 = nullptr; }
     if (ev_depth) { (void)hipEventDestroy(ev_depth); ev_depth = nullptr; }
@@ -531,6 +593,7 @@ private:
     if (on_device) {
       use_graph = false;                       // the captured graph holds the staging buffers' addresses
       bs = buf_set(ic, 0, 0);
+      if (const hipError_t ce = col_route(&left, &lstride, &lss)) return hip_fail(ce, "grey image");      // colour: k_gray_u8 alone reads the caller's image
       if (und.on) {                            // the two undistortion kernels are the only readers of the caller's memory
         raw_img = left; raw_img_stride = lstride; raw_img_stream = lss;
         raw_dep = depth; raw_dep_stride = dstride; raw_dep_stream = dss;
@@ -540,7 +603,7 @@ private:
         bs.img[0] = left; bs.img[1] = left; bs.img_row_stride = lstride; bs.img_stream_stride = lss;
         depth_src = depth; depth_src_stride = dstride;
       }
-      eq_route(und.on);
+      eq_route(und.on || col.format != VSLAM_PIXEL_GRAY8);
       all_active(bs);
       enqueue_first_attempt(false);
       hipError_t e = hipGetLastError();
@@ -551,7 +614,7 @@ private:
     depth_src = d_depth; depth_src_stride = p.cols;
     uint16_t* const depth_up = und.on ? und.raw_depth : d_depth;     // where the depth images are copied to, re-packed
     // inputs: the caller's row stride kept on the device for the image, the depth image re-packed
-    const size_t ib = (size_t)(rows - 1) * lstride + cols;                 // bytes of one image the caller owns
+    const size_t ib = (size_t)(rows - 1) * lstride + in_bytes();           // bytes of one image the caller owns
     // device bytes per sequence: the caller's own stream stride when the images lie in one (nearly) dense block — then ONE copy brings all of
     // them in (a pageable copy costs ~40 us of host time whatever its size: 128 sequences are 10 ms of copies one by one, 0.6 ms as a block)
     const bool dense = B > 1 && lss >= (size_t)rows * lstride && lss <= (size_t)rows * lstride + 4096;
@@ -581,12 +644,14 @@ private:
     }
     if (e != hipSuccess) return hip_fail(e, "image / depth upload");
     bs = buf_set(ic, 0, 0);
+    const uint8_t* im = d_img; int32_t im_stride = lstride; size_t im_stream = img_stream;
+    if (const hipError_t ce = col_route(&im, &im_stride, &im_stream)) return hip_fail(ce, "grey image");
     if (und.on) {
-      raw_img = d_img; raw_img_stride = lstride; raw_img_stream = img_stream;
+      raw_img = im; raw_img_stride = im_stride; raw_img_stream = im_stream;
       raw_dep = und.raw_depth; raw_dep_stride = cols; raw_dep_stream = (size_t)rows * cols;
       bs.img[0] = und.img; bs.img[1] = und.img; bs.img_row_stride = und.img_stride; bs.img_stream_stride = und.img_stream;
     } else {
-      bs.img[0] = d_img; bs.img[1] = d_img; bs.img_row_stride = lstride; bs.img_stream_stride = img_stream;
+      bs.img[0] = im; bs.img[1] = im; bs.img_row_stride = im_stride; bs.img_stream_stride = im_stream;
     }
     eq_route(true);
     all_active(bs);
@@ -640,6 +705,15 @@ private:
     depth_pending = true;
     // raw image -> undistorted image on the image pipeline's queue, ahead of the detector and behind the fork, so that the space map's
     // queue does not wait for it (once per frame: further attempts read the undistorted image again)
+    // colour -> grey at the head of the image queue's work, once per frame, behind the fork like the undistortion
+    if (col.format) {
+      GrayArgs ga{};
+      ga.src[0] = col.src; ga.src_row_stride = col.src_stride; ga.src_stream_stride = col.src_stream;
+      ga.dst[0] = col.gray; ga.dst_row_stride = col.gray_stride; ga.dst_stream_stride = col.gray_stream;
+      ga.rows = col.rows; ga.cols = col.cols; ga.n = B; ga.sides = 1; ga.format = col.format;
+      std::memcpy(ga.active, bs.active, sizeof ga.active);
+      (void)gray_enqueue(q, ga);
+    }
     if (und.on)
       hipLaunchKernelGGL(k_rectify, undistort_grid(rows, cols, B), dim3(256), 0, q,
                          undistort_image_args(raw_img, raw_img_stream, raw_img_stride, und.raw_rows, und.raw_cols, und.map_xy, und.map_a, und.map_stride, und.img,

@@ -17,12 +17,29 @@ import numpy as np
 
 
 # ---- KITTI calibration -------------------------------------------------------------------------------------
-def parse_kitti_calib(path):
-    """Returns (K 3x3, baseline_homogeneous 3) as getCameraCalibrationMatrixKITTI does."""
+def parse_kitti_calib(path, cameras=(0, 1)):
+    """Returns (K 3x3, baseline_homogeneous 3) as getCameraCalibrationMatrixKITTI does (the grey pair, cameras 0 and 1: the file's first
+    two lines).  Another pair, e.g. the colour cameras (2, 3): the lines are found by their `P2:` / `P3:` labels, K comes from the left
+    camera's matrix and baseline[0] is the difference of the two matrices' [0, 3] entries (the left one need not be the rig's origin)."""
     with open(path) as f:
         lines = [ln for ln in f.read().splitlines()]
     if not lines or not lines[0].strip():
         raise RuntimeError("invalid camera calibration file provided")
+    if tuple(cameras) != (0, 1):
+        rows = {}
+        for ln in lines:
+            a = ln.split()
+            if a and a[0].endswith(":") and len(a) >= 13:
+                rows[a[0][:-1]] = [float(v) for v in a[1:13]]
+        try:
+            pl, pr = rows["P%d" % cameras[0]], rows["P%d" % cameras[1]]
+        except KeyError as e:
+            raise RuntimeError("camera calibration file has no line %s: %s" % (e, path))
+        K = np.eye(3)
+        K[0, 0] = pl[0]; K[0, 2] = pl[2]; K[1, 1] = pl[5]; K[1, 2] = pl[6]
+        baseline = np.zeros(3)
+        baseline[0] = pr[3] - pl[3]
+        return K, baseline
     a = lines[0].split()      # "P0:" fx 0 cx 0 0 fy cy 0 0 0 1 0
     K = np.eye(3)
     K[0, 0] = float(a[1]); K[0, 2] = float(a[3]); K[1, 1] = float(a[6]); K[1, 2] = float(a[7])
@@ -261,15 +278,32 @@ class TumRgbdSequence(object):
             raise RuntimeError("depth image is not 16-bit: " + self.depth[k])
         return gray, depth
 
+    def frame_color(self, k):
+        """(colour array as decoded, its pixel format, depth): RGB8 / RGBA8 [rows, cols, 3 | 4] for the device's conversion
+        (vslam_rgbd_set_color_input); a grey PNG passes through as frame() returns it, with GRAY8."""
+        from . import color
+        img = read_png(os.path.join(self.root, self.rgb[k]))
+        depth = read_png(os.path.join(self.root, self.depth[k]))
+        if depth.dtype != np.uint16:
+            raise RuntimeError("depth image is not 16-bit: " + self.depth[k])
+        if img.ndim == 3:
+            return img, (color.RGB8 if img.shape[2] == 3 else color.RGBA8), depth
+        return (img if img.dtype == np.uint8 else (img >> 8).astype(np.uint8)), color.GRAY8, depth
+
 
 # ---- KITTI odometry sequence folder ---------------------------------------------------------------------------------
 class KittiSequence(object):
-    """<root>/image_0/000000.png, <root>/image_1/000000.png, <root>/calib.txt, <root>/times.txt"""
+    """<root>/image_0/000000.png, <root>/image_1/000000.png, <root>/calib.txt, <root>/times.txt.  color=True: the odometry benchmark's
+    colour cameras instead, <root>/image_2 and image_3 with the calibration of P2 / P3; pair(k) then returns RGB arrays [rows, cols, 3]."""
 
-    def __init__(self, root):
+    def __init__(self, root, color=False):
         self.root = root
-        self.K, self.baseline = parse_kitti_calib(os.path.join(root, "calib.txt"))
-        names = sorted(n for n in os.listdir(os.path.join(root, "image_0")) if n.endswith(".png"))
+        self.color = bool(color)
+        self.dirs = ("image_2", "image_3") if color else ("image_0", "image_1")
+        self.K, self.baseline = parse_kitti_calib(os.path.join(root, "calib.txt"), (2, 3) if color else (0, 1))
+        if color and not os.path.isdir(os.path.join(root, self.dirs[0])):
+            raise RuntimeError("no colour cameras in this folder (image_2 / image_3): " + root)
+        names = sorted(n for n in os.listdir(os.path.join(root, self.dirs[0])) if n.endswith(".png"))
         self.names = names
         tpath = os.path.join(root, "times.txt")
         self.times = [float(v) for v in open(tpath).read().split()] if os.path.exists(tpath) else list(range(len(names)))
@@ -278,6 +312,11 @@ class KittiSequence(object):
         return len(self.names)
 
     def pair(self, k):
+        if self.color:
+            left, right = (read_png(os.path.join(self.root, d, self.names[k])) for d in self.dirs)
+            if left.ndim != 3 or right.ndim != 3 or left.dtype != np.uint8:
+                raise RuntimeError("not an 8-bit colour PNG pair: " + self.names[k])
+            return np.ascontiguousarray(left[:, :, :3]), np.ascontiguousarray(right[:, :, :3])
         left = read_png_gray8(os.path.join(self.root, "image_0", self.names[k]))
         right = read_png_gray8(os.path.join(self.root, "image_1", self.names[k]))
         return left, right
