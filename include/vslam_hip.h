@@ -245,6 +245,32 @@ int vslam_get_equalized_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_
 int vslam_get_equalization_histograms(vslam_ctx* ctx, int stream, uint32_t* hist512);
 int vslam_equalize_hist_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride,
                            uint8_t* dst /* dense */, uint32_t* hist256 /* may be NULL */);
+/* ---- CLAHE of the input pair: the second mode of the equalisation slot (opt-in; csrc/kernels_clahe.h) -------------------
+ * cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply [recalled], bit-exact against the numpy restatement in clahe.py: per-tile
+ * counts of the image extended to whole tiles (BORDER_REFLECT_101), clipped at max((int)(clip_limit * tile_area / 256), 1) with the
+ * excess spread over the bins, one table per tile, and every pixel blended from the four tables around it.  clip_limit <= 0: no clipping.
+ * Same place and same placement as global equalisation (behind colour conversion and rectification, ahead of the detector; host images
+ * in place in the context's slabs, device images read only), two kernels (k_clahe_lut, k_clahe_apply) per frame on the queue of the
+ * image pipeline, under the fused entries and the stage path alike.  A switched-off stream is neither read nor written.
+ * vslam_set_clahe: on != 0 turns it on (its own allocations; again with other arguments: they replace the earlier ones), 0 turns it off
+ *   and frees them; nothing is launched while off.  Synchronises the context.  VSLAM_ERR_STATE between vslam_frame_begin and the end of
+ *   that frame, and while global equalisation is on; vslam_set_equalization(ctx, 1) returns VSLAM_ERR_STATE while CLAHE is on (switching
+ *   either one OFF while the other is on is accepted and changes nothing).  VSLAM_ERR_INVALID: tiles_x or tiles_y outside
+ *   1 .. VSLAM_CLAHE_MAX_TILES, cols <= tiles_x or rows <= tiles_y (the reflected border would leave the image), more than 2^24 pixels,
+ *   clip_limit not finite.  The switch survives vslam_reset and vslam_reset_stream(s).
+ * vslam_get_equalized_images returns the CLAHE pair in this mode; vslam_get_equalization_histograms returns VSLAM_ERR_STATE.
+ * vslam_get_clahe_luts: uint8 [2][tiles_y][tiles_x][256], the tables of the left and right image of the last submitted frame of
+ *   `stream`, with the errors of vslam_get_equalized_images (VSLAM_ERR_STATE also under global equalisation).  Synchronises.
+ * vslam_clahe_u8: the same two kernels stand-alone on one host image: src is rows x cols with row_stride bytes per row, dst with
+ *   dst_row_stride (bytes beyond cols in a row are neither read nor written), each at any alignment — the device copies keep the
+ *   caller's alignment mod 16; dst == src (with equal strides) works in place, otherwise the two must not overlap.  luts (may be NULL)
+ *   receives [tiles_y][tiles_x][256].  VSLAM_ERR_INVALID, nothing written: the refusals of vslam_set_clahe, null src / dst, a stride
+ *   below cols; the context stays usable. */
+#define VSLAM_CLAHE_MAX_TILES 32
+int vslam_set_clahe(vslam_ctx* ctx, int on, double clip_limit, int tiles_x, int tiles_y);
+int vslam_get_clahe_luts(vslam_ctx* ctx, int stream, uint8_t* luts);
+int vslam_clahe_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, double clip_limit, int32_t tiles_x,
+                   int32_t tiles_y, uint8_t* dst, int32_t dst_row_stride, uint8_t* luts /* may be NULL */);
 /* ---- colour input: interleaved 8-bit colour to grey ahead of everything else (opt-in; csrc/kernels_gray.h) -------------
  * The reference converts a colour frame itself before anything else happens to it (slam_assembly.cpp:392-399, cvtColor CV_BGR2GRAY).
  * One definition, cvtColor on 8-bit images with 14 fractional bits [recalled], all integer:
@@ -772,6 +798,17 @@ int vslam_rgbd_get_undistorted(vslam_rgbd* t, int32_t stream, uint8_t* image, ui
  *   when off, before a frame, or with a frame in flight. */
 int vslam_rgbd_set_equalization(vslam_rgbd* t, int on);
 int vslam_rgbd_get_equalized(vslam_rgbd* t, int32_t stream, uint8_t* image);
+/* CLAHE in this mode (opt-in; the definition above vslam_set_clahe): the second mode of the same slot — the intensity image only, the same
+ * place on the image queue, once per frame, inside the captured launch sequence (toggling drops it); a caller's device image is read only.
+ * The switch survives vslam_rgbd_reset.
+ * vslam_rgbd_set_clahe: VSLAM_ERR_STATE with a frame in flight, on the host-driven loop, or while global equalisation is on
+ *   (vslam_rgbd_set_equalization(t, 1) likewise while CLAHE is on; switching either one OFF while the other is on changes nothing);
+ *   VSLAM_ERR_INVALID as vslam_set_clahe.
+ * vslam_rgbd_get_equalized returns the processed image in this mode.
+ * vslam_rgbd_get_clahe_luts: uint8 [tiles_y][tiles_x][256] of the last finished frame of `stream`, with the errors of
+ *   vslam_rgbd_get_equalized. */
+int vslam_rgbd_set_clahe(vslam_rgbd* t, int on, double clip_limit, int tiles_x, int tiles_y);
+int vslam_rgbd_get_clahe_luts(vslam_rgbd* t, int32_t stream, uint8_t* luts);
 /* Colour input in this mode (opt-in; the definition and the VSLAM_PIXEL_* formats above vslam_set_color_input): while the format is not
  * VSLAM_PIXEL_GRAY8 the intensity image of every process / submit / batch entry, host or device, is interleaved colour at the size the
  * tracker otherwise expects; its row and stream strides are in BYTES (row stride >= channels * cols).  The depth image is untouched.

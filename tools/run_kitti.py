@@ -9,6 +9,9 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
     python tools/run_kitti.py <EuRoC dir> --rectify --format tum --out traj.txt   raw images: rectified on the GPU from mav0/cam{0,1}/sensor.yaml
     python tools/run_kitti.py <sequence dir> --equalize   (or -eh, the reference's spelling) cv::equalizeHist on every image, on the GPU,
                               behind --rectify and ahead of the detector: dim, low-contrast sequences; also with --chunks, --map, --observations
+    python tools/run_kitti.py <sequence dir> --clahe [CLIP] [--clahe-tiles X,Y]   cv::CLAHE on every image, on the GPU, in the place of --equalize
+                              (not together with it; clip limit 40.0 and 8,8 tiles by default): unevenly lit sequences; also with --rectify,
+                              --color, --chunks, --map, --observations
     python tools/run_kitti.py <sequence dir with image_2/ image_3/> --color   the odometry benchmark's colour cameras with their own calibration
                               (P2 / P3 of calib.txt); the RGB frames are converted to grey on the GPU; also with --chunks, --equalize, --map, --observations
     python tools/run_kitti.py <sequence dir> --map map.ply   the landmark map as well (binary PLY: x y z id first_frame last_frame updates)
@@ -34,7 +37,7 @@ from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, 
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
 
 
-def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False):
+def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8)):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -47,6 +50,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
         api.set_rectification(rect)
     if equalize:
         api.set_equalization(True)
+    if clahe is not None:
+        api.set_clahe(True, clahe, clahe_tiles)
     if color:
         api.set_color_input(color_mod.RGB8)
     if want_map:
@@ -79,7 +84,7 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False):
+        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8)):
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
     if color and euroc:
         raise SystemExit("--color: an ASL / EuRoC folder holds grey images (it takes a KITTI odometry folder with image_2/ and image_3/)")
@@ -121,9 +126,11 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     else:
         io_formats.apply_calib(cfg, seq.K, seq.baseline, left.shape[0], left.shape[1])
     if color:
-        log("colour cameras (image_2 / image_3, calibration P2 / P3): RGB -> grey on the GPU, ahead of %s" % ("the equalisation" if equalize else "the detector"))
+        log("colour cameras (image_2 / image_3, calibration P2 / P3): RGB -> grey on the GPU, ahead of %s" % ("the equalisation" if equalize else "CLAHE" if clahe is not None else "the detector"))
     if equalize:
         log("equalising histograms on the GPU (cv::equalizeHist on every image%s)" % (", behind the rectification" if rect is not None else ""))
+    if clahe is not None:
+        log("CLAHE on the GPU (cv::CLAHE, clip limit %g, %d x %d tiles, on every image%s)" % (clahe, clahe_tiles[0], clahe_tiles[1], ", behind the rectification" if rect is not None else ""))
     t0 = time.perf_counter()
     flags = 0
     tracking = 0
@@ -131,7 +138,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     obs = None
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
-                                                equalize=equalize, color=color)
+                                                equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles)
         tracking = None
     else:
         cfg.max_history_frames = 512
@@ -140,6 +147,8 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             api.set_rectification(rect)
         if equalize:
             api.set_equalization(True)
+        if clahe is not None:
+            api.set_clahe(True, clahe, clahe_tiles)
         if color:
             api.set_color_input(color_mod.RGB8)
         if want_map:
@@ -208,6 +217,15 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     return result
 
 
+def _tiles(text):
+    """--clahe-tiles X,Y -> (X, Y)"""
+    try:
+        x, y = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected X,Y (two integers)")
+    return x, y
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("sequence")
@@ -227,15 +245,22 @@ def parse_args(argv=None):
                     "to this .npz bundle (io_formats.read_bundle); implies the map")
     ap.add_argument("--equalize", "-eh", action="store_true", help="equalise every image's histogram on the GPU ahead of the detector "
                     "(the reference's -equalize-histogram / -eh): dim or low-contrast sequences")
+    ap.add_argument("--clahe", nargs="?", type=float, const=40.0, default=None, metavar="CLIP", help="contrast-limited adaptive histogram equalisation "
+                    "(cv::CLAHE) of every image on the GPU ahead of the detector, clip limit CLIP (40.0 without a value): dim or unevenly lit "
+                    "sequences; not together with --equalize")
+    ap.add_argument("--clahe-tiles", type=_tiles, default=(8, 8), metavar="X,Y", help="the tile grid of --clahe (8,8)")
     ap.add_argument("--color", action="store_true", help="a KITTI odometry folder's colour cameras (image_2 / image_3 with the calibration of P2 / P3); "
                     "the frames are converted to grey on the GPU")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.clahe is not None and a.equalize:
+        ap.error("--clahe and --equalize exclude each other: one equalisation ahead of the detector")
+    return a
 
 
 def main(argv=None):
     a = parse_args(argv)
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
-        rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color)
+        rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles)
 
 
 if __name__ == "__main__":

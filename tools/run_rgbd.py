@@ -6,6 +6,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
     python tools/run_rgbd.py <folder> [--config icl|tum|xtion] [--intrinsics freiburg1|freiburg2|freiburg3|icl|fx,fy,cx,cy]
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
                              [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color]
+                             [--clahe [CLIP]] [--clahe-tiles X,Y]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -21,6 +22,8 @@ camera); without a value the coefficients are io_formats.TUM_DISTORTION[--intrin
 camera at the raw size; trajectory, map and observations are then in undistorted coordinates.  Device-resident loop only.
 --equalize (or -eh, the reference's spelling) equalises the intensity image's histogram on the GPU (cv::equalizeHist; the depth image is
 untouched), behind --undistort and ahead of the detector: dim or low-contrast sequences.  Device-resident loop only.
+--clahe [CLIP] runs cv::CLAHE (clip limit CLIP, 40.0 without a value; --clahe-tiles X,Y, 8,8 by default) on the intensity image in the place of
+--equalize (not together with it): unevenly lit sequences.  Device-resident loop only.
 --color hands the colour frames over as decoded and converts them to grey on the GPU (vslam_rgbd_set_color_input: the same integers as the
 host conversion without the flag), ahead of --undistort and --equalize.  Device-resident loop only."""
 import argparse
@@ -101,7 +104,7 @@ def distortion_of(undistort, intrinsics):
 
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
-        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False):
+        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8)):
     seq = io_formats.TumRgbdSequence(folder)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
@@ -142,6 +145,9 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
         if equalize:
             tr.set_equalization(True)
             log("equalising histograms on the GPU (cv::equalizeHist on every intensity image%s)" % (", behind the undistortion" if dist is not None else ""))
+        if clahe is not None:
+            tr.set_clahe(True, clahe, clahe_tiles)
+            log("CLAHE on the GPU (cv::CLAHE, clip limit %g, %d x %d tiles, on every intensity image%s)" % (clahe, clahe_tiles[0], clahe_tiles[1], ", behind the undistortion" if dist is not None else ""))
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
         if obs_path:
@@ -213,6 +219,15 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     return result
 
 
+def _tiles(text):
+    """--clahe-tiles X,Y -> (X, Y)"""
+    try:
+        x, y = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected X,Y (two integers)")
+    return x, y
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("folder")
@@ -232,6 +247,10 @@ def parse_args(argv=None):
                     "lens distortion on the GPU ahead of the detector; without a value: the coefficients that belong to a named --intrinsics")
     ap.add_argument("--equalize", "-eh", action="store_true", help="equalise every intensity image's histogram on the GPU ahead of the detector "
                     "(the reference's -equalize-histogram / -eh): dim or low-contrast sequences")
+    ap.add_argument("--clahe", nargs="?", type=float, const=40.0, default=None, metavar="CLIP", help="contrast-limited adaptive histogram equalisation "
+                    "(cv::CLAHE) of every intensity image on the GPU ahead of the detector, clip limit CLIP (40.0 without a value): dim or unevenly "
+                    "lit sequences; not together with --equalize")
+    ap.add_argument("--clahe-tiles", type=_tiles, default=(8, 8), metavar="X,Y", help="the tile grid of --clahe (8,8)")
     ap.add_argument("--color", action="store_true", help="hand the colour frames over as decoded and convert them to grey on the GPU, ahead of "
                     "--undistort and --equalize (without it: converted on the host, frame by frame)")
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -239,13 +258,16 @@ def parse_args(argv=None):
         if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
             argv[i:i + 2] = ["--undistort=" + argv[i + 1]]
             break
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.clahe is not None and a.equalize:
+        ap.error("--clahe and --equalize exclude each other: one equalisation ahead of the detector")
+    return a
 
 
 def main(argv=None):
     a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
-        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color)
+        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles)
 
 
 if __name__ == "__main__":

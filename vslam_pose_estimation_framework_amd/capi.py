@@ -143,6 +143,19 @@ def _p(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
 
 
+CLAHE_MAX_TILES = 32        # VSLAM_CLAHE_MAX_TILES
+
+
+def _clahe_luts(get, tiles, sides):
+    """The tables behind a get_clahe_luts entry as uint8 [sides, tilesY, tilesX, 256].  The entry writes as many tables as the switch in
+    the LIBRARY holds tiles, so it gets a buffer for the largest grid whatever this object believes the grid to be."""
+    buf = np.zeros(sides * CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256, np.uint8)
+    get(buf)
+    if tiles is None:
+        raise ValueError("clahe_luts: the tile grid is unknown, CLAHE was not switched on through this object's set_clahe")
+    return buf[:sides * tiles[0] * tiles[1] * 256].reshape(sides, tiles[1], tiles[0], 256).copy()
+
+
 class CApi(object):
     """One loaded library + one context (n_streams independent sequences)."""
 
@@ -283,6 +296,16 @@ class CApi(object):
         h = np.zeros((2, 256), np.uint32)
         self.check(self.fn("get_equalization_histograms")(self.ctx, C.c_int(stream), _p(h, C.c_uint32)))
         return h
+
+    # -- CLAHE of the input pair, the second mode of the equalisation slot (vslam_set_clahe) ------------------------------
+    def set_clahe(self, on=True, clip_limit=40.0, tiles=(8, 8)):
+        """tiles = (tilesX, tilesY).  equalized_images() returns the CLAHE pair while this is on."""
+        self.check(self.fn("set_clahe")(self.ctx, C.c_int(1 if on else 0), C.c_double(clip_limit), C.c_int(int(tiles[0])), C.c_int(int(tiles[1]))))
+        self.clahe_tiles = (int(tiles[0]), int(tiles[1])) if on else None
+
+    def clahe_luts(self, stream=0):
+        """uint8 [2, tilesY, tilesX, 256]: the tables of the left and right image of the last submitted frame of `stream`."""
+        return _clahe_luts(lambda buf: self.check(self.fn("get_clahe_luts")(self.ctx, C.c_int(stream), _p(buf, C.c_uint8))), getattr(self, "clahe_tiles", None), 2)
 
     # -- colour input (vslam_set_color_input) ---------------------------------------------------------------------------
     def set_color_input(self, fmt):
@@ -704,6 +727,25 @@ class CApi(object):
                                                _p(dst, C.c_uint8), _p(hist, C.c_uint32)))
         return dst, hist
 
+    def clahe_u8(self, image, clip_limit=40.0, tiles=(8, 8), out=None):
+        """vslam_clahe_u8: image (and out, when given) is a 2-D uint8 array or view with unit column stride; row strides and alignments
+        are passed on as they are.  out=None: a dense result; out is image: in place.  -> (dst, luts [tilesY, tilesX, 256])."""
+        img = np.asarray(image)
+        dst = np.zeros(img.shape, np.uint8) if out is None else out
+        for a in (img, dst):
+            if a.dtype != np.uint8 or a.ndim != 2 or (a.shape[1] > 1 and a.strides[1] != 1) or (a.shape[0] > 1 and a.strides[0] < a.shape[1]):
+                raise ValueError("clahe_u8: 2-D uint8 arrays with unit column stride are required")
+        if dst.shape != img.shape:
+            raise ValueError("clahe_u8: out has another shape")
+        rows, cols = img.shape
+        tx, ty = int(tiles[0]), int(tiles[1])
+        luts = np.zeros((max(ty, 0), max(tx, 0), 256), np.uint8)
+        stride = lambda a: a.strides[0] if rows > 1 else max(cols, 1)
+        self.check(self.fn("clahe_u8")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(cols), C.c_int32(stride(img)),
+                                       C.c_double(clip_limit), C.c_int32(tx), C.c_int32(ty), C.c_void_p(dst.ctypes.data), C.c_int32(stride(dst)),
+                                       _p(luts, C.c_uint8)))
+        return dst, luts
+
     def gray_u8(self, image, fmt, cols=None):
         """vslam_gray_u8: image is a uint8 array [rows, cols, channels], or a 2-D array or view [rows, >= channels * cols bytes] with unit
         column stride whose row stride and alignment are passed on as they are (cols is then required) -> grey [rows, cols]."""
@@ -934,6 +976,15 @@ class _RgbdEqualizeApi(object):
         img = np.zeros((int(self.cfg.rows), int(self.cfg.cols)), np.uint8)
         self._check(self.lib.vslam_rgbd_get_equalized(self.h, C.c_int32(stream), _p(img, C.c_uint8)))
         return img
+
+    def set_clahe(self, on=True, clip_limit=40.0, tiles=(8, 8)):
+        """vslam_rgbd_set_clahe: the slot's second mode, tiles = (tilesX, tilesY); equalized() returns the processed image while it is on."""
+        self._check(self.lib.vslam_rgbd_set_clahe(self.h, C.c_int(1 if on else 0), C.c_double(clip_limit), C.c_int(int(tiles[0])), C.c_int(int(tiles[1]))))
+        self._clahe_tiles = (int(tiles[0]), int(tiles[1])) if on else None
+
+    def clahe_luts(self, stream=0):
+        """uint8 [tilesY, tilesX, 256]: the tables of the image the last finished frame of `stream` was processed on."""
+        return _clahe_luts(lambda buf: self._check(self.lib.vslam_rgbd_get_clahe_luts(self.h, C.c_int32(stream), _p(buf, C.c_uint8))), getattr(self, "_clahe_tiles", None), 1)[0]
 
 
 class _RgbdColorApi(object):

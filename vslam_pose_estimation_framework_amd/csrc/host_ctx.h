@@ -84,8 +84,11 @@ struct vslam_ctx {
   // refilled every frame, and where the pair the last frame was processed on lies (out*: inside upload[last_set]).  keep[left/right]: with
   // rectification on as well, k_rectify writes here and the equalised pair goes to upload[parity], so that vslam_get_rectified_images
   // still returns the rectified pair; one pair suffices, its only readers are the same frame's two kernels on the same queue and a getter.
+  // clahe: the slot's second mode (vslam_set_clahe, kernels_clahe.h) — the same placement, the tables [stream][side][tilesY][tilesX][256]
+  // instead of the count table, geo holding what clahe_geometry made of the switch's arguments.
   struct Eq { bool on = false, have_frame = false; uint32_t* hist = nullptr; uint8_t* keep[2] = {nullptr, nullptr};
               const uint8_t* out[2] = {nullptr, nullptr}; int32_t out_row_stride = 0; size_t out_stream_stride = 0;
+              bool clahe = false; double clip_limit = 0; uint8_t* luts = nullptr; ClaheArgs geo{};
               DeviceStore mem, keep_mem; } eq;
   // colour input (vslam_set_color_input, kernels_gray.h): off while format == VSLAM_PIXEL_GRAY8.  slab[step parity][left/right]: what host
   // colour images are copied into (B x in_rows x stride bytes each, allocated on the first host frame at that input size); src*: this step's

@@ -915,6 +915,31 @@ VS_API int vslam_equalize_hist_u8(vslam_ctx* c, const uint8_t* src, int32_t rows
   return k.finish();
 }
 
+// ---- cv::CLAHE::apply on one host image (kernels_clahe.h) -------------------------------------------------------------
+VS_API int vslam_clahe_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, double clip_limit, int32_t tiles_x,
+                          int32_t tiles_y, uint8_t* dst, int32_t dst_row_stride, uint8_t* luts) {
+  if (int rc = entry_begin(c)) return rc;
+  ClaheArgs ca;
+  std::memset(&ca, 0, sizeof ca);
+  const char* why = "";
+  if (!clahe_geometry(rows, cols, clip_limit, tiles_x, tiles_y, ca, &why)) return fail(c, VSLAM_ERR_INVALID, std::string("clahe_u8: ") + why);
+  if (!src || !dst || row_stride < cols || dst_row_stride < cols || (dst == src && dst_row_stride != row_stride)) return fail(c, VSLAM_ERR_INVALID, "clahe_u8: bad argument");
+  Call k(c, c->stream);
+  // the device copies keep the caller's alignment: rows start where they would in place
+  const size_t bytes = (size_t)(rows - 1) * row_stride + cols, off = (size_t)((uintptr_t)src & 15u);
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16);
+  k.up_to(ds + off, src, bytes);
+  const size_t doff = (size_t)((uintptr_t)dst & 15u);
+  uint8_t* dd = dst == src ? ds + off : k.dev<uint8_t>((size_t)(rows - 1) * dst_row_stride + cols + 16) + doff;
+  const size_t nl = (size_t)tiles_x * tiles_y * 256;
+  ca.src[0] = ds + off; ca.src_row_stride = row_stride; ca.dst[0] = dd; ca.dst_row_stride = dst_row_stride;
+  ca.luts = k.dev<uint8_t>(nl); ca.n = 1; ca.sides = 1; ca.active[0] = 1u;
+  if (k.ok()) k.note(clahe_enqueue(c->stream, ca));
+  if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)dst_row_stride, dd, (size_t)dst_row_stride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  if (luts) k.down(luts, ca.luts, nl);
+  return k.finish();
+}
+
 // ---- interleaved 8-bit colour to grey on one host image (kernels_gray.h) --------------------------------------------
 VS_API int vslam_gray_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int format, uint8_t* dst) {
   if (int rc = entry_begin(c)) return rc;

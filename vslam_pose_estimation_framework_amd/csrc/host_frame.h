@@ -58,17 +58,21 @@ static int launch_image_pipeline(vslam_ctx* c) {
     // slabs or from the caller's device images, which these two kernels alone read; everything downstream reads upload[set]
     vslam_ctx::Eq& q = c->eq;
     const bool in_place = !c->rect.on && c->buf.img[0] == c->upload[set][0];
-    EqArgs ea;
-    for (int k = 0; k < 2; ++k) { ea.src[k] = c->rect.on ? q.keep[k] : c->buf.img[k]; ea.dst[k] = c->upload[set][k]; }
-    ea.src_row_stride = c->rect.on ? c->up_stride : c->buf.img_row_stride;
-    ea.src_stream_stride = c->rect.on ? c->up_stream_stride : c->buf.img_stream_stride;
-    ea.dst_row_stride = in_place ? c->buf.img_row_stride : c->up_stride;
-    ea.dst_stream_stride = in_place ? c->buf.img_stream_stride : c->up_stream_stride;
-    ea.hist = q.hist; ea.rows = d.c.rows; ea.cols = d.c.cols; ea.n = n; ea.sides = 2;
-    std::memcpy(ea.active, c->buf.active, sizeof ea.active);
-    HIP_TRY(c, equalize_enqueue(st, ea));
-    c->buf.img[0] = ea.dst[0]; c->buf.img[1] = ea.dst[1]; c->buf.img_row_stride = ea.dst_row_stride; c->buf.img_stream_stride = ea.dst_stream_stride;
-    q.out[0] = ea.dst[0]; q.out[1] = ea.dst[1]; q.out_row_stride = ea.dst_row_stride; q.out_stream_stride = ea.dst_stream_stride;
+    // one placement for both modes of the slot: global equalisation (k_hist_u8, k_equalize_apply) or CLAHE (k_clahe_lut, k_clahe_apply)
+    const int32_t dst_row_stride = in_place ? c->buf.img_row_stride : c->up_stride;
+    const size_t dst_stream_stride = in_place ? c->buf.img_stream_stride : c->up_stream_stride;
+    auto place = [&](auto& x) {
+      for (int k = 0; k < 2; ++k) { x.src[k] = c->rect.on ? q.keep[k] : c->buf.img[k]; x.dst[k] = c->upload[set][k]; }
+      x.src_row_stride = c->rect.on ? c->up_stride : c->buf.img_row_stride;
+      x.src_stream_stride = c->rect.on ? c->up_stream_stride : c->buf.img_stream_stride;
+      x.dst_row_stride = dst_row_stride; x.dst_stream_stride = dst_stream_stride;
+      x.rows = d.c.rows; x.cols = d.c.cols; x.n = n; x.sides = 2;
+      std::memcpy(x.active, c->buf.active, sizeof x.active);
+    };
+    if (q.clahe) { ClaheArgs ca = q.geo; place(ca); ca.luts = q.luts; HIP_TRY(c, clahe_enqueue(st, ca)); }
+    else { EqArgs ea; place(ea); ea.hist = q.hist; HIP_TRY(c, equalize_enqueue(st, ea)); }
+    for (int k = 0; k < 2; ++k) { c->buf.img[k] = c->upload[set][k]; q.out[k] = c->upload[set][k]; }
+    c->buf.img_row_stride = q.out_row_stride = dst_row_stride; c->buf.img_stream_stride = q.out_stream_stride = dst_stream_stride;
   }
   const DevBuf bs = buf_set(c, set, c->img_override ? c->q0_frm : c->q0_img);
   dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * n);
@@ -401,21 +405,51 @@ VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_
 }
 
 // ---- histogram equalisation of the input pair (kernels_equalize.h) -------------------------------
+// The slot's switch.  geo null: global equalisation, else CLAHE with what clahe_geometry made of the caller's arguments.  The two modes
+// exclude each other; switching one off while the other is on changes nothing.
+static int eq_switch(vslam_ctx* c, const char* who, bool on, const ClaheArgs* geo, double clip_limit) {
+  const bool clahe = geo != nullptr;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, std::string(who) + " called inside a frame");
+  if (c->eq.on && c->eq.clahe != clahe)
+    return !on ? VSLAM_OK : fail(c, VSLAM_ERR_STATE, std::string(who) + (clahe ? ": global equalisation is on (vslam_set_equalization)" : ": CLAHE is on (vslam_set_clahe)"));
+  const bool same = !clahe || (c->eq.clip_limit == clip_limit && c->eq.geo.tiles_x == geo->tiles_x && c->eq.geo.tiles_y == geo->tiles_y);
+  if (on ? (c->eq.on && same) : !c->eq.on) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the tables and the slabs
+  eq_free(c);
+  if (!on) return VSLAM_OK;
+  hipError_t e;
+  if (!clahe) {
+    e = c->eq.mem.alloc(&c->eq.hist, (size_t)c->B * 2 * 256);
+    if (e == hipSuccess) e = hipMemset(c->eq.hist, 0, (size_t)c->B * 2 * 256 * sizeof(uint32_t));
+  } else {
+    c->eq.geo = *geo; c->eq.clip_limit = clip_limit;
+    const size_t nl = (size_t)c->B * 2 * geo->tiles_x * geo->tiles_y * 256;
+    e = c->eq.mem.alloc(&c->eq.luts, nl);
+    if (e == hipSuccess) e = hipMemset(c->eq.luts, 0, nl);
+  }
+  c->eq.on = e == hipSuccess;
+  c->eq.clahe = c->eq.on && clahe;
+  if (e == hipSuccess) e = eq_keep_sync(c);
+  if (e != hipSuccess) { eq_free(c); return fail(c, VSLAM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
 VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_equalization called inside a frame");
   if ((size_t)c->cfg.c.rows * c->cfg.c.cols > (size_t)VS_EQ_MAX_PIXELS) return fail(c, VSLAM_ERR_INVALID, "vslam_set_equalization: more than 2^24 pixels per image");
-  if ((on != 0) == c->eq.on) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  sync_all(c);                     // the frames in flight still read the table and the slabs
-  eq_free(c);
-  if (!on) return VSLAM_OK;
-  hipError_t e = c->eq.mem.alloc(&c->eq.hist, (size_t)c->B * 2 * 256);
-  if (e == hipSuccess) e = hipMemset(c->eq.hist, 0, (size_t)c->B * 2 * 256 * sizeof(uint32_t));
-  c->eq.on = e == hipSuccess;
-  if (e == hipSuccess) e = eq_keep_sync(c);
-  if (e != hipSuccess) { eq_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_equalization: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  return eq_switch(c, "vslam_set_equalization", on != 0, nullptr, 0);
+}
+
+// ---- CLAHE of the input pair: the second mode of the equalisation slot (kernels_clahe.h) ----------
+VS_API int vslam_set_clahe(vslam_ctx* c, int on, double clip_limit, int tiles_x, int tiles_y) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_clahe called inside a frame");
+  ClaheArgs geo;
+  std::memset(&geo, 0, sizeof geo);
+  const char* why = "";
+  if (on && !clahe_geometry(c->cfg.c.rows, c->cfg.c.cols, clip_limit, tiles_x, tiles_y, geo, &why)) return fail(c, VSLAM_ERR_INVALID, std::string("vslam_set_clahe: ") + why);
+  return eq_switch(c, "vslam_set_clahe", on != 0, &geo, clip_limit);
 }
 
 // ---- colour input (kernels_gray.h) ---------------------------------------------------------------

@@ -343,7 +343,16 @@ VS_API int vslam_get_equalized_images(vslam_ctx* c, int s, uint8_t* left, uint8_
 }
 VS_API int vslam_get_equalization_histograms(vslam_ctx* c, int s, uint32_t* hist512) {
   if (int rc = eq_readable(c, s, "vslam_get_equalization_histograms")) return rc;
+  if (c->eq.clahe) return fail(c, VSLAM_ERR_STATE, "vslam_get_equalization_histograms: the context runs CLAHE, which keeps tables per tile (vslam_get_clahe_luts)");
   if (!hist512) return fail(c, VSLAM_ERR_INVALID, "vslam_get_equalization_histograms: null output");
   HIP_TRY(c, hipMemcpy(hist512, c->eq.hist + (size_t)s * 512, 512 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return VSLAM_OK;
+}
+VS_API int vslam_get_clahe_luts(vslam_ctx* c, int s, uint8_t* luts) {
+  if (int rc = eq_readable(c, s, "vslam_get_clahe_luts")) return rc;
+  if (!c->eq.clahe) return fail(c, VSLAM_ERR_STATE, "vslam_get_clahe_luts: the context runs global equalisation, not CLAHE");
+  if (!luts) return fail(c, VSLAM_ERR_INVALID, "vslam_get_clahe_luts: null output");
+  const size_t nl = (size_t)2 * c->eq.geo.tiles_x * c->eq.geo.tiles_y * 256;
+  HIP_TRY(c, hipMemcpy(luts, c->eq.luts + (size_t)s * nl, nl, hipMemcpyDeviceToHost));
   return VSLAM_OK;
 }

@@ -185,6 +185,15 @@ VS_API int vslam_rgbd_get_equalized(vslam_rgbd* r, int32_t stream, uint8_t* imag
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_equalized") : r->d.get_equalized(stream, image);
 }
+// ---- CLAHE of the intensity image, the equalisation slot's second mode (kernels_clahe.h): the device-resident loop only ----
+VS_API int vslam_rgbd_set_clahe(vslam_rgbd* r, int on, double clip_limit, int tiles_x, int tiles_y) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_set_clahe") : r->d.set_clahe(on, clip_limit, tiles_x, tiles_y);
+}
+VS_API int vslam_rgbd_get_clahe_luts(vslam_rgbd* r, int32_t stream, uint8_t* luts) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_clahe_luts") : r->d.get_clahe_luts(stream, luts);
+}
 // ---- colour input (kernels_gray.h): the device-resident loop only ----
 static int rgbd_color_host_refusal(vslam_rgbd* r, const char* what) {
   r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes grey frames only; use the device-resident loop";

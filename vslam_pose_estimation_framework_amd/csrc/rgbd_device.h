@@ -277,10 +277,29 @@ public:
   // ---- histogram equalisation of the intensity image (kernels_equalize.h): opt-in, its own allocations, nothing launched while eq.on is
   // false.  The depth image is untouched.  In place in the image the detector reads (the staged copy of a host frame, the undistorted
   // image); a caller's device image without undistortion is equalised into eq.img, so that caller memory is never written.
+  // CLAHE (kernels_clahe.h) is the slot's second mode: the same routing and the same place in the launch sequence, the tables [B][tilesY]
+  // [tilesX][256] instead of the count table.  The two modes exclude each other; switching one off while the other is on changes nothing.
   int set_equalization(int on) {
     if (pending) { err = "vslam_rgbd_set_equalization: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if ((size_t)p.rows * p.cols > (size_t)VS_EQ_MAX_PIXELS) { err = "vslam_rgbd_set_equalization: more than 2^24 pixels per image"; return VSLAM_ERR_INVALID; }
-    if ((on != 0) == eq.on) return VSLAM_OK;
+    return eq_switch("vslam_rgbd_set_equalization", on != 0, nullptr, 0);
+  }
+  int set_clahe(int on, double clip_limit, int tiles_x, int tiles_y) {
+    if (pending) { err = "vslam_rgbd_set_clahe: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    ClaheArgs geo{};
+    const char* why = "";
+    if (on && !clahe_geometry(p.rows, p.cols, clip_limit, tiles_x, tiles_y, geo, &why)) { err = std::string("vslam_rgbd_set_clahe: ") + why; return VSLAM_ERR_INVALID; }
+    return eq_switch("vslam_rgbd_set_clahe", on != 0, &geo, clip_limit);
+  }
+  int eq_switch(const char* who, bool on, const ClaheArgs* geo, double clip_limit) {
+    const bool clahe = geo != nullptr;
+    if (eq.on && eq.clahe != clahe) {
+      if (!on) return VSLAM_OK;
+      err = std::string(who) + (clahe ? ": global equalisation is on (vslam_rgbd_set_equalization)" : ": CLAHE is on (vslam_rgbd_set_clahe)");
+      return VSLAM_ERR_STATE;
+    }
+    const bool same = !clahe || (eq.clip_limit == clip_limit && eq.geo.tiles_x == geo->tiles_x && eq.geo.tiles_y == geo->tiles_y);
+    if (on ? (eq.on && same) : !eq.on) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
     (void)hipStreamSynchronize(q2);
@@ -290,12 +309,31 @@ public:
     Equal u{};
     u.img_stride = (p.cols + 15) & ~15;
     u.img_stream = (size_t)p.rows * u.img_stride;
-    hipError_t e = eq_mem.alloc(&u.hist, (size_t)B * 256);
+    hipError_t e;
+    if (clahe) {
+      u.geo = *geo; u.clip_limit = clip_limit;
+      const size_t nl = (size_t)B * geo->tiles_x * geo->tiles_y * 256;
+      e = eq_mem.alloc(&u.luts, nl);
+      if (e == hipSuccess) e = hipMemset(u.luts, 0, nl);
+    } else {
+      e = eq_mem.alloc(&u.hist, (size_t)B * 256);
+      if (e == hipSuccess) e = hipMemset(u.hist, 0, (size_t)B * 256 * sizeof(uint32_t));
+    }
     if (e == hipSuccess) e = eq_mem.alloc(&u.img, u.img_stream * (size_t)B);
-    if (e == hipSuccess) e = hipMemset(u.hist, 0, (size_t)B * 256 * sizeof(uint32_t));
-    if (e != hipSuccess) { eq_free(); err = std::string("vslam_rgbd_set_equalization: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    u.on = true;
+    if (e != hipSuccess) { eq_free(); err = std::string(who) + ": " + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    u.on = true; u.clahe = clahe;
     eq = u;
+    return VSLAM_OK;
+  }
+  // uint8 [tilesY][tilesX][256]: the tables of the image the last finished frame of `stream` was processed on
+  int get_clahe_luts(int stream, uint8_t* luts) {
+    if (int rc = readable(stream)) return rc;
+    if (!eq.on || !eq.clahe || !eq.have_frame) { err = "vslam_rgbd_get_clahe_luts: no frame has run under CLAHE since vslam_rgbd_set_clahe / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    if (!luts) { err = "vslam_rgbd_get_clahe_luts: null output"; return VSLAM_ERR_INVALID; }
+    (void)hipSetDevice(ic->device);
+    const size_t nl = (size_t)eq.geo.tiles_x * eq.geo.tiles_y * 256;
+    const hipError_t e = hipMemcpy(luts, eq.luts + (size_t)stream * nl, nl, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
     return VSLAM_OK;
   }
   // the equalised image the last finished frame of `stream` was processed on (dense)
@@ -447,6 +485,7 @@ private:
     uint32_t* hist; uint8_t* img; int32_t img_stride; size_t img_stream;
     const uint8_t* src; int32_t src_stride; size_t src_stream;
     uint8_t* out; int32_t out_stride; size_t out_stream;
+    bool clahe; double clip_limit; uint8_t* luts; ClaheArgs geo;     // the second mode: CLAHE, its tables [B][tilesY][tilesX][256]
   } eq{};
   DeviceStore eq_mem;
   // colour input: off while col.format is VSLAM_PIXEL_GRAY8.  The grey image [B] at the input size rows x cols (allocated with the first frame
@@ -720,12 +759,14 @@ private:
                                               und.img_stream, und.img_stride, rows, cols, B));
     // the image equalised, behind the undistortion and ahead of the detector, once per frame like it
     if (eq.on) {
-      EqArgs ea{};
-      ea.src[0] = eq.src; ea.src_row_stride = eq.src_stride; ea.src_stream_stride = eq.src_stream;
-      ea.dst[0] = eq.out; ea.dst_row_stride = eq.out_stride; ea.dst_stream_stride = eq.out_stream;
-      ea.hist = eq.hist; ea.rows = rows; ea.cols = cols; ea.n = B; ea.sides = 1;
-      std::memcpy(ea.active, bs.active, sizeof ea.active);
-      (void)equalize_enqueue(q, ea);
+      auto place = [&](auto& x) {
+        x.src[0] = eq.src; x.src_row_stride = eq.src_stride; x.src_stream_stride = eq.src_stream;
+        x.dst[0] = eq.out; x.dst_row_stride = eq.out_stride; x.dst_stream_stride = eq.out_stream;
+        x.rows = rows; x.cols = cols; x.n = B; x.sides = 1;
+        std::memcpy(x.active, bs.active, sizeof x.active);
+      };
+      if (eq.clahe) { ClaheArgs ca = eq.geo; place(ca); ca.luts = eq.luts; (void)clahe_enqueue(q, ca); }
+      else { EqArgs ea{}; place(ea); ea.hist = eq.hist; (void)equalize_enqueue(q, ea); }
     }
     enqueue_attempt(bs);
     enqueue_tail(bs);
