@@ -281,7 +281,8 @@ int vslam_clahe_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t col
  * vslam_set_color_input: while format is not VSLAM_PIXEL_GRAY8, vslam_process_host, vslam_process_device and vslam_frame_begin take
  *   interleaved colour images of the size the context otherwise expects (raw_rows x raw_cols while rectification is set, else rows x
  *   cols); row_stride and image_stride are in BYTES, row_stride >= channels * cols (else VSLAM_ERR_INVALID).  Host images are copied to
- *   colour slabs of the context's own; device images are READ by this kernel only and never written.  The grey pair is written where the
+ *   colour slabs of the context's own; device images are READ by this kernel only (and, while vslam_enable_map_colors is on, once more
+ *   behind the frame's last launch: see there) and never written.  The grey pair is written where the
  *   next stage reads.  A switched-off stream is neither read nor written.  Synchronises the context; VSLAM_ERR_STATE between
  *   vslam_frame_begin and the end of that frame; VSLAM_ERR_INVALID for a format outside 0 .. 4.  The switch survives vslam_reset and
  *   vslam_reset_stream(s).  GRAY8 turns it off and frees its allocations; nothing is launched while off.
@@ -399,6 +400,31 @@ int vslam_enable_map(vslam_ctx* ctx, int32_t capacity_per_stream);
 int vslam_get_map_size(vslam_ctx* ctx, int stream, int32_t* n);
 int vslam_get_map(vslam_ctx* ctx, int stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz,
                   int32_t* info /* first_frame, last_frame, updates per entry */, uint8_t* desc);
+/* ---- the map's colours (opt-in, on top of the landmark map and colour input; csrc/kernels_map_color.h) ----------------
+ * Every map entry gets the colour of its landmark's LEFT keypoint (xL, yL) in the frame's left colour image at the landmark's last update
+ * (the frames in which the entry's last_frame is written), as (r, g, b) whatever the input's channel order; alpha is ignored.  While
+ * rectification is set the keypoint lies in the rectified image and the colour image is the raw one: each colour plane is then remapped
+ * through the left map with vslam_remap_u8's integer arithmetic at that pixel (four taps, taps outside the raw image count as 0).  One
+ * kernel (k_map_color) directly behind the map's on the frame queue, on vslam_process_* / vslam_frame_finish.  Integer arithmetic only.
+ * vslam_enable_map_colors: needs the map and a colour format (VSLAM_ERR_STATE without either, and inside a frame); synchronises.  Enabled
+ *   between frames of a running sequence, an entry reads (0, 0, 0) until its next update; an entry the map refused (capacity) has no
+ *   colour.  0 frees the store; so do vslam_enable_map (any capacity: ids start over) and vslam_set_color_input(ctx, VSLAM_PIXEL_GRAY8).
+ *   The colours follow the map through vslam_reset and vslam_reset_stream(s); a switched-off stream is neither read nor written.
+ *   LIFETIME of device images while the switch is on: the caller's LEFT image passed to vslam_process_device / vslam_frame_begin is read
+ *   again behind the frame's last launch, so it must stay valid and unchanged until that frame has ended (vslam_synchronize or any
+ *   read-back); host images are copied and may be reused at once, as before.
+ * vslam_get_map_colors: rgb of entries first_id .. first_id + n - 1, n = min(cap, size - first_id), like vslam_get_map; rgb may be NULL.
+ *   Synchronises; VSLAM_ERR_STATE while the switch is off.
+ * vslam_sample_color_u8: the gather stand-alone on one host image (rows x cols pixels, row_stride BYTES per row, any alignment) at n integer
+ *   pixels xy = (x, y): direct when both maps are NULL (a pixel outside the image gives (0, 0, 0)), else through the map pair (map_rows x
+ *   map_cols, dense, vslam_set_rectification's format; a pixel outside the map gives (0, 0, 0)).  n == 0: VSLAM_OK, nothing written.
+ *   VSLAM_ERR_INVALID: null pointers, negative sizes, row_stride < channels * cols, format outside 1 .. 4, one map without the other, a
+ *   map_a entry >= 1024; the context stays usable. */
+int vslam_enable_map_colors(vslam_ctx* ctx, int on);
+int vslam_get_map_colors(vslam_ctx* ctx, int stream, int32_t first_id, int32_t cap, int32_t* n, uint8_t* rgb /* [cap][3] */);
+int vslam_sample_color_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride_bytes, int format,
+                          const int16_t* map_xy, const uint16_t* map_a, int32_t map_rows, int32_t map_cols, /* both NULL: direct */
+                          const int16_t* xy /* [n][2] */, int32_t n, uint8_t* rgb /* [n][3] */);
 /* ---- landmark observations (opt-in, on top of the landmark map) -------------------------------------------------------------
  * Which landmark was seen in which frame at which pixels: with vslam_get_poses and vslam_get_map, the input of a mapping or
  * bundle-adjustment back end, written on the device without a host round trip per frame.
@@ -770,6 +796,18 @@ int vslam_rgbd_enable_observations(vslam_rgbd* t, int32_t capacity_per_stream);
 int vslam_rgbd_get_observation_count(vslam_rgbd* t, int32_t stream, int32_t* n);
 int vslam_rgbd_get_observations(vslam_rgbd* t, int32_t stream, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame2, float* xy, double* cam);
 int vslam_rgbd_get_point_ids(vslam_rgbd* t, int32_t stream, int32_t cap, int32_t* n, int32_t* ids);
+/* The map's colours in this mode (opt-in; the definition above vslam_enable_map_colors): the colour of the pixel of RgbdList::xy — a float,
+ * rounded half to even in float32 and clamped to the image first — in the frame's colour image, written exactly in the frames that create
+ * or update the entry (when its row is written), through the undistortion map when undistortion is on.  One kernel directly behind the
+ * map's on the same queue, once per frame (after the last registration attempt), inside the captured launch sequence as well.
+ * vslam_rgbd_enable_map_colors: VSLAM_ERR_STATE without the map or a colour format, with a frame in flight, and on the host-driven loop;
+ *   0 frees the store, and so do vslam_rgbd_enable_map and vslam_rgbd_set_color_input(t, VSLAM_PIXEL_GRAY8); vslam_rgbd_reset clears
+ *   the colours with the map and leaves them enabled.  LIFETIME: a host frame is coloured from the tracker's staged copy; a DEVICE frame
+ *   (vslam_rgbd_submit_batch_device) is read again by this kernel, so the caller's image must stay valid and unchanged until vslam_rgbd_wait
+ *   has returned (the frame's last registration attempt, and with it this kernel, may run inside vslam_rgbd_wait).
+ * vslam_rgbd_get_map_colors: like vslam_rgbd_get_map; VSLAM_ERR_STATE while the switch is off. */
+int vslam_rgbd_enable_map_colors(vslam_rgbd* t, int on);
+int vslam_rgbd_get_map_colors(vslam_rgbd* t, int32_t stream, int32_t first_id, int32_t cap, int32_t* n, uint8_t* rgb /* [cap][3] */);
 /* Undistortion of raw frames in this mode (opt-in; csrc/kernels_undistort.h): the counterpart of vslam_set_rectification for
  * one camera with a depth image registered to it (TUM, Kinect / RealSense streams).  One map pair in vslam_set_rectification's format at
  * the tracker's rows x cols serves image and depth.  The image is remapped like vslam_remap_u8 (bilinear, the same kernel); the depth

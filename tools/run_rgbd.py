@@ -5,7 +5,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
 
     python tools/run_rgbd.py <folder> [--config icl|tum|xtion] [--intrinsics freiburg1|freiburg2|freiburg3|icl|fx,fy,cx,cy]
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
-                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color]
+                             [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color [--map-color]]
                              [--clahe [CLIP]] [--clahe-tiles X,Y]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
@@ -25,7 +25,9 @@ untouched), behind --undistort and ahead of the detector: dim or low-contrast se
 --clahe [CLIP] runs cv::CLAHE (clip limit CLIP, 40.0 without a value; --clahe-tiles X,Y, 8,8 by default) on the intensity image in the place of
 --equalize (not together with it): unevenly lit sequences.  Device-resident loop only.
 --color hands the colour frames over as decoded and converts them to grey on the GPU (vslam_rgbd_set_color_input: the same integers as the
-host conversion without the flag), ahead of --undistort and --equalize.  Device-resident loop only."""
+host conversion without the flag), ahead of --undistort and --equalize.  Device-resident loop only.
+--map-color (with --color and --map / --observations) samples every landmark's colour on the GPU (vslam_rgbd_enable_map_colors: the pixel of
+its point at the last update, through the --undistort map when that is on): red green blue in the PLY, map_rgb in the bundle."""
 import argparse
 import os
 import sys
@@ -104,7 +106,10 @@ def distortion_of(undistort, intrinsics):
 
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
-        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8)):
+        gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
+        map_color=False):
+    if map_color and not (color and (map_path or obs_path)):
+        raise SystemExit("--map-color needs --color and --map or --observations")
     seq = io_formats.TumRgbdSequence(folder)
     n = len(seq) if max_frames <= 0 else min(len(seq), max_frames)
     if n == 0:
@@ -150,6 +155,11 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             log("CLAHE on the GPU (cv::CLAHE, clip limit %g, %d x %d tiles, on every intensity image%s)" % (clahe, clahe_tiles[0], clahe_tiles[1], ", behind the undistortion" if dist is not None else ""))
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
+        if map_color and fmt == color_mod.GRAY8:
+            log("--map-color: the folder's images are grey, the map stays without colours")
+            map_color = False
+        if map_color:
+            tr.enable_map_colors(True)
         if obs_path:
             tr.enable_observations(n * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
         for k in range(n):
@@ -169,6 +179,8 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
                     k, "tracking" if fi.status == 1 else "localizing", fi.n_points, n_temp, fi.n_tracked, fi.n_inliers, fi.n_active_landmarks))
         if want_map:
             lm_map = tr.map(0)
+            if map_color:
+                lm_map["rgb"] = tr.map_colors(0)
         if obs_path:
             obs = tr.observations(0)
     finally:
@@ -182,7 +194,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
         result["map"] = lm_map
     if map_path:
-        io_formats.write_ply(map_path, lm_map["xyz"], id=lm_map["id"], first_frame=lm_map["first_frame"], last_frame=lm_map["last_frame"],
+        io_formats.write_ply(map_path, lm_map["xyz"], lm_map.get("rgb"), id=lm_map["id"], first_frame=lm_map["first_frame"], last_frame=lm_map["last_frame"],
                              updates=lm_map["updates"])
         log("landmark map: %d landmarks -> %s" % (len(lm_map["id"]), map_path))
     if obs_path:
@@ -253,6 +265,8 @@ def parse_args(argv=None):
     ap.add_argument("--clahe-tiles", type=_tiles, default=(8, 8), metavar="X,Y", help="the tile grid of --clahe (8,8)")
     ap.add_argument("--color", action="store_true", help="hand the colour frames over as decoded and convert them to grey on the GPU, ahead of "
                     "--undistort and --equalize (without it: converted on the host, frame by frame)")
+    ap.add_argument("--map-color", action="store_true", help="with --color and --map / --observations: the colour of every landmark (the pixel of its "
+                    "point at the last update, sampled on the GPU) as red green blue in the PLY and map_rgb in the bundle")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):          # "--undistort -0.28,0.07,0,0": argparse would read the negative list as an option
         if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
@@ -261,13 +275,16 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.clahe is not None and a.equalize:
         ap.error("--clahe and --equalize exclude each other: one equalisation ahead of the detector")
+    if a.map_color and not (a.color and (a.map or a.observations)):
+        ap.error("--map-color needs --color and --map or --observations")
     return a
 
 
 def main(argv=None):
     a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
-        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles)
+        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
+        map_color=a.map_color)
 
 
 if __name__ == "__main__":

@@ -375,6 +375,19 @@ class CApi(object):
         return dict(id=np.arange(int(first), int(first) + k, dtype=np.int32), xyz=xyz[:k].copy(), first_frame=info[:k, 0].copy(),
                     last_frame=info[:k, 1].copy(), updates=info[:k, 2].copy(), desc=desc[:k].copy())
 
+    # -- the map's colours (vslam_enable_map_colors; needs the map and colour input) ------------------------------------
+    def enable_map_colors(self, on=True):
+        """Keep the colour of every map entry (its left keypoint's pixel in the frame's left colour image at the last update)."""
+        self.check(self.fn("enable_map_colors")(self.ctx, C.c_int(1 if on else 0)))
+
+    def map_colors(self, stream=0, first=0):
+        """uint8 [n, 3] (r, g, b) of landmarks first .. of `stream`, in map() order."""
+        cap = max(self.map_size(stream) - int(first), 0)
+        n = C.c_int32()
+        rgb = np.zeros((max(cap, 1), 3), np.uint8)
+        self.check(self.fn("get_map_colors")(self.ctx, C.c_int(stream), C.c_int32(int(first)), C.c_int32(cap), C.byref(n), _p(rgb, C.c_uint8)))
+        return rgb[:n.value].copy()
+
     # -- landmark observations (vslam_enable_observations; needs the map) ----------------------------------------------
     def enable_observations(self, capacity_per_stream):
         """Log (landmark id, frame, keypoints) of every point that carries a map id, capacity_per_stream entries per stream; 0 turns it off."""
@@ -765,6 +778,34 @@ class CApi(object):
                                       _p(dst, C.c_uint8)))
         return dst
 
+    def sample_color_u8(self, image, fmt, xy, maps=None, cols=None):
+        """vslam_sample_color_u8: image as in gray_u8 ([rows, cols, channels], or [rows, bytes] with cols, strides and alignment passed on);
+        xy int16 [n, 2] (x, y); maps None or (map_xy int16 [R, C, 2], map_a uint16 [R, C]) -> uint8 [n, 3] (r, g, b)."""
+        img = np.asarray(image)
+        if img.ndim == 3:
+            img = np.ascontiguousarray(img, np.uint8)
+            cols = img.shape[1]
+            img = img.reshape(img.shape[0], -1)
+        elif img.dtype != np.uint8 or img.ndim != 2 or (img.shape[1] > 1 and img.strides[1] != 1) or (img.shape[0] > 1 and img.strides[0] < img.shape[1]):
+            img = np.ascontiguousarray(image, np.uint8)
+        if img.ndim != 2 or cols is None:
+            raise ValueError("sample_color_u8: a [rows, cols, channels] array, or a [rows, bytes] array together with cols")
+        rows = img.shape[0]
+        stride = img.strides[0] if rows > 1 else max(img.shape[1], 1)
+        pts = np.ascontiguousarray(xy, np.int16).reshape(-1, 2)
+        mxy = ma = None
+        mr = mc = 0
+        if maps is not None:
+            mxy = np.ascontiguousarray(maps[0], np.int16)
+            ma = np.ascontiguousarray(maps[1], np.uint16)
+            assert mxy.shape[:2] == ma.shape and mxy.shape[2] == 2
+            mr, mc = ma.shape
+        rgb = np.zeros((max(len(pts), 1), 3), np.uint8)
+        self.check(self.fn("sample_color_u8")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(int(cols)), C.c_int32(stride),
+                                              C.c_int(int(fmt)), None if mxy is None else _p(mxy, C.c_int16), None if ma is None else _p(ma, C.c_uint16),
+                                              C.c_int32(mr), C.c_int32(mc), _p(pts, C.c_int16), C.c_int32(len(pts)), _p(rgb, C.c_uint8)))
+        return rgb[:len(pts)].copy()
+
     def remap_u8(self, image, map_xy, map_a, cols=None):
         """vslam_remap_u8: image is rows x stride (cols <= stride bytes used), the maps give the output size."""
         img = np.ascontiguousarray(image, np.uint8)
@@ -909,6 +950,18 @@ class _RgbdMapApi(object):
         k = n.value
         return dict(id=np.arange(int(first), int(first) + k, dtype=np.int32), xyz=xyz[:k].copy(), first_frame=info[:k, 0].copy(),
                     last_frame=info[:k, 1].copy(), updates=info[:k, 2].copy(), desc=desc[:k].copy())
+
+    def enable_map_colors(self, on=True):
+        """Keep the colour of every map entry (the pixel of its point in the frame's colour image when the entry is written)."""
+        self._check(self.lib.vslam_rgbd_enable_map_colors(self.h, C.c_int(1 if on else 0)))
+
+    def map_colors(self, stream=0, first=0):
+        """uint8 [n, 3] (r, g, b) of landmarks first .. of `stream`, in map() order."""
+        cap = max(self.map_size(stream) - int(first), 0)
+        n = C.c_int32()
+        rgb = np.zeros((max(cap, 1), 3), np.uint8)
+        self._check(self.lib.vslam_rgbd_get_map_colors(self.h, C.c_int32(stream), C.c_int32(int(first)), C.c_int32(cap), C.byref(n), _p(rgb, C.c_uint8)))
+        return rgb[:n.value].copy()
 
     def enable_observations(self, capacity_per_stream):
         """Log (landmark id, frame, keypoint, camera coordinates) of every point that carries a map id; needs the map; 0 turns it off."""

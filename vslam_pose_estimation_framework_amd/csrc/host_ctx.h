@@ -104,6 +104,9 @@ struct vslam_ctx {
   // the observation log on top of it (vslam_enable_observations, kernels_obs.h): off while cap == 0; freed by vslam_enable_observations(0),
   // vslam_enable_map(0) and destroy
   struct ObsStore { int32_t cap = 0; DevObs d{}; DeviceStore mem; } obs;
+  // the colour of every map entry (vslam_enable_map_colors, kernels_map_color.h): [B][map.cap] words (r, g, b, 0); off while rgb is null;
+  // freed by vslam_enable_map_colors(0), any vslam_enable_map, vslam_set_color_input(GRAY8) and destroy
+  struct MapColors { uint32_t* rgb = nullptr; DeviceStore mem; } mapcol;
   int sticky = VSLAM_OK;
 };
 
@@ -554,7 +557,12 @@ static void obs_free(vslam_ctx* c) {
   c->obs.d = DevObs{};
   c->obs.cap = 0;
 }
+static void mapcol_free(vslam_ctx* c) {
+  c->mapcol.mem.release();
+  c->mapcol.rgb = nullptr;
+}
 static void map_free(vslam_ctx* c) {
+  mapcol_free(c);                    // the colours are indexed by the map's ids
   c->map.mem.release();
   c->map.d = DevMap{};
   c->map.cap = 0;

@@ -963,3 +963,38 @@ VS_API int vslam_gray_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t
   if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)cols, dd, (size_t)ostride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
   return k.finish();
 }
+
+// ---- the colour of n pixels of one host image, direct or through a remap map pair (kernels_map_color.h) --------------
+VS_API int vslam_sample_color_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int format, const int16_t* map_xy,
+                                 const uint16_t* map_a, int32_t map_rows, int32_t map_cols, const int16_t* xy, int32_t n, uint8_t* rgb) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 0 || cols < 0 || n < 0) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: negative size");
+  if (format < VSLAM_PIXEL_BGR8 || format > VSLAM_PIXEL_RGBA8) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: unknown pixel format");
+  if ((map_xy == nullptr) != (map_a == nullptr)) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: both maps or none");
+  const bool mapped = map_xy != nullptr;
+  if (mapped && (map_rows < 0 || map_cols < 0)) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: negative map size");
+  const int64_t wb = (int64_t)gray_channels(format) * cols;
+  if ((int64_t)row_stride < wb || (!src && rows > 0 && cols > 0)) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: bad argument");
+  if (n == 0) return VSLAM_OK;
+  if (!xy || !rgb) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: bad argument");
+  const size_t nm = mapped ? (size_t)map_rows * (size_t)map_cols : 0;
+  if (mapped && !rect_maps_ok(map_a, nm)) return fail(c, VSLAM_ERR_INVALID, "sample_color_u8: interpolation table index >= 1024");
+  Call k(c, c->stream);
+  const bool empty = rows == 0 || cols == 0;
+  const size_t bytes = empty ? 0 : (size_t)(rows - 1) * row_stride + (size_t)wb;
+  const size_t off = (size_t)((uintptr_t)src & 15u);       // the device copy keeps the caller's alignment: rows start where they would in place
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16);
+  k.up_to(ds + off, src, bytes);
+  ColorSrc cs{};
+  cs.img = ds + off; cs.row_stride = row_stride; cs.rows = rows; cs.cols = cols; cs.format = format;
+  if (mapped) { cs.map_xy = k.up(map_xy, nm * 2); cs.map_a = k.up(map_a, nm); cs.map_stride = map_cols; cs.map_rows = map_rows; cs.map_cols = map_cols; }
+  const int16_t* dxy = k.up(xy, (size_t)n * 2);
+  uint32_t* dw = k.dev<uint32_t>((size_t)n);
+  if (k.ok()) hipLaunchKernelGGL(k_sample_color, dim3((n + 255) / 256), dim3(256), 0, c->stream, cs, dxy, n, dw);
+  std::vector<uint32_t> w((size_t)n);
+  k.down(w.data(), dw, (size_t)n);
+  const int rc = k.finish();
+  if (rc != VSLAM_OK) return rc;
+  for (int32_t i = 0; i < n; ++i) { rgb[3 * i] = (uint8_t)w[i]; rgb[3 * i + 1] = (uint8_t)(w[i] >> 8); rgb[3 * i + 2] = (uint8_t)(w[i] >> 16); }
+  return VSLAM_OK;
+}

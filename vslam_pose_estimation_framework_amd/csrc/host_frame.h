@@ -122,6 +122,14 @@ static int frame_done(vslam_ctx* c) {
 static int cand_blocks(int n_streams) { return std::max(4, std::min(128, 7040 / std::max(n_streams, 1))); }
 // blocks per stream of k_recover_brief (four wavefronts each, one lost point per wavefront)
 static int recover_blocks(int n_streams) { return std::max(4, std::min(64, 1024 / std::max(n_streams, 1))); }
+// this frame's left colour image as k_map_color reads it: the raw image behind the left rectification map while rectifying
+static ColorSrc map_color_src(const vslam_ctx* c) {
+  const vslam_ctx::Col& q = c->col;
+  ColorSrc s{};
+  s.img = q.src[0]; s.stream_stride = q.src_stream_stride; s.row_stride = q.src_row_stride; s.rows = q.out_rows; s.cols = q.out_cols; s.format = q.format;
+  if (c->rect.on) { s.map_xy = c->rect.map_xy[0]; s.map_a = c->rect.map_a[0]; s.map_stride = c->rect.map_stride; s.map_rows = c->cfg.c.rows; s.map_cols = c->cfg.c.cols; }
+  return s;
+}
 static int launch_frame(vslam_ctx* c) {
   const int n = c->B;
   hipStream_t st = c->stream;
@@ -146,6 +154,8 @@ static int launch_frame(vslam_ctx* c) {
   if (c->map.cap) hipLaunchKernelGGL(k_map_commit, dim3(n), dim3(VS_MAP_WG), 0, st, c->cfg, bs, c->map.d);
   // the observation log, behind the ids k_map_commit has just left for this frame
   if (c->obs.cap) hipLaunchKernelGGL(k_obs_append, dim3(n), dim3(VS_OBS_WG), 0, st, c->cfg, bs, c->map.d, c->obs.d);
+  // the map's colours, from this frame's left colour image (through the left rectification map when rectifying) at the ids of this frame
+  if (c->mapcol.rgb) hipLaunchKernelGGL(k_map_color, dim3(n), dim3(VS_MAP_COLOR_WG), 0, st, c->cfg, bs, c->map.d, map_color_src(c), c->mapcol.rgb);
   HIP_TRY(c, hipGetLastError());
   return frame_done(c);
 }
@@ -250,7 +260,7 @@ static int set_raw_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int3
   return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], c->up_stride, c->up_stream_stride);
 }
 // Colour input: host pairs go to the colour slabs of this step's parity (upload_to with the byte width as cols), device pairs are read in
-// place (by k_gray_u8 only).  The grey pair is written where the next stage reads: the rectifier's raw slabs when rectifying, else
+// place (by k_gray_u8, and by k_map_color behind the frame's last launch while map colours are on).  The grey pair is written where the next stage reads: the rectifier's raw slabs when rectifying, else
 // upload[parity]; DevBuf::img points at upload[parity] either way, as it does for a grey host frame.
 static int set_color_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
   vslam_ctx::Col& q = c->col;
@@ -261,6 +271,15 @@ static int set_color_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, in
   if (row_stride < wb) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than channels * image width");
   ImgLoc o = {{L, R}, row_stride, image_stride};
   if (!on_device) {
+    // map colours: k_map_color read this parity's slab on the FRAME queue two steps ago, and the upload below is issued ahead of the wait in
+    // launch_image_pipeline — it waits for that frame here (without the switch k_gray_u8, on the image queue itself, is the slab's last reader).
+    // Every queue upload_to may copy on: its dense path takes img_override when set (the stage path of one stream: the frame queue itself,
+    // already in order behind k_map_color, hence skipped), its strided paths always the image queue.
+    if (c->mapcol.rgb && c->frm_pending[c->parity]) {
+      hipStream_t up[2] = {c->img_override ? c->img_override : c->stream_img, c->stream_img};
+      for (int k = 0; k < 2; ++k)
+        if (up[k] != c->stream && (k == 0 || up[k] != up[0])) HIP_TRY(c, hipStreamWaitEvent(up[k], c->ev_frm[c->parity], 0));
+    }
     const int rc = upload_to(c, L, R, row_stride, image_stride, rows, wb, q.slab[c->parity], q.stride, q.stream_stride, &o);
     if (rc != VSLAM_OK) return rc;
   }
@@ -460,6 +479,7 @@ VS_API int vslam_set_color_input(vslam_ctx* c, int format) {
   if (format == c->col.format) return VSLAM_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the slabs
+  if (format == VSLAM_PIXEL_GRAY8) mapcol_free(c);     // no colour left to sample
   col_free(c);
   c->col.format = format;
   const hipError_t e = col_slab_sync(c);

@@ -139,6 +139,39 @@ VS_API int vslam_get_map(vslam_ctx* c, int s, int32_t first_id, int32_t cap, int
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VSLAM_OK;
 }
+// ---- the map's colours (kernels_map_color.h) --------------------------------------------------------
+VS_API int vslam_enable_map_colors(vslam_ctx* c, int on) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_enable_map_colors called inside a frame");
+  if (on && !c->map.cap) return fail(c, VSLAM_ERR_STATE, "vslam_enable_map_colors needs the landmark map (vslam_enable_map): colours are indexed by its ids");
+  if (on && c->col.format == VSLAM_PIXEL_GRAY8) return fail(c, VSLAM_ERR_STATE, "vslam_enable_map_colors needs colour input (vslam_set_color_input)");
+  if ((on != 0) == (c->mapcol.rgb != nullptr)) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                        // no frame may still be writing the old store
+  mapcol_free(c);
+  if (!on) return VSLAM_OK;
+  uint32_t* rgb = nullptr;
+  hipError_t e = c->mapcol.mem.alloc_fill(&rgb, (size_t)c->B * (size_t)c->map.cap, 0, c->stream);     // (0, 0, 0) until an entry's next update
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { mapcol_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_enable_map_colors: ") + hipGetErrorString(e)); }
+  c->mapcol.rgb = rgb;
+  return VSLAM_OK;
+}
+VS_API int vslam_get_map_colors(vslam_ctx* c, int s, int32_t first_id, int32_t cap, int32_t* n, uint8_t* rgb) {
+  if (c && (!n || first_id < 0 || cap < 0)) return fail(c, VSLAM_ERR_INVALID, "vslam_get_map_colors: null count, negative first id or capacity");
+  int32_t size = 0;
+  int rc = map_size(c, s, &size);
+  if (rc) return rc;
+  if (!c->mapcol.rgb) return fail(c, VSLAM_ERR_STATE, "the map's colours are not enabled (vslam_enable_map_colors)");
+  const int32_t cnt = std::max(0, std::min(cap, size - first_id));
+  *n = cnt;
+  if (!cnt || !rgb) return VSLAM_OK;
+  std::vector<uint32_t> w((size_t)cnt);
+  HIP_TRY(c, d2h(c, w.data(), c->mapcol.rgb + (size_t)s * c->map.cap + (size_t)first_id, (size_t)cnt));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int32_t i = 0; i < cnt; ++i) { rgb[3 * i] = (uint8_t)w[i]; rgb[3 * i + 1] = (uint8_t)(w[i] >> 8); rgb[3 * i + 2] = (uint8_t)(w[i] >> 16); }
+  return VSLAM_OK;
+}
 // ---- the observation log (kernels_obs.h) ------------------------------------------------------------
 VS_API int vslam_enable_observations(vslam_ctx* c, int32_t cap) {
   if (!c) return VSLAM_ERR_INVALID;

@@ -159,6 +159,14 @@ VS_API int vslam_rgbd_get_point_ids(vslam_rgbd* r, int32_t stream, int32_t cap, 
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_point_ids") : r->d.get_point_ids(stream, cap, n, ids);
 }
+VS_API int vslam_rgbd_enable_map_colors(vslam_rgbd* r, int on) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_enable_map_colors") : r->d.enable_map_colors(on);
+}
+VS_API int vslam_rgbd_get_map_colors(vslam_rgbd* r, int32_t stream, int32_t first_id, int32_t cap, int32_t* n, uint8_t* rgb) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_map_colors") : r->d.get_map_colors(stream, first_id, cap, n, rgb);
+}
 // ---- undistortion of raw frames (kernels_undistort.h): the device-resident loop only ----
 static int rgbd_undistort_host_refusal(vslam_rgbd* r, const char* what) {
   r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes undistorted frames only; use the device-resident loop";

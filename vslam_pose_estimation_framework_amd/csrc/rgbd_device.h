@@ -160,6 +160,45 @@ public:
     mp.ocap = cap;
     return VSLAM_OK;
   }
+  // the map's colours (kernels_map_color.h): [B][cap] words (r, g, b, 0) and the kernel's per-sequence mark; they need the map and a colour
+  // format, and leave with either
+  int enable_map_colors(int on) {
+    if (pending) { err = "vslam_rgbd_enable_map_colors: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (on && !mp.cap) { err = "vslam_rgbd_enable_map_colors needs the landmark map (vslam_rgbd_enable_map): colours are indexed by its ids"; return VSLAM_ERR_STATE; }
+    if (on && !col.format) { err = "vslam_rgbd_enable_map_colors needs colour input (vslam_rgbd_set_color_input)"; return VSLAM_ERR_STATE; }
+    if ((on != 0) == (mc.rgb != nullptr)) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    mapcol_free();
+    drop_graph();                                   // a captured launch sequence holds the kernel (or lacks it)
+    if (!on) return VSLAM_OK;
+    RgbdMapColor d{};
+    hipError_t e = mapcol_mem.alloc_fill(&d.rgb, (size_t)B * (size_t)mp.cap, 0, q);      // (0, 0, 0) until an entry's next update
+    if (e == hipSuccess) e = mapcol_mem.alloc(&d.colored, (size_t)B);
+    // the frames so far are not coloured: the mark starts at every sequence's frame count, as the commit's does after its frame
+    std::vector<int32_t> fc((size_t)B);
+    for (int s = 0; s < B; ++s) fc[s] = hosts[s].frame_count;
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    if (e == hipSuccess) e = hipMemcpy(d.colored, fc.data(), fc.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { mapcol_free(); err = std::string("vslam_rgbd_enable_map_colors: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    mc = d;
+    return VSLAM_OK;
+  }
+  int get_map_colors(int stream, int32_t first_id, int32_t cap, int32_t* n, uint8_t* rgb) {
+    if (!n || first_id < 0 || cap < 0) { err = "vslam_rgbd_get_map_colors: null count, negative first id or capacity"; return VSLAM_ERR_INVALID; }
+    int32_t size = 0;
+    const int rc = map_ready(stream, false, &size);
+    if (rc) return rc;
+    if (!mc.rgb) { err = "the map's colours are not enabled (vslam_rgbd_enable_map_colors)"; return VSLAM_ERR_STATE; }
+    const int32_t cnt = std::max(0, std::min(cap, size - first_id));
+    *n = cnt;
+    if (!cnt || !rgb) return VSLAM_OK;
+    std::vector<uint32_t> w((size_t)cnt);
+    const hipError_t e = hipMemcpy(w.data(), mc.rgb + (size_t)stream * mp.cap + (size_t)first_id, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    for (int32_t i = 0; i < cnt; ++i) { rgb[3 * i] = (uint8_t)w[i]; rgb[3 * i + 1] = (uint8_t)(w[i] >> 8); rgb[3 * i + 2] = (uint8_t)(w[i] >> 16); }
+    return VSLAM_OK;
+  }
   // what every getter below checks first; *size: entries of the store the call reads
   int map_ready(int stream, bool log, int32_t* size) {
     if (int rc = readable(stream)) return rc;
@@ -359,6 +398,7 @@ public:
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
     (void)hipStreamSynchronize(q2);
+    if (format == VSLAM_PIXEL_GRAY8) mapcol_free();  // no colour left to sample
     col_free();
     drop_graph();                                   // a captured launch sequence holds the kernel (or lacks it)
     col.format = format;
@@ -468,6 +508,8 @@ private:
   // store is turned off or replaced (the inner context's allocation list only grows until destroy)
   RgbdMap mp{};
   DeviceStore map_mem, obs_mem;
+  RgbdMapColor mc{};             // the map's colours: off while mc.rgb is null
+  DeviceStore mapcol_mem;
   // undistortion of raw frames: off while und.on is false.  The maps at the tracker's size (rows padded to map_stride entries), the
   // undistorted images the image pipeline reads, and the raw depth images of a host frame (raw images go through d_img; the
   // undistorted depth images are d_depth).  raw_*: where this frame's raw images are — the staging buffers or the caller's device memory
@@ -544,8 +586,22 @@ private:
     und_mem.release();
     und = Undist{};
   }
+  void mapcol_free() {
+    mapcol_mem.release();
+    mc = RgbdMapColor{};
+  }
+  // this frame's colour image as k_rgbd_map_color reads it (col.src: the staged copy of a host frame, which the next submit overwrites, or the
+  // caller's device memory, which must stay as it is until wait() has returned: further attempts colour the frame from there); the raw
+  // image behind the undistortion map while undistorting
+  ColorSrc map_color_src() const {
+    ColorSrc s{};
+    s.img = col.src; s.stream_stride = col.src_stream; s.row_stride = col.src_stride; s.rows = col.rows; s.cols = col.cols; s.format = col.format;
+    if (und.on) { s.map_xy = und.map_xy; s.map_a = und.map_a; s.map_stride = und.map_stride; s.map_rows = p.rows; s.map_cols = p.cols; }
+    return s;
+  }
   void map_free() {
     obs_free();
+    mapcol_free();                                  // the colours are indexed by the map's ids
     map_mem.release();
     mp = RgbdMap{};
   }
@@ -558,6 +614,8 @@ private:
     if (e == hipSuccess) e = hipMemsetAsync(mp.committed, 0, nB * sizeof(int32_t), q);
     if (e == hipSuccess) e = hipMemsetAsync(mp.ids, 0xff, 2 * nB * (size_t)rb.MAXP * sizeof(int32_t), q);
     if (e == hipSuccess && mp.ocap) e = hipMemsetAsync(mp.ocount, 0, nB * sizeof(int32_t), q);
+    if (e == hipSuccess && mc.rgb) e = hipMemsetAsync(mc.rgb, 0, n * sizeof(uint32_t), q);
+    if (e == hipSuccess && mc.rgb) e = hipMemsetAsync(mc.colored, 0, nB * sizeof(int32_t), q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
     return e;
   }
@@ -623,6 +681,8 @@ private:
     // opt-in: ids, map rows and log entries of the frame k_rgbd_finish has just closed, ahead of the state block's copy out (it raises the
     // capacity bits in the frame's report); skips itself like the rest of the tail, and serves a frame once however many attempts it took
     if (mp.cap) hipLaunchKernelGGL(k_rgbd_map_commit, dim3(B), dim3(VS_RGBD_MAP_WG), 0, q, rb, mp);
+    // opt-in: the colour of every entry the commit has just written, on the same queue directly behind it, once per frame like it
+    if (mc.rgb) hipLaunchKernelGGL(k_rgbd_map_color, dim3(B), dim3(VS_MAP_COLOR_WG), 0, q, rb, mp, map_color_src(), mc);
   }
 
   int submit_frame(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t lss, size_t dss, bool on_device) {

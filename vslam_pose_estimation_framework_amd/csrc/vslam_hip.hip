@@ -22,6 +22,7 @@
 #include "kernels_gray.h"
 #include "kernels_map.h"
 #include "kernels_obs.h"
+#include "kernels_map_color.h"
 
 #define VS_API extern "C" __attribute__((visibility("default")))
 

@@ -460,19 +460,28 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def write_ply(path, xyz, **ints):
+def write_ply(path, xyz, rgb=None, **ints):
     """Binary little-endian PLY point cloud: x y z (double) plus one int property per keyword (default: the landmark map's
-    id, first_frame, last_frame, updates; missing ones are written as -1)."""
+    id, first_frame, last_frame, updates; missing ones are written as -1).  rgb (uint8 [n, 3]): three uchar properties red, green, blue
+    behind the int properties, the names point-cloud viewers colour by; without it the file has none."""
     xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
     n = xyz.shape[0]
     names = list(PLY_INT_FIELDS) + [k for k in ints if k not in PLY_INT_FIELDS]
-    dt = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8")] + [(k, "<i4") for k in names])
+    colours = [] if rgb is None else ["red", "green", "blue"]
+    dt = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8")] + [(k, "<i4") for k in names] + [(k, "u1") for k in colours])
     rec = np.zeros(n, dt)
     rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     for k in names:
         rec[k] = np.asarray(ints[k], np.int32).reshape(n) if k in ints else -1
+    if colours:
+        c = np.asarray(rgb)
+        if c.dtype != np.uint8 or c.shape != (n, 3):
+            raise ValueError("write_ply: rgb must be uint8 [%d, 3], got %s %r" % (n, c.dtype, c.shape))
+        for j, k in enumerate(colours):
+            rec[k] = c[:, j]
     head = ["ply", "format binary_little_endian 1.0", "comment landmark map", "element vertex %d" % n,
-            "property double x", "property double y", "property double z"] + ["property int %s" % k for k in names] + ["end_header"]
+            "property double x", "property double y", "property double z"] + ["property int %s" % k for k in names] + \
+           ["property uchar %s" % k for k in colours] + ["end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(head) + "\n").encode("ascii"))
         f.write(rec.tobytes())
@@ -515,7 +524,7 @@ def read_ply(path):
 
 
 # ---- the structure-and-motion bundle: trajectory + landmark map + observation log --------------------------------------------
-BUNDLE_MAP_FIELDS = ("id", "xyz", "first_frame", "last_frame", "updates")      # always there; desc / chunk when the map has them
+BUNDLE_MAP_FIELDS = ("id", "xyz", "first_frame", "last_frame", "updates")      # always there; desc / chunk / rgb when the map has them
 
 
 def write_bundle(path, K, baseline_h, poses, lm_map, obs):
@@ -528,7 +537,7 @@ def write_bundle(path, K, baseline_h, poses, lm_map, obs):
               "poses": np.asarray(poses, np.float64).reshape(-1, 12)}
     for k in BUNDLE_MAP_FIELDS:
         arrays["map_" + k] = np.asarray(lm_map[k])
-    for k in ("desc", "chunk"):
+    for k in ("desc", "chunk", "rgb"):
         if k in lm_map:
             arrays["map_" + k] = np.asarray(lm_map[k])
     arrays["obs_id"] = np.asarray(obs["id"], np.int32)
@@ -553,8 +562,9 @@ def write_bundle_rgbd(path, K, poses, lm_map, obs):
     arrays = {"K": np.asarray(K, np.float64).reshape(3, 3), "poses": np.asarray(poses, np.float64).reshape(-1, 12)}
     for k in BUNDLE_MAP_FIELDS:
         arrays["map_" + k] = np.asarray(lm_map[k])
-    if "desc" in lm_map:
-        arrays["map_desc"] = np.asarray(lm_map["desc"])
+    for k in ("desc", "rgb"):
+        if k in lm_map:
+            arrays["map_" + k] = np.asarray(lm_map[k])
     arrays["obs_id"] = np.asarray(obs["id"], np.int32)
     arrays["obs_frame"] = np.asarray(obs["frame"], np.int32)
     arrays["obs_xy"] = np.asarray(obs["xy"], np.float32).reshape(-1, 2)

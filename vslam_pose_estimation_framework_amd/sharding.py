@@ -148,10 +148,12 @@ def assemble_map(chunk_maps, chunk_poses, plan, seam_frames=1):
     frame) -> one map in the first chunk's world frame, through the seam transforms of assemble_trajectory.  A landmark is kept only
     when the chunk created it inside its own range (first_frame in [first_unique, end)): what a chunk creates in its warm-up frames
     duplicates the preceding chunk's landmarks.  Frame indices become global frame numbers, ids are renumbered 0 .. n-1 in chunk order.
-    Returns dict: id, xyz [n, 3], first_frame, last_frame, updates, chunk (and desc [n, 32] when every chunk map has descriptors)."""
+    Returns dict: id, xyz [n, 3], first_frame, last_frame, updates, chunk (and desc [n, 32] when every chunk map has descriptors, rgb
+    [n, 3] when every chunk map has colours)."""
     _, anchors = _assemble(chunk_poses, plan, seam_frames)
-    parts = {k: [] for k in ("xyz", "first_frame", "last_frame", "updates", "chunk", "desc")}
+    parts = {k: [] for k in ("xyz", "first_frame", "last_frame", "updates", "chunk", "desc", "rgb")}
     with_desc = all("desc" in m for m in chunk_maps)
+    with_rgb = bool(chunk_maps) and all("rgb" in m for m in chunk_maps)
     for c, (start, first, end) in enumerate(plan):
         if anchors[c] is None:
             continue
@@ -167,11 +169,15 @@ def assemble_map(chunk_maps, chunk_poses, plan, seam_frames=1):
         parts["chunk"].append(np.full(int(keep.sum()), c, np.int64))
         if with_desc:
             parts["desc"].append(np.asarray(m["desc"], np.uint8).reshape(-1, 32)[keep])
+        if with_rgb:
+            parts["rgb"].append(np.asarray(m["rgb"], np.uint8).reshape(-1, 3)[keep])
     out = {"xyz": np.concatenate(parts["xyz"]) if parts["xyz"] else np.zeros((0, 3))}
     for k in ("first_frame", "last_frame", "updates", "chunk"):
         out[k] = (np.concatenate(parts[k]) if parts[k] else np.zeros(0, np.int64)).astype(np.int32)
     if with_desc:
         out["desc"] = np.concatenate(parts["desc"]) if parts["desc"] else np.zeros((0, 32), np.uint8)
+    if with_rgb:
+        out["rgb"] = np.concatenate(parts["rgb"]) if parts["rgb"] else np.zeros((0, 3), np.uint8)
     out["id"] = np.arange(out["xyz"].shape[0], dtype=np.int32)
     return out
 
