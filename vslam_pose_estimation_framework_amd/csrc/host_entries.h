@@ -637,6 +637,10 @@ static int pattern_io(int device, int which, const int8_t* in, int8_t* out) {
   if (hipSetDevice(device) != hipSuccess) { g_create_error = "pattern: no such HIP device"; return VSLAM_ERR_NO_DEVICE; }
   hipError_t e = hipDeviceSynchronize();
   if (e == hipSuccess && in) e = which == 0 ? hipMemcpyToSymbol(HIP_SYMBOL(c_brief), in, 1024) : hipMemcpyToSymbol(HIP_SYMBOL(c_orb), in, 1024);
+  if (e == hipSuccess && in && which == 0) {   // the footprint follows its pattern, inside the same pair of device synchronisations
+    const BriefFootprint fp = brief_footprint(reinterpret_cast<const int8_t (*)[4]>(in));
+    e = hipMemcpyToSymbol(HIP_SYMBOL(c_brief_fp), &fp, sizeof(fp));
+  }
   if (e == hipSuccess && out) e = which == 0 ? hipMemcpyFromSymbol(out, HIP_SYMBOL(c_brief), 1024) : hipMemcpyFromSymbol(out, HIP_SYMBOL(c_orb), 1024);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) { g_create_error = std::string("pattern: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }

@@ -12,8 +12,13 @@
 #include "dev_types.h"
 #include "../../include/vslam_brief_pattern.h"
 #include "../../include/vslam_orb_pattern.h"
+#include "brief_footprint.h"
 
 __constant__ int8_t c_brief[256][4] = VSLAM_BRIEF_PATTERN_INIT;
+// the footprint of c_brief: the two travel together (pattern_io uploads both); the built-in pattern's is made at compile time
+constexpr int8_t k_brief_builtin[256][4] = VSLAM_BRIEF_PATTERN_INIT;
+constexpr BriefFootprint k_brief_builtin_fp = brief_footprint(k_brief_builtin);
+__constant__ BriefFootprint c_brief_fp = k_brief_builtin_fp;
 __constant__ int8_t c_orb[256][4] = VSLAM_ORB_PATTERN_INIT;
 
 // ---- indexing helpers ------------------------------------------------------------------------
@@ -610,7 +615,7 @@ __device__ __forceinline__ void brief_wave(const uint16_t* box, int bstride, int
 #define VS_BT_H 64      // <= 64: the per-row keypoint counts of a tile are scanned by one wavefront
 #endif
 #define VS_BT_RW (VS_BT_W + 2 * VSLAM_BRIEF_PATCH_HALF)   // 176
-#define VS_BT_RH (VS_BT_H + 2 * VSLAM_BRIEF_PATCH_HALF)   // 80
+#define VS_BT_RH (VS_BT_H + 2 * VSLAM_BRIEF_PATCH_HALF)   // 112
 __global__ __launch_bounds__(256) void k_brief(const DevCfg c, const DevBuf b) {
   __shared__ __align__(16) uint16_t reg[VS_BT_RH * VS_BT_RW];
   __shared__ int row_lo[VS_BT_H], row_off[VS_BT_H + 1];
@@ -645,9 +650,10 @@ __global__ __launch_bounds__(256) void k_brief(const DevCfg c, const DevBuf b) {
   // stage the box region with 16-byte loads, ALL of a thread's loads in flight before the first LDS store (the loop
   // is otherwise a chain of dependent L2 round trips).  x0 - 24 is a multiple of 8 pixels and the row stride a multiple
   // of 64, so a chunk lies entirely inside or outside the padded row; outside chunks (never sampled by a keypoint that
-  // passed the 28 px border filter) are zero.
+  // passed the 28 px border filter) are zero.  (Leaving out the region rows no tap of the pattern reaches — c_brief_fp.row_lo / row_hi:
+  // 10 of the 112 with the built-in pattern — was measured and changed nothing: neighbouring tiles share those rows through L2.)
   constexpr int CPR = VS_BT_RW / 8;                              // 16-byte chunks per region row (22)
-  constexpr int NLD = (VS_BT_RH * CPR + 255) / 256;              // loads per thread (7)
+  constexpr int NLD = (VS_BT_RH * CPR + 255) / 256;              // loads per thread (10)
   uint4 stage[NLD];
 #pragma unroll
   for (int u = 0; u < NLD; ++u) {

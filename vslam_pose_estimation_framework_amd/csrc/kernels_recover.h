@@ -183,17 +183,29 @@ __device__ __forceinline__ void recover_orb_wave(const DevCfg& c, const DevBuf& 
 
 // Same computation with the two 49 x 49 box patches staged in LDS by coalesced 16-byte row loads (7 lanes per row):
 // the 1024 scattered 2-byte gathers per point of recover_brief_wave keep the CU's texture-address unit busy for ~1000
-// cycles; 12 wide loads take a fraction of that.  `patch` = this wavefront's LDS area, VS_RPATCH bytes.
-#define VS_RP_W 56
-#define VS_RP_H (2 * VSLAM_BRIEF_PATCH_HALF + 1)
+// cycles; a dozen wide loads at most take a fraction of that.  `patch` = this wavefront's LDS area, VS_RPATCH bytes.
+// Only the chunks the loaded pattern samples are fetched (c_brief_fp, brief_footprint.h; with the built-in pattern 142 - 147 loads per
+// side, by alignment, against the rectangle's 343): the phase is bound by the bytes a workgroup pulls through its CU's memory pipe, and
+// the taps read nothing else.
+#define VS_RP_W (8 * VS_FP_CPR)
+#define VS_RP_H VS_FP_ROWS
 #define VS_RPATCH (2 * VS_RP_H * VS_RP_W * 2)
+#define VS_RP_NLD ((VS_FP_MAX_ITEMS + 63) / 64)   // 6: loads per lane and side when the pattern samples the whole rectangle
+// a lane's share of the footprint's work list, items lane, lane + 64, ...: the same for every point, so it is fetched once per recovery
+struct RecoverItems { uint32_t it[VS_RP_NLD]; };
+__device__ __forceinline__ RecoverItems recover_items(int lane) {
+  RecoverItems w;
+#pragma unroll
+  for (int u = 0; u < VS_RP_NLD; ++u) w.it[u] = lane + 64 * u < c_brief_fp.n_items ? c_brief_fp.item[lane + 64 * u] : VS_FP_NO_ITEM;
+  return w;
+}
 __device__ __forceinline__ void recover_brief_patch(const DevCfg& c, const DevBuf& b, int s, int pb_prev, int q, int ip, int xL, int yL,
-                                                    int xR, int yR, int lane, double tau_track, double tau_tri, uint16_t* patch) {
+                                                    int xR, int yR, int lane, double tau_track, double tau_tri, uint16_t* patch,
+                                                    const RecoverItems& w) {
   int32_t* rec = b.rec + (size_t)s * c.MAXP * 6;
   const PtView pv = pts_of(c, b, s, pb_prev);
   const int xy[2][2] = {{xL, yL}, {xR, yR}};
-  constexpr int NLD = (VS_RP_H * 7 + 63) / 64;   // 6
-  uint4 v[2][NLD];
+  uint4 v[2][VS_RP_NLD];
   int cx[2];
 #pragma unroll
   for (int sd = 0; sd < 2; ++sd) {
@@ -201,10 +213,10 @@ __device__ __forceinline__ void recover_brief_patch(const DevCfg& c, const DevBu
     cx[sd] = xy[sd][0] - col0;
     const uint16_t* base = box_of(c, b, s, sd) + (size_t)(xy[sd][1] - VSLAM_BRIEF_PATCH_HALF) * c.bstride + col0;
 #pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const int t = lane + 64 * u, row = t / 7, seg = t - 7 * row;
+    for (int u = 0; u < VS_RP_NLD; ++u) {
+      const int row = brief_footprint_row(w.it[u]), seg = brief_footprint_chunk(w.it[u]);   // row < VS_RP_H, seg < VS_FP_CPR by construction
       v[sd][u] = make_uint4(0u, 0u, 0u, 0u);
-      if (row < VS_RP_H) v[sd][u] = *reinterpret_cast<const uint4*>(base + (size_t)row * c.bstride + 8 * seg);
+      if (brief_footprint_needs(w.it[u], cx[sd] - VSLAM_BRIEF_PATCH_HALF)) v[sd][u] = *reinterpret_cast<const uint4*>(base + (size_t)row * c.bstride + 8 * seg);
     }
   }
   unsigned long long pd[8];
@@ -213,9 +225,9 @@ __device__ __forceinline__ void recover_brief_patch(const DevCfg& c, const DevBu
 #pragma unroll
   for (int sd = 0; sd < 2; ++sd)
 #pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const int t = lane + 64 * u, row = t / 7, seg = t - 7 * row;
-      if (row < VS_RP_H) *reinterpret_cast<uint4*>(patch + (sd * VS_RP_H + row) * VS_RP_W + 8 * seg) = v[sd][u];
+    for (int u = 0; u < VS_RP_NLD; ++u) {
+      const int row = brief_footprint_row(w.it[u]), seg = brief_footprint_chunk(w.it[u]);
+      if (brief_footprint_needs(w.it[u], cx[sd] - VSLAM_BRIEF_PATCH_HALF)) *reinterpret_cast<uint4*>(patch + (sd * VS_RP_H + row) * VS_RP_W + 8 * seg) = v[sd][u];
     }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -284,17 +296,18 @@ __device__ __forceinline__ void wg_recover_brief(const DevCfg& c, const DevBuf& 
     }
     return;
   }
+  const RecoverItems items = recover_items(lane);
   if (n_list <= VS_RLIST_CAP) {
     for (int k = w; k < n_list; k += VS_WG / 64) {
       const int32_t* e = list + 6 * k;
-      recover_brief_patch(c, b, s, pb_prev, e[0], e[1], e[2], e[3], e[4], e[5], lane, tau_track, tau_tri, patch);
+      recover_brief_patch(c, b, s, pb_prev, e[0], e[1], e[2], e[3], e[4], e[5], lane, tau_track, tau_tri, patch, items);
     }
   } else {
     const int32_t* rec = b.rec + (size_t)s * c.MAXP * 6;
     const int32_t* lost = b.lost + (size_t)s * c.MAXP;
     for (int q = w; q < n_lost; q += VS_WG / 64) {
       if (rec[6 * q] != 2) continue;   // wave-uniform
-      recover_brief_patch(c, b, s, pb_prev, q, lost[q], rec[6 * q + 1], rec[6 * q + 2], rec[6 * q + 3], rec[6 * q + 4], lane, tau_track, tau_tri, patch);
+      recover_brief_patch(c, b, s, pb_prev, q, lost[q], rec[6 * q + 1], rec[6 * q + 2], rec[6 * q + 3], rec[6 * q + 4], lane, tau_track, tau_tri, patch, items);
     }
   }
 }
