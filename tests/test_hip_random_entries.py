@@ -102,3 +102,29 @@ def test_depth_track_random(gpu, oracle):
     total, temp = rc.sweep_depth_track(gpu, oracle, rej)
     rej.check("depth_track")
     assert total > 3200 and temp > 380
+
+
+@pytest.mark.parametrize("shape", rc.REC_SHAPES, ids=["%dx%d" % s for s in rc.REC_SHAPES])
+def test_stereo_recover_random(shape):
+    """vslam_stereo_recover on four image shapes (one with a single recoverable row pair), n = 0 .. 4096, both poses: more than VS_WG lost points
+    in wg_recover_project, runs of 2 .. 8 lost points per thread in wg_recover_append, the work list in LDS up to 1802 projected points and the
+    rec[] walk beyond, the scratch context's 1024 rounding, padded rows, every gate on its equality (random_cases, section F)."""
+    total = rc.sweep_stereo_recover(hip.load, Oracle, shapes=[shape])
+    sizes = rc.stereo_recover_sizes(shape)
+    assert total["recovered"] > 0.9 * sum(sizes) and total["cases"] == 2 * len(sizes) and total["exact"] == 28 * sum(1 for n in sizes if n >= 64)
+
+
+def test_stereo_recover_context_reuse_and_patterns():
+    reuse = rc.sweep_stereo_recover_reuse(hip.load, Oracle)
+    patterns = rc.sweep_stereo_recover_patterns(hip.load, Oracle)
+    orb = rc.sweep_stereo_recover_orb(hip.load, Oracle)
+    assert reuse > 5100 and patterns > 2000 and orb > 4100
+
+
+def test_depth_recover_random(gpu, oracle):
+    """vslam_depth_recover, n = 0 .. 3000: more than one block of k_depth_recover_project, more than one grid pass of k_brief_at / k_orb_at,
+    three passes of k_depth_recover_finish with survivors on both sides of each seam, the resident map, padded rows, the gates' equalities."""
+    rej = rc.Rejections()
+    total = rc.sweep_depth_recover(gpu, oracle, rej)
+    rej.check("depth_recover")
+    assert total["recovered"] > 10700 and total["cases"] == 38 and total["exact"] == 14 * 19 and total["resident"] > 850 and total["orb"] > 2400

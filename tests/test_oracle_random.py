@@ -96,3 +96,28 @@ def test_depth_track_random(oracle):
     rej.check("depth_track")
     print("tracked", total, "temporary", temp)
     assert total > 3200 and temp > 380
+
+
+def test_stereo_recover_random():
+    """orc_stereo_recover == stereo_recover_ref at every size of the sweep, premises and exact cases included (random_cases, section F)"""
+    total = rc.sweep_stereo_recover(Oracle, None, python_max=10 ** 9)
+    print("stereo_recover", total)
+    assert total["recovered"] > 19000 and total["projected_max"] > 2 * rc.VS_RLIST_CAP and total["cases"] == 54 and total["exact"] == 21 * 28
+
+
+def test_stereo_recover_context_reuse_and_patterns():
+    """the oracle keeps no scratch context, so reuse only validates the cases; the patterns run against the restatement under the same table;
+    the ORB extractor has no restatement: the oracle runs alone and the volume is checked"""
+    reuse = rc.sweep_stereo_recover_reuse(Oracle, None)
+    patterns = rc.sweep_stereo_recover_patterns(Oracle, None, python=True)
+    orb = rc.sweep_stereo_recover_orb(Oracle, None)
+    print("stereo_recover reuse", reuse, "patterns", patterns, "ORB", orb)
+    assert reuse > 5100 and patterns > 2000 and orb > 4100
+
+
+def test_depth_recover_random(oracle):
+    rej = rc.Rejections()
+    total = rc.sweep_depth_recover(oracle, None, rej)
+    rej.check("depth_recover")
+    print("depth_recover", total)
+    assert total["recovered"] > 10700 and total["cases"] == 38 and total["exact"] == 14 * 19 and total["orb"] > 2400

@@ -625,10 +625,15 @@ class CApi(object):
                                            C.c_int32(cap), C.byref(n), _p(out, C.c_int32)))
         return out[:n.value].copy()
 
-    def stereo_recover(self, image_left, image_right, w2c, has_landmark, landmark_world, prev_desc_left, prev_desc_right, tau_track, tau_tri):
+    def stereo_recover(self, image_left, image_right, w2c, has_landmark, landmark_world, prev_desc_left, prev_desc_right, tau_track, tau_tri,
+                       row_stride=None):
         """StereoFramePointGenerator::recoverPoints on caller-provided lost points (known-answer tests): dict of
-        index / xy4 / dist / desc / xyz rows of the recovered points in lost-list order."""
+        index / xy4 / dist / desc / xyz rows of the recovered points in lost-list order.  row_stride: the images are [rows, row_stride]
+        arrays (padded rows); default: their own width."""
         L = np.ascontiguousarray(image_left, np.uint8); R = np.ascontiguousarray(image_right, np.uint8)
+        stride = L.shape[1] if row_stride is None else int(row_stride)
+        if L.shape[1] != stride or R.shape != L.shape:
+            raise ValueError("stereo_recover: images must be two [rows, row_stride] arrays")
         w = np.ascontiguousarray(w2c, np.float64).reshape(12)
         hl = np.ascontiguousarray(has_landmark, np.uint8); lm = np.ascontiguousarray(landmark_world, np.float64)
         pdl = np.ascontiguousarray(prev_desc_left, np.uint8); pdr = np.ascontiguousarray(prev_desc_right, np.uint8)
@@ -637,7 +642,7 @@ class CApi(object):
         desc = np.zeros((max(n, 1), 64), np.uint8); xyz = np.zeros((max(n, 1), 3), np.float64)
         k = C.c_int32()
         head = (self.ctx,) if self.prefix == "vslam_" else (C.byref(self.cfg),)
-        self.check(self.fn("stereo_recover")(*head, _p(L, C.c_uint8), _p(R, C.c_uint8), C.c_int32(L.shape[1]), _p(w, C.c_double), C.c_int32(n),
+        self.check(self.fn("stereo_recover")(*head, _p(L, C.c_uint8), _p(R, C.c_uint8), C.c_int32(stride), _p(w, C.c_double), C.c_int32(n),
                                              _p(hl, C.c_uint8), _p(lm, C.c_double), _p(pdl, C.c_uint8), _p(pdr, C.c_uint8),
                                              C.c_double(float(tau_track)), C.c_double(float(tau_tri)), C.byref(k), _p(idx, C.c_int32),
                                              _p(xy4, C.c_int32), _p(dist, C.c_int32), _p(desc, C.c_uint8), _p(xyz, C.c_double)))
@@ -689,9 +694,14 @@ class CApi(object):
                                           C.byref(ntmp), _p(tmp2, C.c_int32), C.byref(nl), _p(lost, C.c_int32), C.byref(nlm)))
         return out2[:nt.value].copy(), xyz[:nt.value].copy(), tmp2[:ntmp.value].copy(), lost[:nl.value].copy(), nlm.value
 
-    def depth_recover(self, params, space, image_left, world_to_camera_left, has_landmark, landmark_world, prev_desc, keypoint_size, tau):
-        """DepthFramePointGenerator::recoverPoints on caller-provided data: (lost-list index, keypoint xy, descriptor, xyz)."""
+    def depth_recover(self, params, space, image_left, world_to_camera_left, has_landmark, landmark_world, prev_desc, keypoint_size, tau,
+                      row_stride=None):
+        """DepthFramePointGenerator::recoverPoints on caller-provided data: (lost-list index, keypoint xy, descriptor, xyz).
+        row_stride: the image is a [rows, row_stride] array (padded rows); default: its own width."""
         img = np.ascontiguousarray(image_left, np.uint8)
+        stride = img.shape[1] if row_stride is None else int(row_stride)
+        if img.shape[1] != stride:
+            raise ValueError("depth_recover: the image must be a [rows, row_stride] array")
         w2c = np.ascontiguousarray(world_to_camera_left, np.float64).reshape(12)
         hl = np.ascontiguousarray(has_landmark, np.uint8); lm = np.ascontiguousarray(landmark_world, np.float64).reshape(-1, 3)
         pd = np.ascontiguousarray(prev_desc, np.uint8)
@@ -701,7 +711,7 @@ class CApi(object):
         desc, xyz = np.zeros((max(n, 1), 32), np.uint8), np.zeros((max(n, 1), 3), np.float64)
         nr = C.c_int32()
         self.check(self.fn("depth_recover")(*self._ctx_args(), C.byref(params), None if sp is None else _p(sp, C.c_float), _p(img, C.c_uint8),
-                                            C.c_int32(img.shape[1]), _p(w2c, C.c_double), C.c_int32(n), _p(hl, C.c_uint8), _p(lm, C.c_double),
+                                            C.c_int32(stride), _p(w2c, C.c_double), C.c_int32(n), _p(hl, C.c_uint8), _p(lm, C.c_double),
                                             _p(pd, C.c_uint8), C.c_float(float(keypoint_size)), C.c_double(float(tau)), C.byref(nr),
                                             _p(idx, C.c_int32), _p(xy, C.c_float), _p(desc, C.c_uint8), _p(xyz, C.c_double)))
         k = nr.value
