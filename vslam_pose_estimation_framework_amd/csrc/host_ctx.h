@@ -1,6 +1,7 @@
 // host_ctx.h — the context behind the C ABI: vslam_ctx and what it owns (device buffers, the per-call scratch arena, event timers, the
 // switchable stores), configuration, create / destroy / reset, the scratch-context pool of the stand-alone entries, pending setters, the
-// stream index checks and the per-stream lifetime calls.  Host code, included first by vslam_hip.hip.
+// stream index checks and the per-stream lifetime calls.  Host code, included by vslam_hip.hip behind host_prestage.h (whose types the
+// context holds).
 #pragma once
 
 static thread_local std::string g_create_error;
@@ -75,30 +76,22 @@ struct vslam_ctx {
   // rectification of raw input pairs (vslam_set_rectification): maps at the rectified size, padded to map_stride entries per row, and
   // the raw slabs [step parity][left/right] host images are copied into (B x raw_rows x raw_stride each).  k_rectify writes the rectified
   // pair into upload[parity], so everything downstream, and the two-parity lifetime of the image slabs, is unchanged.
-  struct Rect { bool on = false, have_frame = false; int raw_rows = 0, raw_cols = 0, raw_stride = 0, map_stride = 0; size_t raw_stream_stride = 0;
-                int16_t* map_xy[2] = {nullptr, nullptr}; uint16_t* map_a[2] = {nullptr, nullptr};
+  struct Rect { bool on = false, have_frame = false; RemapMaps maps; int raw_stride = 0; size_t raw_stream_stride = 0;
                 uint8_t* raw[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-                const uint8_t* src[2] = {nullptr, nullptr}; int32_t src_row_stride = 0; size_t src_stream_stride = 0;   // this step's raw input
                 DeviceStore mem; } rect;
-  // histogram equalisation of the input pair (vslam_set_equalization, kernels_equalize.h): the count table [stream][side][256], zeroed and
-  // refilled every frame, and where the pair the last frame was processed on lies (out*: inside upload[last_set]).  keep[left/right]: with
-  // rectification on as well, k_rectify writes here and the equalised pair goes to upload[parity], so that vslam_get_rectified_images
-  // still returns the rectified pair; one pair suffices, its only readers are the same frame's two kernels on the same queue and a getter.
-  // clahe: the slot's second mode (vslam_set_clahe, kernels_clahe.h) — the same placement, the tables [stream][side][tilesY][tilesX][256]
-  // instead of the count table, geo holding what clahe_geometry made of the switch's arguments.
-  struct Eq { bool on = false, have_frame = false; uint32_t* hist = nullptr; uint8_t* keep[2] = {nullptr, nullptr};
-              const uint8_t* out[2] = {nullptr, nullptr}; int32_t out_row_stride = 0; size_t out_stream_stride = 0;
-              bool clahe = false; double clip_limit = 0; uint8_t* luts = nullptr; ClaheArgs geo{};
-              DeviceStore mem, keep_mem; } eq;
+  // the equalisation slot of the input pair (vslam_set_equalization / vslam_set_clahe: EqSlot, host_prestage.h), its tables [stream][side];
+  // dst: where the pair the last frame was processed on lies (inside upload[last_set]).  keep[left/right]: with rectification on as well,
+  // k_rectify writes here and the equalised pair goes to upload[parity], so that vslam_get_rectified_images still returns the rectified
+  // pair; one pair suffices, its only readers are the same frame's two kernels on the same queue and a getter.
+  struct Eq : EqSlot { uint8_t* keep[2] = {nullptr, nullptr}; DeviceStore keep_mem; } eq;
   // colour input (vslam_set_color_input, kernels_gray.h): off while format == VSLAM_PIXEL_GRAY8.  slab[step parity][left/right]: what host
-  // colour images are copied into (B x in_rows x stride bytes each, allocated on the first host frame at that input size); src*: this step's
-  // colour pair (a slab or the caller's device memory); out*: where k_gray_u8 writes the grey pair — the rectifier's raw slabs when
-  // rectifying, else upload[parity] — and so where vslam_get_gray_images reads it.
+  // colour images are copied into (B x in_rows x stride bytes each, at the size of the frames that come in).
   struct Col { int format = 0; bool have_frame = false; int slab_rows = 0, slab_cols = 0, stride = 0; size_t stream_stride = 0;
                uint8_t* slab[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-               const uint8_t* src[2] = {nullptr, nullptr}; int32_t src_row_stride = 0; size_t src_stream_stride = 0;
-               uint8_t* out[2] = {nullptr, nullptr}; int32_t out_row_stride = 0; size_t out_stream_stride = 0; int out_rows = 0, out_cols = 0;
                DeviceStore mem; } col;
+  // this frame's routing through the three stages (route_frame, host_frame.h): the colour pair (a slab or the caller's device memory) and
+  // where k_gray_u8 writes the grey pair, so where vslam_get_gray_images reads it; the raw pair k_rectify reads and the pair it writes
+  PrePlan pre;
   // the landmark map (vslam_enable_map, kernels_map.h): off while cap == 0; its own allocations, freed by vslam_enable_map(0) and destroy
   struct MapStore { int32_t cap = 0; DevMap d{}; DeviceStore mem; } map;
   // the observation log on top of it (vslam_enable_observations, kernels_obs.h): off while cap == 0; freed by vslam_enable_observations(0),
@@ -507,51 +500,8 @@ static hipError_t depth_map_resize(vslam_ctx* c, int rows, int cols) {
   m.rows = rows; m.cols = cols;
   return hipSuccess;
 }
-// the switchable stores: what vslam_set_rectification(off), vslam_enable_observations(0), vslam_enable_map(0) and vslam_destroy call
-static void rect_free(vslam_ctx* c) {
-  c->rect.mem.release();
-  c->rect = vslam_ctx::Rect();
-}
-static void eq_free(vslam_ctx* c) {
-  c->eq.mem.release();
-  c->eq.keep_mem.release();
-  c->eq = vslam_ctx::Eq();
-}
-// the rectified pair's own slabs exist exactly while rectification and equalisation are both on (called by both setters, queues idle)
-static hipError_t eq_keep_sync(vslam_ctx* c) {
-  vslam_ctx::Eq& q = c->eq;
-  const bool want = q.on && c->rect.on;
-  if (want == (q.keep[0] != nullptr)) return hipSuccess;
-  q.keep_mem.release();
-  q.keep[0] = q.keep[1] = nullptr;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && want && e == hipSuccess; ++k) e = q.keep_mem.alloc(&q.keep[k], (size_t)c->B * c->up_stream_stride);
-  if (e != hipSuccess) { q.keep_mem.release(); q.keep[0] = q.keep[1] = nullptr; }
-  return e;
-}
-static void col_free(vslam_ctx* c) {
-  c->col.mem.release();
-  c->col = vslam_ctx::Col();
-}
-// the colour slabs exist while the switch is on, at the size of the frames that come in: the raw size while rectification is set (called by
-// both setters, queues idle)
-static hipError_t col_slab_sync(vslam_ctx* c) {
-  vslam_ctx::Col& q = c->col;
-  const int fmt = q.format;
-  const int rows = c->rect.on ? c->rect.raw_rows : c->cfg.c.rows, cols = c->rect.on ? c->rect.raw_cols : c->cfg.c.cols;
-  const int wb = fmt == 0 ? 0 : (fmt <= 2 ? 3 : 4) * cols;
-  if (fmt != 0 && q.slab[0][0] && q.slab_rows == rows && q.slab_cols == wb) return hipSuccess;
-  col_free(c);
-  q.format = fmt;
-  if (fmt == 0) return hipSuccess;
-  q.slab_rows = rows; q.slab_cols = wb;
-  q.stride = (wb + 63) & ~63;
-  q.stream_stride = (size_t)rows * q.stride;
-  hipError_t e = hipSuccess;
-  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = q.mem.alloc(&q.slab[p][k], (size_t)c->B * q.stream_stride);
-  if (e != hipSuccess) col_free(c);
-  return e;
-}
+// the switchable stores: what vslam_enable_observations(0), vslam_enable_map(0) and vslam_destroy call (those of the input stages:
+// host_switches.h)
 static void obs_free(vslam_ctx* c) {
   c->obs.mem.release();
   c->obs.d = DevObs{};
@@ -580,9 +530,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (auto& e : c->scratch) vslam_destroy(e.t);
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
-  rect_free(c);
-  eq_free(c);
-  col_free(c);
+  for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem}) m->release();     // the input stages' stores
   map_free(c);
   obs_free(c);
   tmp_free(c);

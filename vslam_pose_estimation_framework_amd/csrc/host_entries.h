@@ -260,7 +260,7 @@ VS_API int vslam_depth_recover(vslam_ctx* c, const vslam_depth_params* p, const 
   uint8_t* dkeep = k.dev<uint8_t>(N); uint8_t* ddesc = k.dev<uint8_t>(N * 32);
   a.keep = dkeep; a.desc = ddesc;
   a.rec_index = k.dev<int32_t>(N); a.rec_xy = k.dev<float>(N * 2); a.rec_desc = k.dev<uint8_t>(N * 32); a.rec_xyz = k.dev<double>(N * 3);
-  rc = k.ok() ? upload_images(t, img, img, row_stride, 0) : k.status();
+  rc = k.ok() ? set_inputs(t, img, img, row_stride, 0, false) : k.status();
   if (rc == VSLAM_OK) {
     if (!space) (void)hipStreamSynchronize(c->stream);   // the resident map was written on the parent's stream
     hipLaunchKernelGGL(k_depth_recover_project, dim3((n + 255) / 256), dim3(256), 0, q, a);
@@ -437,7 +437,7 @@ VS_API int vslam_orb_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int3
     t->cfg.regions[0].x = 0; t->cfg.regions[0].y = 0; t->cfg.regions[0].w = lcols; t->cfg.regions[0].h = lrows;
     edit_stream_state(k, t, nullptr, sst, [&](StreamState& s) { s.thr[0] = fast_threshold; });
     if (!k.ok()) break;
-    rc = set_images_device(t, lev, lev, lstride, 0);
+    rc = set_inputs(t, lev, lev, lstride, 0, true);
     if (rc != VSLAM_OK) break;
     const size_t N = t->cfg.NMAX;
     int16_t* xy1 = k.dev<int16_t>(N * 2); int16_t* xy2 = k.dev<int16_t>(N * 2);
@@ -480,7 +480,7 @@ VS_API int vslam_fast_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int
   Call k(c, t->stream_img);
   StreamState st;
   edit_stream_state(k, t, nullptr, st, [&](StreamState& s) { s.thr[0] = threshold; });
-  rc = k.ok() ? upload_images(t, img, img, stride, 0) : k.status();
+  rc = k.ok() ? set_inputs(t, img, img, stride, 0, false) : k.status();
   if (rc == VSLAM_OK) {
     launch_fast_box(t, t->stream_img, 2);
     hipLaunchKernelGGL(k_emit, dim3(1, 2), dim3(512), 0, t->stream_img, t->cfg, t->buf, 0, 0);
@@ -511,7 +511,7 @@ VS_API int vslam_brief_describe(vslam_ctx* c, const uint8_t* img, int32_t rows, 
   if (rc != VSLAM_OK) return rc;
   Call k(c, t->stream_img);
   int16_t* dxy = k.up(xy, (size_t)n * 2); uint8_t* dkeep = k.dev<uint8_t>(n); uint8_t* ddesc = k.dev<uint8_t>((size_t)n * 32);
-  rc = k.ok() ? upload_images(t, img, img, stride, 0) : k.status();
+  rc = k.ok() ? set_inputs(t, img, img, stride, 0, false) : k.status();
   if (rc == VSLAM_OK && n) {
     launch_fast_box(t, t->stream_img, 2);
     hipLaunchKernelGGL(k_brief_at, dim3(std::min(64, (n + 3) / 4)), dim3(256), 0, t->stream_img, t->buf.box, t->cfg.bstride, rows, cols,
@@ -865,7 +865,7 @@ VS_API int vslam_stereo_recover(vslam_ctx* c, const uint8_t* imgL, const uint8_t
   Call k(c, q);
   k.up_to(t->buf.p_desc, desc.data(), desc.size()); k.up_to(t->buf.p_meta, meta.data(), meta.size());
   k.up_to(t->buf.p_lm, lm, (size_t)n * 3); k.up_to(t->buf.lost, lost.data(), lost.size());
-  rc = k.ok() ? upload_images(t, imgL, imgR, row_stride, 0) : k.status();
+  rc = k.ok() ? set_inputs(t, imgL, imgR, row_stride, 0, false) : k.status();
   if (rc == VSLAM_OK) {
     if (t->cfg.c.descriptor_type == VSLAM_DESCRIPTOR_ORB)
       hipLaunchKernelGGL(k_gauss7, dim3(t->cfg.TX, (t->cfg.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2), dim3(256), 0, q, t->cfg, t->buf, gauss7_of(t->cfg));
@@ -909,10 +909,9 @@ VS_API int vslam_equalize_hist_u8(vslam_ctx* c, const uint8_t* src, int32_t rows
   k.up_to(ds + off, src, bytes);
   const int ostride = (cols + 15) & ~15;
   uint8_t* dd = k.dev<uint8_t>((size_t)rows * ostride);
-  EqArgs ea;
-  std::memset(&ea, 0, sizeof ea);
-  ea.src[0] = ds + off; ea.src_row_stride = row_stride; ea.dst[0] = dd; ea.dst_row_stride = ostride;
-  ea.hist = k.dev<uint32_t>(256); ea.rows = rows; ea.cols = cols; ea.n = 1; ea.sides = 1; ea.active[0] = 1u;
+  EqArgs ea{};
+  place(ea, ds + off, row_stride, dd, ostride, rows, cols);
+  ea.hist = k.dev<uint32_t>(256);
   if (k.ok()) k.note(equalize_enqueue(c->stream, ea));
   if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)cols, dd, (size_t)ostride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
   if (hist256) k.down(hist256, ea.hist, 256);
@@ -936,8 +935,8 @@ VS_API int vslam_clahe_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_
   const size_t doff = (size_t)((uintptr_t)dst & 15u);
   uint8_t* dd = dst == src ? ds + off : k.dev<uint8_t>((size_t)(rows - 1) * dst_row_stride + cols + 16) + doff;
   const size_t nl = (size_t)tiles_x * tiles_y * 256;
-  ca.src[0] = ds + off; ca.src_row_stride = row_stride; ca.dst[0] = dd; ca.dst_row_stride = dst_row_stride;
-  ca.luts = k.dev<uint8_t>(nl); ca.n = 1; ca.sides = 1; ca.active[0] = 1u;
+  place(ca, ds + off, row_stride, dd, dst_row_stride, rows, cols);
+  ca.luts = k.dev<uint8_t>(nl);
   if (k.ok()) k.note(clahe_enqueue(c->stream, ca));
   if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)dst_row_stride, dd, (size_t)dst_row_stride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
   if (luts) k.down(luts, ca.luts, nl);
@@ -959,10 +958,9 @@ VS_API int vslam_gray_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t
   k.up_to(ds + off, src, bytes);
   const int ostride = (cols + 15) & ~15;
   uint8_t* dd = k.dev<uint8_t>((size_t)rows * ostride);
-  GrayArgs ga;
-  std::memset(&ga, 0, sizeof ga);
-  ga.src[0] = ds + off; ga.src_row_stride = row_stride; ga.dst[0] = dd; ga.dst_row_stride = ostride;
-  ga.rows = rows; ga.cols = cols; ga.n = 1; ga.sides = 1; ga.format = format; ga.active[0] = 1u;
+  GrayArgs ga{};
+  place(ga, ds + off, row_stride, dd, ostride, rows, cols);
+  ga.format = format;
   if (k.ok()) k.note(gray_enqueue(c->stream, ga));
   if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)cols, dd, (size_t)ostride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
   return k.finish();

@@ -1,6 +1,6 @@
-// host_frame.h — one frame on a context: where its input images come from (device pointers, host uploads through pinned staging, raw
-// pairs of a rectifying context), the image pipeline and the frame's launch sequence, the fused entries vslam_process_*, and the
-// rectification, equalisation and colour-input switches.  Host code, included by vslam_hip.hip after host_ctx.h.
+// host_frame.h — one frame on a context: where its input images come from (device pointers, host uploads through pinned staging), its
+// routing through the input stages (route_frame), the image pipeline and the frame's launch sequence, and the fused entries
+// vslam_process_*.  Host code, included by vslam_hip.hip after host_switches.h.
 #pragma once
 
 // ---- launches ------------------------------------------------------------------------------------
@@ -30,50 +30,8 @@ static int launch_image_pipeline(vslam_ctx* c) {
   // the image products of this set were last read by the frame kernel two steps ago; the detector thresholds come
   // from the controller in k_emit of the previous step (same queue)
   if (c->frm_pending[set] && st != c->stream) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_frm[set], 0));
-  if (c->col.format != VSLAM_PIXEL_GRAY8) {
-    // colour pair -> grey pair where the next stage reads (set_color_inputs has chosen: the rectifier's raw slabs or upload[set])
-    const vslam_ctx::Col& q = c->col;
-    GrayArgs ga;
-    for (int k = 0; k < 2; ++k) { ga.src[k] = q.src[k]; ga.dst[k] = q.out[k]; }
-    ga.src_row_stride = q.src_row_stride; ga.src_stream_stride = q.src_stream_stride;
-    ga.dst_row_stride = q.out_row_stride; ga.dst_stream_stride = q.out_stream_stride;
-    ga.rows = q.out_rows; ga.cols = q.out_cols; ga.n = n; ga.sides = 2; ga.format = q.format;
-    std::memcpy(ga.active, c->buf.active, sizeof ga.active);
-    HIP_TRY(c, gray_enqueue(st, ga));
-  }
-  if (c->rect.on) {
-    // raw pair -> rectified pair in upload[set] (the slab the wait above has freed), ahead of the detector
-    const vslam_ctx::Rect& q = c->rect;
-    RectArgs ra;
-    // (with equalisation on as well: in slabs of its own, the equalised pair goes to upload[set])
-    for (int k = 0; k < 2; ++k) { ra.src[k] = q.src[k]; ra.map_xy[k] = q.map_xy[k]; ra.map_a[k] = q.map_a[k]; ra.dst[k] = c->eq.keep[0] ? c->eq.keep[k] : c->upload[set][k]; }
-    ra.src_stream_stride = q.src_stream_stride; ra.src_row_stride = q.src_row_stride; ra.src_rows = q.raw_rows; ra.src_cols = q.raw_cols;
-    ra.map_stride = q.map_stride; ra.dst_stream_stride = c->up_stream_stride; ra.dst_row_stride = c->up_stride;
-    ra.rows = d.c.rows; ra.cols = d.c.cols; ra.s0 = 0; ra.n = n; ra.sides = 2;
-    std::memcpy(ra.active, c->buf.active, sizeof ra.active);
-    hipLaunchKernelGGL(k_rectify, dim3((d.c.cols + 255) / 256, (d.c.rows + 3) / 4, 2 * ((n + VS_RECT_SB - 1) / VS_RECT_SB)), dim3(256), 0, st, ra);
-  }
-  if (c->eq.on) {
-    // equalised pair in upload[set]: in place when the input is already there (host upload), written there from the rectified pair's own
-    // slabs or from the caller's device images, which these two kernels alone read; everything downstream reads upload[set]
-    vslam_ctx::Eq& q = c->eq;
-    const bool in_place = !c->rect.on && c->buf.img[0] == c->upload[set][0];
-    // one placement for both modes of the slot: global equalisation (k_hist_u8, k_equalize_apply) or CLAHE (k_clahe_lut, k_clahe_apply)
-    const int32_t dst_row_stride = in_place ? c->buf.img_row_stride : c->up_stride;
-    const size_t dst_stream_stride = in_place ? c->buf.img_stream_stride : c->up_stream_stride;
-    auto place = [&](auto& x) {
-      for (int k = 0; k < 2; ++k) { x.src[k] = c->rect.on ? q.keep[k] : c->buf.img[k]; x.dst[k] = c->upload[set][k]; }
-      x.src_row_stride = c->rect.on ? c->up_stride : c->buf.img_row_stride;
-      x.src_stream_stride = c->rect.on ? c->up_stream_stride : c->buf.img_stream_stride;
-      x.dst_row_stride = dst_row_stride; x.dst_stream_stride = dst_stream_stride;
-      x.rows = d.c.rows; x.cols = d.c.cols; x.n = n; x.sides = 2;
-      std::memcpy(x.active, c->buf.active, sizeof x.active);
-    };
-    if (q.clahe) { ClaheArgs ca = q.geo; place(ca); ca.luts = q.luts; HIP_TRY(c, clahe_enqueue(st, ca)); }
-    else { EqArgs ea; place(ea); ea.hist = q.hist; HIP_TRY(c, equalize_enqueue(st, ea)); }
-    for (int k = 0; k < 2; ++k) { c->buf.img[k] = c->upload[set][k]; q.out[k] = c->upload[set][k]; }
-    c->buf.img_row_stride = q.out_row_stride = dst_row_stride; c->buf.img_stream_stride = q.out_stream_stride = dst_stream_stride;
-  }
+  // grey, rectify, equalise as route_frame has planned them (the slabs they write are those the wait above has freed)
+  HIP_TRY(c, prestage_enqueue(st, c->pre, c->rect.maps, c->eq, n, 2, c->buf.active));
   const DevBuf bs = buf_set(c, set, c->img_override ? c->q0_frm : c->q0_img);
   dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * n);
   const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
@@ -124,11 +82,7 @@ static int cand_blocks(int n_streams) { return std::max(4, std::min(128, 7040 / 
 static int recover_blocks(int n_streams) { return std::max(4, std::min(64, 1024 / std::max(n_streams, 1))); }
 // this frame's left colour image as k_map_color reads it: the raw image behind the left rectification map while rectifying
 static ColorSrc map_color_src(const vslam_ctx* c) {
-  const vslam_ctx::Col& q = c->col;
-  ColorSrc s{};
-  s.img = q.src[0]; s.stream_stride = q.src_stream_stride; s.row_stride = q.src_row_stride; s.rows = q.out_rows; s.cols = q.out_cols; s.format = q.format;
-  if (c->rect.on) { s.map_xy = c->rect.map_xy[0]; s.map_a = c->rect.map_a[0]; s.map_stride = c->rect.map_stride; s.map_rows = c->cfg.c.rows; s.map_cols = c->cfg.c.cols; }
-  return s;
+  return color_src(c->pre.color, c->pre.in_rows, c->pre.in_cols, c->col.format, c->rect.on ? &c->rect.maps : nullptr);
 }
 static int launch_frame(vslam_ctx* c) {
   const int n = c->B;
@@ -159,20 +113,10 @@ static int launch_frame(vslam_ctx* c) {
   HIP_TRY(c, hipGetLastError());
   return frame_done(c);
 }
-static int set_images_device(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride) {
-  if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");  // stereo_framepoint_generator.cpp:75-78
-  if (row_stride < c->cfg.c.cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
-  c->buf.img[0] = L; c->buf.img[1] = R;
-  c->buf.img_row_stride = row_stride;
-  c->buf.img_stream_stride = image_stride;
-  return VSLAM_OK;
-}
-// where a step's input images live on the device
-struct ImgLoc { const uint8_t* p[2]; int32_t row_stride; size_t stream_stride; };
 // Host images of all streams (rows x cols each) into the device slabs dst[left/right] (dst_stride bytes per row, dst_stream_stride per
 // stream); *out receives where they landed: one copy per side keeps the caller's strides.
 static int upload_to(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, int rows, int cols,
-                     uint8_t* const dst[2], int32_t dst_stride, size_t dst_stream_stride, ImgLoc* out) {
+                     uint8_t* const dst[2], int32_t dst_stride, size_t dst_stream_stride, ImgPlanes* out) {
   if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");
   if (row_stride < cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than image width");
   // Host images of all streams in one (nearly) dense block: one copy per side, the caller's strides kept on the device
@@ -240,61 +184,54 @@ static int upload_to(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t r
   *out = {{dst[0], dst[1]}, dst_stride, dst_stream_stride};
   return VSLAM_OK;
 }
-static int upload_images(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride) {
-  ImgLoc o;
-  const int rc = upload_to(c, L, R, row_stride, image_stride, c->cfg.c.rows, c->cfg.c.cols, c->upload[c->parity], c->up_stride, c->up_stream_stride, &o);
-  return rc != VSLAM_OK ? rc : set_images_device(c, o.p[0], o.p[1], o.row_stride, o.stream_stride);
+// This frame's routing through the input stages, from which switches are on and where the incoming pair `in` lies (a slab the upload
+// filled, or the caller's device memory): c->pre, the slot's src / dst, and DevBuf::img, which the detector reads.  The one place that
+// decides it (the table: host_prestage.h, PrePlan).
+static void route_frame(vslam_ctx* c, const ImgPlanes& in) {
+  const int set = c->parity;
+  const ImgPlanes up = upload_planes(c, set);
+  PrePlan& p = c->pre;
+  p.format = c->col.format; p.remap = c->rect.on;
+  p.rows = c->cfg.c.rows; p.cols = c->cfg.c.cols;
+  p.in_rows = p.remap ? c->rect.maps.raw_rows : p.rows; p.in_cols = p.remap ? c->rect.maps.raw_cols : p.cols;
+  ImgPlanes cur = in;                                  // where the pair lies behind the stages so far
+  const vslam_ctx::Rect& r = c->rect;
+  if (p.format != VSLAM_PIXEL_GRAY8) { p.color = cur; p.gray = p.remap ? ImgPlanes{{r.raw[set][0], r.raw[set][1]}, r.raw_stride, r.raw_stream_stride} : up; cur = p.gray; }
+  if (p.remap) { p.raw = cur; p.mapped = rectified_planes(c, set); cur = p.mapped; }
+  // equalised pair in upload[set]: in place when the input is already there (a host upload keeps the caller's strides), written there
+  // from the rectified pair's own slabs or from the caller's device images, which these kernels alone read
+  if (c->eq.on) { c->eq.src = cur; c->eq.dst = cur.p[0] == up.p[0] ? cur : up; cur = c->eq.dst; }
+  buf_set_planes(c->buf, cur);
 }
-// Raw input of a rectifying context: host images go to the raw slabs of this step's parity, device images are read in place (by k_rectify
-// only); the image pipeline reads the rectified pair k_rectify leaves in upload[parity].
-static int set_raw_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
-  vslam_ctx::Rect& q = c->rect;
-  if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");
-  if (row_stride < q.raw_cols) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than the raw image width");
-  ImgLoc o = {{L, R}, row_stride, image_stride};
-  if (!on_device) {
-    const int rc = upload_to(c, L, R, row_stride, image_stride, q.raw_rows, q.raw_cols, q.raw[c->parity], q.raw_stride, q.raw_stream_stride, &o);
-    if (rc != VSLAM_OK) return rc;
-  }
-  q.src[0] = o.p[0]; q.src[1] = o.p[1]; q.src_row_stride = o.row_stride; q.src_stream_stride = o.stream_stride;
-  return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], c->up_stride, c->up_stream_stride);
-}
-// Colour input: host pairs go to the colour slabs of this step's parity (upload_to with the byte width as cols), device pairs are read in
-// place (by k_gray_u8, and by k_map_color behind the frame's last launch while map colours are on).  The grey pair is written where the next stage reads: the rectifier's raw slabs when rectifying, else
-// upload[parity]; DevBuf::img points at upload[parity] either way, as it does for a grey host frame.
-static int set_color_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
-  vslam_ctx::Col& q = c->col;
-  vslam_ctx::Rect& rq = c->rect;
-  const int rows = rq.on ? rq.raw_rows : c->cfg.c.rows, cols = rq.on ? rq.raw_cols : c->cfg.c.cols;
-  const int wb = gray_channels(q.format) * cols;
-  if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");
-  if (row_stride < wb) return fail(c, VSLAM_ERR_INVALID, "row stride smaller than channels * image width");
-  ImgLoc o = {{L, R}, row_stride, image_stride};
+// A frame's input pair.  Host images go to the slabs of this step's parity that the first stage reads — the colour slabs (upload_to with
+// the byte width as cols), the rectifier's raw slabs, else upload[parity]; device images are read in place, by the first stage alone
+// (and, colour, by k_map_color behind the frame's last launch while map colours are on).
+static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
+  const bool colour = c->col.format != VSLAM_PIXEL_GRAY8, raw = c->rect.on;
+  const int rows = raw ? c->rect.maps.raw_rows : c->cfg.c.rows, cols = raw ? c->rect.maps.raw_cols : c->cfg.c.cols;
+  const int wb = colour ? gray_channels(c->col.format) * cols : cols;
+  if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");  // stereo_framepoint_generator.cpp:75-78
+  if (row_stride < wb)
+    return fail(c, VSLAM_ERR_INVALID, colour ? "row stride smaller than channels * image width" : raw ? "row stride smaller than the raw image width" : "row stride smaller than image width");
+  ImgPlanes in = {{L, R}, row_stride, image_stride};
   if (!on_device) {
     // map colours: k_map_color read this parity's slab on the FRAME queue two steps ago, and the upload below is issued ahead of the wait in
     // launch_image_pipeline — it waits for that frame here (without the switch k_gray_u8, on the image queue itself, is the slab's last reader).
     // Every queue upload_to may copy on: its dense path takes img_override when set (the stage path of one stream: the frame queue itself,
     // already in order behind k_map_color, hence skipped), its strided paths always the image queue.
-    if (c->mapcol.rgb && c->frm_pending[c->parity]) {
+    if (colour && c->mapcol.rgb && c->frm_pending[c->parity]) {
       hipStream_t up[2] = {c->img_override ? c->img_override : c->stream_img, c->stream_img};
       for (int k = 0; k < 2; ++k)
         if (up[k] != c->stream && (k == 0 || up[k] != up[0])) HIP_TRY(c, hipStreamWaitEvent(up[k], c->ev_frm[c->parity], 0));
     }
-    const int rc = upload_to(c, L, R, row_stride, image_stride, rows, wb, q.slab[c->parity], q.stride, q.stream_stride, &o);
+    const int p = c->parity;
+    const int rc = colour ? upload_to(c, L, R, row_stride, image_stride, rows, wb, c->col.slab[p], c->col.stride, c->col.stream_stride, &in)
+                   : raw  ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->rect.raw[p], c->rect.raw_stride, c->rect.raw_stream_stride, &in)
+                          : upload_to(c, L, R, row_stride, image_stride, rows, cols, c->upload[p], c->up_stride, c->up_stream_stride, &in);
     if (rc != VSLAM_OK) return rc;
   }
-  q.src[0] = o.p[0]; q.src[1] = o.p[1]; q.src_row_stride = o.row_stride; q.src_stream_stride = o.stream_stride;
-  q.out_rows = rows; q.out_cols = cols;
-  for (int k = 0; k < 2; ++k) q.out[k] = rq.on ? rq.raw[c->parity][k] : c->upload[c->parity][k];
-  q.out_row_stride = rq.on ? rq.raw_stride : c->up_stride;
-  q.out_stream_stride = rq.on ? rq.raw_stream_stride : c->up_stream_stride;
-  if (rq.on) { rq.src[0] = q.out[0]; rq.src[1] = q.out[1]; rq.src_row_stride = q.out_row_stride; rq.src_stream_stride = q.out_stream_stride; }
-  return set_images_device(c, c->upload[c->parity][0], c->upload[c->parity][1], c->up_stride, c->up_stream_stride);
-}
-static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
-  if (c->col.format != VSLAM_PIXEL_GRAY8) return set_color_inputs(c, L, R, row_stride, image_stride, on_device);
-  if (c->rect.on) return set_raw_inputs(c, L, R, row_stride, image_stride, on_device);
-  return on_device ? set_images_device(c, L, R, row_stride, image_stride) : upload_images(c, L, R, row_stride, image_stride);
+  route_frame(c, in);
+  return VSLAM_OK;
 }
 
 // the fused frame.  Host images: the context's device is made current first.  Device images: the caller's current device is left as it
@@ -316,186 +253,6 @@ VS_API int vslam_process_device(vslam_ctx* c, const uint8_t* L, const uint8_t* R
 }
 VS_API int vslam_process_host(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride) {
   return process_frame(c, L, R, row_stride, image_stride, false);
-}
-
-// ---- rectification of raw input pairs ------------------------------------------------------------
-// Host maps in the CV_16SC2 + CV_16UC1 layout -> device maps with rows padded to a multiple of 4 entries (the padding is zero: in range,
-// never stored), so that every lane's 16-B / 8-B map loads are aligned and inside the allocation.
-static int rect_maps_ok(const uint16_t* map_a, size_t n) {
-  for (size_t i = 0; i < n; ++i) if (map_a[i] >= 1024) return 0;
-  return 1;
-}
-static void rect_pad_maps(const int16_t* xy, const uint16_t* fa, int rows, int cols, int ms, std::vector<int16_t>& pxy, std::vector<uint16_t>& pa) {
-  pxy.assign((size_t)rows * ms * 2, 0);
-  pa.assign((size_t)rows * ms, 0);
-  for (int r = 0; r < rows; ++r) {
-    std::memcpy(&pxy[(size_t)r * ms * 2], xy + (size_t)r * cols * 2, (size_t)cols * 4);
-    std::memcpy(&pa[(size_t)r * ms], fa + (size_t)r * cols, (size_t)cols * 2);
-  }
-}
-VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_cols, const int16_t* xyL, const uint16_t* aL, const int16_t* xyR,
-                                   const uint16_t* aR) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification called inside a frame");
-  const bool off = !xyL && !aL && !xyR && !aR;
-  if (!off && (!xyL || !aL || !xyR || !aR)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification: all four maps or none");
-  if (!off && (raw_rows < 1 || raw_cols < 1 || raw_rows > 32767 || raw_cols > 32767))
-    return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification: invalid raw image dimensions");
-  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols;
-  if (!off && (!rect_maps_ok(aL, (size_t)rows * cols) || !rect_maps_ok(aR, (size_t)rows * cols)))
-    return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification: interpolation table index >= 1024");
-  HIP_TRY(c, hipSetDevice(c->device));
-  sync_all(c);                     // the frames in flight still read the old maps and raw slabs
-  rect_free(c);
-  if (off) { (void)eq_keep_sync(c); return col_slab_sync(c) == hipSuccess ? VSLAM_OK : fail(c, VSLAM_ERR_HIP, "vslam_set_rectification: colour slabs"); }
-  vslam_ctx::Rect& q = c->rect;
-  q.raw_rows = raw_rows; q.raw_cols = raw_cols;
-  q.raw_stride = (raw_cols + 63) & ~63;
-  q.raw_stream_stride = (size_t)raw_rows * q.raw_stride;
-  q.map_stride = (cols + 3) & ~3;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    e = q.mem.alloc(&q.map_xy[k], (size_t)rows * q.map_stride * 2);
-    if (e == hipSuccess) e = q.mem.alloc(&q.map_a[k], (size_t)rows * q.map_stride);
-    for (int p = 0; p < 2 && e == hipSuccess; ++p) e = q.mem.alloc(&q.raw[p][k], (size_t)c->B * q.raw_stream_stride);
-  }
-  std::vector<int16_t> pxy;
-  std::vector<uint16_t> pa;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    rect_pad_maps(k ? xyR : xyL, k ? aR : aL, rows, cols, q.map_stride, pxy, pa);
-    e = hipMemcpy(q.map_xy[k], pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(q.map_a[k], pa.data(), pa.size() * 2, hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
-  q.on = true;
-  e = eq_keep_sync(c);
-  if (e == hipSuccess) e = col_slab_sync(c);
-  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
-}
-VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, const int16_t* map_xy,
-                          const uint16_t* map_a, int32_t drows, int32_t dcols, uint8_t* dst) {
-  if (!c) return VSLAM_ERR_INVALID;
-  tmp_reset(c);
-  if (c->sticky != VSLAM_OK) return c->sticky;
-  if (!src || !dst || !map_xy || !map_a || rows < 1 || cols < 1 || row_stride < cols || drows < 1 || dcols < 1)
-    return fail(c, VSLAM_ERR_INVALID, "remap: bad argument");
-  if (!rect_maps_ok(map_a, (size_t)drows * dcols)) return fail(c, VSLAM_ERR_INVALID, "remap: interpolation table index >= 1024");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int ms = (dcols + 3) & ~3;
-  std::vector<int16_t> pxy;
-  std::vector<uint16_t> pa;
-  rect_pad_maps(map_xy, map_a, drows, dcols, ms, pxy, pa);
-  uint8_t *ds = nullptr, *dd = nullptr;
-  int16_t* dxy = nullptr;
-  uint16_t* da = nullptr;
-  hipError_t e = tmp_get(c, (void**)&ds, (size_t)rows * row_stride);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dxy, pxy.size() * 2);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&da, pa.size() * 2);
-  if (e == hipSuccess) e = tmp_get(c, (void**)&dd, (size_t)drows * ms);
-  if (e == hipSuccess) e = hipMemcpyAsync(ds, src, (size_t)(rows - 1) * row_stride + cols, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dxy, pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(da, pa.data(), pa.size() * 2, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    RectArgs ra;
-    std::memset(&ra, 0, sizeof ra);
-    ra.src[0] = ds; ra.src_row_stride = row_stride; ra.src_rows = rows; ra.src_cols = cols;
-    ra.map_xy[0] = dxy; ra.map_a[0] = da; ra.map_stride = ms;
-    ra.dst[0] = dd; ra.dst_row_stride = ms; ra.dst_stream_stride = (size_t)drows * ms;
-    ra.rows = drows; ra.cols = dcols; ra.s0 = 0; ra.n = 1; ra.sides = 1; ra.active[0] = 1u;
-    hipLaunchKernelGGL(k_rectify, dim3((dcols + 255) / 256, (drows + 3) / 4, 1), dim3(256), 0, c->stream, ra);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy2DAsync(dst, dcols, dd, ms, dcols, drows, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
-  return VSLAM_OK;
-}
-VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
-  const int rc = check_stream(c, s);
-  if (rc != VSLAM_OK) return rc;
-  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_rectified_images: null output");
-  if (!c->rect.on || !c->rect.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_rectified_images: no frame has been rectified since vslam_set_rectification");
-  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols;
-  for (int k = 0; k < 2; ++k)
-    HIP_TRY(c, hipMemcpy2D(k ? right : left, cols, (c->eq.keep[0] ? c->eq.keep[k] : c->upload[c->last_set][k]) + (size_t)s * c->up_stream_stride,
-                           c->up_stride, cols, rows, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
-}
-
-// ---- histogram equalisation of the input pair (kernels_equalize.h) -------------------------------
-// The slot's switch.  geo null: global equalisation, else CLAHE with what clahe_geometry made of the caller's arguments.  The two modes
-// exclude each other; switching one off while the other is on changes nothing.
-static int eq_switch(vslam_ctx* c, const char* who, bool on, const ClaheArgs* geo, double clip_limit) {
-  const bool clahe = geo != nullptr;
-  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, std::string(who) + " called inside a frame");
-  if (c->eq.on && c->eq.clahe != clahe)
-    return !on ? VSLAM_OK : fail(c, VSLAM_ERR_STATE, std::string(who) + (clahe ? ": global equalisation is on (vslam_set_equalization)" : ": CLAHE is on (vslam_set_clahe)"));
-  const bool same = !clahe || (c->eq.clip_limit == clip_limit && c->eq.geo.tiles_x == geo->tiles_x && c->eq.geo.tiles_y == geo->tiles_y);
-  if (on ? (c->eq.on && same) : !c->eq.on) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  sync_all(c);                     // the frames in flight still read the tables and the slabs
-  eq_free(c);
-  if (!on) return VSLAM_OK;
-  hipError_t e;
-  if (!clahe) {
-    e = c->eq.mem.alloc(&c->eq.hist, (size_t)c->B * 2 * 256);
-    if (e == hipSuccess) e = hipMemset(c->eq.hist, 0, (size_t)c->B * 2 * 256 * sizeof(uint32_t));
-  } else {
-    c->eq.geo = *geo; c->eq.clip_limit = clip_limit;
-    const size_t nl = (size_t)c->B * 2 * geo->tiles_x * geo->tiles_y * 256;
-    e = c->eq.mem.alloc(&c->eq.luts, nl);
-    if (e == hipSuccess) e = hipMemset(c->eq.luts, 0, nl);
-  }
-  c->eq.on = e == hipSuccess;
-  c->eq.clahe = c->eq.on && clahe;
-  if (e == hipSuccess) e = eq_keep_sync(c);
-  if (e != hipSuccess) { eq_free(c); return fail(c, VSLAM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
-  return VSLAM_OK;
-}
-VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_equalization called inside a frame");
-  if ((size_t)c->cfg.c.rows * c->cfg.c.cols > (size_t)VS_EQ_MAX_PIXELS) return fail(c, VSLAM_ERR_INVALID, "vslam_set_equalization: more than 2^24 pixels per image");
-  return eq_switch(c, "vslam_set_equalization", on != 0, nullptr, 0);
-}
-
-// ---- CLAHE of the input pair: the second mode of the equalisation slot (kernels_clahe.h) ----------
-VS_API int vslam_set_clahe(vslam_ctx* c, int on, double clip_limit, int tiles_x, int tiles_y) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_clahe called inside a frame");
-  ClaheArgs geo;
-  std::memset(&geo, 0, sizeof geo);
-  const char* why = "";
-  if (on && !clahe_geometry(c->cfg.c.rows, c->cfg.c.cols, clip_limit, tiles_x, tiles_y, geo, &why)) return fail(c, VSLAM_ERR_INVALID, std::string("vslam_set_clahe: ") + why);
-  return eq_switch(c, "vslam_set_clahe", on != 0, &geo, clip_limit);
-}
-
-// ---- colour input (kernels_gray.h) ---------------------------------------------------------------
-VS_API int vslam_set_color_input(vslam_ctx* c, int format) {
-  if (!c) return VSLAM_ERR_INVALID;
-  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_color_input called inside a frame");
-  if (format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8) return fail(c, VSLAM_ERR_INVALID, "vslam_set_color_input: unknown pixel format");
-  if (format == c->col.format) return VSLAM_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  sync_all(c);                     // the frames in flight still read the slabs
-  if (format == VSLAM_PIXEL_GRAY8) mapcol_free(c);     // no colour left to sample
-  col_free(c);
-  c->col.format = format;
-  const hipError_t e = col_slab_sync(c);
-  if (e != hipSuccess) { col_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_color_input: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
-}
-VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
-  const int rc = check_stream(c, s);
-  if (rc != VSLAM_OK) return rc;
-  const vslam_ctx::Col& q = c->col;
-  if (q.format == VSLAM_PIXEL_GRAY8 || !q.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_gray_images: no frame has been converted since vslam_set_color_input");
-  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_gray_images: null output");
-  for (int k = 0; k < 2; ++k)
-    HIP_TRY(c, hipMemcpy2D(k ? right : left, q.out_cols, q.out[k] + (size_t)s * q.out_stream_stride, q.out_row_stride, q.out_cols, q.out_rows,
-                           hipMemcpyDeviceToHost));
-  return VSLAM_OK;
 }
 
 // ---- pinned host memory for the caller's images -------------------------------------------------------------------------------------

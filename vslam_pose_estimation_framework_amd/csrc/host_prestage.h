@@ -1,0 +1,222 @@
+// host_prestage.h — the input stages ahead of the detector, written once for the stereo context and the RGB-D tracker: colour to grey
+// (kernels_gray.h), remap (rectification / undistortion, kernels_rectify.h) and the equalisation slot (global or CLAHE,
+// kernels_equalize.h / kernels_clahe.h).  Where an image pair lies (ImgPlanes), the one filler of the kernels' argument blocks (place),
+// the slot (EqSlot), the intake of remap maps, the per-frame plan (PrePlan) with its one enqueue, the plane read-out of the getters and the
+// colour source of the map's colours.  Owner-independent host code: no context, no tracker; errors come back as hipError_t or as text.
+// Included by vslam_hip.hip ahead of host_ctx.h (the context holds these types); rgbd_device.h uses it too.
+#pragma once
+
+// ---- where an image pair lies --------------------------------------------------------------------
+// stream s of side k at p[k] + s * stream_stride, rows row_stride bytes apart.  One image per stream (RGB-D): p[1] stays null.
+struct ImgPlanes { const uint8_t* p[2] = {nullptr, nullptr}; int32_t row_stride = 0; size_t stream_stride = 0; };
+// DevBuf::img*, which the kernels read, pointed at a pair (a one-sided one is mirrored into img[1])
+static void buf_set_planes(DevBuf& b, const ImgPlanes& x) {
+  b.img[0] = x.p[0]; b.img[1] = x.p[1] ? x.p[1] : x.p[0];
+  b.img_row_stride = x.row_stride; b.img_stream_stride = x.stream_stride;
+}
+// streams 0 .. n - 1 switched on, in the form of DevBuf::active
+static void active_all(uint32_t* active, int n) {
+  std::memset(active, 0, sizeof(uint32_t) * (VS_MAX_STREAMS / 32));
+  for (int s = 0; s < n; ++s) active[s >> 5] |= 1u << (s & 31);
+}
+
+// ---- the one argument filler -----------------------------------------------------------------------
+// what GrayArgs, EqArgs, ClaheArgs and RectArgs have in common
+template <class A>
+static void place(A& a, const ImgPlanes& src, const ImgPlanes& dst, int rows, int cols, int n, int sides, const uint32_t* active) {
+  for (int k = 0; k < 2; ++k) { a.src[k] = src.p[k]; a.dst[k] = const_cast<uint8_t*>(dst.p[k]); }
+  a.src_row_stride = src.row_stride; a.src_stream_stride = src.stream_stride;
+  a.dst_row_stride = dst.row_stride; a.dst_stream_stride = dst.stream_stride;
+  a.rows = rows; a.cols = cols; a.n = n; a.sides = sides;
+  std::memcpy(a.active, active, sizeof a.active);
+}
+// one image (the stand-alone entries)
+template <class A>
+static void place(A& a, const uint8_t* src, int32_t src_row_stride, uint8_t* dst, int32_t dst_row_stride, int rows, int cols) {
+  uint32_t active[VS_MAX_STREAMS / 32];
+  active_all(active, 1);
+  place(a, ImgPlanes{{src, nullptr}, src_row_stride, 0}, ImgPlanes{{dst, nullptr}, dst_row_stride, 0}, rows, cols, 1, 1, active);
+}
+
+// ---- remap maps ------------------------------------------------------------------------------------
+// Host maps in the CV_16SC2 + CV_16UC1 layout -> device maps with rows padded to a multiple of 4 entries (the padding is zero: in range,
+// never stored), so that every lane's 16-B / 8-B map loads are aligned and inside the allocation.
+static int rect_maps_ok(const uint16_t* map_a, size_t n) {
+  for (size_t i = 0; i < n; ++i) if (map_a[i] >= 1024) return 0;
+  return 1;
+}
+static void rect_pad_maps(const int16_t* xy, const uint16_t* fa, int rows, int cols, int ms, std::vector<int16_t>& pxy, std::vector<uint16_t>& pa) {
+  pxy.assign((size_t)rows * ms * 2, 0);
+  pa.assign((size_t)rows * ms, 0);
+  for (int r = 0; r < rows; ++r) {
+    std::memcpy(&pxy[(size_t)r * ms * 2], xy + (size_t)r * cols * 2, (size_t)cols * 4);
+    std::memcpy(&pa[(size_t)r * ms], fa + (size_t)r * cols, (size_t)cols * 2);
+  }
+}
+// the device maps of a switch: `sides` pairs at rows x cols (stride entries per row) over raw images of raw_rows x raw_cols
+struct RemapMaps {
+  int16_t* xy[2] = {nullptr, nullptr}; uint16_t* a[2] = {nullptr, nullptr};
+  int32_t stride = 0, rows = 0, cols = 0, raw_rows = 0, raw_cols = 0;
+};
+// What a map setter refuses before it touches anything: 0, or the status with *why filled (`who`: the entry's name).  *off: every map
+// is null, the switch goes off.
+static int remap_maps_check(const char* who, int sides, int raw_rows, int raw_cols, int rows, int cols, const int16_t* const* xy, const uint16_t* const* a,
+                            bool* off, std::string* why) {
+  int given = 0;
+  for (int k = 0; k < sides; ++k) given += (xy[k] != nullptr) + (a[k] != nullptr);
+  *off = given == 0;
+  if (*off) return VSLAM_OK;
+  const char* what = nullptr;
+  if (given != 2 * sides) what = sides == 2 ? ": all four maps or none" : ": both maps or none";
+  else if (raw_rows < 1 || raw_cols < 1 || raw_rows > 32767 || raw_cols > 32767) what = ": invalid raw image dimensions";
+  else
+    for (int k = 0; k < sides && !what; ++k)
+      if (!rect_maps_ok(a[k], (size_t)rows * cols)) what = ": interpolation table index >= 1024";
+  if (!what) return VSLAM_OK;
+  *why = std::string(who) + what;
+  return VSLAM_ERR_INVALID;
+}
+// checked maps -> m: padded, allocated from mem and uploaded.  On failure the caller releases mem (it holds the half-built maps).
+static hipError_t remap_maps_upload(DeviceStore& mem, RemapMaps& m, int sides, int raw_rows, int raw_cols, int rows, int cols, const int16_t* const* xy,
+                                    const uint16_t* const* a) {
+  m = RemapMaps();
+  m.rows = rows; m.cols = cols; m.raw_rows = raw_rows; m.raw_cols = raw_cols;
+  m.stride = (cols + 3) & ~3;
+  std::vector<int16_t> pxy;
+  std::vector<uint16_t> pa;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < sides && e == hipSuccess; ++k) {
+    rect_pad_maps(xy[k], a[k], rows, cols, m.stride, pxy, pa);
+    e = mem.alloc(&m.xy[k], pxy.size());
+    if (e == hipSuccess) e = mem.alloc(&m.a[k], pa.size());
+    if (e == hipSuccess) e = hipMemcpy(m.xy[k], pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.a[k], pa.data(), pa.size() * 2, hipMemcpyHostToDevice);
+  }
+  return e;
+}
+// k_rectify on n streams of `sides` images: src (raw size of m) -> dst (m's own size)
+static void remap_enqueue(hipStream_t st, const RemapMaps& m, const ImgPlanes& src, const ImgPlanes& dst, int n, int sides, const uint32_t* active) {
+  RectArgs ra{};
+  place(ra, src, dst, m.rows, m.cols, n, sides, active);
+  for (int k = 0; k < 2; ++k) { ra.map_xy[k] = m.xy[k]; ra.map_a[k] = m.a[k]; }
+  ra.map_stride = m.stride; ra.src_rows = m.raw_rows; ra.src_cols = m.raw_cols; ra.s0 = 0;
+  dim3 grid = undistort_grid(m.rows, m.cols, n);
+  grid.z *= sides;
+  hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, st, ra);
+}
+
+// ---- the equalisation slot -------------------------------------------------------------------------
+// Global equalisation (k_hist_u8, k_equalize_apply: the count table [image][256], zeroed and refilled every frame) or CLAHE (k_clahe_lut,
+// k_clahe_apply: the tables [image][tilesY][tilesX][256], geo holding what clahe_geometry made of the switch's arguments), image = stream *
+// sides + side.  The two modes exclude each other; switching one off while the other is on changes nothing.  The owner says which
+// queues drain before a switch and what else goes with it, and when have_frame holds; src / dst are this frame's routing.
+struct EqSlot {
+  bool on = false, clahe = false, have_frame = false;
+  double clip_limit = 0;
+  ClaheArgs geo{};
+  uint32_t* hist = nullptr;
+  uint8_t* luts = nullptr;
+  int sides = 0;
+  DeviceStore mem;
+  ImgPlanes src, dst;
+  size_t luts_per_image() const { return (size_t)geo.tiles_x * geo.tiles_y * 256; }
+
+  void release() {
+    mem.release();
+    on = clahe = have_frame = false; clip_limit = 0; geo = ClaheArgs{}; hist = nullptr; luts = nullptr; sides = 0; src = dst = ImgPlanes();
+  }
+  // The switch.  new_geo null: global equalisation, else CLAHE; names: the two entries {global, CLAHE}, for the messages; tables for n *
+  // sides_ images, zeroed.  clear(): the owner drains its queues and frees the slot (release()) with what goes with it; more(): it
+  // allocates what it routes through.  0, or the status with *why filled.
+  template <class Clear, class More>
+  int switch_to(bool want, const ClaheArgs* new_geo, double new_clip, int n, int sides_, const char* const names[2], std::string* why, Clear&& clear, More&& more) {
+    const bool want_clahe = new_geo != nullptr;
+    if (on && clahe != want_clahe) {
+      if (!want) return VSLAM_OK;
+      *why = std::string(names[want_clahe]) + (want_clahe ? ": global equalisation is on (" : ": CLAHE is on (") + names[!want_clahe] + ")";
+      return VSLAM_ERR_STATE;
+    }
+    const bool same = !want_clahe || (clip_limit == new_clip && geo.tiles_x == new_geo->tiles_x && geo.tiles_y == new_geo->tiles_y);
+    if (want ? (on && same) : !on) return VSLAM_OK;
+    clear();
+    if (!want) return VSLAM_OK;
+    const size_t images = (size_t)n * sides_;
+    hipError_t e;
+    if (!want_clahe) {
+      e = mem.alloc(&hist, images * 256);
+      if (e == hipSuccess) e = hipMemset(hist, 0, images * 256 * sizeof(uint32_t));
+    } else {
+      geo = *new_geo; clip_limit = new_clip;
+      e = mem.alloc(&luts, images * luts_per_image());
+      if (e == hipSuccess) e = hipMemset(luts, 0, images * luts_per_image());
+    }
+    on = e == hipSuccess;
+    clahe = on && want_clahe;
+    sides = sides_;
+    if (e == hipSuccess) e = more();
+    if (e == hipSuccess) return VSLAM_OK;
+    clear();
+    *why = std::string(names[want_clahe]) + ": " + hipGetErrorString(e);
+    return VSLAM_ERR_HIP;
+  }
+  // src -> dst (may be src: in place) on streams 0 .. n - 1
+  hipError_t enqueue(hipStream_t st, int rows, int cols, int n, int sides_, const uint32_t* active) const {
+    if (clahe) { ClaheArgs ca = geo; place(ca, src, dst, rows, cols, n, sides_, active); ca.luts = luts; return clahe_enqueue(st, ca); }
+    EqArgs ea{};
+    place(ea, src, dst, rows, cols, n, sides_, active);
+    ea.hist = hist;
+    return equalize_enqueue(st, ea);
+  }
+  // the tables of stream s: uint32 [sides][256] / uint8 [sides][tilesY][tilesX][256]
+  hipError_t hist_to_host(uint32_t* out, int s) const { return hipMemcpy(out, hist + (size_t)s * sides * 256, (size_t)sides * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost); }
+  hipError_t luts_to_host(uint8_t* out, int s) const { return hipMemcpy(out, luts + (size_t)s * sides * luts_per_image(), sides * luts_per_image(), hipMemcpyDeviceToHost); }
+};
+
+// ---- a frame's plan and its enqueue ----------------------------------------------------------------
+// Which stage runs on this frame and where it reads and writes; the slot's part is EqSlot::on / src / dst.  Each owner fills it in ONE
+// function (route_frame in host_frame.h and in rgbd_device.h), from which switches are on and whether the frame is the caller's device memory.
+//
+// Stereo (the final pair is always in upload[parity], except an untouched caller device pair):
+//   stage     reads                                                              writes
+//   grey      colour slab[parity] (host) or caller memory (device)               rect.raw[parity] if rectifying, else upload[parity]
+//   rectify   rect.raw[parity] (host or grey output) or caller memory            eq.keep if equalising, else upload[parity]
+//   equalise  eq.keep if rectifying, else DevBuf::img (in place when that        upload[parity]
+//             already is upload[parity])
+// RGB-D (single buffers; caller memory is never written):
+//   grey      d_img (host) or caller memory                                      col.gray
+//   undistort previous                                                           und.img
+//   equalise  previous                                                           in place if the image is ours (host frame, grey,
+//                                                                                undistorted), else eq.img
+struct PrePlan {
+  int format = 0;               // VSLAM_PIXEL_*: the grey stage runs unless GRAY8
+  bool remap = false;
+  int in_rows = 0, in_cols = 0; // the frames that come in (the raw size while remapping)
+  int rows = 0, cols = 0;       // the size the detector works on
+  ImgPlanes color, gray;        // grey stage: source, result (in_rows x in_cols)
+  ImgPlanes raw, mapped;        // remap: source (in_rows x in_cols), result (rows x cols)
+};
+// grey, then remap, then equalise, on one queue
+static hipError_t prestage_enqueue(hipStream_t st, const PrePlan& pl, const RemapMaps& maps, const EqSlot& eq, int n, int sides, const uint32_t* active) {
+  if (pl.format != VSLAM_PIXEL_GRAY8) {
+    GrayArgs ga{};
+    place(ga, pl.color, pl.gray, pl.in_rows, pl.in_cols, n, sides, active);
+    ga.format = pl.format;
+    const hipError_t e = gray_enqueue(st, ga);
+    if (e != hipSuccess) return e;
+  }
+  if (pl.remap) remap_enqueue(st, maps, pl.raw, pl.mapped, n, sides, active);
+  return eq.on ? eq.enqueue(st, pl.rows, pl.cols, n, sides, active) : hipSuccess;
+}
+
+// ---- read-out ----------------------------------------------------------------------------------------
+// plane `side` of stream s, rows x cols, dense into out
+static hipError_t planes_to_host(uint8_t* out, const ImgPlanes& x, int side, int s, int rows, int cols) {
+  return hipMemcpy2D(out, (size_t)cols, x.p[side] + (size_t)s * x.stream_stride, (size_t)x.row_stride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost);
+}
+// a frame's left colour image as the map-colour kernels read it: through the left map while remapping (maps non-null)
+static ColorSrc color_src(const ImgPlanes& colour, int rows, int cols, int format, const RemapMaps* maps) {
+  ColorSrc s{};
+  s.img = colour.p[0]; s.stream_stride = colour.stream_stride; s.row_stride = colour.row_stride; s.rows = rows; s.cols = cols; s.format = format;
+  if (maps) { s.map_xy = maps->xy[0]; s.map_a = maps->a[0]; s.map_stride = maps->stride; s.map_rows = maps->rows; s.map_cols = maps->cols; }
+  return s;
+}

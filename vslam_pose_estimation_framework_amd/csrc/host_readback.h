@@ -357,35 +357,3 @@ VS_API int vslam_debug_stream_ticks(vslam_ctx* c, unsigned long long* out /* [B]
   }
   return VSLAM_OK;
 }
-
-// ---- the equalised input pair and its counts (vslam_set_equalization) ----------------------------
-static int eq_readable(vslam_ctx* c, int s, const char* who) {
-  const int rc = check_stream(c, s);
-  if (rc != VSLAM_OK) return rc;
-  if (!c->eq.on || !c->eq.have_frame) return fail(c, VSLAM_ERR_STATE, std::string(who) + ": no frame has been equalised since vslam_set_equalization");
-  return VSLAM_OK;
-}
-VS_API int vslam_get_equalized_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
-  if (int rc = eq_readable(c, s, "vslam_get_equalized_images")) return rc;
-  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_equalized_images: null output");
-  const vslam_ctx::Eq& q = c->eq;
-  for (int k = 0; k < 2; ++k)
-    HIP_TRY(c, hipMemcpy2D(k ? right : left, c->cfg.c.cols, q.out[k] + (size_t)s * q.out_stream_stride, q.out_row_stride, c->cfg.c.cols, c->cfg.c.rows,
-                           hipMemcpyDeviceToHost));
-  return VSLAM_OK;
-}
-VS_API int vslam_get_equalization_histograms(vslam_ctx* c, int s, uint32_t* hist512) {
-  if (int rc = eq_readable(c, s, "vslam_get_equalization_histograms")) return rc;
-  if (c->eq.clahe) return fail(c, VSLAM_ERR_STATE, "vslam_get_equalization_histograms: the context runs CLAHE, which keeps tables per tile (vslam_get_clahe_luts)");
-  if (!hist512) return fail(c, VSLAM_ERR_INVALID, "vslam_get_equalization_histograms: null output");
-  HIP_TRY(c, hipMemcpy(hist512, c->eq.hist + (size_t)s * 512, 512 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return VSLAM_OK;
-}
-VS_API int vslam_get_clahe_luts(vslam_ctx* c, int s, uint8_t* luts) {
-  if (int rc = eq_readable(c, s, "vslam_get_clahe_luts")) return rc;
-  if (!c->eq.clahe) return fail(c, VSLAM_ERR_STATE, "vslam_get_clahe_luts: the context runs global equalisation, not CLAHE");
-  if (!luts) return fail(c, VSLAM_ERR_INVALID, "vslam_get_clahe_luts: null output");
-  const size_t nl = (size_t)2 * c->eq.geo.tiles_x * c->eq.geo.tiles_y * 256;
-  HIP_TRY(c, hipMemcpy(luts, c->eq.luts + (size_t)s * nl, nl, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
-}

@@ -1,0 +1,206 @@
+// host_switches.h — the stereo context's input-stage switches and their getters: rectification (vslam_set_rectification), the equalisation
+// slot (vslam_set_equalization, vslam_set_clahe) and colour input (vslam_set_color_input), the stores behind them, and the stand-alone
+// vslam_remap_u8.  What the switches share with the RGB-D tracker is host_prestage.h; a frame's routing through the stages is route_frame
+// in host_frame.h.  Host code, included by vslam_hip.hip after host_ctx.h and ahead of host_frame.h.
+#pragma once
+
+// ---- the stores ------------------------------------------------------------------------------------
+static void rect_free(vslam_ctx* c) {
+  c->rect.mem.release();
+  c->rect = vslam_ctx::Rect();
+}
+static void eq_free(vslam_ctx* c) {
+  c->eq.release();
+  c->eq.keep_mem.release();
+  c->eq.keep[0] = c->eq.keep[1] = nullptr;
+}
+// the rectified pair's own slabs exist exactly while rectification and equalisation are both on (called by both setters, queues idle)
+static hipError_t eq_keep_sync(vslam_ctx* c) {
+  vslam_ctx::Eq& q = c->eq;
+  const bool want = q.on && c->rect.on;
+  if (want == (q.keep[0] != nullptr)) return hipSuccess;
+  q.keep_mem.release();
+  q.keep[0] = q.keep[1] = nullptr;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && want && e == hipSuccess; ++k) e = q.keep_mem.alloc(&q.keep[k], (size_t)c->B * c->up_stream_stride);
+  if (e != hipSuccess) { q.keep_mem.release(); q.keep[0] = q.keep[1] = nullptr; }
+  return e;
+}
+static void col_free(vslam_ctx* c) {
+  c->col.mem.release();
+  c->col = vslam_ctx::Col();
+}
+// the colour slabs exist while the switch is on, at the size of the frames that come in: the raw size while rectification is set (called by
+// both setters, queues idle)
+static hipError_t col_slab_sync(vslam_ctx* c) {
+  vslam_ctx::Col& q = c->col;
+  const int fmt = q.format;
+  const int rows = c->rect.on ? c->rect.maps.raw_rows : c->cfg.c.rows, cols = c->rect.on ? c->rect.maps.raw_cols : c->cfg.c.cols;
+  const int wb = fmt == VSLAM_PIXEL_GRAY8 ? 0 : gray_channels(fmt) * cols;
+  if (fmt != 0 && q.slab[0][0] && q.slab_rows == rows && q.slab_cols == wb) return hipSuccess;
+  col_free(c);
+  q.format = fmt;
+  if (fmt == 0) return hipSuccess;
+  q.slab_rows = rows; q.slab_cols = wb;
+  q.stride = (wb + 63) & ~63;
+  q.stream_stride = (size_t)rows * q.stride;
+  hipError_t e = hipSuccess;
+  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = q.mem.alloc(&q.slab[p][k], (size_t)c->B * q.stream_stride);
+  if (e != hipSuccess) col_free(c);
+  return e;
+}
+// the slabs of the context as image pairs: upload[set], and where k_rectify writes the pair of product set `set` (with equalisation on as
+// well: in slabs of its own, the equalised pair goes to upload[set])
+static ImgPlanes upload_planes(const vslam_ctx* c, int set) { return {{c->upload[set][0], c->upload[set][1]}, c->up_stride, c->up_stream_stride}; }
+static ImgPlanes rectified_planes(const vslam_ctx* c, int set) {
+  return c->eq.keep[0] ? ImgPlanes{{c->eq.keep[0], c->eq.keep[1]}, c->up_stride, c->up_stream_stride} : upload_planes(c, set);
+}
+// both sides of stream s of a pair, rows x cols, dense
+static int pair_to_host(vslam_ctx* c, const ImgPlanes& x, int s, int rows, int cols, uint8_t* left, uint8_t* right) {
+  for (int k = 0; k < 2; ++k) HIP_TRY(c, planes_to_host(k ? right : left, x, k, s, rows, cols));
+  return VSLAM_OK;
+}
+
+// ---- rectification of raw input pairs ------------------------------------------------------------
+VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_cols, const int16_t* xyL, const uint16_t* aL, const int16_t* xyR,
+                                   const uint16_t* aR) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification called inside a frame");
+  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols;
+  const int16_t* const xy[2] = {xyL, xyR};
+  const uint16_t* const a[2] = {aL, aR};
+  bool off = false;
+  std::string why;
+  if (const int rc = remap_maps_check("vslam_set_rectification", 2, raw_rows, raw_cols, rows, cols, xy, a, &off, &why)) return fail(c, rc, why);
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the old maps and raw slabs
+  rect_free(c);
+  if (off) { (void)eq_keep_sync(c); return col_slab_sync(c) == hipSuccess ? VSLAM_OK : fail(c, VSLAM_ERR_HIP, "vslam_set_rectification: colour slabs"); }
+  vslam_ctx::Rect& q = c->rect;
+  q.raw_stride = (raw_cols + 63) & ~63;
+  q.raw_stream_stride = (size_t)raw_rows * q.raw_stride;
+  hipError_t e = remap_maps_upload(q.mem, q.maps, 2, raw_rows, raw_cols, rows, cols, xy, a);
+  for (int k = 0; k < 2; ++k)
+    for (int p = 0; p < 2 && e == hipSuccess; ++p) e = q.mem.alloc(&q.raw[p][k], (size_t)c->B * q.raw_stream_stride);
+  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
+  q.on = true;
+  e = eq_keep_sync(c);
+  if (e == hipSuccess) e = col_slab_sync(c);
+  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_rectified_images: null output");
+  if (!c->rect.on || !c->rect.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_rectified_images: no frame has been rectified since vslam_set_rectification");
+  return pair_to_host(c, rectified_planes(c, c->last_set), s, c->cfg.c.rows, c->cfg.c.cols, left, right);
+}
+VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, const int16_t* map_xy,
+                          const uint16_t* map_a, int32_t drows, int32_t dcols, uint8_t* dst) {
+  if (!c) return VSLAM_ERR_INVALID;
+  tmp_reset(c);
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  if (!src || !dst || !map_xy || !map_a || rows < 1 || cols < 1 || row_stride < cols || drows < 1 || dcols < 1)
+    return fail(c, VSLAM_ERR_INVALID, "remap: bad argument");
+  if (!rect_maps_ok(map_a, (size_t)drows * dcols)) return fail(c, VSLAM_ERR_INVALID, "remap: interpolation table index >= 1024");
+  HIP_TRY(c, hipSetDevice(c->device));
+  RemapMaps m;
+  m.rows = drows; m.cols = dcols; m.raw_rows = rows; m.raw_cols = cols;
+  m.stride = (dcols + 3) & ~3;
+  std::vector<int16_t> pxy;
+  std::vector<uint16_t> pa;
+  rect_pad_maps(map_xy, map_a, drows, dcols, m.stride, pxy, pa);
+  uint8_t *ds = nullptr, *dd = nullptr;
+  hipError_t e = tmp_get(c, (void**)&ds, (size_t)rows * row_stride);
+  if (e == hipSuccess) e = tmp_get(c, (void**)&m.xy[0], pxy.size() * 2);
+  if (e == hipSuccess) e = tmp_get(c, (void**)&m.a[0], pa.size() * 2);
+  if (e == hipSuccess) e = tmp_get(c, (void**)&dd, (size_t)drows * m.stride);
+  if (e == hipSuccess) e = hipMemcpyAsync(ds, src, (size_t)(rows - 1) * row_stride + cols, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m.xy[0], pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m.a[0], pa.data(), pa.size() * 2, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    uint32_t active[VS_MAX_STREAMS / 32];
+    active_all(active, 1);
+    remap_enqueue(c->stream, m, ImgPlanes{{ds, nullptr}, row_stride, 0}, ImgPlanes{{dd, nullptr}, m.stride, (size_t)drows * m.stride}, 1, 1, active);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy2DAsync(dst, dcols, dd, m.stride, dcols, drows, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, VSLAM_ERR_HIP, hipGetErrorString(e));
+  return VSLAM_OK;
+}
+
+// ---- the equalisation slot of the input pair: global (kernels_equalize.h) or CLAHE (kernels_clahe.h) ---------------
+// geo null: global equalisation, else CLAHE with what clahe_geometry made of the caller's arguments
+static int eq_switch(vslam_ctx* c, bool on, const ClaheArgs* geo, double clip_limit) {
+  static const char* const names[2] = {"vslam_set_equalization", "vslam_set_clahe"};
+  std::string why;
+  const int rc = c->eq.switch_to(on, geo, clip_limit, c->B, 2, names, &why,
+                                 [&] { (void)hipSetDevice(c->device); sync_all(c); eq_free(c); },     // the frames in flight still read the tables and the slabs
+                                 [&] { return eq_keep_sync(c); });
+  return rc ? fail(c, rc, why) : VSLAM_OK;
+}
+VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_equalization called inside a frame");
+  if ((size_t)c->cfg.c.rows * c->cfg.c.cols > (size_t)VS_EQ_MAX_PIXELS) return fail(c, VSLAM_ERR_INVALID, "vslam_set_equalization: more than 2^24 pixels per image");
+  return eq_switch(c, on != 0, nullptr, 0);
+}
+VS_API int vslam_set_clahe(vslam_ctx* c, int on, double clip_limit, int tiles_x, int tiles_y) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_clahe called inside a frame");
+  ClaheArgs geo;
+  std::memset(&geo, 0, sizeof geo);
+  const char* why = "";
+  if (on && !clahe_geometry(c->cfg.c.rows, c->cfg.c.cols, clip_limit, tiles_x, tiles_y, geo, &why)) return fail(c, VSLAM_ERR_INVALID, std::string("vslam_set_clahe: ") + why);
+  return eq_switch(c, on != 0, &geo, clip_limit);
+}
+static int eq_readable(vslam_ctx* c, int s, const char* who) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (!c->eq.on || !c->eq.have_frame) return fail(c, VSLAM_ERR_STATE, std::string(who) + ": no frame has been equalised since vslam_set_equalization");
+  return VSLAM_OK;
+}
+VS_API int vslam_get_equalized_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  if (int rc = eq_readable(c, s, "vslam_get_equalized_images")) return rc;
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_equalized_images: null output");
+  return pair_to_host(c, c->eq.dst, s, c->cfg.c.rows, c->cfg.c.cols, left, right);
+}
+VS_API int vslam_get_equalization_histograms(vslam_ctx* c, int s, uint32_t* hist512) {
+  if (int rc = eq_readable(c, s, "vslam_get_equalization_histograms")) return rc;
+  if (c->eq.clahe) return fail(c, VSLAM_ERR_STATE, "vslam_get_equalization_histograms: the context runs CLAHE, which keeps tables per tile (vslam_get_clahe_luts)");
+  if (!hist512) return fail(c, VSLAM_ERR_INVALID, "vslam_get_equalization_histograms: null output");
+  HIP_TRY(c, c->eq.hist_to_host(hist512, s));
+  return VSLAM_OK;
+}
+VS_API int vslam_get_clahe_luts(vslam_ctx* c, int s, uint8_t* luts) {
+  if (int rc = eq_readable(c, s, "vslam_get_clahe_luts")) return rc;
+  if (!c->eq.clahe) return fail(c, VSLAM_ERR_STATE, "vslam_get_clahe_luts: the context runs global equalisation, not CLAHE");
+  if (!luts) return fail(c, VSLAM_ERR_INVALID, "vslam_get_clahe_luts: null output");
+  HIP_TRY(c, c->eq.luts_to_host(luts, s));
+  return VSLAM_OK;
+}
+
+// ---- colour input (kernels_gray.h) ---------------------------------------------------------------
+VS_API int vslam_set_color_input(vslam_ctx* c, int format) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_color_input called inside a frame");
+  if (format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8) return fail(c, VSLAM_ERR_INVALID, "vslam_set_color_input: unknown pixel format");
+  if (format == c->col.format) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the slabs
+  if (format == VSLAM_PIXEL_GRAY8) mapcol_free(c);     // no colour left to sample
+  col_free(c);
+  c->col.format = format;
+  const hipError_t e = col_slab_sync(c);
+  if (e != hipSuccess) { col_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_color_input: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (c->col.format == VSLAM_PIXEL_GRAY8 || !c->col.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_gray_images: no frame has been converted since vslam_set_color_input");
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_gray_images: null output");
+  return pair_to_host(c, c->pre.gray, s, c->pre.in_rows, c->pre.in_cols, left, right);
+}

@@ -2,7 +2,7 @@
 //
 // One fixed-point map pair (kernels_rectify.h's format: map_xy = integer source coordinate, map_a = ay * 32 + ax in 1/32 px) serves the
 // image and the depth image registered to it.
-//   image: k_rectify in its one-sided form (undistort_image_args fills its argument block): bilinear, rect_pixel's arithmetic.
+//   image: k_rectify in its one-sided form (remap_enqueue of host_prestage.h fills its argument block): bilinear, rect_pixel's arithmetic.
 //   depth: k_undistort_depth, nearest neighbour on the same maps, ties up — this repository's own rule, depth is never blended (a mix
 //          across a depth edge invents a surface):
 //            x = x0 + (ax >> 4), y = y0 + (ay >> 4), out = src[y][x] inside the raw image, else 0 (0 = no measurement: kernels_depth.h).
@@ -60,16 +60,5 @@ __global__ __launch_bounds__(256) void k_undistort_depth(UndistortDepthArgs a) {
   }
 }
 
-// k_rectify's argument block for n one-sided images (all of them active) and its grid
-static inline RectArgs undistort_image_args(const uint8_t* src, size_t src_stream_stride, int32_t src_row_stride, int32_t src_rows, int32_t src_cols,
-                                            const int16_t* map_xy, const uint16_t* map_a, int32_t map_stride, uint8_t* dst, size_t dst_stream_stride,
-                                            int32_t dst_row_stride, int32_t rows, int32_t cols, int32_t n) {
-  RectArgs ra{};
-  ra.src[0] = src; ra.src_stream_stride = src_stream_stride; ra.src_row_stride = src_row_stride; ra.src_rows = src_rows; ra.src_cols = src_cols;
-  ra.map_xy[0] = map_xy; ra.map_a[0] = map_a; ra.map_stride = map_stride;
-  ra.dst[0] = dst; ra.dst_stream_stride = dst_stream_stride; ra.dst_row_stride = dst_row_stride;
-  ra.rows = rows; ra.cols = cols; ra.s0 = 0; ra.n = n; ra.sides = 1;
-  for (int s = 0; s < n; ++s) ra.active[s >> 5] |= 1u << (s & 31);
-  return ra;
-}
+// grid of k_undistort_depth, and of k_rectify per side, on n sequences
 static inline dim3 undistort_grid(int32_t rows, int32_t cols, int32_t n) { return dim3((cols + 255) / 256, (rows + 3) / 4, (n + VS_RECT_SB - 1) / VS_RECT_SB); }

@@ -1,5 +1,6 @@
 // rgbd_device.h — host side of the device-resident RGB-D loop (kernels_rgbd.h): buffers, the per-frame launch sequence on one HIP stream,
-// one small read-back per frame.  Included by host_rgbd.h after the context code (it uses create_internal / buf_set / fail of host_ctx.h).
+// one small read-back per frame.  Included by host_rgbd.h after the context code (it uses create_internal / buf_set / fail of host_ctx.h
+// and the input stages of host_prestage.h).
 //
 // A frame is: two host-to-device copies (image, depth), ~17 kernel launches on two streams (the space map runs beside the image pipeline), one 1.2 KB device-to-host copy, one stream synchronisation.
 // A context tracks n_streams independent sequences side by side (vslam_rgbd_create_batch): the same ~17 launches serve all of them — one
@@ -268,13 +269,11 @@ public:
 
   // ---- undistortion of raw frames (kernels_undistort.h): opt-in, its own allocations, nothing launched while und.on is false ----
   // size of the frames the submit entries take: the raw camera's while the maps are set
-  int in_rows() const { return und.on ? und.raw_rows : p.rows; }
-  int in_cols() const { return und.on ? und.raw_cols : p.cols; }
+  int in_rows() const { return und.on ? und.maps.raw_rows : p.rows; }
+  int in_cols() const { return und.on ? und.maps.raw_cols : p.cols; }
   int set_undistortion(int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a) {
-    const bool off = !map_xy && !map_a;
-    if (!off && (!map_xy || !map_a)) { err = "vslam_rgbd_set_undistortion: both maps or none"; return VSLAM_ERR_INVALID; }
-    if (!off && (raw_rows < 1 || raw_cols < 1 || raw_rows > 32767 || raw_cols > 32767)) { err = "vslam_rgbd_set_undistortion: invalid raw image dimensions"; return VSLAM_ERR_INVALID; }
-    if (!off && !rect_maps_ok(map_a, (size_t)p.rows * p.cols)) { err = "vslam_rgbd_set_undistortion: interpolation table index >= 1024"; return VSLAM_ERR_INVALID; }
+    bool off = false;
+    if (const int rc = remap_maps_check("vslam_rgbd_set_undistortion", 1, raw_rows, raw_cols, p.rows, p.cols, &map_xy, &map_a, &off, &err)) return rc;
     if (pending) { err = "vslam_rgbd_set_undistortion: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
@@ -282,23 +281,15 @@ public:
     und_free();
     drop_graph();                                   // a captured launch sequence holds the old maps and buffers (or none)
     if (off) return VSLAM_OK;
-    Undist u{};
-    u.raw_rows = raw_rows; u.raw_cols = raw_cols;
-    u.map_stride = (p.cols + 3) & ~3;
-    u.img_stride = u.map_stride;                    // k_rectify stores words: rows 4-byte aligned
-    u.img_stream = ((size_t)p.rows * u.img_stride + 255) & ~(size_t)255;
-    std::vector<int16_t> pxy;
-    std::vector<uint16_t> pa;
-    rect_pad_maps(map_xy, map_a, p.rows, p.cols, u.map_stride, pxy, pa);
-    hipError_t e = und_mem.alloc(&u.map_xy, pxy.size());
-    if (e == hipSuccess) e = und_mem.alloc(&u.map_a, pa.size());
-    if (e == hipSuccess) e = und_mem.alloc(&u.img, u.img_stream * (size_t)B + 64);
-    if (e == hipSuccess) e = und_mem.alloc(&u.raw_depth, (size_t)B * raw_rows * raw_cols);
-    if (e == hipSuccess) e = hipMemcpy(u.map_xy, pxy.data(), pxy.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(u.map_a, pa.data(), pa.size() * 2, hipMemcpyHostToDevice);
+    hipError_t e = remap_maps_upload(und_mem, und.maps, 1, raw_rows, raw_cols, p.rows, p.cols, &map_xy, &map_a);
+    und.img.row_stride = und.maps.stride;           // k_rectify stores words: rows 4-byte aligned
+    und.img.stream_stride = ((size_t)p.rows * und.img.row_stride + 255) & ~(size_t)255;
+    uint8_t* img = nullptr;
+    if (e == hipSuccess) e = und_mem.alloc(&img, und.img.stream_stride * (size_t)B + 64);
+    if (e == hipSuccess) e = und_mem.alloc(&und.raw_depth, (size_t)B * raw_rows * raw_cols);
     if (e != hipSuccess) { und_free(); err = std::string("vslam_rgbd_set_undistortion: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    u.on = true;
-    und = u;
+    und.img.p[0] = img;
+    und.on = true;
     return VSLAM_OK;
   }
   // the undistorted image and depth image the last finished frame of `stream` was processed on (dense; either may be null)
@@ -306,11 +297,9 @@ public:
     if (int rc = readable(stream)) return rc;
     if (!und.on || !und.have_frame) { err = "vslam_rgbd_get_undistorted: no frame has been undistorted since vslam_rgbd_set_undistortion / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
     (void)hipSetDevice(ic->device);
-    hipError_t e = hipSuccess;
-    if (image) e = hipMemcpy2D(image, (size_t)p.cols, und.img + (size_t)stream * und.img_stream, (size_t)und.img_stride, (size_t)p.cols, (size_t)p.rows, hipMemcpyDeviceToHost);
+    hipError_t e = image ? planes_to_host(image, und.img, 0, stream, p.rows, p.cols) : hipSuccess;
     if (e == hipSuccess && depth) e = hipMemcpy(depth, d_depth + (size_t)stream * p.rows * p.cols, (size_t)p.rows * p.cols * 2, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    return VSLAM_OK;
+    return fetched(e);
   }
 
   // ---- histogram equalisation of the intensity image (kernels_equalize.h): opt-in, its own allocations, nothing launched while eq.on is
@@ -321,48 +310,27 @@ public:
   int set_equalization(int on) {
     if (pending) { err = "vslam_rgbd_set_equalization: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if ((size_t)p.rows * p.cols > (size_t)VS_EQ_MAX_PIXELS) { err = "vslam_rgbd_set_equalization: more than 2^24 pixels per image"; return VSLAM_ERR_INVALID; }
-    return eq_switch("vslam_rgbd_set_equalization", on != 0, nullptr, 0);
+    return eq_switch(on != 0, nullptr, 0);
   }
   int set_clahe(int on, double clip_limit, int tiles_x, int tiles_y) {
     if (pending) { err = "vslam_rgbd_set_clahe: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     ClaheArgs geo{};
     const char* why = "";
     if (on && !clahe_geometry(p.rows, p.cols, clip_limit, tiles_x, tiles_y, geo, &why)) { err = std::string("vslam_rgbd_set_clahe: ") + why; return VSLAM_ERR_INVALID; }
-    return eq_switch("vslam_rgbd_set_clahe", on != 0, &geo, clip_limit);
+    return eq_switch(on != 0, &geo, clip_limit);
   }
-  int eq_switch(const char* who, bool on, const ClaheArgs* geo, double clip_limit) {
-    const bool clahe = geo != nullptr;
-    if (eq.on && eq.clahe != clahe) {
-      if (!on) return VSLAM_OK;
-      err = std::string(who) + (clahe ? ": global equalisation is on (vslam_rgbd_set_equalization)" : ": CLAHE is on (vslam_rgbd_set_clahe)");
-      return VSLAM_ERR_STATE;
-    }
-    const bool same = !clahe || (eq.clip_limit == clip_limit && eq.geo.tiles_x == geo->tiles_x && eq.geo.tiles_y == geo->tiles_y);
-    if (on ? (eq.on && same) : !eq.on) return VSLAM_OK;
-    (void)hipSetDevice(ic->device);
-    (void)hipStreamSynchronize(q);
-    (void)hipStreamSynchronize(q2);
-    eq_free();
-    drop_graph();                                   // a captured launch sequence holds the two kernels (or lacks them)
-    if (!on) return VSLAM_OK;
-    Equal u{};
-    u.img_stride = (p.cols + 15) & ~15;
-    u.img_stream = (size_t)p.rows * u.img_stride;
-    hipError_t e;
-    if (clahe) {
-      u.geo = *geo; u.clip_limit = clip_limit;
-      const size_t nl = (size_t)B * geo->tiles_x * geo->tiles_y * 256;
-      e = eq_mem.alloc(&u.luts, nl);
-      if (e == hipSuccess) e = hipMemset(u.luts, 0, nl);
-    } else {
-      e = eq_mem.alloc(&u.hist, (size_t)B * 256);
-      if (e == hipSuccess) e = hipMemset(u.hist, 0, (size_t)B * 256 * sizeof(uint32_t));
-    }
-    if (e == hipSuccess) e = eq_mem.alloc(&u.img, u.img_stream * (size_t)B);
-    if (e != hipSuccess) { eq_free(); err = std::string(who) + ": " + hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    u.on = true; u.clahe = clahe;
-    eq = u;
-    return VSLAM_OK;
+  int eq_switch(bool on, const ClaheArgs* geo, double clip_limit) {
+    static const char* const names[2] = {"vslam_rgbd_set_equalization", "vslam_rgbd_set_clahe"};
+    return eq.switch_to(on, geo, clip_limit, B, 1, names, &err,
+                        // (a captured launch sequence holds the two kernels, or lacks them)
+                        [&] { (void)hipSetDevice(ic->device); (void)hipStreamSynchronize(q); (void)hipStreamSynchronize(q2); eq_free(); drop_graph(); },
+                        [&] {                             // the image a caller's device frame is equalised into
+                          uint8_t* img = nullptr;
+                          const int32_t stride = (p.cols + 15) & ~15;
+                          const hipError_t e = eq.mem.alloc(&img, (size_t)p.rows * stride * (size_t)B);
+                          eq.img = {{img, nullptr}, stride, (size_t)p.rows * stride};
+                          return e;
+                        });
   }
   // uint8 [tilesY][tilesX][256]: the tables of the image the last finished frame of `stream` was processed on
   int get_clahe_luts(int stream, uint8_t* luts) {
@@ -370,10 +338,7 @@ public:
     if (!eq.on || !eq.clahe || !eq.have_frame) { err = "vslam_rgbd_get_clahe_luts: no frame has run under CLAHE since vslam_rgbd_set_clahe / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
     if (!luts) { err = "vslam_rgbd_get_clahe_luts: null output"; return VSLAM_ERR_INVALID; }
     (void)hipSetDevice(ic->device);
-    const size_t nl = (size_t)eq.geo.tiles_x * eq.geo.tiles_y * 256;
-    const hipError_t e = hipMemcpy(luts, eq.luts + (size_t)stream * nl, nl, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    return VSLAM_OK;
+    return fetched(eq.luts_to_host(luts, stream));
   }
   // the equalised image the last finished frame of `stream` was processed on (dense)
   int get_equalized(int stream, uint8_t* image) {
@@ -381,9 +346,7 @@ public:
     if (!eq.on || !eq.have_frame) { err = "vslam_rgbd_get_equalized: no frame has been equalised since vslam_rgbd_set_equalization / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
     if (!image) { err = "vslam_rgbd_get_equalized: null output"; return VSLAM_ERR_INVALID; }
     (void)hipSetDevice(ic->device);
-    const hipError_t e = hipMemcpy2D(image, (size_t)p.cols, eq.out + (size_t)stream * eq.out_stream, (size_t)eq.out_stride, (size_t)p.cols, (size_t)p.rows, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    return VSLAM_OK;
+    return fetched(planes_to_host(image, eq.dst, 0, stream, p.rows, p.cols));
   }
 
   // ---- colour input (kernels_gray.h): opt-in, its own allocation, nothing launched while col.format is VSLAM_PIXEL_GRAY8.  The intensity
@@ -410,9 +373,7 @@ public:
     if (!col.format || !col.have_frame) { err = "vslam_rgbd_get_gray: no frame has been converted since vslam_rgbd_set_color_input / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
     if (!image) { err = "vslam_rgbd_get_gray: null output"; return VSLAM_ERR_INVALID; }
     (void)hipSetDevice(ic->device);
-    const hipError_t e = hipMemcpy2D(image, (size_t)col.cols, col.gray + (size_t)stream * col.gray_stream, (size_t)col.gray_stride, (size_t)col.cols, (size_t)col.rows, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
-    return VSLAM_OK;
+    return fetched(planes_to_host(image, col.gray, 0, stream, col.rows, col.cols));
   }
 
   int process(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t left_stream_stride = 0, size_t depth_stream_stride = 0) {
@@ -428,7 +389,7 @@ public:
     if (on_device && !und.on && B > 1 && depth_stream_stride != (size_t)p.rows * dstride) { err = "RGB-D batch on device images: depth images must be dense per sequence"; return VSLAM_ERR_INVALID; }
     if (failed) { err = "RGB-D tracker: an earlier frame failed (" + failed_why + "); reset() before the next frame"; return VSLAM_ERR_STATE; }
     if (pending) { err = "RGB-D tracker: the previous frame has not been waited for"; return VSLAM_ERR_STATE; }
-    if (und.on && (size_t)und.raw_rows * (size_t)dstride > 0x7fffffffu) { err = "RGB-D frame: raw depth row stride too large"; return VSLAM_ERR_INVALID; }   // k_undistort_depth's 32-bit tap offsets
+    if (und.on && (size_t)und.maps.raw_rows * (size_t)dstride > 0x7fffffffu) { err = "RGB-D frame: raw depth row stride too large"; return VSLAM_ERR_INVALID; }   // k_undistort_depth's 32-bit tap offsets
     if (B > 1 && (left_stream_stride < (size_t)(in_rows() - 1) * lstride + in_bytes() || depth_stream_stride < (size_t)(in_rows() - 1) * dstride + in_cols())) {
       err = "RGB-D batch: stream strides smaller than an image"; return VSLAM_ERR_INVALID;
     }
@@ -514,31 +475,20 @@ private:
   // undistorted images the image pipeline reads, and the raw depth images of a host frame (raw images go through d_img; the
   // undistorted depth images are d_depth).  raw_*: where this frame's raw images are — the staging buffers or the caller's device memory
   struct Undist {
-    bool on, have_frame;
-    int32_t raw_rows, raw_cols, map_stride, img_stride;
-    size_t img_stream;
-    int16_t* map_xy; uint16_t* map_a; uint8_t* img; uint16_t* raw_depth;
-  } und{};
+    bool on = false, have_frame = false;
+    RemapMaps maps;
+    ImgPlanes img;
+    uint16_t* raw_depth = nullptr;
+  } und;
   DeviceStore und_mem;
-  // equalisation of the intensity image: off while eq.on is false.  The count table [B][256], the image a caller's device frame is
-  // equalised into, and this frame's source (src*) and result (out*: what the image pipeline reads)
-  struct Equal {
-    bool on, have_frame;
-    uint32_t* hist; uint8_t* img; int32_t img_stride; size_t img_stream;
-    const uint8_t* src; int32_t src_stride; size_t src_stream;
-    uint8_t* out; int32_t out_stride; size_t out_stream;
-    bool clahe; double clip_limit; uint8_t* luts; ClaheArgs geo;     // the second mode: CLAHE, its tables [B][tilesY][tilesX][256]
-  } eq{};
-  DeviceStore eq_mem;
+  // equalisation of the intensity image: the slot (EqSlot, host_prestage.h: tables [B], this frame's src and dst, dst being what the image
+  // pipeline reads) and the image a caller's device frame is equalised into, allocated from the slot's store
+  struct Equal : EqSlot { ImgPlanes img; } eq;
   // colour input: off while col.format is VSLAM_PIXEL_GRAY8.  The grey image [B] at the input size rows x cols (allocated with the first frame
-  // at that size) and this frame's colour source
-  struct Colour {
-    int format; bool have_frame;
-    uint8_t* gray; int32_t gray_stride; size_t gray_stream; int32_t rows, cols;
-    const uint8_t* src; int32_t src_stride; size_t src_stream;
-  } col{};
+  // at that size)
+  struct Colour { int format = 0; bool have_frame = false; ImgPlanes gray; int32_t rows = 0, cols = 0; } col;
   DeviceStore col_mem;
-  const uint8_t* raw_img = nullptr; int32_t raw_img_stride = 0; size_t raw_img_stream = 0;
+  PrePlan pre;                   // this frame's routing through the three stages (route_frame): pre.color is its colour source
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
 
@@ -547,40 +497,38 @@ private:
     mp.log = nullptr; mp.ocount = nullptr; mp.ocap = 0;
   }
   void eq_free() {
-    eq_mem.release();
-    eq = Equal{};
+    eq.release();
+    eq.img = ImgPlanes();
   }
   void col_free() {
     col_mem.release();
     col = Colour{};
   }
-  // this frame's intensity image (*img: the staged copy or the caller's device memory) becomes the conversion's source; *img is pointed at
-  // the grey image everything downstream reads
-  hipError_t col_route(const uint8_t** img, int32_t* stride, size_t* stream) {
-    if (!col.format) return hipSuccess;
-    const int rows = in_rows(), cols = in_cols();
-    if (!col.gray || col.rows != rows || col.cols != cols) {
-      (void)hipStreamSynchronize(q);
-      col_mem.release();
-      col.gray = nullptr;
-      drop_graph();                              // it holds the old image
-      col.rows = rows; col.cols = cols;
-      col.gray_stride = (cols + 15) & ~15;
-      col.gray_stream = (size_t)rows * col.gray_stride;
-      const hipError_t e = col_mem.alloc(&col.gray, col.gray_stream * (size_t)B);
-      if (e != hipSuccess) { col.gray = nullptr; return e; }
+  // This frame's routing through the input stages (the table: host_prestage.h, PrePlan), from which switches are on: `in` is
+  // the intensity image that came in (the staged copy or the caller's device memory), own: it is ours to overwrite.  Fills pre and the
+  // slot's src / dst and points bs at what the detector reads.  The grey image is allocated here, with the first frame at its size.
+  hipError_t route_frame(ImgPlanes in, bool own) {
+    pre.format = col.format; pre.remap = und.on;
+    pre.in_rows = in_rows(); pre.in_cols = in_cols(); pre.rows = p.rows; pre.cols = p.cols;
+    if (col.format) {
+      if (!col.gray.p[0] || col.rows != pre.in_rows || col.cols != pre.in_cols) {
+        (void)hipStreamSynchronize(q);
+        col_mem.release();
+        col.gray = ImgPlanes();
+        drop_graph();                              // it holds the old image
+        col.rows = pre.in_rows; col.cols = pre.in_cols;
+        uint8_t* g = nullptr;
+        const int32_t stride = (col.cols + 15) & ~15;
+        const hipError_t e = col_mem.alloc(&g, (size_t)col.rows * stride * (size_t)B);
+        if (e != hipSuccess) return e;
+        col.gray = {{g, nullptr}, stride, (size_t)col.rows * stride};
+      }
+      pre.color = in; pre.gray = col.gray; in = col.gray; own = true;
     }
-    col.src = *img; col.src_stride = *stride; col.src_stream = *stream;
-    *img = col.gray; *stride = col.gray_stride; *stream = col.gray_stream;
+    if (und.on) { pre.raw = in; pre.mapped = und.img; in = und.img; own = true; }
+    if (eq.on) { eq.src = in; eq.dst = own ? in : eq.img; in = eq.dst; }
+    buf_set_planes(bs, in);
     return hipSuccess;
-  }
-  // this frame's image bs points at becomes the equalisation's source; bs is pointed at its result.  own: the image is ours to overwrite
-  void eq_route(bool own) {
-    if (!eq.on) return;
-    eq.src = bs.img[0]; eq.src_stride = bs.img_row_stride; eq.src_stream = bs.img_stream_stride;
-    if (own) { eq.out = const_cast<uint8_t*>(eq.src); eq.out_stride = eq.src_stride; eq.out_stream = eq.src_stream; }
-    else { eq.out = eq.img; eq.out_stride = eq.img_stride; eq.out_stream = eq.img_stream; }
-    bs.img[0] = eq.out; bs.img[1] = eq.out; bs.img_row_stride = eq.out_stride; bs.img_stream_stride = eq.out_stream;
   }
   void und_free() {
     und_mem.release();
@@ -590,15 +538,10 @@ private:
     mapcol_mem.release();
     mc = RgbdMapColor{};
   }
-  // this frame's colour image as k_rgbd_map_color reads it (col.src: the staged copy of a host frame, which the next submit overwrites, or the
+  // this frame's colour image as k_rgbd_map_color reads it (pre.color: the staged copy of a host frame, which the next submit overwrites, or the
   // caller's device memory, which must stay as it is until wait() has returned: further attempts colour the frame from there); the raw
   // image behind the undistortion map while undistorting
-  ColorSrc map_color_src() const {
-    ColorSrc s{};
-    s.img = col.src; s.stream_stride = col.src_stream; s.row_stride = col.src_stride; s.rows = col.rows; s.cols = col.cols; s.format = col.format;
-    if (und.on) { s.map_xy = und.map_xy; s.map_a = und.map_a; s.map_stride = und.map_stride; s.map_rows = p.rows; s.map_cols = p.cols; }
-    return s;
-  }
+  ColorSrc map_color_src() const { return color_src(pre.color, col.rows, col.cols, col.format, und.on ? &und.maps : nullptr); }
   void map_free() {
     obs_free();
     mapcol_free();                                  // the colours are indexed by the map's ids
@@ -637,11 +580,8 @@ private:
     if (d_img) { (void)hipFree(d_img); d_img = nullptr; }
     if (ic) { vslam_destroy(ic); ic = nullptr; }      // frees everything dalloc() registered
   }
+  int fetched(hipError_t e) { if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; } return VSLAM_OK; }     // the end of an image getter
   int hip_fail(hipError_t e, const char* where) { err = std::string(where) + ": " + hipGetErrorString(e); return VSLAM_ERR_HIP; }
-  void all_active(DevBuf& b) const {
-    std::memset(b.active, 0, sizeof b.active);
-    for (int s = 0; s < B; ++s) b.active[s >> 5] |= 1u << (s & 31);
-  }
 
   // initialize() .. registration of one attempt: the image pipeline on ONE image per sequence (DevCfg::mono: grid z = sequences; k_emit with
   // its one-image controller), track, aligner.  Sequences whose bit in b.active is cleared are skipped by every kernel.
@@ -692,18 +632,15 @@ private:
     if (on_device) {
       use_graph = false;                       // the captured graph holds the staging buffers' addresses
       bs = buf_set(ic, 0, 0);
-      if (const hipError_t ce = col_route(&left, &lstride, &lss)) return hip_fail(ce, "grey image");      // colour: k_gray_u8 alone reads the caller's image
-      if (und.on) {                            // the two undistortion kernels are the only readers of the caller's memory
-        raw_img = left; raw_img_stride = lstride; raw_img_stream = lss;
+      // the first stage that is on (k_gray_u8, else the undistortion, else the equalisation) alone reads the caller's image
+      if (const hipError_t ce = route_frame({{left, nullptr}, lstride, lss}, false)) return hip_fail(ce, "grey image");
+      if (und.on) {                            // k_undistort_depth is the only reader of the caller's depth images
         raw_dep = depth; raw_dep_stride = dstride; raw_dep_stream = dss;
-        bs.img[0] = und.img; bs.img[1] = und.img; bs.img_row_stride = und.img_stride; bs.img_stream_stride = und.img_stream;
         depth_src = d_depth; depth_src_stride = p.cols;
       } else {
-        bs.img[0] = left; bs.img[1] = left; bs.img_row_stride = lstride; bs.img_stream_stride = lss;
         depth_src = depth; depth_src_stride = dstride;
       }
-      eq_route(und.on || col.format != VSLAM_PIXEL_GRAY8);
-      all_active(bs);
+      active_all(bs.active, B);
       enqueue_first_attempt(false);
       hipError_t e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(pinned, rb.st, sizeof(RgbdState) * (size_t)B, hipMemcpyDeviceToHost, q);
@@ -743,17 +680,9 @@ private:
     }
     if (e != hipSuccess) return hip_fail(e, "image / depth upload");
     bs = buf_set(ic, 0, 0);
-    const uint8_t* im = d_img; int32_t im_stride = lstride; size_t im_stream = img_stream;
-    if (const hipError_t ce = col_route(&im, &im_stride, &im_stream)) return hip_fail(ce, "grey image");
-    if (und.on) {
-      raw_img = im; raw_img_stride = im_stride; raw_img_stream = im_stream;
-      raw_dep = und.raw_depth; raw_dep_stride = cols; raw_dep_stream = (size_t)rows * cols;
-      bs.img[0] = und.img; bs.img[1] = und.img; bs.img_row_stride = und.img_stride; bs.img_stream_stride = und.img_stream;
-    } else {
-      bs.img[0] = im; bs.img[1] = im; bs.img_row_stride = im_stride; bs.img_stream_stride = im_stream;
-    }
-    eq_route(true);
-    all_active(bs);
+    if (const hipError_t ce = route_frame({{d_img, nullptr}, lstride, img_stream}, true)) return hip_fail(ce, "grey image");
+    if (und.on) { raw_dep = und.raw_depth; raw_dep_stride = cols; raw_dep_stream = (size_t)rows * cols; }
+    active_all(bs.active, B);
     if (use_graph && (!graph_exec || graph_stride != lstride || graph_img != d_img)) capture_graph(lstride);
     if (use_graph && graph_exec) {
       e = hipGraphLaunch(graph_exec, q);
@@ -782,8 +711,8 @@ private:
     // raw depth -> undistorted depth on the space map's queue, behind the depth upload and ahead of the map's first kernel
     if (und.on) {
       UndistortDepthArgs ua{};
-      ua.src = raw_dep; ua.src_stream_stride = raw_dep_stream; ua.src_row_stride = raw_dep_stride; ua.src_rows = und.raw_rows; ua.src_cols = und.raw_cols;
-      ua.map_xy = und.map_xy; ua.map_a = und.map_a; ua.map_stride = und.map_stride;
+      ua.src = raw_dep; ua.src_stream_stride = raw_dep_stream; ua.src_row_stride = raw_dep_stride; ua.src_rows = und.maps.raw_rows; ua.src_cols = und.maps.raw_cols;
+      ua.map_xy = und.maps.xy[0]; ua.map_a = und.maps.a[0]; ua.map_stride = und.maps.stride;
       ua.dst = d_depth; ua.dst_stream_stride = (size_t)rows * cols; ua.dst_row_stride = cols; ua.rows = rows; ua.cols = cols; ua.n = B;
       hipLaunchKernelGGL(k_undistort_depth, undistort_grid(rows, cols, B), dim3(256), 0, q2, ua);
     }
@@ -804,30 +733,9 @@ private:
     depth_pending = true;
     // raw image -> undistorted image on the image pipeline's queue, ahead of the detector and behind the fork, so that the space map's
     // queue does not wait for it (once per frame: further attempts read the undistorted image again)
-    // colour -> grey at the head of the image queue's work, once per frame, behind the fork like the undistortion
-    if (col.format) {
-      GrayArgs ga{};
-      ga.src[0] = col.src; ga.src_row_stride = col.src_stride; ga.src_stream_stride = col.src_stream;
-      ga.dst[0] = col.gray; ga.dst_row_stride = col.gray_stride; ga.dst_stream_stride = col.gray_stream;
-      ga.rows = col.rows; ga.cols = col.cols; ga.n = B; ga.sides = 1; ga.format = col.format;
-      std::memcpy(ga.active, bs.active, sizeof ga.active);
-      (void)gray_enqueue(q, ga);
-    }
-    if (und.on)
-      hipLaunchKernelGGL(k_rectify, undistort_grid(rows, cols, B), dim3(256), 0, q,
-                         undistort_image_args(raw_img, raw_img_stream, raw_img_stride, und.raw_rows, und.raw_cols, und.map_xy, und.map_a, und.map_stride, und.img,
-                                              und.img_stream, und.img_stride, rows, cols, B));
-    // the image equalised, behind the undistortion and ahead of the detector, once per frame like it
-    if (eq.on) {
-      auto place = [&](auto& x) {
-        x.src[0] = eq.src; x.src_row_stride = eq.src_stride; x.src_stream_stride = eq.src_stream;
-        x.dst[0] = eq.out; x.dst_row_stride = eq.out_stride; x.dst_stream_stride = eq.out_stream;
-        x.rows = rows; x.cols = cols; x.n = B; x.sides = 1;
-        std::memcpy(x.active, bs.active, sizeof x.active);
-      };
-      if (eq.clahe) { ClaheArgs ca = eq.geo; place(ca); ca.luts = eq.luts; (void)clahe_enqueue(q, ca); }
-      else { EqArgs ea{}; place(ea); ea.hist = eq.hist; (void)equalize_enqueue(q, ea); }
-    }
+    // colour -> grey at the head of the image queue's work, once per frame, behind the fork like the undistortion; the image equalised
+    // behind the undistortion and ahead of the detector, once per frame like it
+    (void)prestage_enqueue(q, pre, und.maps, eq, B, 1, bs.active);
     enqueue_attempt(bs);
     enqueue_tail(bs);
   }

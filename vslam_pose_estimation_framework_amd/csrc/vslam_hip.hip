@@ -27,8 +27,10 @@
 #define VS_API extern "C" __attribute__((visibility("default")))
 
 #include "device_store.h"    // memory a switchable feature owns on the device
+#include "host_prestage.h"   // the input stages (grey, remap, equalisation slot) as the stereo context and the RGB-D tracker share them
 #include "host_ctx.h"        // the context: allocation, scratch, timers, configuration, create / destroy / reset, stream lifetime
-#include "host_frame.h"      // a frame's inputs and its two launch sequences, rectification
+#include "host_switches.h"   // the context's input-stage switches and their getters: rectification, equalisation / CLAHE, colour input
+#include "host_frame.h"      // a frame's inputs, its routing through the input stages and its two launch sequences
 #include "host_readback.h"   // vslam_get_*: frame results, the landmark map, the observation log, poses, timers
 #include "host_entries.h"    // stand-alone component entries (one piece of the pipeline on caller data)
 #include "host_stage.h"      // stage entries (the reference's plug-in virtuals), stage reports and their views
