@@ -343,6 +343,42 @@ int vslam_set_tracker_state(vslam_ctx* ctx, int stream, int status, const double
                             int window_pixels, double tau_track);
 int vslam_set_pose(vslam_ctx* ctx, int stream, const double camera_left_to_world[12]);
 
+/* ---- motion models (Parameters::MotionModel, src/types/parameters.h:17-19; pose_tracker_3d.cpp:40-66) ----------------------------
+ * The prior a frame of vslam_process_* / vslam_frame_finish starts with.  VSLAM_MOTION_CONSTANT_VELOCITY (the default) keeps the last
+ * refined motion and launches nothing new.  VSLAM_MOTION_NONE starts every frame from identity.  VSLAM_MOTION_CAMERA_ODOMETRY takes
+ * inverse(guess) * guess_previous from the external pose handed over with every frame (vslam_set_pose_guess*), computed on the device
+ * ahead of everything that reads the prior; under it the registration never breaks the track and never retries by appearance with
+ * an identity prior: without tracked landmarks, on the third attempt, and in every fallback, the frame's pose is previous *
+ * inverse(prior) and the prior is kept (:316-341, :405-417, :551-566).  Such a frame reports fallback = 1 and track_broken = 0.
+ * Every stream holds a guess and the previous frame's guess (camera_left_to_world, 3 x 4 row-major), identity after vslam_create,
+ * vslam_reset and vslam_reset_stream(s); a frame for which no guess was set re-uses the last one.  Guesses are in the frame of the left
+ * camera: a caller with poses of a robot base composes cameraToRobot itself.
+ * vslam_set_motion_model: dead_reckoning_limit N > 0 (CAMERA_ODOMETRY only; no reference counterpart): after N
+ *   consecutive frames whose pose is not an accepted aligner result a Tracking stream localizes again at the end of the frame, pose
+ *   and prior untouched; 0 is off.  Synchronises the context.  VSLAM_ERR_STATE inside a frame; VSLAM_ERR_INVALID (not sticky): unknown
+ *   model, negative limit, a limit with another model.  The model survives vslam_reset and vslam_reset_stream(s).  The stage entries
+ *   (vslam_track ..) leave the model to their caller, which owns the control flow and sets the prior (vslam_set_tracker_state).
+ * vslam_set_pose_guess: the guess of one stream's next frame; host-side, applied at the head of the next frame.
+ * vslam_set_pose_guesses: those of all streams, [n_streams][12]; a stream that is switched off when the frame starts is neither read nor
+ *   written.  on_device != 0: T is device memory, read on the context's queue at the head of the next frame without a host
+ *   synchronisation; the caller keeps it alive and unchanged until that frame is finished.  A guess set for one stream afterwards
+ *   takes precedence for that stream.  The array applies to every stream that is active at that frame, one restarted by
+ *   vslam_reset_stream(s) in between included; vslam_reset_stream(s) drops only what was set for that stream on the host.
+ *   Both: VSLAM_ERR_STATE inside a frame, VSLAM_ERR_INVALID for a bad stream or a null pointer.  Under another model a guess is
+ *   stored and ignored: under VSLAM_MOTION_NONE in the stream state; under VSLAM_MOTION_CONSTANT_VELOCITY on the host alone, where
+ *   nothing is launched, copied or allocated for it — host guesses wait for the first frame under another model, a device array ends
+ *   with the next frame.
+ * vslam_get_pose_guess: guess and guess_previous of `stream` as the last frame left them (either may be NULL).  Synchronises.
+ * vslam_motion_prior: out[i] = inverse(guess[i]) * guess_previous[i] for n transforms, the arithmetic of the frame start stand-alone. */
+typedef enum { VSLAM_MOTION_CONSTANT_VELOCITY = 0, VSLAM_MOTION_NONE = 1, VSLAM_MOTION_CAMERA_ODOMETRY = 2 } vslam_motion_model;
+int vslam_set_motion_model(vslam_ctx* ctx, int model, int32_t dead_reckoning_limit);
+int vslam_get_motion_model(vslam_ctx* ctx, int* model, int32_t* dead_reckoning_limit);
+int vslam_set_pose_guess(vslam_ctx* ctx, int stream, const double camera_left_to_world[12]);
+int vslam_set_pose_guesses(vslam_ctx* ctx, const double* camera_left_to_world /* [n_streams][12] */, int on_device);
+int vslam_get_pose_guess(vslam_ctx* ctx, int stream, double guess[12], double guess_previous[12]);
+int vslam_motion_prior(vslam_ctx* ctx, int32_t n, const double* guess /* [n][12] */, const double* guess_previous /* [n][12] */,
+                       double* out /* [n][12] */);
+
 /* ---- readback (synchronises the context stream) -------------------------------------------- */
 int vslam_get_frame_info(vslam_ctx* ctx, int stream, vslam_frame_info* out);
 /* Frame::keypointsLeft/Right + descriptorsLeft/Right (frame.h:64-67).  xy = (x,y) int16 pairs
@@ -860,6 +896,17 @@ int vslam_rgbd_get_clahe_luts(vslam_rgbd* t, int32_t stream, uint8_t* luts);
  *   and undistortion off the image is equalised in place afterwards, and this getter returns it so. */
 int vslam_rgbd_set_color_input(vslam_rgbd* t, int format);
 int vslam_rgbd_get_gray(vslam_rgbd* t, int32_t stream, uint8_t* image);
+
+/* Motion models in this mode (opt-in; the definition above vslam_set_motion_model): the device loop computes the prior inside the frame's
+ * launch sequence (captured or not), once per frame; the host-driven loop through vslam_motion_prior.  VSLAM_ERR_STATE with a frame in
+ * flight (between submit and wait), VSLAM_ERR_INVALID as for the stereo calls.  The device form of vslam_rgbd_set_pose_guesses is copied
+ * on the tracker's queue at the call (no host synchronisation; VSLAM_ERR_STATE on the host-driven loop); a host guess set after it waits
+ * for that copy, so whichever was set last holds.  A guess is kept until the next one is set, under every model.  The model survives
+ * vslam_rgbd_reset, the guesses do not. */
+int vslam_rgbd_set_motion_model(vslam_rgbd* t, int model, int32_t dead_reckoning_limit);
+int vslam_rgbd_get_motion_model(vslam_rgbd* t, int* model, int32_t* dead_reckoning_limit);
+int vslam_rgbd_set_pose_guess(vslam_rgbd* t, int32_t stream, const double camera_left_to_world[12]);
+int vslam_rgbd_set_pose_guesses(vslam_rgbd* t, const double* camera_left_to_world /* [n_streams][12] */, int on_device);
 int vslam_remap_nearest_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride,
                             const int16_t* map_xy, const uint16_t* map_a, int32_t dst_rows, int32_t dst_cols, uint16_t* dst);
 

@@ -19,6 +19,11 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
                               frame at which pixels, in one file (io_formats.read_bundle); implies the map; also with --chunks
     python tools/run_kitti.py <sequence dir with image_2/ image_3/> --color --map map.ply --map-color   a coloured cloud: red green blue per
                               landmark (its left keypoint's pixel at the last update, sampled on the GPU); map_rgb in the --observations bundle
+    python tools/run_kitti.py <sequence dir> --motion-model odometry --odometry poses.txt [--dead-reckoning-limit N]   the reference's
+                              CAMERA_ODOMETRY model: every frame starts from the motion an external pose source reports (a KITTI pose file, line k
+                              for frame k, or a TUM trajectory associated by time stamp; camera frame) and dead-reckons on it where the images
+                              fail, in the place of a broken track; N > 0 localizes again after N such frames in a row.  --motion-model none
+                              starts every frame from identity.  Also with --chunks: every chunk gets its own frames' poses
 
 The sequence runs in exact mode (one stream, whole sequence, bit-for-bit the reference port's arithmetic); images are
 uploaded frame by frame through vslam_process_host.  With --gt (KITTI 3x4 rows) the ATE-RMSE after rigid alignment is
@@ -40,7 +45,7 @@ MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a
 
 
 def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-                map_color=False):
+                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -63,6 +68,7 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
         api.enable_map_colors(True)
     if want_obs:
         api.enable_observations(steps * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
+    api.set_motion_model(motion_model, dead_reckoning_limit)
     rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
     Lb = np.zeros((len(plan), rows, cols) + ((3,) if color else ()), np.uint8)
     Rb = np.zeros_like(Lb)
@@ -74,6 +80,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
             elif live[c]:
                 api.set_stream_active(c, False)
                 live[c] = False
+        if guesses is not None:      # every chunk its own frame's pose (a chunk that has ended is switched off: its entry is not read)
+            api.set_pose_guesses(np.stack([guesses[min(st + k, en - 1)] for (st, fi, en) in plan]))
         api.process_host(Lb, Rb)
         if k % 20 == 19 or k == steps - 1:
             log("step %5d of %d (%d chunks side by side)" % (k + 1, steps, sum(live)))
@@ -92,7 +100,9 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
-        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8), map_color=False):
+        chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8), map_color=False,
+        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0):
+    check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
     euroc = layout == "euroc" or os.path.isdir(os.path.join(seq_dir, "mav0"))
@@ -141,15 +151,24 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         log("equalising histograms on the GPU (cv::equalizeHist on every image%s)" % (", behind the rectification" if rect is not None else ""))
     if clahe is not None:
         log("CLAHE on the GPU (cv::CLAHE, clip limit %g, %d x %d tiles, on every image%s)" % (clahe, clahe_tiles[0], clahe_tiles[1], ", behind the rectification" if rect is not None else ""))
+    guesses = None
+    if odometry:
+        guesses, own = io_formats.read_pose_guesses(odometry, seq.times[:n])
+        log("motion model camera odometry: %d of %d frames have a pose of their own in %s%s" % (
+            int(own.sum()), n, odometry, ", dead-reckoning limit %d" % dead_reckoning_limit if dead_reckoning_limit else ""))
+    model = MOTION_MODELS[motion_model]
     t0 = time.perf_counter()
     flags = 0
     tracking = 0
+    dead_reckoned = 0
     want_map = bool(map_path or obs_path)        # the log's ids are the map's
     obs = None
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
-                                                equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles, map_color=map_color)
+                                                equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles, map_color=map_color,
+                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses)
         tracking = None
+        dead_reckoned = None
     else:
         cfg.max_history_frames = 512
         api.create(cfg, device, 1)
@@ -167,13 +186,17 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             api.enable_map_colors(True)
         if obs_path:
             api.enable_observations(n * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
+        api.set_motion_model(model, dead_reckoning_limit)
         for k in range(n):
             if k:
                 left, right = seq.pair(k)
+            if guesses is not None and own[k]:
+                api.set_pose_guess(guesses[k], 0)
             api.process_host(left, right)
             fi = api.frame_info(0)
             flags |= fi.error_flags
             tracking += int(fi.status == 1)
+            dead_reckoned += int(model == 2 and fi.fallback == 1)
             if k % 100 == 99 or k == n - 1:
                 log("frame %6d  status %s  points %5d  tracked %5d  inliers %5d" % (
                     k, "tracking" if fi.status == 1 else "localizing", fi.n_points, fi.n_tracked, fi.n_inliers))
@@ -193,6 +216,10 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             io_formats.write_trajectory_kitti(out_path, poses)
         log("trajectory (%s) -> %s" % (fmt, out_path))
     result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses, "tracking_frames": tracking}     # tracking_frames: exact mode only
+    if model == 2:
+        result["dead_reckoned_frames"] = dead_reckoned     # frames whose pose was taken from the odometry (exact mode only)
+        if dead_reckoned:
+            log("%d frames took their pose from the odometry" % dead_reckoned)
     if map_path:
         if flags & 8:
             log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
@@ -231,6 +258,21 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     return result
 
 
+MOTION_MODELS = {"constant-velocity": 0, "none": 1, "odometry": 2}     # enum vslam_motion_model
+
+
+def check_motion_args(motion_model, odometry, dead_reckoning_limit, error):
+    """What --motion-model, --odometry and --dead-reckoning-limit allow together (tools/run_rgbd.py takes the same flags)."""
+    if motion_model not in MOTION_MODELS:
+        raise error("--motion-model: one of %s" % ", ".join(sorted(MOTION_MODELS)))
+    if motion_model == "odometry" and not odometry:
+        raise error("--motion-model odometry needs --odometry FILE (a KITTI pose file or a TUM trajectory)")
+    if odometry and motion_model != "odometry":
+        raise error("--odometry is read under --motion-model odometry only")
+    if dead_reckoning_limit < 0 or (dead_reckoning_limit and motion_model != "odometry"):
+        raise error("--dead-reckoning-limit N >= 0 needs --motion-model odometry")
+
+
 def _tiles(text):
     """--clahe-tiles X,Y -> (X, Y)"""
     try:
@@ -267,7 +309,17 @@ def parse_args(argv=None):
                     "the frames are converted to grey on the GPU")
     ap.add_argument("--map-color", action="store_true", help="with --color and --map / --observations: the colour of every landmark (its left keypoint's "
                     "pixel at the last update, sampled on the GPU) as red green blue in the PLY and map_rgb in the bundle")
+    ap.add_argument("--motion-model", choices=sorted(MOTION_MODELS), default="constant-velocity", help="the prior every frame starts with: the last "
+                    "refined motion (the default), identity (none), or the motion an external pose source reports (odometry, with --odometry)")
+    ap.add_argument("--odometry", default=None, metavar="FILE", help="--motion-model odometry: camera_left_to_world per frame, a KITTI pose file (line k "
+                    "for frame k) or a TUM trajectory (associated by time stamp)")
+    ap.add_argument("--dead-reckoning-limit", type=int, default=0, metavar="N", help="--motion-model odometry: localize again after N frames in a row "
+                    "whose pose was taken from the odometry (0: never)")
     a = ap.parse_args(argv)
+    try:
+        check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
+    except ValueError as e:
+        ap.error(str(e))
     if a.clahe is not None and a.equalize:
         ap.error("--clahe and --equalize exclude each other: one equalisation ahead of the detector")
     if a.map_color and not (a.color and (a.map or a.observations)):
@@ -279,7 +331,7 @@ def main(argv=None):
     a = parse_args(argv)
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
         rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
-        map_color=a.map_color)
+        map_color=a.map_color, motion_model=a.motion_model, odometry=a.odometry, dead_reckoning_limit=a.dead_reckoning_limit)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,8 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
     python tools/run_rgbd.py <folder> [--config icl|tum|xtion] [--intrinsics freiburg1|freiburg2|freiburg3|icl|fx,fy,cx,cy]
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
                              [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color [--map-color]]
-                             [--clahe [CLIP]] [--clahe-tiles X,Y]
+                             [--clahe [CLIP]] [--clahe-tiles X,Y] [--motion-model constant-velocity|none|odometry] [--odometry FILE]
+                             [--dead-reckoning-limit N]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -27,7 +28,12 @@ untouched), behind --undistort and ahead of the detector: dim or low-contrast se
 --color hands the colour frames over as decoded and converts them to grey on the GPU (vslam_rgbd_set_color_input: the same integers as the
 host conversion without the flag), ahead of --undistort and --equalize.  Device-resident loop only.
 --map-color (with --color and --map / --observations) samples every landmark's colour on the GPU (vslam_rgbd_enable_map_colors: the pixel of
-its point at the last update, through the --undistort map when that is on): red green blue in the PLY, map_rgb in the bundle."""
+its point at the last update, through the --undistort map when that is on): red green blue in the PLY, map_rgb in the bundle.
+--motion-model odometry --odometry FILE starts every frame from the motion an external pose source reports (the reference's CAMERA_ODOMETRY,
+configuration_xtion.yaml's own model; FILE: a TUM trajectory associated by time stamp, or a KITTI pose file, in the camera's frame) and
+dead-reckons on it where the images fail, in the place of a broken track; --dead-reckoning-limit N localizes again after N such frames in a
+row (without it one failed frame means dead reckoning for good: DESIGN.md 6j).  --motion-model none starts every frame from identity.  Both
+loops."""
 import argparse
 import os
 import sys
@@ -40,6 +46,9 @@ import numpy as np  # noqa: E402
 
 from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, hip, io_formats  # noqa: E402
 from vslam_pose_estimation_framework_amd.capi import DepthParams, RgbdTracker  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from run_kitti import MOTION_MODELS, check_motion_args  # noqa: E402  (--motion-model / --odometry / --dead-reckoning-limit: one set of rules)
 
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per processed frame, as tools/run_kitti.py chooses it
 
@@ -107,7 +116,8 @@ def distortion_of(undistort, intrinsics):
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
         gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-        map_color=False):
+        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0):
+    check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
     seq = io_formats.TumRgbdSequence(folder)
@@ -130,8 +140,13 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     if dist is not None and not any(dist):
         log("--undistort: all distortion coefficients are zero, there is nothing to undo")
         dist = None
+    guesses = own = None
+    if odometry:
+        guesses, own = io_formats.read_pose_guesses(odometry, seq.times[:n])
+        log("motion model camera odometry: %d of %d frames have a pose of their own in %s%s" % (
+            int(own.sum()), n, odometry, ", dead-reckoning limit %d" % dead_reckoning_limit if dead_reckoning_limit else ""))
     tr = RgbdTracker(api, cfg, p, device)
-    poses, flags, tracking = [], 0, 0
+    poses, flags, tracking, dead_reckoned = [], 0, 0, 0
     want_map = bool(map_path or obs_path)        # the log's ids are the map's
     lm_map = obs = None
     t0 = time.perf_counter()
@@ -153,6 +168,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
         if clahe is not None:
             tr.set_clahe(True, clahe, clahe_tiles)
             log("CLAHE on the GPU (cv::CLAHE, clip limit %g, %d x %d tiles, on every intensity image%s)" % (clahe, clahe_tiles[0], clahe_tiles[1], ", behind the undistortion" if dist is not None else ""))
+        tr.set_motion_model(MOTION_MODELS[motion_model], dead_reckoning_limit)
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
         if map_color and fmt == color_mod.GRAY8:
@@ -170,7 +186,10 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
                         raise SystemExit("--color: frame %d is %s, the sequence began as %s" % (k, color_mod.NAMES[fmt_k], color_mod.NAMES[fmt]))
                 else:
                     gray, depth = seq.frame(k)
+            if guesses is not None and own[k]:
+                tr.set_pose_guess(guesses[k])
             fi, n_temp = tr.process(gray, depth)
+            dead_reckoned += int(motion_model == "odometry" and fi.fallback == 1)
             poses.append(np.array(fi.camera_left_to_world))
             flags |= fi.error_flags
             tracking += int(fi.status == 1)
@@ -189,6 +208,10 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     poses = np.array(poses).reshape(-1, 3, 4)
     log("%d frames in %.2f s (%.1f frames/s incl. PNG decode and upload), error flags %d" % (n, dt, n / dt, flags))
     result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses, "times": seq.times[:n], "tracking_frames": tracking}
+    if motion_model == "odometry":
+        result["dead_reckoned_frames"] = dead_reckoned     # frames whose pose was taken from the odometry
+        if dead_reckoned:
+            log("%d frames took their pose from the odometry" % dead_reckoned)
     if want_map:
         if flags & 8:
             log("warning: the landmark map ran out of capacity (error flag 8): landmarks created after that are missing")
@@ -272,7 +295,18 @@ def parse_args(argv=None):
         if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
             argv[i:i + 2] = ["--undistort=" + argv[i + 1]]
             break
+    ap.add_argument("--motion-model", choices=sorted(MOTION_MODELS), default="constant-velocity", help="the prior every frame starts with: the last "
+                    "refined motion (the default), identity (none), or the motion an external pose source reports (odometry, with --odometry; "
+                    "configuration_xtion.yaml's own model)")
+    ap.add_argument("--odometry", default=None, metavar="FILE", help="--motion-model odometry: camera_left_to_world per frame, a TUM trajectory "
+                    "(associated by time stamp) or a KITTI pose file (line k for frame k)")
+    ap.add_argument("--dead-reckoning-limit", type=int, default=0, metavar="N", help="--motion-model odometry: localize again after N frames in a row "
+                    "whose pose was taken from the odometry (0: never)")
     a = ap.parse_args(argv)
+    try:
+        check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
+    except ValueError as e:
+        ap.error(str(e))
     if a.clahe is not None and a.equalize:
         ap.error("--clahe and --equalize exclude each other: one equalisation ahead of the detector")
     if a.map_color and not (a.color and (a.map or a.observations)):
@@ -283,7 +317,8 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
-        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
+        map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles, motion_model=a.motion_model, odometry=a.odometry,
+        dead_reckoning_limit=a.dead_reckoning_limit,
         map_color=a.map_color)
 
 

@@ -14,6 +14,7 @@ MAX_REGIONS = 16
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_STATE = 0, -1, -2, -3, -4, -5
 LOCALIZING, TRACKING = 0, 1
+MOTION_CONSTANT_VELOCITY, MOTION_NONE, MOTION_CAMERA_ODOMETRY = 0, 1, 2      # enum vslam_motion_model
 
 
 class Config(C.Structure):
@@ -322,6 +323,49 @@ class CApi(object):
         R = np.zeros((rows, cols), np.uint8)
         self.check(self.fn("get_gray_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
         return L, R
+
+    # -- motion models and pose guesses (vslam_set_motion_model, vslam_set_pose_guess*) -----------------------------------
+    def set_motion_model(self, model, dead_reckoning_limit=0):
+        """model: MOTION_CONSTANT_VELOCITY (default) / MOTION_NONE / MOTION_CAMERA_ODOMETRY; dead_reckoning_limit N > 0 (odometry only): a
+        Tracking stream localizes again after N consecutive frames without an accepted aligner result."""
+        self.check(self.fn("set_motion_model")(self.ctx, C.c_int(int(model)), C.c_int32(int(dead_reckoning_limit))))
+
+    def motion_model(self):
+        m, n = C.c_int(), C.c_int32()
+        self.check(self.fn("get_motion_model")(self.ctx, C.byref(m), C.byref(n)))
+        return m.value, n.value
+
+    def set_pose_guess(self, T, stream=0):
+        """The external camera_left_to_world (3 x 4, or 12 values row-major) of the stream's next frame."""
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        assert t.size == 12, t.shape
+        self.check(self.fn("set_pose_guess")(self.ctx, C.c_int(stream), _p(t, C.c_double)))
+
+    def set_pose_guesses(self, T):
+        """Those of all streams: float64 [n_streams, 12] (or [n_streams, 3, 4])."""
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        assert t.size == 12 * self.n_streams, (t.shape, self.n_streams)
+        self.check(self.fn("set_pose_guesses")(self.ctx, _p(t, C.c_double), C.c_int(0)))
+
+    def set_pose_guesses_device(self, ptr):
+        """ptr: device memory, float64 [n_streams][12], read at the head of the next frame; the caller keeps it alive until that frame is
+        finished."""
+        self.check(self.fn("set_pose_guesses")(self.ctx, C.c_void_p(ptr), C.c_int(1)))
+
+    def pose_guess(self, stream=0):
+        """(guess, guess_previous) of the stream as its last frame left them, float64 [12] each."""
+        g, p = np.zeros(12, np.float64), np.zeros(12, np.float64)
+        self.check(self.fn("get_pose_guess")(self.ctx, C.c_int(stream), _p(g, C.c_double), _p(p, C.c_double)))
+        return g, p
+
+    def motion_prior(self, guess, guess_previous):
+        """vslam_motion_prior: inverse(guess[i]) * guess_previous[i], float64 [n, 12] -> [n, 12]."""
+        g = np.ascontiguousarray(guess, np.float64).reshape(-1, 12)
+        p = np.ascontiguousarray(guess_previous, np.float64).reshape(-1, 12)
+        assert g.shape == p.shape, (g.shape, p.shape)
+        out = np.zeros_like(g)
+        self.check(self.fn("motion_prior")(self.ctx, C.c_int32(len(g)), _p(g, C.c_double), _p(p, C.c_double), _p(out, C.c_double)))
+        return out
 
     # -- readback -----------------------------------------------------------------------------
     def frame_info(self, stream=0):
@@ -1065,12 +1109,40 @@ class _RgbdColorApi(object):
         return img
 
 
+class _RgbdMotionApi(object):
+    """vslam_rgbd_set_motion_model / _set_pose_guess(es), shared by RgbdTracker and RgbdBatch (both loops)."""
+
+    def set_motion_model(self, model, dead_reckoning_limit=0):
+        self._check(self.lib.vslam_rgbd_set_motion_model(self.h, C.c_int(int(model)), C.c_int32(int(dead_reckoning_limit))))
+
+    def motion_model(self):
+        m, n = C.c_int(), C.c_int32()
+        self._check(self.lib.vslam_rgbd_get_motion_model(self.h, C.byref(m), C.byref(n)))
+        return m.value, n.value
+
+    def set_pose_guess(self, T, stream=0):
+        """The external camera_left_to_world (12 values row-major) of the sequence's next frame; kept until the next one is set."""
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        assert t.size == 12, t.shape
+        self._check(self.lib.vslam_rgbd_set_pose_guess(self.h, C.c_int32(stream), _p(t, C.c_double)))
+
+    def set_pose_guesses(self, T):
+        """Those of all sequences, float64 [n_streams, 12]."""
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        assert t.size == 12 * getattr(self, "n", 1), t.shape
+        self._check(self.lib.vslam_rgbd_set_pose_guesses(self.h, _p(t, C.c_double), C.c_int(0)))
+
+    def set_pose_guesses_device(self, ptr):
+        """ptr: device memory, float64 [n_streams][12], copied on the tracker's queue without a host synchronisation."""
+        self._check(self.lib.vslam_rgbd_set_pose_guesses(self.h, C.c_void_p(ptr), C.c_int(1)))
+
+
 def _row_bytes(left, image_ndim):
     """Row stride in bytes of a C-contiguous image array or batch: its trailing channel axis, when it has one, belongs to the row."""
     return int(left.shape[-1]) if left.ndim == image_ndim else int(left.shape[-2] * left.shape[-1])
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi):
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -1127,7 +1199,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorAp
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

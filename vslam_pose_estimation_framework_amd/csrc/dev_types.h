@@ -59,12 +59,16 @@ struct DevCfg {
   // OpenCV does — angle *= (float)(CV_PI/180.f); (float)cos(angle), (float)sin(angle) — and the fixed-point Gaussian taps
   float orb_cos, orb_sin;
   int32_t gauss7[4];
+  // the motion model of the frame start and of the registration (vslam_set_motion_model; pose_tracker_3d.cpp:40-66, :316-341, :405-417,
+  // :551-566) and the opt-in limit on consecutive frames without an accepted aligner result (0: off)
+  int32_t motion_model, dead_reckoning_limit;
 };
 
 // scalars of the frame in flight, handed from one phase kernel of the frame to the next
 struct FrameCarry {
   int32_t status, status0, win, attempts, broken, fallback, n_after_prune, aligner_valid, n_tracked_landmarks;
   int32_t n_cur, n_lost, n_recovered, n_active;
+  int32_t moved;          // the frame's pose is an accepted aligner result (not the previous pose, not the guess)
   int32_t lm_pb, lm_f;    // point buffer and frame index of the frame whose landmarks lm_teams_body refines (it runs beside the frame's last phase, which advances StreamState::cur / frame_count)
   double tau_track, tau_gen, tau_tri;
   double prior[12];
@@ -86,6 +90,9 @@ struct StreamState {
   double tau_tri;                        // _current_maximum_descriptor_distance_triangulation
   double prior[12];                      // _previous_to_current_camera
   double pose[12];                       // WorldMap::robot_to_world (camera_left_to_world)
+  double guess[12];                      // _camera_left_in_world_guess (pose_tracker_3d.h:34): the external pose of the frame, identity until one is set
+  double guess_prev[12];                 // _camera_left_in_world_guess_previous
+  int32_t dr_count;                      // consecutive frames whose pose is not an accepted aligner result (dead_reckoning_limit)
   // scratch scalars of the frame in flight
   int32_t by_appearance;                 // mode the candidate kernel must use for attempt 0
   int32_t n_trk, n_lost, n_tracked_landmarks;

@@ -100,6 +100,13 @@ struct vslam_ctx {
   // the colour of every map entry (vslam_enable_map_colors, kernels_map_color.h): [B][map.cap] words (r, g, b, 0); off while rgb is null;
   // freed by vslam_enable_map_colors(0), any vslam_enable_map, vslam_set_color_input(GRAY8) and destroy
   struct MapColors { uint32_t* rgb = nullptr; DeviceStore mem; } mapcol;
+  // pose guesses waiting for the head of the next frame (vslam_set_pose_guess*, kernels_motion.h): `dev` the caller's device array, `host` /
+  // `mask` [B][12] / [B] what was set one stream at a time or as a host array (any: some mask entry is set), d_host / d_mask their device
+  // copies, pin[turn] / pin_ev[turn] the two pinned staging buffers (guesses | mask) the copies leave from in turn, each reused once its
+  // last copy has finished; the device side is allocated with the first frame that hands guesses over and freed by destroy.  The model itself lives in cfg (DevCfg::motion_model).
+  struct Guess { const double* dev = nullptr; std::vector<double> host; std::vector<int32_t> mask; bool any = false;
+                 double* d_host = nullptr; int32_t* d_mask = nullptr; DeviceStore mem;
+                 unsigned char* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int turn = 0; } guess;
   int sticky = VSLAM_OK;
 };
 
@@ -307,6 +314,14 @@ static void fresh_stream_state(const vslam_ctx* c, StreamState& x) {
   x.tau_tri = 0.1 * 256;
   tf_identity(x.prior);
   tf_identity(x.pose);
+  tf_identity(x.guess);
+  tf_identity(x.guess_prev);
+}
+// guesses that were waiting for a frame belong to the sequence that ended
+static void guess_drop_pending(vslam_ctx* c, int s = -1) {
+  vslam_ctx::Guess& g = c->guess;
+  if (s < 0) { g.dev = nullptr; std::fill(g.mask.begin(), g.mask.end(), 0); g.any = false; return; }
+  if (!g.mask.empty()) { g.mask[s] = 0; g.any = std::any_of(g.mask.begin(), g.mask.end(), [](int32_t m) { return m != 0; }); }
 }
 static int upload_buffer_tables(vslam_ctx* c) {
   const DevBuf hb[2] = {buf_set(c, 0, c->q0_frm), buf_set(c, 1, c->q0_frm)};
@@ -315,6 +330,7 @@ static int upload_buffer_tables(vslam_ctx* c) {
 }
 static int init_state(vslam_ctx* c) {
   c->pend.flags = 0;          // a reset drops setters that were waiting for a stage launch: the fresh state is the state
+  guess_drop_pending(c);
   c->report_have = 0;
   std::vector<StreamState> st(c->B);
   for (int s = 0; s < c->B; ++s) fresh_stream_state(c, st[s]);
@@ -531,6 +547,8 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
   for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem}) m->release();     // the input stages' stores
+  c->guess.mem.release();
+  for (int q = 0; q < 2; ++q) { if (c->guess.pin[q]) (void)hipHostFree(c->guess.pin[q]); if (c->guess.pin_ev[q]) (void)hipEventDestroy(c->guess.pin_ev[q]); }
   map_free(c);
   obs_free(c);
   tmp_free(c);
@@ -643,6 +661,7 @@ VS_API int vslam_reset_streams(vslam_ctx* c, int32_t n, const int32_t* streams) 
     return VSLAM_OK;
   };
   for (int i = 0; i < n; ++i) {
+    guess_drop_pending(c, streams[i]);
     l.ids[l.n++] = streams[i];
     if (l.n == 63) { int rc = flush(); if (rc) return rc; }
   }

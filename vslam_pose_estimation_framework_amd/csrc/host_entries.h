@@ -298,6 +298,18 @@ VS_API int vslam_point_in_camera(vslam_ctx* c, int32_t n, const float* xp, const
   return k.finish();
 }
 
+// the CAMERA_ODOMETRY prior of the frame start (kernels_motion.h) on caller data
+VS_API int vslam_motion_prior(vslam_ctx* c, int32_t n, const double* guess, const double* guess_previous, double* out) {
+  if (int rc = entry_begin(c)) return rc;
+  if (n < 0 || (n && (!guess || !guess_previous || !out))) return fail(c, VSLAM_ERR_INVALID, "motion_prior: bad argument");
+  if (n == 0) return VSLAM_OK;
+  Call k(c, c->stream);
+  double* dg = k.up(guess, (size_t)n * 12); double* dp = k.up(guess_previous, (size_t)n * 12); double* dout = k.dev<double>((size_t)n * 12);
+  if (k.ok()) hipLaunchKernelGGL(k_motion_prior_entry, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dg, dp, dout);
+  k.down(out, dout, (size_t)n * 12);
+  return k.finish();
+}
+
 VS_API int vslam_landmark_update(vslam_ctx* c, int32_t n, const int32_t* offsets, const int32_t* frame_of, int32_t n_frames, const double* w2c,
                                  const double* c2w, const double* cam, double* world, int32_t* updates) {
   if (int rc = entry_begin(c)) return rc;

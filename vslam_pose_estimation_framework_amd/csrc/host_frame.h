@@ -90,6 +90,8 @@ static int launch_frame(vslam_ctx* c) {
   const DevBuf bs = buf_set(c, c->last_set, c->q0_frm);
   ConstDevCfg* kc = (ConstDevCfg*)c->d_cfg;
   ConstDevBuf* kb = (ConstDevBuf*)(c->d_bufs + c->last_set);
+  // the frame's motion prior, ahead of the candidate kernel that reads it (nothing under CONSTANT_VELOCITY)
+  if (const int rc = launch_motion_prior(c)) return rc;
   { KernelTimer t(c, 3, st); hipLaunchKernelGGL(k_track_candidates, dim3(cand_blocks(n), n), dim3(256), 0, st, c->cfg, bs, -1); }
   if (c->split == 0) {
     KernelTimer t(c, 4, st);

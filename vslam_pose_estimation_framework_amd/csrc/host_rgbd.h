@@ -215,3 +215,31 @@ VS_API int vslam_rgbd_get_gray(vslam_rgbd* r, int32_t stream, uint8_t* image) {
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_color_host_refusal(r, "vslam_rgbd_get_gray") : r->d.get_gray(stream, image);
 }
+
+// ---- motion models (the definition above vslam_set_motion_model) ---------------------------------------------------------
+VS_API int vslam_rgbd_set_motion_model(vslam_rgbd* r, int model, int32_t dead_reckoning_limit) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (r->on_host && r->host_pending) { r->t.err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+  return r->on_host ? r->t.set_motion_model(model, dead_reckoning_limit) : r->d.set_motion_model(model, dead_reckoning_limit);
+}
+VS_API int vslam_rgbd_get_motion_model(vslam_rgbd* r, int* model, int32_t* dead_reckoning_limit) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (model) *model = r->on_host ? r->t.motion_model : r->d.motion_model;
+  if (dead_reckoning_limit) *dead_reckoning_limit = r->on_host ? r->t.dead_reckoning_limit : r->d.dead_reckoning_limit;
+  return VSLAM_OK;
+}
+static int rgbd_set_guess(vslam_rgbd* r, int32_t stream, const double* T, bool on_device) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (!r->on_host) return r->d.set_pose_guess(stream, T, on_device);
+  if (!T) { r->t.err = "vslam_rgbd_set_pose_guess: null pose"; return VSLAM_ERR_INVALID; }
+  if (stream > 0) { r->t.err = "stream index out of range"; return VSLAM_ERR_INVALID; }
+  if (on_device) { r->t.err = "vslam_rgbd_set_pose_guesses: device memory on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB)"; return VSLAM_ERR_STATE; }
+  if (r->host_pending) { r->t.err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+  std::memcpy(r->t.guess, T, 96);
+  return VSLAM_OK;
+}
+VS_API int vslam_rgbd_set_pose_guess(vslam_rgbd* r, int32_t stream, const double T[12]) {
+  if (r && stream < 0) { r->err() = "stream index out of range"; return VSLAM_ERR_INVALID; }
+  return rgbd_set_guess(r, stream, T, false);
+}
+VS_API int vslam_rgbd_set_pose_guesses(vslam_rgbd* r, const double* T, int on_device) { return rgbd_set_guess(r, -1, T, on_device != 0); }

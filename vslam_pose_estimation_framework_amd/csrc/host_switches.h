@@ -1,6 +1,7 @@
 // host_switches.h — the stereo context's input-stage switches and their getters: rectification (vslam_set_rectification), the equalisation
 // slot (vslam_set_equalization, vslam_set_clahe) and colour input (vslam_set_color_input), the stores behind them, and the stand-alone
-// vslam_remap_u8.  What the switches share with the RGB-D tracker is host_prestage.h; a frame's routing through the stages is route_frame
+// vslam_remap_u8; behind them the motion model and the pose guesses of CAMERA_ODOMETRY (vslam_set_motion_model, vslam_set_pose_guess*),
+// with launch_motion_prior, the head of the frame's launch sequence.  What the switches share with the RGB-D tracker is host_prestage.h; a frame's routing through the stages is route_frame
 // in host_frame.h.  Host code, included by vslam_hip.hip after host_ctx.h and ahead of host_frame.h.
 #pragma once
 
@@ -203,4 +204,106 @@ VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* ri
   if (c->col.format == VSLAM_PIXEL_GRAY8 || !c->col.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_gray_images: no frame has been converted since vslam_set_color_input");
   if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_gray_images: null output");
   return pair_to_host(c, c->pre.gray, s, c->pre.in_rows, c->pre.in_cols, left, right);
+}
+
+// ---- motion models and the pose guesses of CAMERA_ODOMETRY (kernels_motion.h) --------------------------------------
+VS_API int vslam_set_motion_model(vslam_ctx* c, int model, int32_t dead_reckoning_limit) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_motion_model called inside a frame");
+  if (model < VSLAM_MOTION_CONSTANT_VELOCITY || model > VSLAM_MOTION_CAMERA_ODOMETRY) return fail(c, VSLAM_ERR_INVALID, "vslam_set_motion_model: unknown motion model");
+  if (dead_reckoning_limit < 0) return fail(c, VSLAM_ERR_INVALID, "vslam_set_motion_model: negative dead_reckoning_limit");
+  if (dead_reckoning_limit > 0 && model != VSLAM_MOTION_CAMERA_ODOMETRY) return fail(c, VSLAM_ERR_INVALID, "vslam_set_motion_model: dead_reckoning_limit needs VSLAM_MOTION_CAMERA_ODOMETRY");
+  if (model == c->cfg.motion_model && dead_reckoning_limit == c->cfg.dead_reckoning_limit) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the configuration's device copy
+  c->cfg.motion_model = model; c->cfg.dead_reckoning_limit = dead_reckoning_limit;
+  HIP_TRY(c, hipMemcpy(c->d_cfg, &c->cfg, sizeof(DevCfg), hipMemcpyHostToDevice));
+  return VSLAM_OK;
+}
+VS_API int vslam_get_motion_model(vslam_ctx* c, int* model, int32_t* dead_reckoning_limit) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (model) *model = c->cfg.motion_model;
+  if (dead_reckoning_limit) *dead_reckoning_limit = c->cfg.dead_reckoning_limit;
+  return VSLAM_OK;
+}
+// the host side of the guesses set one stream at a time or as a host array, with the first one
+static void guess_host_ready(vslam_ctx* c) {
+  vslam_ctx::Guess& g = c->guess;
+  if (g.mask.empty()) { g.host.assign((size_t)c->B * 12, 0.0); g.mask.assign((size_t)c->B, 0); }
+}
+// their device copy and its pinned staging, with the first frame that hands them over (never under CONSTANT_VELOCITY)
+static int guess_store_ready(vslam_ctx* c) {
+  vslam_ctx::Guess& g = c->guess;
+  if (g.d_host) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipError_t e = g.mem.alloc(&g.d_host, (size_t)c->B * 12);
+  if (e == hipSuccess) e = g.mem.alloc(&g.d_mask, (size_t)c->B);
+  for (int q = 0; q < 2 && e == hipSuccess; ++q) {
+    void* h = nullptr;
+    e = hipHostMalloc(&h, (size_t)c->B * (12 * sizeof(double) + sizeof(int32_t)), hipHostMallocDefault);
+    if (e == hipSuccess) { g.pin[q] = (unsigned char*)h; e = hipEventCreateWithFlags(&g.pin_ev[q], hipEventDisableTiming); }
+  }
+  if (e != hipSuccess) {
+    g.mem.release(); g.d_host = nullptr; g.d_mask = nullptr;
+    for (int q = 0; q < 2; ++q) { if (g.pin[q]) (void)hipHostFree(g.pin[q]); if (g.pin_ev[q]) (void)hipEventDestroy(g.pin_ev[q]); g.pin[q] = nullptr; g.pin_ev[q] = nullptr; }
+    return fail(c, VSLAM_ERR_HIP, std::string("pose guess store: ") + hipGetErrorString(e));
+  }
+  return VSLAM_OK;
+}
+VS_API int vslam_set_pose_guess(vslam_ctx* c, int s, const double T[12]) {
+  if (int rc = check_stream_index(c, s)) return rc;
+  if (!T) return fail(c, VSLAM_ERR_INVALID, "vslam_set_pose_guess: null pose");
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_pose_guess called inside a frame");
+  guess_host_ready(c);
+  std::memcpy(&c->guess.host[(size_t)s * 12], T, 12 * sizeof(double));
+  c->guess.mask[s] = 1; c->guess.any = true;
+  return VSLAM_OK;
+}
+VS_API int vslam_set_pose_guesses(vslam_ctx* c, const double* T, int on_device) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (!T) return fail(c, VSLAM_ERR_INVALID, "vslam_set_pose_guesses: null array");
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_pose_guesses called inside a frame");
+  guess_host_ready(c);
+  vslam_ctx::Guess& g = c->guess;
+  if (on_device) {                 // supersedes what was set before it, stream by stream or as a host array
+    g.dev = T; std::fill(g.mask.begin(), g.mask.end(), 0); g.any = false;
+    return VSLAM_OK;
+  }
+  std::memcpy(g.host.data(), T, (size_t)c->B * 12 * sizeof(double));
+  std::fill(g.mask.begin(), g.mask.end(), 1);
+  g.dev = nullptr; g.any = true;
+  return VSLAM_OK;
+}
+// Head of the frame's launch sequence, on the queue the candidate kernel runs on.  Under CONSTANT_VELOCITY nothing is launched, copied or
+// allocated: host guesses stay where they are (the first frame under another model hands them over), a device array ends with the frame.  The host's guesses leave from pinned staging, two buffers in turn: a buffer is refilled once the copy that last read it is done.
+static int launch_motion_prior(vslam_ctx* c) {
+  vslam_ctx::Guess& g = c->guess;
+  if (c->cfg.motion_model == VSLAM_MOTION_CONSTANT_VELOCITY) { g.dev = nullptr; return VSLAM_OK; }
+  GuessSrc src = {g.dev, nullptr, nullptr};
+  if (g.any) {
+    if (int rc = guess_store_ready(c)) return rc;
+    const int q = g.turn;
+    g.turn ^= 1;
+    if (g.pin_used[q]) HIP_TRY(c, hipEventSynchronize(g.pin_ev[q]));
+    const size_t nb = g.host.size() * sizeof(double), mb = g.mask.size() * sizeof(int32_t);
+    std::memcpy(g.pin[q], g.host.data(), nb);
+    std::memcpy(g.pin[q] + nb, g.mask.data(), mb);
+    HIP_TRY(c, hipMemcpyAsync(g.d_host, g.pin[q], nb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g.d_mask, g.pin[q] + nb, mb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(g.pin_ev[q], c->stream));
+    g.pin_used[q] = true;
+    src.host = g.d_host; src.mask = g.d_mask;
+  }
+  hipLaunchKernelGGL(k_motion_prior, dim3((c->B + 63) / 64), dim3(64), 0, c->stream, c->buf, c->B, c->cfg.motion_model, src);
+  HIP_TRY(c, hipGetLastError());
+  guess_drop_pending(c);
+  return VSLAM_OK;
+}
+VS_API int vslam_get_pose_guess(vslam_ctx* c, int s, double guess[12], double guess_previous[12]) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  StreamState* st = c->buf.st + s;
+  if (guess) HIP_TRY(c, hipMemcpy(guess, st->guess, sizeof st->guess, hipMemcpyDeviceToHost));
+  if (guess_previous) HIP_TRY(c, hipMemcpy(guess_previous, st->guess_prev, sizeof st->guess_prev, hipMemcpyDeviceToHost));
+  return VSLAM_OK;
 }

@@ -48,6 +48,11 @@ __device__ __forceinline__ void frame_phase2(const DevCfg& c, const DevBuf& b, i
   wg_stereo(c, b, s, sh, pb_cur, tau_tri2, f, arena);
   if (tid == 0) {
     st.ticks[4] += wall_clock64() - ts;
+    // the dead-reckoning limit (no reference counterpart): frames in a row whose pose is not an accepted aligner result;
+    // at the limit a Tracking stream localizes again — pose and prior stay
+    const int dr = fc.moved ? 0 : min(st.dr_count, 0x3fffffff) + 1;     // saturates: a stream may stand still for ever
+    st.dr_count = dr;
+    if (c.dead_reckoning_limit > 0 && dr >= c.dead_reckoning_limit && status == VSLAM_TRACKING) status = VSLAM_LOCALIZING;
     const double* c2w = hpose_of(c, b, s, f);
     st.status = status; st.win = fc.win; st.tau_track = fc.tau_track; st.tau_tri = tau_tri2;
     for (int k = 0; k < 12; ++k) { st.prior[k] = fc.prior[k]; st.pose[k] = c2w[k]; }
@@ -121,6 +126,10 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
   const double* prev_c2w = hpose_of(c, b, s, f > 0 ? f - 1 : 0);
   int n_tracked_landmarks = 0, n_after_prune = 0;
   bool aligner_valid = false;
+  bool moved = false;                       // the pose is an accepted aligner result
+  // CAMERA_ODOMETRY never breaks the track and never retries by appearance with an identity prior: it dead-reckons on the guess
+  // (:316-341, :405-417, :555-559)
+  const bool odometry = c.motion_model == VSLAM_MOTION_CAMERA_ODOMETRY;
 
   if (has_prev) {
     const PtView pv = pts_of(c, b, s, pb_prev);
@@ -184,7 +193,11 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
       } else {
         const double rel = (double)n_tracked_landmarks / (double)n_lm_prev;
         if (n_tracked_landmarks == 0 || rel < 0.1) {
-          if (attempt < 2) {
+          if (odometry) {
+            // stick to the odometry guess (:323-328); on the third attempt _fallbackEstimate in the place of breakTrack (:333-336) — under
+            // this model the same pose, previous · inverse(prior), with the prior kept (:555-559)
+            fall = true; done = true;
+          } else if (attempt < 2) {
             if (tid == 0) tf_identity(sh.prior);
             by_app = 1;
           } else {
@@ -200,29 +213,35 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
           } else if (attempt < 2) {
             if (win < c.c.maximum_projection_tracking_distance_pixels) ++win;
             by_app = 0;
+          } else if (odometry) {
+            fall = true; done = true;     // _fallbackEstimate in the place of breakTrack (:408-411)
           } else {
             brk = true; done = true;
           }
         }
       }
+      bool move = false;     // the frame's pose is previous · inverse(prior)
       if (accept) {
         // accept-or-fallback on the size of the motion (:139-159, :372-388)
         const double dang = rotation_angle(sh.T);
         const double dtr = sqrt((sh.T[3] * sh.T[3] + sh.T[7] * sh.T[7]) + sh.T[11] * sh.T[11]);
         if (dang > c.c.minimum_delta_angular_for_movement || dtr > c.c.minimum_delta_translational_for_movement) {
-          if (tid == 0) {
-            for (int k = 0; k < 12; ++k) sh.prior[k] = sh.T[k];
-            double inv[12], c2w[12];
-            tf_inverse(sh.T, inv);
-            tf_mul(prev_c2w, inv, c2w);
-            set_pose(c, b, s, f, c2w);
-          }
+          if (tid == 0) for (int k = 0; k < 12; ++k) sh.prior[k] = sh.T[k];
+          move = true; moved = true;
         } else {
           fall = true;
         }
       }
-      if (fall) {  // _fallbackEstimate (:551-566)
-        if (tid == 0) { tf_identity(sh.prior); set_pose(c, b, s, f, prev_c2w); sh.fallback = 1; }
+      if (fall) {  // _fallbackEstimate (:551-566): under CAMERA_ODOMETRY the pose the guess gives, the prior kept (:555-559)
+        if (tid == 0) sh.fallback = 1;
+        if (odometry) move = true;
+        else if (tid == 0) { tf_identity(sh.prior); set_pose(c, b, s, f, prev_c2w); }
+      }
+      if (move && tid == 0) {
+        double inv[12], c2w[12];
+        tf_inverse(sh.prior, inv);
+        tf_mul(prev_c2w, inv, c2w);
+        set_pose(c, b, s, f, c2w);
       }
       if (brk) {   // breakTrack (:422-435)
         if (tid == 0) { tf_identity(sh.prior); set_pose(c, b, s, f, prev_c2w); sh.broken = 1; sh.status = VSLAM_LOCALIZING; }
@@ -255,7 +274,7 @@ __global__ VS_FRAME_BOUNDS void k_frame(ConstDevCfg* cp, ConstDevBuf* bp, int ph
   __syncthreads();
   if (tid == 0) {
     fc.status = sh.status; fc.status0 = status0; fc.win = win; fc.attempts = sh.attempts; fc.broken = sh.broken; fc.fallback = sh.fallback;
-    fc.n_after_prune = n_after_prune; fc.aligner_valid = aligner_valid ? 1 : 0; fc.n_tracked_landmarks = n_tracked_landmarks;
+    fc.n_after_prune = n_after_prune; fc.aligner_valid = aligner_valid ? 1 : 0; fc.n_tracked_landmarks = n_tracked_landmarks; fc.moved = moved ? 1 : 0;
     fc.n_cur = sh.n_cur; fc.n_lost = (has_prev && c.c.enable_landmark_recovery) ? sh.n_lost : 0; fc.n_recovered = 0; fc.n_active = 0;
     fc.tau_track = tau_track; fc.tau_gen = tau_gen; fc.tau_tri = tau_tri; fc.t0 = tK0;
     for (int k = 0; k < 12; ++k) fc.prior[k] = prior[k];
@@ -345,6 +364,7 @@ __global__ void k_reset_stream_trk(const DevCfg c, const DevBuf b, const ResetLi
   st.n_tracked_landmarks_prev = 0; st.cur = 0; st.aligner_valid = 0; atomicAnd(&st.error_flags, 1);
   st.tau_track = c.c.minimum_descriptor_distance_tracking; st.tau_tri = 0.1 * 256;
   tf_identity(st.prior); tf_identity(st.pose);
+  tf_identity(st.guess); tf_identity(st.guess_prev); st.dr_count = 0;
   st.by_appearance = 0; st.n_trk = 0; st.n_lost = 0; st.n_tracked_landmarks = 0;
   st.al_n = 0; st.al_inliers = 0; st.al_outliers = 0; st.al_iterations = 0; st.al_converged = 0; st.al_wsize = 0; st.al_total_error = 0;
   st.tau_gen = 0; st.n_cur = 0; st.n_active = 0; st.n_after_prune = 0; st.n_recovered = 0; st.n_new = 0; st.track_calls = 0;

@@ -28,6 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_depth.h"
+#include "kernels_motion.h"
 #include "landmark_math.h"
 
 #define RGBD_F_LM 1      // FramePoint::landmark() is set (the point went through Landmark::Landmark or Landmark::update)
@@ -52,7 +53,11 @@ struct RgbdState {
   // tracker state carried from frame to frame
   int32_t status, win, frame_count, n_lm_prev, wsize, error_flags;
   int32_t last_points, last_all;            // previous frame: framepoints, framepoints + temporary points
+  // motion model (vslam_rgbd_set_motion_model; kernels_motion.h): survives a reset; dr_count: consecutive frames whose pose is not an
+  // accepted aligner result; moved: this frame's is one
+  int32_t motion_model, dead_reckoning_limit, dr_count, moved;
   double tau_track, prior[12], world[12];
+  double guess_prev[12];                    // _camera_left_in_world_guess_previous; the guess itself is RgbdBuf::guess_in, which keeps the last one set
   // frame in flight
   int32_t n_points, n_temps, n_detected, n_raw, n_lost, n_tracked, n_tracked_lm, attempts, recursion;
   int32_t do_align, inverse_depth, done, tail_done, next_by_app, status0;
@@ -97,6 +102,7 @@ struct RgbdBuf {
   double* h_cam;              // [H][MAXP][4] camera coordinates and 1 / z (Measurement::inverse_depth_meters, divided once)
   double* h_pose;             // [H][24] camera_to_world, world_to_camera
   double* pose_log;           // [VS_POSE_LOG][12]
+  double* guess_in;           // [n_streams][12] _camera_left_in_world_guess of every sequence (vslam_rgbd_set_pose_guess*), identity after create / reset
   int32_t* cross;             // [n_streams] k_depth_direct: some depth pixel of the image projects onto another pixel (the general z-buffer runs)
 };
 
@@ -144,6 +150,13 @@ __device__ __forceinline__ void rgbd_copy_desc(uint8_t* dst, const uint8_t* src)
   reinterpret_cast<uint4*>(dst)[0] = a; reinterpret_cast<uint4*>(dst)[1] = b;
 }
 
+// vslam_rgbd_set_motion_model: the model of every sequence, between two frames
+__global__ void k_rgbd_set_motion_model(const RgbdBuf all, int model, int limit) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= all.n_streams) return;
+  all.st[s].motion_model = model; all.st[s].dead_reckoning_limit = limit;
+}
+
 // ---- frame start (PoseTracker3D::compute up to the first initialize) ---------------------------------------------------------------------
 __global__ void k_rgbd_begin(const RgbdBuf all) {
   if (threadIdx.x != 0) return;
@@ -157,7 +170,15 @@ __global__ void k_rgbd_begin(const RgbdBuf all) {
   st.n_points = 0; st.n_temps = 0; st.n_lost = 0; st.n_tracked = 0; st.n_tracked_lm = 0; st.attempts = 0; st.recursion = 0;
   st.do_align = 0; st.inverse_depth = 0; st.aligner_valid = 0; st.al_inliers = 0; st.al_iterations = 0; st.al_total = 0; st.al_n = 0;
   st.n_registered = 0; st.n_after_prune = 0; st.n_recovered = 0; st.n_active = 0; st.n_new = 0; st.fallback = 0; st.broken = 0;
-  st.tail_done = 0; st.n_acc = 0; st.merged = 0;
+  st.tail_done = 0; st.n_acc = 0; st.merged = 0; st.moved = 0;
+  // the frame's motion prior (pose_tracker_3d.cpp:40-66), once per frame and ahead of the candidate kernel that reads it
+  if (st.motion_model == VSLAM_MOTION_NONE) tf_identity(st.prior);
+  else if (st.motion_model == VSLAM_MOTION_CAMERA_ODOMETRY) {
+    double g[12], gp[12], T[12];
+    for (int k = 0; k < 12; ++k) { g[k] = all.guess_in[(size_t)blockIdx.x * 12 + k]; gp[k] = st.guess_prev[k]; }
+    if (st.frame_count > 0) { motion_prior(g, gp, T); for (int k = 0; k < 12; ++k) st.prior[k] = T[k]; }
+    for (int k = 0; k < 12; ++k) st.guess_prev[k] = g[k];
+  }
   st.done = st.frame_count == 0 ? 1 : 0;                 // the first frame has nothing to register against
   st.next_by_app = st.status == VSLAM_LOCALIZING ? 1 : 0;  // _track(..., _status == Localizing)
 }
@@ -306,10 +327,17 @@ __global__ __launch_bounds__(256) void k_rgbd_track_candidates(const DevCfg c, c
   depth_track_candidates_body(a, keys, cnt);
 }
 
-__device__ __forceinline__ void rgbd_fallback(RgbdState& st) {        // _fallbackEstimate
-  tf_identity(st.prior);
-  for (int k = 0; k < 12; ++k) st.c2w[k] = st.world[k];
-  tf_inverse(st.world, st.w2c);
+__device__ __forceinline__ void rgbd_fallback(RgbdState& st) {        // _fallbackEstimate (:551-566)
+  if (st.motion_model == VSLAM_MOTION_CAMERA_ODOMETRY) {             // the pose the guess gives, the prior kept (:555-559)
+    double inv[12];
+    tf_inverse(st.prior, inv);
+    tf_mul(st.world, inv, st.c2w);
+    tf_inverse(st.c2w, st.w2c);
+  } else {
+    tf_identity(st.prior);
+    for (int k = 0; k < 12; ++k) st.c2w[k] = st.world[k];
+    tf_inverse(st.world, st.w2c);
+  }
   st.fallback = 1;
 }
 __device__ __forceinline__ void rgbd_break_track(RgbdState& st) {     // breakTrack
@@ -329,6 +357,7 @@ __device__ __forceinline__ void rgbd_accept(const DevCfg& c, RgbdState& st) {
     tf_inverse(st.prior, inv);
     tf_mul(st.world, inv, st.c2w);
     tf_inverse(st.c2w, st.w2c);
+    st.moved = 1;
   } else {
     rgbd_fallback(st);
   }
@@ -421,7 +450,9 @@ __global__ __launch_bounds__(1024) void k_rgbd_track(const DevCfg c, const DevBu
     } else {
       const double rel = (double)nlm / (double)st.n_lm_prev;
       if (nlm == 0 || rel < 0.1) {
-        if (st.recursion < 2) { tf_identity(st.prior); st.next_by_app = 1; st.recursion += 1; }
+        // CAMERA_ODOMETRY sticks to the guess (:323-328), on the third attempt through _fallbackEstimate (:333-336): the same pose
+        if (st.motion_model == VSLAM_MOTION_CAMERA_ODOMETRY) { rgbd_fallback(st); st.done = 1; }
+        else if (st.recursion < 2) { tf_identity(st.prior); st.next_by_app = 1; st.recursion += 1; }
         else { rgbd_break_track(st); st.done = 1; }
       } else { st.do_align = 1; st.inverse_depth = 1; }
     }
@@ -477,7 +508,7 @@ __global__ VS_ALIGN_BOUNDS void k_rgbd_align(const DevCfg c, const DevBuf b, con
       if (st.win < c.c.maximum_projection_tracking_distance_pixels) st.win += 1;
       st.next_by_app = 0; st.recursion += 1;
     } else {
-      rgbd_break_track(st);
+      if (st.motion_model == VSLAM_MOTION_CAMERA_ODOMETRY) rgbd_fallback(st); else rgbd_break_track(st);     // :408-416
       st.done = 1;
     }
   }
@@ -805,6 +836,9 @@ __global__ __launch_bounds__(1024) void k_rgbd_finish(const DevCfg c, const DevB
     if (tid == 0) {
       st.n_temps = out;
       if (st.n_active > c.c.minimum_number_of_landmarks_to_track) st.status = VSLAM_TRACKING;     // :105-107
+      // the dead-reckoning limit (no reference counterpart): pose and prior stay
+      st.dr_count = st.moved ? 0 : min(st.dr_count, 0x3fffffff) + 1;     // saturates
+      if (st.dead_reckoning_limit > 0 && st.dr_count >= st.dead_reckoning_limit && st.status == VSLAM_TRACKING) st.status = VSLAM_LOCALIZING;
     }
     __syncthreads();
   }

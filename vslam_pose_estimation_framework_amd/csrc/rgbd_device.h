@@ -69,7 +69,7 @@ public:
     A(&rb.rrdesc, MAXP * 32); A(&rb.rxyz, MAXP * 3);
     A(&rb.rcF, NMAX * 2); A(&rb.remf, NMAX); A(&rb.rcT, MAXP * 2); A(&rb.bins, nbins); A(&rb.cls, NMAX);
     A(&rb.new_feat, NMAX); A(&rb.new_xyz, NMAX * 3); A(&rb.temp_feat, NMAX); A(&rb.temp_xyz, NMAX * 3);
-    A(&rb.weights, MAXP); A(&rb.cross, 1);
+    A(&rb.weights, MAXP); A(&rb.cross, 1); A(&rb.guess_in, 12);
     A(&rb.h_cam, (size_t)H * MAXP * 4); A(&rb.h_pose, (size_t)H * 24); A(&rb.pose_log, (size_t)VS_POSE_LOG * 12);
     if (e == hipSuccess) e = hipHostMalloc((void**)&pinned, sizeof(RgbdState) * nB, hipHostMallocDefault);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&q2, hipStreamNonBlocking);
@@ -101,10 +101,16 @@ public:
     s.status = VSLAM_LOCALIZING;
     s.win = cfg.maximum_projection_tracking_distance_pixels;
     s.tau_track = cfg.minimum_descriptor_distance_tracking;
-    tf_identity(s.prior); tf_identity(s.world);
+    tf_identity(s.prior); tf_identity(s.world); tf_identity(s.guess_prev);
+    s.motion_model = motion_model; s.dead_reckoning_limit = dead_reckoning_limit;      // the model survives a reset, the guesses do not
     for (int i = 0; i < B; ++i) hosts[i] = s;
     host = s;
     hipError_t e = hipMemcpy(rb.st, hosts.data(), sizeof(RgbdState) * (size_t)B, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      std::vector<double> id((size_t)B * 12);
+      for (int i = 0; i < B; ++i) tf_identity(&id[(size_t)i * 12]);
+      e = hipMemcpy(rb.guess_in, id.data(), id.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) { err = hipGetErrorString(e); return VSLAM_ERR_HIP; }
     {   // the space maps' z-buffers: initialised here, every frame's k_depth_write puts them back
       const size_t npx = (size_t)p.rows * p.cols;
@@ -120,6 +126,36 @@ public:
     eq.have_frame = false;                                                   // and so does the equalisation switch
     col.have_frame = false;                                                  // and the colour format
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
+    return VSLAM_OK;
+  }
+
+  // ---- motion models (kernels_motion.h): the model lives in every sequence's state block, the guesses in rb.guess_in, both read
+  // by k_rgbd_begin inside the frame's (possibly captured) launch sequence ----
+  int motion_model = VSLAM_MOTION_CONSTANT_VELOCITY, dead_reckoning_limit = 0;
+  int set_motion_model(int model, int32_t limit) {
+    if (model < VSLAM_MOTION_CONSTANT_VELOCITY || model > VSLAM_MOTION_CAMERA_ODOMETRY) { err = "vslam_rgbd_set_motion_model: unknown motion model"; return VSLAM_ERR_INVALID; }
+    if (limit < 0) { err = "vslam_rgbd_set_motion_model: negative dead_reckoning_limit"; return VSLAM_ERR_INVALID; }
+    if (limit > 0 && model != VSLAM_MOTION_CAMERA_ODOMETRY) { err = "vslam_rgbd_set_motion_model: dead_reckoning_limit needs VSLAM_MOTION_CAMERA_ODOMETRY"; return VSLAM_ERR_INVALID; }
+    if (pending) { err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    motion_model = model; dead_reckoning_limit = limit;
+    hipLaunchKernelGGL(k_rgbd_set_motion_model, dim3((B + 63) / 64), dim3(64), 0, q, rb, model, (int)limit);
+    if (hipGetLastError() != hipSuccess) { err = "vslam_rgbd_set_motion_model: launch failed"; return VSLAM_ERR_HIP; }
+    return VSLAM_OK;
+  }
+  // T: one sequence's guess (stream >= 0) or all of them (stream < 0, [B][12]); on_device: read on the frame's queue, no host synchronisation
+  int set_pose_guess(int stream, const double* T, bool on_device) {
+    if (!T) { err = "vslam_rgbd_set_pose_guess: null pose"; return VSLAM_ERR_INVALID; }
+    if (stream >= B) { err = "stream index out of range"; return VSLAM_ERR_INVALID; }
+    if (pending) { err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    double* dst = rb.guess_in + (stream < 0 ? 0 : (size_t)stream * 12);
+    const size_t bytes = (stream < 0 ? (size_t)B : 1) * 12 * sizeof(double);
+    // no frame is in flight: the queue holds at most the copy of a device array set before; the host form waits for it, so that whichever
+    // was set last holds, and its blocking copy is then in order with the next frame's kernels
+    hipError_t e = on_device ? hipMemcpyAsync(dst, T, bytes, hipMemcpyDeviceToDevice, q) : hipStreamSynchronize(q);
+    if (e == hipSuccess && !on_device) e = hipMemcpy(dst, T, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { err = std::string("vslam_rgbd_set_pose_guess: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
     return VSLAM_OK;
   }
 

@@ -71,6 +71,16 @@ public:
   std::string err;
   vslam_frame_info info;
   int n_temporary = 0, threshold = 0;
+  // motion model (pose_tracker_3d.cpp:40-66): survives reset(); the guess is kept until the next one is set
+  int motion_model = VSLAM_MOTION_CONSTANT_VELOCITY, dead_reckoning_limit = 0;
+  double guess[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, guess_prev[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  int set_motion_model(int model, int32_t limit) {
+    if (model < VSLAM_MOTION_CONSTANT_VELOCITY || model > VSLAM_MOTION_CAMERA_ODOMETRY) { err = "vslam_rgbd_set_motion_model: unknown motion model"; return VSLAM_ERR_INVALID; }
+    if (limit < 0) { err = "vslam_rgbd_set_motion_model: negative dead_reckoning_limit"; return VSLAM_ERR_INVALID; }
+    if (limit > 0 && model != VSLAM_MOTION_CAMERA_ODOMETRY) { err = "vslam_rgbd_set_motion_model: dead_reckoning_limit needs VSLAM_MOTION_CAMERA_ODOMETRY"; return VSLAM_ERR_INVALID; }
+    motion_model = model; dead_reckoning_limit = limit;
+    return VSLAM_OK;
+  }
 
   int create(const vslam_config& c, const vslam_depth_params& dp, int device) {
     cfg = c; p = dp;
@@ -84,7 +94,7 @@ public:
   }
   ~Tracker() { if (ctx) vslam_destroy(ctx); }
   void reset() {
-    status = VSLAM_LOCALIZING; tf_id(prior); tf_id(world); win = cfg.maximum_projection_tracking_distance_pixels;
+    status = VSLAM_LOCALIZING; tf_id(prior); tf_id(world); tf_id(guess); tf_id(guess_prev); dr_count = 0; win = cfg.maximum_projection_tracking_distance_pixels;
     tau_track = cfg.minimum_descriptor_distance_tracking;
     target = (cfg.cols / cfg.bin_size_pixels + 1) * (cfg.rows / cfg.bin_size_pixels + 1);
     // BaseFramePointGenerator::configure (base_framepoint_generator.cpp:229-312): detector regions with their overlaps, one
@@ -125,6 +135,13 @@ private:
     std::memset(&info, 0, sizeof info);
     info.status_at_start = status;
     const int fi = (int)frames.size();
+    // the frame's motion prior (:40-66), through the same device arithmetic as the device loop (vslam_motion_prior)
+    moved = false;
+    if (motion_model == VSLAM_MOTION_NONE) tf_id(prior);
+    else if (motion_model == VSLAM_MOTION_CAMERA_ODOMETRY) {
+      if (fi > 0) { const int rc = vslam_motion_prior(ctx, 1, guess, guess_prev, prior); if (rc) return fail(rc, "motion_prior"); }
+      std::memcpy(guess_prev, guess, 96);
+    }
     frames.emplace_back();
     set_pose(frames[fi], world);
     n_tracked = 0; n_tracked_lm = 0; aligner_valid = false; lost.clear(); attempts = 0;
@@ -158,6 +175,8 @@ private:
     rc = update_points(fi);
     if (rc) return rc;
     if (n_active > cfg.minimum_number_of_landmarks_to_track) status = VSLAM_TRACKING;
+    dr_count = moved ? 0 : std::min(dr_count, 0x3fffffff) + 1;        // the dead-reckoning limit (saturating count): pose and prior stay
+    if (dead_reckoning_limit > 0 && dr_count >= dead_reckoning_limit && status == VSLAM_TRACKING) status = VSLAM_LOCALIZING;
     rc = compute(fi);
     if (rc) return rc;
     n_lm_prev = n_active;
@@ -190,6 +209,7 @@ private:
   int target_per_detector = 0;
   int status = VSLAM_LOCALIZING, win = 0, target = 0, n_lm_prev = 0, n_tracked = 0, n_tracked_lm = 0, n_active = 0, n_detected = 0, n_raw = 0, attempts = 0;
   double tau_track = 0, prior[12], world[12];
+  int dr_count = 0; bool moved = false;     // consecutive frames whose pose is not an accepted aligner result; this frame's is one
   std::vector<Pt> pool; std::vector<Lm> lms; std::vector<Fr> frames; std::vector<int> lost;
   std::vector<double> weights;          // UVDAligner::_weights_translation: a member, resize(n, 1) keeps what it holds (uvd_aligner.cpp:22)
   bool aligner_valid = false; int al_inliers = 0, al_iterations = 0; double al_total = 0, al_T[12];
@@ -442,13 +462,20 @@ private:
       double inv[12], c2w[12];
       tf_inv(prior, inv); tf_mul(frames[fi - 1].c2w, inv, c2w);
       set_pose(frames[fi], c2w);
+      moved = true;
     } else fallback(fi);
   }
-  void fallback(int fi) { tf_id(prior); set_pose(frames[fi], frames[fi - 1].c2w); info.fallback = 1; }
+  bool odometry() const { return motion_model == VSLAM_MOTION_CAMERA_ODOMETRY; }
+  void fallback(int fi) {      // _fallbackEstimate (:551-566): under CAMERA_ODOMETRY the pose the guess gives, the prior kept
+    if (odometry()) { double inv[12], c2w[12]; tf_inv(prior, inv); tf_mul(frames[fi - 1].c2w, inv, c2w); set_pose(frames[fi], c2w); }
+    else { tf_id(prior); set_pose(frames[fi], frames[fi - 1].c2w); }
+    info.fallback = 1;
+  }
   void break_track(int fi) { status = VSLAM_LOCALIZING; set_pose(frames[fi], frames[fi - 1].c2w); tf_id(prior); n_tracked = 0; info.track_broken = 1; }
   int register_recursive(int fi, int recursion) {
     const double rel = (double)n_tracked_lm / (double)n_lm_prev;
     if (n_tracked_lm == 0 || rel < 0.1) {
+      if (odometry()) { fallback(fi); return VSLAM_OK; }      // stick to the guess (:323-328); third attempt: _fallbackEstimate (:333-336)
       if (recursion < 2) {
         tf_id(prior);
         int rc = initialize(); if (rc) return rc;
@@ -467,7 +494,7 @@ private:
       rc = track(fi, false); if (rc) return rc;
       return register_recursive(fi, recursion + 1);
     }
-    break_track(fi);
+    if (odometry()) fallback(fi); else break_track(fi);       // :408-416
     return VSLAM_OK;
   }
 

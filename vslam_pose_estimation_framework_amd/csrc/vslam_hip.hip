@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels_stage.h"     // -> kernels_frame2.h -> kernels_stereo.h -> kernels_recover.h -> kernels_frame.h
+#include "kernels_motion.h"    // the frame's motion prior under VSLAM_MOTION_NONE / CAMERA_ODOMETRY
 #include "kernels_depth.h"
 #include "kernels_orb.h"
 #include "kernels_landmark.h"

@@ -9,7 +9,7 @@ import math
 
 import numpy as np
 
-from .capi import LOCALIZING, TRACKING
+from .capi import LOCALIZING, TRACKING, MOTION_CONSTANT_VELOCITY, MOTION_NONE, MOTION_CAMERA_ODOMETRY
 
 
 def _identity():
@@ -55,12 +55,21 @@ def _div(a, b):
 class PoseTracker3D(object):
     """pose_tracker_3d.h:14-134 — state and methods named as in the reference."""
 
-    def __init__(self, api, one_launch_compute=False):
+    def __init__(self, api, one_launch_compute=False, motion_model=MOTION_CONSTANT_VELOCITY, dead_reckoning_limit=0):
         """one_launch_compute: _updatePoints and the generator's compute() as ONE call (vslam_compute, what the shim issues) instead of
-        vslam_update_points + vslam_stereo_new."""
+        vslam_update_points + vslam_stereo_new.
+        motion_model: Parameters::MotionModel (parameters.h:17-19); under MOTION_CAMERA_ODOMETRY set_guess() hands over the external pose
+        of the next frame.  dead_reckoning_limit N > 0 (odometry only, no reference counterpart): Tracking becomes Localizing at the end of
+        the N-th consecutive frame whose pose is not an accepted aligner result."""
+        if motion_model not in (MOTION_CONSTANT_VELOCITY, MOTION_NONE, MOTION_CAMERA_ODOMETRY):
+            raise ValueError("unknown motion model %r" % (motion_model,))
+        if dead_reckoning_limit < 0 or (dead_reckoning_limit > 0 and motion_model != MOTION_CAMERA_ODOMETRY):
+            raise ValueError("dead_reckoning_limit needs MOTION_CAMERA_ODOMETRY")
         self.api = api
         self.cfg = api.cfg
         self.one_launch_compute = bool(one_launch_compute)
+        self.motion_model = motion_model
+        self.dead_reckoning_limit = int(dead_reckoning_limit)
         self.configure()
 
     def _target_number_of_keypoints(self):
@@ -81,8 +90,27 @@ class PoseTracker3D(object):
         self._previous_pose = None                  # previous_frame->cameraLeftToWorld()
         self._previous_points = 0                   # previous_frame->points().size()
         self._frame_pose = _identity()
+        self._camera_left_in_world_guess = _identity()             # pose_tracker_3d.h:34
+        self._camera_left_in_world_guess_previous = _identity()
+        self._frames_without_aligner_pose = 0
+        self._pose_from_aligner = False
         self.fallback = 0
         self.track_broken = 0
+
+    def set_guess(self, camera_left_in_world):
+        """setCameraLeftInWorldGuess (pose_tracker_3d.h:34): kept until the next one, as the reference's member."""
+        g = [float(v) for v in np.asarray(camera_left_in_world, np.float64).reshape(-1)]
+        assert len(g) == 12, len(g)
+        self._camera_left_in_world_guess = g
+
+    def _odometry(self):
+        return self.motion_model == MOTION_CAMERA_ODOMETRY
+
+    def _close_dead_reckoning(self):
+        """The limit where the frame closes: counts frames whose pose is not an accepted aligner result; pose and prior stay."""
+        self._frames_without_aligner_pose = 0 if self._pose_from_aligner else self._frames_without_aligner_pose + 1
+        if (self.dead_reckoning_limit > 0 and self._frames_without_aligner_pose >= self.dead_reckoning_limit and self._status == TRACKING):
+            self._status = LOCALIZING
 
     # -- helpers ---------------------------------------------------------------------------------------
     def _push_state(self):
@@ -101,6 +129,15 @@ class PoseTracker3D(object):
         self.fallback = 0
         self.track_broken = 0
         self._number_of_tracked_points = 0
+        self._pose_from_aligner = False
+        # the motion prior of the frame (:40-66), through the same device arithmetic as the fused path (vslam_motion_prior)
+        if self.motion_model == MOTION_CAMERA_ODOMETRY:
+            if self._previous_pose is not None:     # _context->currentFrame()
+                self._previous_to_current_camera = [float(v) for v in api.motion_prior(
+                    self._camera_left_in_world_guess, self._camera_left_in_world_guess_previous)[0]]
+            self._camera_left_in_world_guess_previous = list(self._camera_left_in_world_guess)
+        elif self.motion_model == MOTION_NONE:
+            self._previous_to_current_camera = _identity()
         left = np.ascontiguousarray(left, np.uint8)
         right = np.ascontiguousarray(right, np.uint8)
         stride = left.shape[1]
@@ -134,11 +171,13 @@ class PoseTracker3D(object):
             self._number_of_active_landmarks = api.frame_info(0).n_active_landmarks
             if self._number_of_active_landmarks > c.minimum_number_of_landmarks_to_track:
                 self._status = TRACKING
+            self._close_dead_reckoning()
         else:
             api.check(api.fn("update_points")(api.ctx))          # _updatePoints
             self._number_of_active_landmarks = api.frame_info(0).n_active_landmarks
             if self._number_of_active_landmarks > c.minimum_number_of_landmarks_to_track:
                 self._status = TRACKING
+            self._close_dead_reckoning()
             self._push_state()
             api.check(api.fn("stereo_new")(api.ctx))             # _framepoint_generator->compute(current_frame)
         self._number_of_tracked_landmarks_previous = self._number_of_active_landmarks
@@ -194,6 +233,7 @@ class PoseTracker3D(object):
         if delta_angular > c.minimum_delta_angular_for_movement or delta_translational > c.minimum_delta_translational_for_movement:
             self._previous_to_current_camera = list(T)
             self._frame_pose = _mul(self._previous_pose, _inverse(self._previous_to_current_camera))
+            self._pose_from_aligner = True
         else:
             self._fallbackEstimate()
 
@@ -203,10 +243,16 @@ class PoseTracker3D(object):
         relative = _div(float(self._number_of_tracked_landmarks), float(self._number_of_tracked_landmarks_previous))
         if self._number_of_tracked_landmarks == 0 or relative < 0.1:
             if recursion < 2:
-                self._previous_to_current_camera = _identity()
-                api.check(api.fn("frame_restore")(api.ctx))   # initialize(current_frame, false)
-                self._track(True)
-                self._registerRecursive(recursion + 1)
+                if not self._odometry():             # :316-322
+                    self._previous_to_current_camera = _identity()
+                    api.check(api.fn("frame_restore")(api.ctx))   # initialize(current_frame, false)
+                    self._track(True)
+                    self._registerRecursive(recursion + 1)
+                else:                                # :323-328 stick to the odometry guess
+                    self._frame_pose = _mul(self._previous_pose, _inverse(self._previous_to_current_camera))
+                    self.fallback = 1                # reported like every pose taken from the guess
+            elif self._odometry():                   # :333-336
+                self._fallbackEstimate()
             else:
                 self.breakTrack()
             return
@@ -220,12 +266,17 @@ class PoseTracker3D(object):
                 api.check(api.fn("frame_restore")(api.ctx))
                 self._track(False)
                 self._registerRecursive(recursion + 1)
+            elif self._odometry():                   # :408-411
+                self._fallbackEstimate()
             else:
                 self.breakTrack()
 
     def _fallbackEstimate(self):  # :551-566
-        self._previous_to_current_camera = _identity()
-        self._frame_pose = list(self._previous_pose)
+        if self._odometry():                         # :555-559: the pose the guess gives, the prior kept
+            self._frame_pose = _mul(self._previous_pose, _inverse(self._previous_to_current_camera))
+        else:
+            self._previous_to_current_camera = _identity()
+            self._frame_pose = list(self._previous_pose)
         self.fallback = 1
 
     def breakTrack(self):  # :422-435

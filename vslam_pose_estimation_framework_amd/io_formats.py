@@ -632,3 +632,56 @@ def write_trajectory_tum(path, poses, timestamps):
 
 def read_trajectory_kitti(path):
     return np.loadtxt(path).reshape(-1, 3, 4)
+
+
+def quaternion_to_rotation(x, y, z, w):
+    """Eigen::Quaternion::toRotationMatrix of the normalised quaternion."""
+    n = np.sqrt(x * x + y * y + z * z + w * w)
+    x, y, z, w = x / n, y / n, z / n, w / n
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
+
+
+def read_trajectory_tum(path):
+    """`timestamp tx ty tz qx qy qz qw` lines (`#` comments): (timestamps float64 [n], poses float64 [n, 3, 4])."""
+    rows = read_tum_list(path)
+    times = np.array([t for t, _ in rows], np.float64)
+    poses = np.zeros((len(rows), 3, 4), np.float64)
+    for k, (_, a) in enumerate(rows):
+        if len(a) != 7:
+            raise ValueError("%s: line %d has %d values behind the time stamp, a TUM trajectory has 7" % (path, k + 1, len(a)))
+        v = [float(s) for s in a]
+        poses[k, :, :3] = quaternion_to_rotation(*v[3:])
+        poses[k, :, 3] = v[:3]
+    return times, poses
+
+
+def read_pose_guesses(path, frame_times, max_difference=0.02):
+    """An odometry file for the frames of a sequence: float64 [n_frames, 12] camera_left_to_world and bool [n_frames] (the frame has a
+    pose of its own).  A KITTI pose file (12 values per line) is taken line k for frame k; a TUM trajectory (8 values) is associated to
+    the frames' time stamps like rgb.txt to depth.txt (associate: nearest first, within max_difference seconds).  A frame without a pose
+    carries the last one before it (identity ahead of the first), as a tracker that is handed no new guess re-uses the last."""
+    n = len(frame_times)
+    with open(path) as f:
+        first = next((ln for ln in f if ln.strip() and ln.strip()[0] != "#"), "")
+    width = len(first.replace(",", " ").split())
+    own = np.zeros(n, bool)
+    out = np.zeros((n, 12), np.float64)
+    if width == 12:
+        poses = read_trajectory_kitti(path).reshape(-1, 12)
+        m = min(n, len(poses))
+        out[:m], own[:m] = poses[:m], True
+    elif width == 8:
+        times, poses = read_trajectory_tum(path)
+        for i, j in associate(list(np.asarray(frame_times, np.float64)), list(times), max_difference):
+            out[i], own[i] = poses[j].reshape(12), True
+    else:
+        raise ValueError("%s: %d values per line (a KITTI pose file has 12, a TUM trajectory 8)" % (path, width))
+    last = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float64)
+    for k in range(n):
+        if own[k]:
+            last = out[k]
+        else:
+            out[k] = last
+    return out, own
