@@ -271,6 +271,24 @@ int vslam_set_clahe(vslam_ctx* ctx, int on, double clip_limit, int tiles_x, int 
 int vslam_get_clahe_luts(vslam_ctx* ctx, int stream, uint8_t* luts);
 int vslam_clahe_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, double clip_limit, int32_t tiles_x,
                    int32_t tiles_y, uint8_t* dst, int32_t dst_row_stride, uint8_t* luts /* may be NULL */);
+/* ---- bilateral filtering of the 16-bit depth image (csrc/kernels_bilateral.h) --------------------------------------------
+ * The optional first step of DepthFramePointGenerator::_computeDepthMap (depth_framepoint_generator.cpp:415-422,
+ * enable_bilateral_filtering): depth to metres as float, cv::bilateralFilter(src, dst, -1, sigma_color, sigma_space), back to 16 bit
+ * [recalled], bit-exact against the numpy restatement in bilateral.py, which fixes every order of operations: v = float(raw) *
+ * float(depth_scale); radius = max(1, cvRound(sigma_space * 1.5)), sigmas <= 0 count as 1; the taps inside the circle in scan order;
+ * BORDER_REFLECT_101; the colour table of 4098 floats over the image's own range (a flat image is returned as it is, its table is zeros);
+ * out = clamp(rint(filtered * float(1.0 / depth_scale)), 0, 65535).  Holes (zeros) are pixels like any other, as in the reference.
+ * vslam_bilateral_depth_u16: three kernels (k_depth_range, k_bilateral_lut, k_bilateral_apply) on one host image: src is rows x cols
+ *   with row_stride ELEMENTS per row, dst with dst_row_stride (elements beyond cols in a row are neither read nor written), each at any
+ *   2-byte alignment; dst == src (with equal strides) works in place, otherwise the two must not overlap.  lut4098 (may be NULL)
+ *   receives the table.  rows == 0 or cols == 0: VSLAM_OK, nothing written.  VSLAM_ERR_INVALID, nothing written: null src / dst, a
+ *   negative size, a stride below cols, depth_scale <= 0 or not finite, a sigma that is not finite, a radius above
+ *   VSLAM_BILATERAL_MAX_RADIUS, more than 2^24 pixels; the context stays usable. */
+#define VSLAM_BILATERAL_MAX_RADIUS 8
+#define VSLAM_BILATERAL_LUT 4098
+int vslam_bilateral_depth_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride /* elements */,
+                              double depth_scale, double sigma_color, double sigma_space, uint16_t* dst, int32_t dst_row_stride,
+                              float* lut4098 /* may be NULL */);
 /* ---- colour input: interleaved 8-bit colour to grey ahead of everything else (opt-in; csrc/kernels_gray.h) -------------
  * The reference converts a colour frame itself before anything else happens to it (slam_assembly.cpp:392-399, cvtColor CV_BGR2GRAY).
  * One definition, cvtColor on 8-bit images with 14 fractional bits [recalled], all integer:
@@ -676,8 +694,8 @@ typedef struct vslam_depth_params {
 #define VSLAM_DETECTOR_FAST 0
 #define VSLAM_DETECTOR_ORB 1
 
-/* DepthFramePointGenerator::_computeDepthMap (depth_framepoint_generator.cpp:410-485) without the optional bilateral
- * filter: every non-zero u16 depth pixel is back-projected through K_right_inverse, moved into the left camera,
+/* DepthFramePointGenerator::_computeDepthMap (depth_framepoint_generator.cpp:410-485) behind its optional bilateral
+ * filter (that step is vslam_bilateral_depth_u16 / vslam_rgbd_set_bilateral below; this entry maps the image it is given): every non-zero u16 depth pixel is back-projected through K_right_inverse, moved into the left camera,
  * projected with K_left and z-buffered (strict "stored float > new double", scan order) into the rows x cols x 3 float
  * space map, initialised to (0, 0, maximum_depth); row_map / col_map receive the winning source pixel (-1: none).
  * depth: host image, row stride in ELEMENTS.  Outputs may be NULL; the map also stays resident in the context for
@@ -883,6 +901,21 @@ int vslam_rgbd_get_equalized(vslam_rgbd* t, int32_t stream, uint8_t* image);
  *   vslam_rgbd_get_equalized. */
 int vslam_rgbd_set_clahe(vslam_rgbd* t, int on, double clip_limit, int tiles_x, int tiles_y);
 int vslam_rgbd_get_clahe_luts(vslam_rgbd* t, int32_t stream, uint8_t* luts);
+/* Bilateral filtering of the depth image in this mode (opt-in; the definition above vslam_bilateral_depth_u16; the reference's
+ * enable_bilateral_filtering with its sigmas 2, 2): the three kernels run on the space map's queue behind the depth upload and the depth
+ * undistortion and ahead of the map's first kernel, once per frame (further registration attempts reuse the map), inside the captured
+ * launch sequence as well (toggling drops it).  They write an image of the tracker's own, which the space map reads instead: a caller's
+ * device depth image is read only, and vslam_rgbd_get_undistorted keeps returning the unfiltered depth.  depth_scale is
+ * depth_scale_factor_intensity_to_meters.  The switch survives vslam_rgbd_reset.  Nothing is launched or allocated while it is off.
+ * vslam_rgbd_set_bilateral: a sigma of 0 selects the reference's 2.  VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop
+ *   (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature; VSLAM_ERR_INVALID for a negative or non-finite sigma, a
+ *   radius above VSLAM_BILATERAL_MAX_RADIUS, a depth scale <= 0 or more than 2^24 pixels.
+ * vslam_rgbd_get_bilateral: the switch and the sigmas in force (any pointer may be NULL).
+ * vslam_rgbd_get_filtered_depth: the depth image (rows*cols uint16, dense) the last finished frame of `stream` was mapped from, and its
+ *   table (4098 floats); either may be NULL.  VSLAM_ERR_STATE when off, before a frame, after vslam_rgbd_reset, or with a frame in flight. */
+int vslam_rgbd_set_bilateral(vslam_rgbd* t, int on, double sigma_color, double sigma_space);
+int vslam_rgbd_get_bilateral(vslam_rgbd* t, int* on, double* sigma_color, double* sigma_space);
+int vslam_rgbd_get_filtered_depth(vslam_rgbd* t, int32_t stream, uint16_t* depth, float* lut4098);
 /* Colour input in this mode (opt-in; the definition and the VSLAM_PIXEL_* formats above vslam_set_color_input): while the format is not
  * VSLAM_PIXEL_GRAY8 the intensity image of every process / submit / batch entry, host or device, is interleaved colour at the size the
  * tracker otherwise expects; its row and stream strides are in BYTES (row stride >= channels * cols).  The depth image is untouched.

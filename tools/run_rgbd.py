@@ -7,7 +7,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
                              [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color [--map-color]]
                              [--clahe [CLIP]] [--clahe-tiles X,Y] [--motion-model constant-velocity|none|odometry] [--odometry FILE]
-                             [--dead-reckoning-limit N]
+                             [--dead-reckoning-limit N] [--bilateral [SIGMA_COLOR,SIGMA_SPACE]]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -33,7 +33,10 @@ its point at the last update, through the --undistort map when that is on): red 
 configuration_xtion.yaml's own model; FILE: a TUM trajectory associated by time stamp, or a KITTI pose file, in the camera's frame) and
 dead-reckons on it where the images fail, in the place of a broken track; --dead-reckoning-limit N localizes again after N such frames in a
 row (without it one failed frame means dead reckoning for good: DESIGN.md 6j).  --motion-model none starts every frame from identity.  Both
-loops."""
+loops.
+--bilateral [SIGMA_COLOR,SIGMA_SPACE] smooths every depth image with the reference's bilateral filter on the GPU ahead of the space map
+(vslam_rgbd_set_bilateral: enable_bilateral_filtering, cv::bilateralFilter on the depth in metres; 2,2 without a value), behind --undistort:
+noisy depth streams.  The intensity image is untouched, so it combines with --color, --equalize and --clahe.  Device-resident loop only."""
 import argparse
 import os
 import sys
@@ -116,7 +119,7 @@ def distortion_of(undistort, intrinsics):
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
         gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0):
+        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None):
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -168,6 +171,10 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
         if clahe is not None:
             tr.set_clahe(True, clahe, clahe_tiles)
             log("CLAHE on the GPU (cv::CLAHE, clip limit %g, %d x %d tiles, on every intensity image%s)" % (clahe, clahe_tiles[0], clahe_tiles[1], ", behind the undistortion" if dist is not None else ""))
+        if bilateral is not None:
+            tr.set_bilateral(True, bilateral[0], bilateral[1])
+            log("bilateral filter on the GPU (cv::bilateralFilter on every depth image in metres, sigma colour %g, sigma space %g%s)" % (
+                tr.get_bilateral()[1:] + (", behind the undistortion" if dist is not None else "",)))
         tr.set_motion_model(MOTION_MODELS[motion_model], dead_reckoning_limit)
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
@@ -263,6 +270,17 @@ def _tiles(text):
     return x, y
 
 
+def _sigmas(text):
+    """--bilateral SIGMA_COLOR,SIGMA_SPACE -> (sigma_color, sigma_space)"""
+    try:
+        sc, ss = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected SIGMA_COLOR,SIGMA_SPACE (two numbers)")
+    if not (sc >= 0 and ss >= 0 and sc < float("inf") and ss < float("inf")):
+        raise argparse.ArgumentTypeError("sigmas must be finite and not negative (0 selects the reference's 2)")
+    return sc, ss
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("folder")
@@ -290,6 +308,8 @@ def parse_args(argv=None):
                     "--undistort and --equalize (without it: converted on the host, frame by frame)")
     ap.add_argument("--map-color", action="store_true", help="with --color and --map / --observations: the colour of every landmark (the pixel of its "
                     "point at the last update, sampled on the GPU) as red green blue in the PLY and map_rgb in the bundle")
+    ap.add_argument("--bilateral", nargs="?", type=_sigmas, const=(2.0, 2.0), default=None, metavar="SIGMA_COLOR,SIGMA_SPACE", help="smooth every depth "
+                    "image with the reference's bilateral filter (enable_bilateral_filtering) on the GPU ahead of the space map; 2,2 without a value")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):          # "--undistort -0.28,0.07,0,0": argparse would read the negative list as an option
         if argv[i] == "--undistort" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in "0123456789.":
@@ -319,7 +339,7 @@ def main(argv=None):
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
         map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles, motion_model=a.motion_model, odometry=a.odometry,
         dead_reckoning_limit=a.dead_reckoning_limit,
-        map_color=a.map_color)
+        map_color=a.map_color, bilateral=a.bilateral)
 
 
 if __name__ == "__main__":

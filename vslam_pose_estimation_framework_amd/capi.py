@@ -813,6 +813,26 @@ class CApi(object):
                                        _p(luts, C.c_uint8)))
         return dst, luts
 
+    def bilateral_depth_u16(self, depth, depth_scale, sigma_color=2.0, sigma_space=2.0, out=None, row_stride=None):
+        """vslam_bilateral_depth_u16: depth (and out, when given) is a 2-D uint16 array or view with unit column stride; row strides and
+        alignments are passed on as they are.  out=None: a dense result; out is depth: in place.  row_stride (elements) overrides the
+        source's own, for the refusal tests.  -> (dst, lut float32 [4098])."""
+        img = np.asarray(depth)
+        dst = np.zeros(img.shape, np.uint16) if out is None else out
+        for a in (img, dst):
+            if a.dtype != np.uint16 or a.ndim != 2 or (a.shape[1] > 1 and a.strides[1] != 2) or (a.shape[0] > 1 and (a.strides[0] < 2 * a.shape[1] or a.strides[0] % 2)):
+                raise ValueError("bilateral_depth_u16: 2-D uint16 arrays with unit column stride are required")
+        if dst.shape != img.shape:
+            raise ValueError("bilateral_depth_u16: out has another shape")
+        rows, cols = img.shape
+        lut = np.zeros(4098, np.float32)
+        stride = lambda a: a.strides[0] // 2 if rows > 1 else max(cols, 1)
+        self.check(self.fn("bilateral_depth_u16")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(cols),
+                                                  C.c_int32(stride(img) if row_stride is None else int(row_stride)), C.c_double(depth_scale),
+                                                  C.c_double(sigma_color), C.c_double(sigma_space), C.c_void_p(dst.ctypes.data),
+                                                  C.c_int32(stride(dst)), _p(lut, C.c_float)))
+        return dst, lut
+
     def gray_u8(self, image, fmt, cols=None):
         """vslam_gray_u8: image is a uint8 array [rows, cols, channels], or a 2-D array or view [rows, >= channels * cols bytes] with unit
         column stride whose row stride and alignment are passed on as they are (cols is then required) -> grey [rows, cols]."""
@@ -1094,6 +1114,27 @@ class _RgbdEqualizeApi(object):
         return _clahe_luts(lambda buf: self._check(self.lib.vslam_rgbd_get_clahe_luts(self.h, C.c_int32(stream), _p(buf, C.c_uint8))), getattr(self, "_clahe_tiles", None), 1)[0]
 
 
+class _RgbdBilateralApi(object):
+    """vslam_rgbd_set_bilateral / _get_bilateral / _get_filtered_depth (the device-resident loop only), shared by RgbdTracker and RgbdBatch."""
+
+    def set_bilateral(self, on=True, sigma_color=0.0, sigma_space=0.0):
+        """The depth image's bilateral filter ahead of the space map; a sigma of 0 selects the reference's 2."""
+        self._check(self.lib.vslam_rgbd_set_bilateral(self.h, C.c_int(1 if on else 0), C.c_double(sigma_color), C.c_double(sigma_space)))
+
+    def get_bilateral(self):
+        """(on, sigma_color, sigma_space) in force."""
+        on, sc, ss = C.c_int(), C.c_double(), C.c_double()
+        self._check(self.lib.vslam_rgbd_get_bilateral(self.h, C.byref(on), C.byref(sc), C.byref(ss)))
+        return bool(on.value), sc.value, ss.value
+
+    def filtered_depth(self, stream=0):
+        """(depth uint16 [rows, cols], lut float32 [4098]) the last finished frame of `stream` was mapped from."""
+        dep = np.zeros((int(self.cfg.rows), int(self.cfg.cols)), np.uint16)
+        lut = np.zeros(4098, np.float32)
+        self._check(self.lib.vslam_rgbd_get_filtered_depth(self.h, C.c_int32(stream), _p(dep, C.c_uint16), _p(lut, C.c_float)))
+        return dep, lut
+
+
 class _RgbdColorApi(object):
     """vslam_rgbd_set_color_input / _get_gray (the device-resident loop only), shared by RgbdTracker and RgbdBatch.  While a colour format
     is set, process / submit take the intensity image as [rows, cols, channels] (a batch: [n_streams, rows, cols, channels])."""
@@ -1142,7 +1183,7 @@ def _row_bytes(left, image_ndim):
     return int(left.shape[-1]) if left.ndim == image_ndim else int(left.shape[-2] * left.shape[-1])
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi, _RgbdMotionApi):
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdColorApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -1199,7 +1240,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorAp
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdColorApi, _RgbdMotionApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdColorApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

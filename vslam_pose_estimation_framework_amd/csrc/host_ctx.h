@@ -107,6 +107,9 @@ struct vslam_ctx {
   struct Guess { const double* dev = nullptr; std::vector<double> host; std::vector<int32_t> mask; bool any = false;
                  double* d_host = nullptr; int32_t* d_mask = nullptr; DeviceStore mem;
                  unsigned char* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int turn = 0; } guess;
+  // the range cells of vslam_bilateral_depth_u16 (kernels_bilateral.h): four words, armed when allocated with the first call and re-armed
+  // by every call's k_bilateral_lut
+  uint32_t* bl_cells = nullptr;
   int sticky = VSLAM_OK;
 };
 

@@ -955,6 +955,38 @@ VS_API int vslam_clahe_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_
   return k.finish();
 }
 
+// ---- the depth image's bilateral filter on one host image (kernels_bilateral.h) ----------------------------------------
+VS_API int vslam_bilateral_depth_u16(vslam_ctx* c, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride, double depth_scale,
+                                     double sigma_color, double sigma_space, uint16_t* dst, int32_t dst_row_stride, float* lut4098) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 0 || cols < 0) return fail(c, VSLAM_ERR_INVALID, "bilateral_depth_u16: negative size");
+  BilateralArgs ba;
+  std::memset(&ba, 0, sizeof ba);
+  const char* why = "";
+  if (!bilateral_args(std::max(rows, 1), std::max(cols, 1), depth_scale, sigma_color, sigma_space, ba, &why)) return fail(c, VSLAM_ERR_INVALID, std::string("bilateral_depth_u16: ") + why);
+  if (rows == 0 || cols == 0) return VSLAM_OK;
+  if (!src || !dst || row_stride < cols || dst_row_stride < cols || (dst == src && dst_row_stride != row_stride)) return fail(c, VSLAM_ERR_INVALID, "bilateral_depth_u16: bad argument");
+  if (!c->bl_cells) {                                                    // the first call allocates and arms the cells; every call leaves them armed
+    uint32_t* cells = nullptr;
+    HIP_TRY(c, dalloc(c, &cells, 4));
+    HIP_TRY(c, bilateral_arm(cells, 1, c->stream));
+    c->bl_cells = cells;
+  }
+  Call k(c, c->stream);
+  // the device copies keep the caller's 4-byte phase: the filter stores words where the caller's image would take them.  Source and
+  // destination are two buffers on the device also when they are one on the host: a tile reads its neighbours' pixels
+  const size_t ne = (size_t)(rows - 1) * row_stride + cols, nd = (size_t)(rows - 1) * dst_row_stride + cols;
+  uint16_t* ds = k.dev<uint16_t>(ne + 2) + (((uintptr_t)src & 3u) >> 1);
+  k.up_to(ds, src, ne);
+  uint16_t* dd = k.dev<uint16_t>(nd + 2) + (((uintptr_t)dst & 3u) >> 1);
+  ba.src = ds; ba.src_row_stride = row_stride; ba.dst = dd; ba.dst_row_stride = dst_row_stride; ba.n = 1;
+  ba.cells = c->bl_cells; ba.lut = k.dev<float>(VS_BL_LUT);
+  if (k.ok()) bilateral_enqueue(c->stream, ba);
+  if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)dst_row_stride * 2, dd, (size_t)dst_row_stride * 2, (size_t)cols * 2, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+  if (lut4098) k.down(lut4098, ba.lut, VS_BL_LUT);
+  return k.finish();
+}
+
 // ---- interleaved 8-bit colour to grey on one host image (kernels_gray.h) --------------------------------------------
 VS_API int vslam_gray_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int format, uint8_t* dst) {
   if (int rc = entry_begin(c)) return rc;

@@ -202,6 +202,24 @@ VS_API int vslam_rgbd_get_clahe_luts(vslam_rgbd* r, int32_t stream, uint8_t* lut
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_clahe_luts") : r->d.get_clahe_luts(stream, luts);
 }
+// ---- bilateral filtering of the depth image (kernels_bilateral.h): the device-resident loop only ----
+static int rgbd_bilateral_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) does not filter the depth image; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_bilateral(vslam_rgbd* r, int on, double sigma_color, double sigma_space) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_bilateral_host_refusal(r, "vslam_rgbd_set_bilateral") : r->d.set_bilateral(on, sigma_color, sigma_space);
+}
+VS_API int vslam_rgbd_get_bilateral(vslam_rgbd* r, int* on, double* sigma_color, double* sigma_space) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (r->on_host) return rgbd_bilateral_host_refusal(r, "vslam_rgbd_get_bilateral");
+  return r->d.get_bilateral(on, sigma_color, sigma_space);
+}
+VS_API int vslam_rgbd_get_filtered_depth(vslam_rgbd* r, int32_t stream, uint16_t* depth, float* lut4098) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_bilateral_host_refusal(r, "vslam_rgbd_get_filtered_depth") : r->d.get_filtered_depth(stream, depth, lut4098);
+}
 // ---- colour input (kernels_gray.h): the device-resident loop only ----
 static int rgbd_color_host_refusal(vslam_rgbd* r, const char* what) {
   r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes grey frames only; use the device-resident loop";

@@ -11,6 +11,7 @@
 #include "kernels_rgbd.h"
 #include "kernels_rgbd_map.h"
 #include "kernels_undistort.h"
+#include "kernels_bilateral.h"
 
 namespace vs_rgbd {
 
@@ -125,6 +126,7 @@ public:
     und.have_frame = false;                                                  // the maps stay (like the rig of a rectifying context)
     eq.have_frame = false;                                                   // and so does the equalisation switch
     col.have_frame = false;                                                  // and the colour format
+    bl.have_frame = false;                                                   // and the depth image's bilateral filter
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
     return VSLAM_OK;
   }
@@ -385,6 +387,55 @@ public:
     return fetched(planes_to_host(image, eq.dst, 0, stream, p.rows, p.cols));
   }
 
+  // ---- bilateral filtering of the depth image (kernels_bilateral.h): opt-in, its own allocations, nothing launched while bl.on is false.
+  // The three kernels read this frame's depth image (d_depth: the upload or the undistorted image; else the caller's device images) and
+  // write bl.depth, which the space map's kernels read instead: caller memory and d_depth (vslam_rgbd_get_undistorted) are never written.
+  int set_bilateral(int on, double sigma_color, double sigma_space) {
+    if (pending) { err = "vslam_rgbd_set_bilateral: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    BilateralArgs ba;
+    std::memset(&ba, 0, sizeof ba);
+    if (on) {
+      if (!(sigma_color >= 0) || !(sigma_space >= 0)) { err = "vslam_rgbd_set_bilateral: negative or non-finite sigma"; return VSLAM_ERR_INVALID; }
+      if (sigma_color == 0) sigma_color = 2.0;      // depth_framepoint_generator.cpp:419: cv::bilateralFilter(.., -1, 2, 2)
+      if (sigma_space == 0) sigma_space = 2.0;
+      const char* why = "";
+      if (!bilateral_args(p.rows, p.cols, p.depth_scale_factor_intensity_to_meters, sigma_color, sigma_space, ba, &why)) { err = std::string("vslam_rgbd_set_bilateral: ") + why; return VSLAM_ERR_INVALID; }
+    }
+    if (!on && !bl.on) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    (void)hipStreamSynchronize(q2);
+    bl_free();
+    drop_graph();                                   // a captured launch sequence holds the three kernels (or lacks them)
+    if (!on) return VSLAM_OK;
+    const size_t npx = (size_t)p.rows * p.cols;
+    hipError_t e = bl.mem.alloc(&bl.depth, npx * (size_t)B + 2);
+    if (e == hipSuccess) e = bl.mem.alloc(&ba.cells, (size_t)B * 4);
+    if (e == hipSuccess) e = bl.mem.alloc(&ba.lut, (size_t)B * VS_BL_LUT);
+    if (e == hipSuccess) e = bilateral_arm(ba.cells, B, q);
+    if (e != hipSuccess) { bl_free(); err = std::string("vslam_rgbd_set_bilateral: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    ba.dst = bl.depth; ba.dst_stream_stride = npx; ba.dst_row_stride = p.cols; ba.n = B;
+    bl.args = ba; bl.sigma_color = sigma_color; bl.sigma_space = sigma_space;
+    bl.on = true;
+    return VSLAM_OK;
+  }
+  int get_bilateral(int* on, double* sigma_color, double* sigma_space) const {
+    if (on) *on = bl.on ? 1 : 0;
+    if (sigma_color) *sigma_color = bl.on ? bl.sigma_color : 0.0;
+    if (sigma_space) *sigma_space = bl.on ? bl.sigma_space : 0.0;
+    return VSLAM_OK;
+  }
+  // the filtered depth image the last finished frame of `stream` was mapped from (dense) and its colour table; either may be null
+  int get_filtered_depth(int stream, uint16_t* depth, float* lut4098) {
+    if (int rc = readable(stream)) return rc;
+    if (!bl.on || !bl.have_frame) { err = "vslam_rgbd_get_filtered_depth: no frame has been filtered since vslam_rgbd_set_bilateral / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    const size_t npx = (size_t)p.rows * p.cols;
+    hipError_t e = depth ? hipMemcpy(depth, bl.depth + (size_t)stream * npx, npx * 2, hipMemcpyDeviceToHost) : hipSuccess;
+    if (e == hipSuccess && lut4098) e = hipMemcpy(lut4098, bl.args.lut + (size_t)stream * VS_BL_LUT, VS_BL_LUT * sizeof(float), hipMemcpyDeviceToHost);
+    return fetched(e);
+  }
+
   // ---- colour input (kernels_gray.h): opt-in, its own allocation, nothing launched while col.format is VSLAM_PIXEL_GRAY8.  The intensity
   // image of every entry is interleaved colour then (strides in bytes); k_gray_u8 converts it into col.gray, an image of the tracker's own at
   // the input size, which everything behind it reads — the undistortion, else the equalisation (in place) and the detector.  The caller's
@@ -439,7 +490,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; }
+    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; bl.have_frame = bl.on; }
     return rc;
   }
 
@@ -524,6 +575,9 @@ private:
   // at that size)
   struct Colour { int format = 0; bool have_frame = false; ImgPlanes gray; int32_t rows = 0, cols = 0; } col;
   DeviceStore col_mem;
+  // bilateral filtering of the depth image: off while bl.on is false.  depth: the filtered images [B][rows * cols] the space map reads;
+  // args: what the three kernels get but for this frame's source (sizes, scales, taps, the range cells [B][4] and the tables [B][4098])
+  struct Bilateral { bool on = false, have_frame = false; double sigma_color = 0, sigma_space = 0; uint16_t* depth = nullptr; BilateralArgs args; DeviceStore mem; } bl;
   PrePlan pre;                   // this frame's routing through the three stages (route_frame): pre.color is its colour source
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
@@ -535,6 +589,11 @@ private:
   void eq_free() {
     eq.release();
     eq.img = ImgPlanes();
+  }
+  void bl_free() {
+    bl.mem.release();
+    bl.on = false; bl.have_frame = false; bl.depth = nullptr;
+    std::memset(&bl.args, 0, sizeof bl.args);
   }
   void col_free() {
     col_mem.release();
@@ -610,6 +669,7 @@ private:
     und_free();
     eq_free();
     col_free();
+    bl_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (q2) { (void)hipStreamDestroy(q2); q2 = nullptr; }
     if (ev_depth) { (void)hipEventDestroy(ev_depth); ev_depth = nullptr; }
@@ -751,6 +811,14 @@ private:
       ua.map_xy = und.maps.xy[0]; ua.map_a = und.maps.a[0]; ua.map_stride = und.maps.stride;
       ua.dst = d_depth; ua.dst_stream_stride = (size_t)rows * cols; ua.dst_row_stride = cols; ua.rows = rows; ua.cols = cols; ua.n = B;
       hipLaunchKernelGGL(k_undistort_depth, undistort_grid(rows, cols, B), dim3(256), 0, q2, ua);
+    }
+    // the depth image's bilateral filter behind it: range, table and filter into bl.depth, which the map's kernels read from here on
+    // (dense images: a batch's stream stride is rows * row stride on either source)
+    if (bl.on) {
+      BilateralArgs ba = bl.args;
+      ba.src = depth_src; ba.src_row_stride = depth_src_stride; ba.src_stream_stride = (size_t)rows * depth_src_stride;
+      bilateral_enqueue(q2, ba);
+      depth_src = bl.depth; depth_src_stride = cols;
     }
     // pinhole matrices, identity offset: one direct pass; the general three passes stay enqueued behind it and skip every image whose depth
     // pixels all landed on themselves (k_depth_direct checks that and raises rb.cross[image] otherwise)

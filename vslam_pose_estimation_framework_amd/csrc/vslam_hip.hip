@@ -20,6 +20,7 @@
 #include "kernels_undistort.h"
 #include "kernels_equalize.h"
 #include "kernels_clahe.h"
+#include "kernels_bilateral.h"
 #include "kernels_gray.h"
 #include "kernels_map.h"
 #include "kernels_obs.h"
