@@ -428,6 +428,67 @@ __device__ __forceinline__ void evaluate_point(const DevCfg& c, const DevBuf& b,
   out[0] = fl; out[1] = fr; out[2] = (int)dbest; out[3] = 1; out[4] = flx; out[5] = tt.xyR[2 * fr + 1];
 }
 
+// What a sweep needs of a point on the usual path, kept in the arena behind the kill tables from the first sweep on: nothing of it changes
+// between sweeps (k_track_candidates wrote it), so a later sweep reads no global memory for such a point.  Five planes of uint4, point i at
+// plane[i] (a thread's points are VS_WG apart, so the lanes of a wavefront read consecutive 16-byte slots):
+//   plane 0, 1   the 16 left candidates, feature index only (the low half of a key: all the resolution compares)
+//   plane 2, 3   the 8 tabulated right keys of the first left candidate, whole
+//   plane 4      x = fl | fr << 16 and y = dist | flag << 15 | (x of fl) << 17: the point's result of the last sweep (fl, fr mean something
+//                with flag bit 0 only), z = (x of the first left candidate) | (cnt + 1) << 16 | (n_right + 1) << 24 with cnt clamped to
+//                -1 .. VS_MAXCAND + 1 and n_right to -1 .. VS_MAXRCAND + 1; bit 30: the point is on a landmark (M_LMUP > 0), bit 31: M_NEXT is set
+//                (the two things the compaction asks of a point; neither changes while the resolution runs)
+#define VS_TC_PLANES 5
+struct TrackCached { uint4 k0, k1, r0, r1; uint32_t meta; };
+__device__ __forceinline__ uint32_t tc_pack2(uint32_t a, uint32_t b) { return (a & 0xFFFFu) | (b << 16); }
+__device__ __forceinline__ TrackCached track_cache_fill(const DevCfg& c, const DevBuf& b, int s, const PtView& pv, int i) {
+  const size_t gi = (size_t)s * c.MAXP + i;
+  const int4 pr = *reinterpret_cast<const int4*>(b.proj + gi * 8);
+  const int4 pr2 = *reinterpret_cast<const int4*>(b.proj + gi * 8 + 4);
+  uint4 kv[VS_MAXCAND / 4];
+#pragma unroll
+  for (int k = 0; k < VS_MAXCAND / 4; ++k) kv[k] = reinterpret_cast<const uint4*>(b.cand_key + gi * VS_MAXCAND)[k];
+  TrackCached t;
+  t.r0 = reinterpret_cast<const uint4*>(b.cand_rkey + gi * VS_MAXRCAND)[0];
+  t.r1 = reinterpret_cast<const uint4*>(b.cand_rkey + gi * VS_MAXRCAND)[1];
+  static_assert(M_LMUP + 1 == M_NEXT && M_LMUP % 2 == 0 && META % 2 == 0, "M_LMUP, M_NEXT are read as one aligned pair");
+  const int2 ln = *reinterpret_cast<const int2*>(pv.meta + (size_t)i * META + M_LMUP);   // M_LMUP, M_NEXT: what the compaction asks of a point
+  t.k0 = make_uint4(tc_pack2(kv[0].x, kv[0].y), tc_pack2(kv[0].z, kv[0].w), tc_pack2(kv[1].x, kv[1].y), tc_pack2(kv[1].z, kv[1].w));
+  t.k1 = make_uint4(tc_pack2(kv[2].x, kv[2].y), tc_pack2(kv[2].z, kv[2].w), tc_pack2(kv[3].x, kv[3].y), tc_pack2(kv[3].z, kv[3].w));
+  const int cnt = min(max(pr.z, -1), VS_MAXCAND + 1);
+  const int nr = cnt < 0 ? -1 : min(max(pr2.x, -1), VS_MAXRCAND + 1);     // a projection outside the image leaves the second half of proj unwritten
+  t.meta = ((uint32_t)pr2.y & 0xFFFFu) | ((uint32_t)(cnt + 1) << 16) | ((uint32_t)(nr + 1) << 24) | (ln.x > 0 ? 1u << 30 : 0u) | (ln.y ? 1u << 31 : 0u);
+  return t;
+}
+// evaluate_point for a cached point whose kill tables are in LDS (killL, killR, xyR: the arena itself, so these are LDS instructions and not
+// FLAT ones).  false: the point is off the usual path (list overflowed, first left candidate removed, right candidates not tabulated) and
+// evaluate_point has to do it; `out` is untouched then.
+__device__ __forceinline__ bool evaluate_cached(const TrackCached& t, int i, const int32_t* killL, const int32_t* killR, const uint16_t* xyR, int* out) {
+  const int cnt = (int)((t.meta >> 16) & 0xFFu) - 1, n_right = (int)((t.meta >> 24) & 0xFu) - 1;
+  if (cnt > VS_MAXCAND) return false;
+  out[0] = -1; out[1] = -1; out[2] = 0; out[3] = 0; out[4] = 0; out[5] = 0;
+  if (cnt < 0) return true;
+  const uint32_t kw[8] = {t.k0.x, t.k0.y, t.k0.z, t.k0.w, t.k1.x, t.k1.y, t.k1.z, t.k1.w};
+  int fl = -1;
+#pragma unroll
+  for (int k = 0; k < VS_MAXCAND; ++k) {
+    const int f = (int)((kw[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
+    if (fl < 0 && k < cnt && ld_kill(killL + f) >= i) fl = f;
+  }
+  if (fl < 0) { out[3] = 2; return true; }
+  if (fl != (int)(kw[0] & 0xFFFFu) || n_right > VS_MAXRCAND) return false;
+  if (n_right < 0) return true;
+  const uint32_t rk[8] = {t.r0.x, t.r0.y, t.r0.z, t.r0.w, t.r1.x, t.r1.y, t.r1.z, t.r1.w};
+  uint32_t pick = 0xFFFFFFFFu;
+#pragma unroll
+  for (int k = 0; k < VS_MAXRCAND; ++k)
+    if (pick == 0xFFFFFFFFu && k < n_right && ld_kill(killR + (rk[k] & 0xFFFFu)) >= i) pick = rk[k];
+  if (pick == 0xFFFFFFFFu) { out[3] = 2; return true; }
+  if (pick & 0x80000000u) return true;
+  const int fr = (int)(pick & 0xFFFFu);
+  out[0] = fl; out[1] = fr; out[2] = (int)((pick >> 16) & 0x7FFFu); out[3] = 1; out[4] = (int)(int16_t)(t.meta & 0xFFFFu); out[5] = xyR[2 * fr + 1];
+  return true;
+}
+
 // Order-exact resolution of track(): Jacobi iteration on "who removed which lattice cell".
 // kill[f] = smallest index of a previous point whose (tentative) success removes feature f; point i
 // sees f as present iff kill[f] >= i.  A fixed point equals the sequential result (induction on i:
@@ -452,8 +513,17 @@ __device__ __forceinline__ void wg_track_resolve(const DevCfg& c, const DevBuf& 
     tt.killR = kill_of(c, b, s, 1);
     tt.xyR = reinterpret_cast<const uint16_t*>(kxyR);
   }
+  // points 0 .. n_tc - 1 keep their tables and their result in the arena behind the kill tables (TrackCached); the others, and every point
+  // when the kill tables are in HBM, go through global memory in every sweep
+  const size_t tc_off = ((size_t)nL * 4 + (size_t)nR * 8 + 15) & ~(size_t)15;
+  const int n_tc = in_lds ? (int)min((size_t)P, ((size_t)VS_ARENA - tc_off) / (16 * VS_TC_PLANES)) : 0;
+  uint4* tc = reinterpret_cast<uint4*>(arena + tc_off);
+  int32_t* lkillL = reinterpret_cast<int32_t*>(arena);
+  int32_t* lkillR = lkillL + nL;
+  const uint16_t* lxyR = reinterpret_cast<const uint16_t*>(lkillR + nR);
   int32_t* res = b.res + (size_t)s * c.MAXP * 8;
-  for (int i = tid; i < P; i += VS_WG) { res[8 * i] = -1; res[8 * i + 1] = -1; res[8 * i + 2] = 0; res[8 * i + 3] = 0; }
+  for (int i = tid; i < P; i += VS_WG)
+    if (i >= n_tc) { res[8 * i] = -1; res[8 * i + 1] = -1; res[8 * i + 2] = 0; res[8 * i + 3] = 0; }
   __syncthreads();
   for (int iter = 0; iter <= P + 1; ++iter) {
     VS_PHASE_COUNT(7);
@@ -461,14 +531,26 @@ __device__ __forceinline__ void wg_track_resolve(const DevCfg& c, const DevBuf& 
     for (int f = tid; f < nR; f += VS_WG) __hip_atomic_store(tt.killR + f, 0x7FFFFFFF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __syncthreads();
     if (iter > 0) {
+      // every tentative success removes its two features and (parallax clearing, :612-621) the right features strictly between fR.col and
+      // fL.col on fR.row; a cached point's result comes from the arena, the row of fR from the right coordinates there
       for (int i = tid; i < P; i += VS_WG) {
+        if (i < n_tc) {
+          const uint2 r2 = *reinterpret_cast<const uint2*>(tc + 4 * (size_t)n_tc + i);
+          if (r2.y & 0x8000u) {
+            const int fl = (int)(r2.x & 0xFFFFu), fr = (int)(r2.x >> 16);
+            const int lim = (int)(r2.y >> 17), rowR = lxyR[2 * fr + 1];
+            atomicMin(lkillL + fl, i);
+            atomicMin(lkillR + fr, i);
+            for (int g = fr + 1; g < nR && lxyR[2 * g + 1] == rowR && lxyR[2 * g] < lim; ++g) atomicMin(lkillR + g, i);
+          }
+          continue;
+        }
         const int4 r4 = *reinterpret_cast<const int4*>(res + 8 * i);
         if (r4.w & 1) {
           const int fl = r4.x, fr = r4.y;
           const int lim = res[8 * i + 4], rowR = res[8 * i + 5];
           atomicMin(tt.killL + fl, i);
           atomicMin(tt.killR + fr, i);
-          // parallax clearing (:612-621): right features strictly between fR.col and fL.col on fR.row
           for (int g = fr + 1; g < nR && tt.xyR[2 * g + 1] == rowR && tt.xyR[2 * g] < lim; ++g) atomicMin(tt.killR + g, i);
         }
       }
@@ -477,11 +559,34 @@ __device__ __forceinline__ void wg_track_resolve(const DevCfg& c, const DevBuf& 
     int changed = 0;
     for (int i = tid; i < P; i += VS_WG) {
       int o[6];
-      evaluate_point(c, b, s, pb_prev, i, tt, d, tau_track, tau_tri, by_app, o);
-      const int4 old = *reinterpret_cast<const int4*>(res + 8 * i);
-      if (o[0] != old.x || o[1] != old.y || o[3] != old.w) changed = 1;
-      *reinterpret_cast<int4*>(res + 8 * i) = make_int4(o[0], o[1], o[2], o[3]);
-      res[8 * i + 4] = o[4]; res[8 * i + 5] = o[5];
+      const bool cached = i < n_tc;
+      bool done = false;
+      uint2 old2 = make_uint2(0xFFFFFFFFu, 0u);     // fl = fr = -1, dist = 0, flag = 0
+      if (cached) {
+        TrackCached t;
+        if (iter == 0) {
+          t = track_cache_fill(c, b, s, pv, i);
+          tc[i] = t.k0; tc[(size_t)n_tc + i] = t.k1; tc[2 * (size_t)n_tc + i] = t.r0; tc[3 * (size_t)n_tc + i] = t.r1;
+          tc[4 * (size_t)n_tc + i] = make_uint4(old2.x, old2.y, t.meta, 0u);
+        } else {
+          t.k0 = tc[i]; t.k1 = tc[(size_t)n_tc + i]; t.r0 = tc[2 * (size_t)n_tc + i]; t.r1 = tc[3 * (size_t)n_tc + i];
+          const uint4 m = tc[4 * (size_t)n_tc + i];
+          old2 = make_uint2(m.x, m.y); t.meta = m.z;
+        }
+        done = evaluate_cached(t, i, lkillL, lkillR, lxyR, o);
+      }
+      if (!done) evaluate_point(c, b, s, pb_prev, i, tt, d, tau_track, tau_tri, by_app, o);
+      if (cached) {
+        // fl, fr are -1 exactly when flag bit 0 is clear, so the packed words differ exactly when (fl, fr, flag) do
+        const uint2 new2 = make_uint2(tc_pack2((uint32_t)o[0], (uint32_t)o[1]), ((uint32_t)o[2] & 0x7FFFu) | ((uint32_t)o[3] << 15) | ((uint32_t)o[4] << 17));
+        if (new2.x != old2.x || ((new2.y ^ old2.y) & 0x18000u)) changed = 1;
+        if (new2.x != old2.x || new2.y != old2.y) *reinterpret_cast<uint2*>(tc + 4 * (size_t)n_tc + i) = new2;
+      } else {
+        const int4 old = *reinterpret_cast<const int4*>(res + 8 * i);
+        if (o[0] != old.x || o[1] != old.y || o[3] != old.w) changed = 1;
+        *reinterpret_cast<int4*>(res + 8 * i) = make_int4(o[0], o[1], o[2], o[3]);
+        res[8 * i + 4] = o[4]; res[8 * i + 5] = o[5];
+      }
     }
     if (!__syncthreads_or(changed)) break;
   }
@@ -490,32 +595,59 @@ __device__ __forceinline__ void wg_track_resolve(const DevCfg& c, const DevBuf& 
   uint8_t* usedR = used_of(c, b, s, 1);
   for (int f = tid; f < nL; f += VS_WG) usedL[f] = ld_kill(tt.killL + f) != 0x7FFFFFFF;
   for (int f = tid; f < nR; f += VS_WG) usedR[f] = ld_kill(tt.killR + f) != 0x7FFFFFFF;
-  // compaction in previous-point order: tracked list, lost list, landmark count
+  // compaction in previous-point order: tracked list, lost list, landmark count.  It divides the points differently (a run per thread), and
+  // the barrier that ended the iteration made every result visible: a cached point's, with its two meta bits, in the arena (it never goes
+  // to HBM), the others' in res.
   int32_t* trk = b.trk + (size_t)s * c.MAXP * 4;
   int32_t* lost = b.lost + (size_t)s * c.MAXP;
   const int per = (P + VS_WG - 1) / VS_WG;
   const int i0 = tid * per, i1 = min(i0 + per, P);
+  // x, y as in plane 4 of the cache; z bit 0: tracked, bit 1: lost, bit 2: tracked and on a landmark
+  auto final_of = [&](int i) -> uint4 {
+    uint4 m;
+    int lmup, next;
+    if (i < n_tc) {
+      m = tc[4 * (size_t)n_tc + i];
+      lmup = (int)((m.z >> 30) & 1u); next = (int)(m.z >> 31);
+    } else {
+      const int4 r4 = *reinterpret_cast<const int4*>(res + 8 * i);
+      m.x = tc_pack2((uint32_t)r4.x, (uint32_t)r4.y); m.y = ((uint32_t)r4.z & 0x7FFFu) | ((uint32_t)r4.w << 15);
+      lmup = pv.meta[(size_t)i * META + M_LMUP] > 0; next = pv.meta[(size_t)i * META + M_NEXT] != 0;
+    }
+    const uint32_t flag = (m.y >> 15) & 3u;
+    m.z = (flag & 1u) ? (1u | (lmup ? 4u : 0u)) : (((flag & 2u) && !next) ? 2u : 0u);
+    return m;
+  };
   int nt = 0, nl = 0, nlm = 0;
   for (int i = i0; i < i1; ++i) {
-    const int fl = res[8 * i + 3];
-    if (fl & 1) { ++nt; if (pv.meta[(size_t)i * META + M_LMUP] > 0) ++nlm; }
-    else if ((fl & 2) && !pv.meta[(size_t)i * META + M_NEXT]) ++nl;
+    const uint32_t k = final_of(i).z;
+    nt += k & 1u; nl += (k >> 1) & 1u; nlm += (k >> 2) & 1u;
   }
-  int tot_t, tot_l, tot_lm;
-  int ot = block_exclusive_scan(nt, sh.scan, &tot_t);
-  int ol = block_exclusive_scan(nl, sh.scan, &tot_l);
-  block_exclusive_scan(nlm, sh.scan, &tot_lm);
+  int tot_t, tot_l;
+  int ot, ol;
+  if (tid == 0) sh.n_lm = 0;     // the landmark count needs no offsets: summed per wavefront, then in LDS (behind the scan's barriers)
+  if (P < 0x8000) {       // the tracked and the lost counts scanned as one word (neither total exceeds P)
+    int tot;
+    const int o2 = block_exclusive_scan(nt | (nl << 16), sh.scan, &tot);
+    ot = o2 & 0xFFFF; ol = o2 >> 16; tot_t = tot & 0xFFFF; tot_l = tot >> 16;
+  } else {
+    ot = block_exclusive_scan(nt, sh.scan, &tot_t);
+    ol = block_exclusive_scan(nl, sh.scan, &tot_l);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nlm += __shfl_down(nlm, o, 64);
+  if ((tid & 63) == 0 && nlm) atomicAdd(&sh.n_lm, nlm);
   for (int i = i0; i < i1; ++i) {
-    const int fl = res[8 * i + 3];
-    if (fl & 1) {
-      trk[4 * ot] = i; trk[4 * ot + 1] = res[8 * i]; trk[4 * ot + 2] = res[8 * i + 1]; trk[4 * ot + 3] = res[8 * i + 2];
+    const uint4 m = final_of(i);
+    if (m.z & 1u) {
+      *reinterpret_cast<int4*>(trk + 4 * (size_t)ot) = make_int4(i, (int)(m.x & 0xFFFFu), (int)(m.x >> 16), (int)(m.y & 0x7FFFu));
       ++ot;
       pv.meta[(size_t)i * META + M_NEXT] = 1;
-    } else if ((fl & 2) && !pv.meta[(size_t)i * META + M_NEXT]) {
+    } else if (m.z & 2u) {
       lost[ol++] = i;
     }
   }
-  if (tid == 0) { sh.n_trk = tot_t; sh.n_lost = tot_l; sh.n_lm = tot_lm; }
+  if (tid == 0) { sh.n_trk = tot_t; sh.n_lost = tot_l; }
   __syncthreads();
 }
 

@@ -125,7 +125,7 @@ __device__ __forceinline__ int stereo_append(const StereoView& v, FrameShared& s
     const int g = sm & 0xFFFF;
     int dist = sm >> 16;
     if (dist & VS_SD_TAG) dist = dist_of(i, dist & 15);
-    v.sc[4 * off] = i; v.sc[4 * off + 1] = g; v.sc[4 * off + 2] = dist; v.sc[4 * off + 3] = o;
+    reinterpret_cast<int4*>(v.sc)[off] = make_int4(i, g, dist, o);
     v.usedL[i] = 1; v.usedR[g] = 1;
     ++off;
   }
