@@ -124,7 +124,7 @@ typedef struct vslam_frame_info {
   int32_t status;              /* tracker status AFTER the frame (vslam_tracker_status)       */
   int32_t status_at_start;     /* status the frame was created with                           */
   int32_t n_keypoints_left, n_keypoints_right;   /* after the descriptor border filter        */
-  int32_t n_detected_left, n_detected_right;     /* raw FAST detections (controller input)    */
+  int32_t n_detected_left, n_detected_right;     /* raw FAST detections (controller input); behind a detection mask: the masked counts */
   int32_t thresholds[VSLAM_MAX_REGIONS];         /* detector thresholds AFTER adjust          */
   int32_t track_attempts;      /* 1 + recursive re-registrations (pose_tracker_3d.cpp:300)    */
   int32_t n_tracked;           /* points linked by the final track() call                     */
@@ -320,6 +320,48 @@ int vslam_set_color_input(vslam_ctx* ctx, int format);
 int vslam_get_gray_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
 int vslam_gray_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride_bytes, int format,
                   uint8_t* dst /* dense */);
+/* ---- detection masks: keep keypoints off masked pixels (opt-in; csrc/kernels_mask.h, mask.py) ----------------------------
+ * cv::Feature2D::detect(image, keypoints, mask) [recalled]: the detector and its non-maximum suppression run on the whole image, and
+ * every keypoint whose pixel reads 0 in the mask is dropped afterwards (KeyPointsFilter::runByPixelsMask), ahead of the count the
+ * threshold controller sees.  A mask is an 8-bit single-channel image at the processed size (rows x cols of the context: the rectified
+ * image's coordinates while rectification is set), row_stride_bytes >= cols per row; non-zero = keep.  `margin` m, 0 .. 64, erodes the
+ * keep-mask by the (2m+1) x (2m+1) square (a pixel stays kept only if every pixel within Chebyshev distance m is kept; pixels outside
+ * the image count as kept).  Packed form: (cols + 63) / 64 little-endian 64-bit words per row, bit b of word t = column 64 t + b, bits
+ * beyond cols 0.  A context holds a static mask (all streams) and a frame mask (per stream, the next frame only) per image side; the
+ * effective keep-mask is their AND, each eroded by its own margin, a missing one all-keep.  It is ANDed into the corner words between
+ * k_fast_box and k_emit, on the image pipeline's queue, under the fused entries and the stage path alike; nothing is launched,
+ * allocated or copied while no mask is set.  A switched-off stream's mask is neither read nor applied.  The mask governs detection only:
+ * landmark recovery and projection tracking sample the image wherever a landmark projects.  vslam_frame_info.n_detected_* are the
+ * masked counts, which is what the controller used.
+ * vslam_set_detection_mask: the static masks; host pointers, copied and packed before the call returns (it synchronises the context).
+ *   Either side may be NULL (unmasked); both NULL switches the static mask off and frees it.  Survives vslam_reset and
+ *   vslam_reset_stream(s).
+ * vslam_set_frame_masks: n_streams masks per side, stream s at side + s * image_stride_bytes, as the images of vslam_process_* are
+ *   addressed; either side may be NULL.  Consumed by the next frame (vslam_process_* or vslam_frame_begin).  Host masks (on_device 0)
+ *   are copied on the image pipeline's queue by that frame's call and, like device masks (read in place by that frame's kernel, never
+ *   written), must stay valid and unchanged until that frame has been synchronised (vslam_synchronize or any getter).  With more than one
+ *   stream image_stride_bytes must hold one mask (VSLAM_ERR_INVALID otherwise).  The kernel loads aligned 32-bit words: of a mask whose
+ *   rows do not start on a multiple of four bytes, up to 3 bytes either side of every row are read as well (and ignored).  Both NULL
+ *   cancels a pending set, and so does vslam_reset.
+ * Both: VSLAM_ERR_STATE between vslam_frame_begin and the end of that frame; VSLAM_ERR_INVALID (not sticky, nothing changed) for a
+ *   stride below cols or a margin outside 0 .. 64.  Frames of the fused entries that are still queued are no refusal: the static
+ *   setter waits for them (it synchronises), the frame-mask setter only records its arguments for the next frame.
+ * vslam_get_detection_mask: the effective packed keep-mask (rows * ((cols + 63) / 64) words) the last submitted frame of `stream` used
+ *   on `side` (0 left, 1 right).  Synchronises.  VSLAM_ERR_STATE when that frame used no mask at all or the stream was switched off
+ *   during it; VSLAM_ERR_INVALID for a bad
+ *   stream, side or a null pointer.
+ * vslam_mask_pack_u8: the pack kernel stand-alone on one host image of any size up to 32767 x 32767 (any alignment): `words` receives
+ *   rows * ((cols + 63) / 64) words.  rows or cols 0: VSLAM_OK, nothing written.  VSLAM_ERR_INVALID, nothing written: null src / words, a
+ *   negative size, a stride below cols, a margin outside 0 .. 64; the context stays usable.
+ * Not built: frame masks in RGB-D mode, masks in the shim (the reference's generator has no mask argument), masks for the stand-alone
+ * vslam_fast_detect / vslam_orb_detect entries. */
+#define VSLAM_MASK_MAX_MARGIN 64
+int vslam_set_detection_mask(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t row_stride_bytes, int32_t margin);
+int vslam_set_frame_masks(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t row_stride_bytes, size_t image_stride_bytes,
+                          int32_t margin, int on_device);
+int vslam_get_detection_mask(vslam_ctx* ctx, int stream, int side, uint64_t* words);
+int vslam_mask_pack_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride_bytes, int32_t margin,
+                       uint64_t* words);
 /* Block until all queued work of the context is done; returns the sticky HIP error state (VSLAM_ERR_HIP once a runtime
  * call has failed, else VSLAM_OK; capacity overflows are reported in vslam_frame_info.error_flags, see VSLAM_ERR_CAPACITY). */
 int vslam_synchronize(vslam_ctx* ctx);
@@ -916,6 +958,19 @@ int vslam_rgbd_get_clahe_luts(vslam_rgbd* t, int32_t stream, uint8_t* luts);
 int vslam_rgbd_set_bilateral(vslam_rgbd* t, int on, double sigma_color, double sigma_space);
 int vslam_rgbd_get_bilateral(vslam_rgbd* t, int* on, double* sigma_color, double* sigma_space);
 int vslam_rgbd_get_filtered_depth(vslam_rgbd* t, int32_t stream, uint16_t* depth, float* lut4098);
+/* The static detection mask in this mode (opt-in; the definition above vslam_set_detection_mask; csrc/kernels_mask.h): one
+ * 8-bit image at the processed size (the undistorted image's coordinates while undistortion is set), shared by every sequence of a batch.
+ * Its eroded packed words are ANDed into the corner words between k_fast_box and k_emit of EVERY attempt of a frame, re-registration
+ * attempts included, inside the captured launch sequence as well; nothing is launched while it is off.  There are no per-frame masks in
+ * this mode.  n_detected_left of the frame report is the masked count.
+ * vslam_rgbd_set_detection_mask: host pointer, copied and packed before the call returns; NULL switches the mask off and frees it.  The
+ *   mask survives vslam_rgbd_reset.  VSLAM_ERR_STATE with a frame in flight (between submit and wait), or on the host-driven loop
+ *   (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature; VSLAM_ERR_INVALID (nothing changed) for a stride below cols
+ *   or a margin outside 0 .. 64.
+ * vslam_rgbd_get_detection_mask: the packed keep-mask (rows * ((cols + 63) / 64) words) the last finished frame used; VSLAM_ERR_STATE
+ *   when off, before a frame, after vslam_rgbd_reset, or with a frame in flight. */
+int vslam_rgbd_set_detection_mask(vslam_rgbd* t, const uint8_t* mask, int32_t row_stride_bytes, int32_t margin);
+int vslam_rgbd_get_detection_mask(vslam_rgbd* t, uint64_t* words);
 /* Colour input in this mode (opt-in; the definition and the VSLAM_PIXEL_* formats above vslam_set_color_input): while the format is not
  * VSLAM_PIXEL_GRAY8 the intensity image of every process / submit / batch entry, host or device, is interleaved colour at the size the
  * tracker otherwise expects; its row and stream strides are in BYTES (row stride >= channels * cols).  The depth image is untouched.

@@ -24,6 +24,12 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
                               for frame k, or a TUM trajectory associated by time stamp; camera frame) and dead-reckons on it where the images
                               fail, in the place of a broken track; N > 0 localizes again after N such frames in a row.  --motion-model none
                               starts every frame from identity.  Also with --chunks: every chunk gets its own frames' poses
+    python tools/run_kitti.py <sequence dir> --mask LEFT.png[,RIGHT.png] [--mask-margin N] [--frame-masks DIR]   detection masks (8-bit PNGs at
+                              the processed size, the rectified one under --rectify; zero = no keypoints there, N = 0 .. 64 widens every
+                              masked region by N pixels): --mask for the whole run (the bonnet, overlays, vignetted corners), --frame-masks
+                              a folder that mirrors the two image folders file name for file name (moving objects from a segmentation
+                              network; a missing file: no mask for that frame).  Also with --chunks (every chunk its own frame's mask),
+                              --rectify, --color, --equalize / --clahe, --map, --observations
 
 The sequence runs in exact mode (one stream, whole sequence, bit-for-bit the reference port's arithmetic); images are
 uploaded frame by frame through vslam_process_host.  With --gt (KITTI 3x4 rows) the ATE-RMSE after rigid alignment is
@@ -45,7 +51,7 @@ MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a
 
 
 def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None):
+                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -69,6 +75,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
     if want_obs:
         api.enable_observations(steps * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
     api.set_motion_model(motion_model, dead_reckoning_limit)
+    if masks is not None:
+        masks.set_static(api)
     rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
     Lb = np.zeros((len(plan), rows, cols) + ((3,) if color else ()), np.uint8)
     Rb = np.zeros_like(Lb)
@@ -82,6 +90,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
                 live[c] = False
         if guesses is not None:      # every chunk its own frame's pose (a chunk that has ended is switched off: its entry is not read)
             api.set_pose_guesses(np.stack([guesses[min(st + k, en - 1)] for (st, fi, en) in plan]))
+        if masks is not None:        # every chunk its own frame's mask (a chunk that has ended is switched off: its mask is not read)
+            masks.set_frame(api, [st + k if st + k < en else None for (st, fi, en) in plan])
         api.process_host(Lb, Rb)
         if k % 20 == 19 or k == steps - 1:
             log("step %5d of %d (%d chunks side by side)" % (k + 1, steps, sum(live)))
@@ -101,7 +111,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
         chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8), map_color=False,
-        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0):
+        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, mask=None, mask_margin=0, frame_masks=None):
+    check_mask_args(mask, mask_margin, frame_masks, SystemExit)
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -157,6 +168,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         log("motion model camera odometry: %d of %d frames have a pose of their own in %s%s" % (
             int(own.sum()), n, odometry, ", dead-reckoning limit %d" % dead_reckoning_limit if dead_reckoning_limit else ""))
     model = MOTION_MODELS[motion_model]
+    masks = DetectionMasks(seq, int(cfg.rows), int(cfg.cols), mask, mask_margin, frame_masks, log) if (mask or frame_masks) else None
     t0 = time.perf_counter()
     flags = 0
     tracking = 0
@@ -166,7 +178,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
                                                 equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles, map_color=map_color,
-                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses)
+                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks)
         tracking = None
         dead_reckoned = None
     else:
@@ -187,11 +199,15 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         if obs_path:
             api.enable_observations(n * int(cfg.max_points))      # a frame logs at most max_points entries: the log cannot overflow
         api.set_motion_model(model, dead_reckoning_limit)
+        if masks is not None:
+            masks.set_static(api)
         for k in range(n):
             if k:
                 left, right = seq.pair(k)
             if guesses is not None and own[k]:
                 api.set_pose_guess(guesses[k], 0)
+            if masks is not None:
+                masks.set_frame(api, [k])
             api.process_host(left, right)
             fi = api.frame_info(0)
             flags |= fi.error_flags
@@ -258,6 +274,73 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     return result
 
 
+class DetectionMasks(object):
+    """--mask / --mask-margin / --frame-masks: the static masks (read once) and each frame's masks, looked up under the folder that
+    mirrors the sequence's two image folders."""
+
+    def __init__(self, seq, rows, cols, mask, margin, frame_dir, log=print):
+        self.seq, self.rows, self.cols, self.margin, self.frame_dir = seq, rows, cols, int(margin), frame_dir
+        self.static = None
+        if mask:
+            paths = mask.split(",")
+            self.static = [self._read(p) for p in paths] + [None] * (2 - len(paths))
+            log("detection mask: %s, margin %d px" % (" / ".join(paths), self.margin))
+        if frame_dir:
+            log("per-frame detection masks from %s, margin %d px" % (frame_dir, self.margin))
+
+    def _read(self, path):
+        m = io_formats.read_png_gray8(path)
+        if m.shape != (self.rows, self.cols):
+            raise SystemExit("mask %s is %dx%d, the detector works on %dx%d images" % (path, m.shape[0], m.shape[1], self.rows, self.cols))
+        return m
+
+    def relative(self, k):
+        """Where frame k's two images lie under the sequence folder, so where its masks lie under --frame-masks."""
+        s = self.seq
+        if isinstance(s, io_formats.EurocSequence):
+            return os.path.join("cam0", "data", s.left[k]), os.path.join("cam1", "data", s.right[k])
+        return tuple(os.path.join(d, s.names[k]) for d in s.dirs)
+
+    def set_static(self, api):
+        if self.static is not None:
+            api.set_detection_mask(self.static[0], self.static[1], self.margin)
+
+    def set_frame(self, api, frames):
+        """frames: the frame index of every stream's next frame (None: the stream has ended).  A side for which no stream has a file gets
+        no mask; a stream without a file among streams with one gets an all-keep mask."""
+        if not self.frame_dir:
+            return
+        sides = [None, None]
+        for c, k in enumerate(frames):
+            if k is None:
+                continue
+            for d, rel in enumerate(self.relative(k)):
+                path = os.path.join(self.frame_dir, rel)
+                if os.path.exists(path):
+                    if sides[d] is None:
+                        sides[d] = np.full((len(frames), self.rows, self.cols), 255, np.uint8)
+                    sides[d][c] = self._read(path)
+        if sides[0] is not None or sides[1] is not None:
+            api.set_frame_masks(sides[0], sides[1], self.margin)
+
+
+def check_mask_args(mask, mask_margin, frame_masks, error):
+    """What --mask, --mask-margin and --frame-masks allow together (tools/run_rgbd.py takes the first two)."""
+    if mask_margin < 0 or mask_margin > 64:
+        raise error("--mask-margin: a whole number of pixels in 0 .. 64")
+    if mask_margin and not (mask or frame_masks):
+        raise error("--mask-margin needs --mask or --frame-masks")
+    if mask is not None:
+        paths = mask.split(",")
+        if len(paths) > 2 or not all(paths):
+            raise error("--mask LEFT.png[,RIGHT.png]")
+        for p in paths:
+            if not os.path.isfile(p):
+                raise error("--mask: no such file: %s" % p)
+    if frame_masks is not None and not os.path.isdir(frame_masks):
+        raise error("--frame-masks: no such folder: %s" % frame_masks)
+
+
 MOTION_MODELS = {"constant-velocity": 0, "none": 1, "odometry": 2}     # enum vslam_motion_model
 
 
@@ -315,8 +398,14 @@ def parse_args(argv=None):
                     "for frame k) or a TUM trajectory (associated by time stamp)")
     ap.add_argument("--dead-reckoning-limit", type=int, default=0, metavar="N", help="--motion-model odometry: localize again after N frames in a row "
                     "whose pose was taken from the odometry (0: never)")
+    ap.add_argument("--mask", default=None, metavar="LEFT.png[,RIGHT.png]", help="detection masks for the whole run: 8-bit PNGs at the processed size, "
+                    "zero = no keypoints on that pixel (the bonnet, overlays, vignetted corners); one file masks the left image only")
+    ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask / --frame-masks by N pixels (0 .. 64)")
+    ap.add_argument("--frame-masks", default=None, metavar="DIR", help="per-frame detection masks: a folder that mirrors the sequence's two image folders "
+                    "file name for file name; a missing file means no mask for that frame")
     a = ap.parse_args(argv)
     try:
+        check_mask_args(a.mask, a.mask_margin, a.frame_masks, ValueError)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
@@ -331,7 +420,8 @@ def main(argv=None):
     a = parse_args(argv)
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
         rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
-        map_color=a.map_color, motion_model=a.motion_model, odometry=a.odometry, dead_reckoning_limit=a.dead_reckoning_limit)
+        map_color=a.map_color, motion_model=a.motion_model, odometry=a.odometry, dead_reckoning_limit=a.dead_reckoning_limit,
+        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
                              [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color [--map-color]]
                              [--clahe [CLIP]] [--clahe-tiles X,Y] [--motion-model constant-velocity|none|odometry] [--odometry FILE]
-                             [--dead-reckoning-limit N] [--bilateral [SIGMA_COLOR,SIGMA_SPACE]]
+                             [--dead-reckoning-limit N] [--bilateral [SIGMA_COLOR,SIGMA_SPACE]] [--mask MASK.png [--mask-margin N]]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -119,7 +119,8 @@ def distortion_of(undistort, intrinsics):
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
         gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None):
+        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None, mask=None, mask_margin=0):
+    check_mask_args(mask, mask_margin, SystemExit)
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -175,6 +176,12 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             tr.set_bilateral(True, bilateral[0], bilateral[1])
             log("bilateral filter on the GPU (cv::bilateralFilter on every depth image in metres, sigma colour %g, sigma space %g%s)" % (
                 tr.get_bilateral()[1:] + (", behind the undistortion" if dist is not None else "",)))
+        if mask:
+            mk = io_formats.read_png_gray8(mask)
+            if mk.shape != (int(cfg.rows), int(cfg.cols)):
+                raise SystemExit("--mask: %s is %dx%d, the detector works on %dx%d images" % (mask, mk.shape[0], mk.shape[1], cfg.rows, cfg.cols))
+            tr.set_detection_mask(mk, mask_margin)
+            log("detection mask: %s, margin %d px (no keypoints on its zero pixels, every re-registration attempt included)" % (mask, mask_margin))
         tr.set_motion_model(MOTION_MODELS[motion_model], dead_reckoning_limit)
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
@@ -322,8 +329,12 @@ def parse_args(argv=None):
                     "(associated by time stamp) or a KITTI pose file (line k for frame k)")
     ap.add_argument("--dead-reckoning-limit", type=int, default=0, metavar="N", help="--motion-model odometry: localize again after N frames in a row "
                     "whose pose was taken from the odometry (0: never)")
+    ap.add_argument("--mask", default=None, metavar="MASK.png", help="detection mask for the whole run: an 8-bit PNG at the processed size (the undistorted "
+                    "one under --undistort), zero = no keypoints on that pixel (the robot's own body, overlays, vignetted corners)")
+    ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask by N pixels (0 .. 64)")
     a = ap.parse_args(argv)
     try:
+        check_mask_args(a.mask, a.mask_margin, ValueError)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
@@ -334,12 +345,22 @@ def parse_args(argv=None):
     return a
 
 
+def check_mask_args(mask, mask_margin, error):
+    """What --mask and --mask-margin allow together."""
+    if mask_margin < 0 or mask_margin > 64:
+        raise error("--mask-margin: a whole number of pixels in 0 .. 64")
+    if mask_margin and not mask:
+        raise error("--mask-margin needs --mask")
+    if mask is not None and not os.path.isfile(mask):
+        raise error("--mask: no such file: %s" % mask)
+
+
 def main(argv=None):
     a = parse_args(argv)
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
         map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles, motion_model=a.motion_model, odometry=a.odometry,
         dead_reckoning_limit=a.dead_reckoning_limit,
-        map_color=a.map_color, bilateral=a.bilateral)
+        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin)
 
 
 if __name__ == "__main__":

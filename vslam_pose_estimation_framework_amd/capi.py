@@ -324,6 +324,75 @@ class CApi(object):
         self.check(self.fn("get_gray_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
         return L, R
 
+    # -- detection masks (vslam_set_detection_mask, vslam_set_frame_masks; semantics: mask.py) ------------------------------
+    def _mask_side(self, m, lead):
+        """One side's masks as (address, row stride, image stride, keep-alive): a uint8 numpy array or a torch tensor, [rows, stride] or
+        with `lead` a leading stream axis, unit column stride.  None stays None."""
+        if m is None:
+            return None
+        if hasattr(m, "data_ptr"):            # a torch tensor: read in place
+            if str(m.dtype) != "torch.uint8" or m.stride(-1) != 1:
+                raise ValueError("mask: a uint8 tensor with unit column stride is required")
+            shape, strides, addr, keep = tuple(m.shape), tuple(m.stride()), m.data_ptr(), m
+        else:
+            a = np.asarray(m)
+            if a.dtype != np.uint8 or a.ndim < 2 or (a.shape[-1] > 1 and a.strides[-1] != 1) or a.strides[-2] < a.shape[-1]:
+                a = np.ascontiguousarray(m, np.uint8)
+            shape, strides, addr, keep = a.shape, a.strides, a.ctypes.data, a
+        if lead and len(shape) == 2:
+            shape, strides = (1,) + tuple(shape), (0,) + tuple(strides)
+        if len(shape) != (3 if lead else 2) or shape[-2] != self.cfg.rows or shape[-1] < self.cfg.cols:
+            raise ValueError("mask: expected %s%d x >= %d, got %s" % ("n_streams x " if lead else "", self.cfg.rows, self.cfg.cols, tuple(shape)))
+        if lead and shape[0] != self.n_streams:
+            raise ValueError("mask: %d masks for %d streams" % (shape[0], self.n_streams))
+        return addr, int(strides[-2]), int(strides[0]) if lead else 0, keep
+
+    def set_detection_mask(self, left=None, right=None, margin=0):
+        """The static masks of the two sides (2-D uint8, non-zero = keep; None: that side unmasked; both None: off)."""
+        L, R = self._mask_side(left, False), self._mask_side(right, False)
+        if L is not None and R is not None and L[1] != R[1]:
+            R = self._mask_side(np.ascontiguousarray(right), False)
+            L = self._mask_side(np.ascontiguousarray(left), False)
+        stride = (L or R or (0, int(self.cfg.cols)))[1]
+        self.check(self.fn("set_detection_mask")(self.ctx, C.c_void_p(L[0] if L else None), C.c_void_p(R[0] if R else None), C.c_int32(stride),
+                                                 C.c_int32(int(margin))))
+
+    def set_frame_masks(self, left=None, right=None, margin=0):
+        """The next frame's masks: uint8 [n_streams, rows, stride] (or [rows, stride] on one stream) per side, numpy arrays (host) or torch
+        device tensors (read in place; the caller keeps them alive until that frame has finished).  None: that side has none; both None
+        cancels a pending set."""
+        dev = [hasattr(m, "data_ptr") and m.is_cuda for m in (left, right) if m is not None]
+        if dev and any(dev) != all(dev):
+            raise ValueError("set_frame_masks: both sides on the host or both on the device")
+        L, R = self._mask_side(left, True), self._mask_side(right, True)
+        if L is not None and R is not None and L[1:3] != R[1:3]:
+            raise ValueError("set_frame_masks: the two sides differ in their strides")
+        _, stride, istride, _ = L or R or (0, int(self.cfg.cols), 0, None)
+        self.check(self.fn("set_frame_masks")(self.ctx, C.c_void_p(L[0] if L else None), C.c_void_p(R[0] if R else None), C.c_int32(stride),
+                                              C.c_size_t(istride), C.c_int32(int(margin)), C.c_int(1 if dev and dev[0] else 0)))
+        # the masks stay valid until their frame has been synchronised: the sets of the frames that may still be queued are kept alive
+        self._frame_masks_alive = (getattr(self, "_frame_masks_alive", ()) + ((L, R),))[-3:]
+
+    def detection_mask(self, stream=0, side=0):
+        """The effective packed keep-mask the last frame of `stream` used: uint64 [rows, (cols + 63) // 64] (mask.unpack)."""
+        rows, tx = int(self.cfg.rows), (int(self.cfg.cols) + 63) // 64
+        w = np.zeros((rows, tx), np.uint64)
+        self.check(self.fn("get_detection_mask")(self.ctx, C.c_int(stream), C.c_int(side), _p(w, C.c_uint64)))
+        return w
+
+    def mask_pack_u8(self, image, margin=0):
+        """vslam_mask_pack_u8: image is a 2-D uint8 array or view with unit column stride (its row stride and alignment are passed on as
+        they are) -> uint64 [rows, (cols + 63) // 64]."""
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 2 or (img.shape[1] > 1 and img.strides[1] != 1) or (img.shape[0] > 1 and img.strides[0] < img.shape[1]):
+            img = np.ascontiguousarray(image, np.uint8)
+        rows, cols = img.shape
+        stride = img.strides[0] if rows > 1 else max(cols, 1)
+        w = np.zeros((rows, (cols + 63) // 64), np.uint64)
+        self.check(self.fn("mask_pack_u8")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(cols), C.c_int32(stride),
+                                           C.c_int32(int(margin)), _p(w, C.c_uint64)))
+        return w
+
     # -- motion models and pose guesses (vslam_set_motion_model, vslam_set_pose_guess*) -----------------------------------
     def set_motion_model(self, model, dead_reckoning_limit=0):
         """model: MOTION_CONSTANT_VELOCITY (default) / MOTION_NONE / MOTION_CAMERA_ODOMETRY; dead_reckoning_limit N > 0 (odometry only): a
@@ -1135,6 +1204,26 @@ class _RgbdBilateralApi(object):
         return dep, lut
 
 
+class _RgbdMaskApi(object):
+    """vslam_rgbd_set_detection_mask / _get_detection_mask (the device-resident loop only), shared by RgbdTracker and RgbdBatch."""
+
+    def set_detection_mask(self, mask_u8=None, margin=0):
+        """The static detection mask of every sequence (2-D uint8 at the processed size, non-zero = keep; semantics: mask.py); None: off."""
+        if mask_u8 is None:
+            self._check(self.lib.vslam_rgbd_set_detection_mask(self.h, None, C.c_int32(0), C.c_int32(0)))
+            return
+        m = np.ascontiguousarray(mask_u8, np.uint8)
+        if m.shape != (int(self.cfg.rows), int(self.cfg.cols)):
+            raise ValueError("set_detection_mask: the mask is %s, the tracker works on %d x %d images" % (m.shape, self.cfg.rows, self.cfg.cols))
+        self._check(self.lib.vslam_rgbd_set_detection_mask(self.h, _p(m, C.c_uint8), C.c_int32(m.shape[1]), C.c_int32(int(margin))))
+
+    def detection_mask(self):
+        """The packed keep-mask the last finished frame used: uint64 [rows, (cols + 63) // 64] (mask.unpack)."""
+        w = np.zeros((int(self.cfg.rows), (int(self.cfg.cols) + 63) // 64), np.uint64)
+        self._check(self.lib.vslam_rgbd_get_detection_mask(self.h, _p(w, C.c_uint64)))
+        return w
+
+
 class _RgbdColorApi(object):
     """vslam_rgbd_set_color_input / _get_gray (the device-resident loop only), shared by RgbdTracker and RgbdBatch.  While a colour format
     is set, process / submit take the intensity image as [rows, cols, channels] (a batch: [n_streams, rows, cols, channels])."""
@@ -1183,7 +1272,7 @@ def _row_bytes(left, image_ndim):
     return int(left.shape[-1]) if left.ndim == image_ndim else int(left.shape[-2] * left.shape[-1])
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdColorApi, _RgbdMotionApi):
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -1240,7 +1329,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilater
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdColorApi, _RgbdMotionApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

@@ -107,6 +107,17 @@ struct vslam_ctx {
   struct Guess { const double* dev = nullptr; std::vector<double> host; std::vector<int32_t> mask; bool any = false;
                  double* d_host = nullptr; int32_t* d_mask = nullptr; DeviceStore mem;
                  unsigned char* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int turn = 0; } guess;
+  // detection masks (vslam_set_detection_mask / vslam_set_frame_masks, kernels_mask.h).  stat[side]: the static mask's eroded packed words
+  // [rows][TX], null: that side is unmasked; freed when both go.  The frame masks wait here for the next frame's image pipeline: src the
+  // caller's pointers (null: that side has none), read in place on the device, copied into `slab` at the caller's strides when they are
+  // host memory; eff [B][2][rows][TX]: the effective words of the last frame that had frame masks.  last: what the last frame used (bit 0
+  // static, bit 1 frame masks) and on which streams (last_active).  Nothing of this is allocated, launched or copied while no mask is set.
+  struct DetMask { unsigned long long* stat[2] = {nullptr, nullptr}; DeviceStore stat_mem;
+                   bool pending = false, on_device = false; const uint8_t* src[2] = {nullptr, nullptr}; int32_t row_stride = 0; size_t image_stride = 0; int margin = 0;
+                   uint8_t* slab[2] = {nullptr, nullptr}; size_t slab_bytes = 0; DeviceStore slab_mem;
+                   unsigned long long* eff = nullptr; DeviceStore eff_mem;
+                   MaskPackArgs job{}; bool job_ready = false;
+                   int last = 0; uint32_t last_active[VS_MAX_STREAMS / 32] = {}; } dmask;
   // the range cells of vslam_bilateral_depth_u16 (kernels_bilateral.h): four words, armed when allocated with the first call and re-armed
   // by every call's k_bilateral_lut
   uint32_t* bl_cells = nullptr;
@@ -334,6 +345,8 @@ static int upload_buffer_tables(vslam_ctx* c) {
 static int init_state(vslam_ctx* c) {
   c->pend.flags = 0;          // a reset drops setters that were waiting for a stage launch: the fresh state is the state
   guess_drop_pending(c);
+  c->dmask.pending = false;   // frame masks that were waiting for a frame belong to the sequence that ended (the static mask stays)
+  c->dmask.last = 0;
   c->report_have = 0;
   std::vector<StreamState> st(c->B);
   for (int s = 0; s < c->B; ++s) fresh_stream_state(c, st[s]);
@@ -550,6 +563,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
   for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem}) m->release();     // the input stages' stores
+  for (DeviceStore* m : {&c->dmask.stat_mem, &c->dmask.slab_mem, &c->dmask.eff_mem}) m->release();    // detection masks
   c->guess.mem.release();
   for (int q = 0; q < 2; ++q) { if (c->guess.pin[q]) (void)hipHostFree(c->guess.pin[q]); if (c->guess.pin_ev[q]) (void)hipEventDestroy(c->guess.pin_ev[q]); }
   map_free(c);

@@ -930,6 +930,29 @@ VS_API int vslam_equalize_hist_u8(vslam_ctx* c, const uint8_t* src, int32_t rows
   return k.finish();
 }
 
+// ---- a detection mask's eroded packed words from one host image (kernels_mask.h) ----------------------------------------
+VS_API int vslam_mask_pack_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int32_t margin, uint64_t* words) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 0 || cols < 0) return fail(c, VSLAM_ERR_INVALID, "mask_pack: negative size");
+  if (margin < 0 || margin > VS_MASK_MAX_MARGIN) return fail(c, VSLAM_ERR_INVALID, "mask_pack: margin outside 0 .. 64");
+  if (rows == 0 || cols == 0) return VSLAM_OK;
+  if (!src || !words || row_stride < cols || rows > 32767 || cols > 32767) return fail(c, VSLAM_ERR_INVALID, "mask_pack: bad argument");
+  Call k(c, c->stream);
+  const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
+  const size_t off = (size_t)((uintptr_t)src & 15u);       // the device copy keeps the caller's alignment: rows start where they would in place
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16);
+  k.up_to(ds + off, src, bytes);
+  MaskPackArgs a{};
+  a.src[0] = ds + off; a.src_row_stride = row_stride; a.rows = rows; a.cols = cols; a.TX = (cols + 63) / 64; a.margin = margin; a.n = 1; a.sides = 1;
+  const size_t nw = (size_t)rows * a.TX;
+  a.dst = k.dev<unsigned long long>(nw);
+  active_all(a.active, 1);
+  if (k.ok()) mask_pack_enqueue(c->stream, a);
+  k.launched();
+  k.down(reinterpret_cast<unsigned long long*>(words), a.dst, nw);
+  return k.finish();
+}
+
 // ---- cv::CLAHE::apply on one host image (kernels_clahe.h) -------------------------------------------------------------
 VS_API int vslam_clahe_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, double clip_limit, int32_t tiles_x,
                           int32_t tiles_y, uint8_t* dst, int32_t dst_row_stride, uint8_t* luts) {

@@ -32,13 +32,16 @@ static int launch_image_pipeline(vslam_ctx* c) {
   if (c->frm_pending[set] && st != c->stream) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_frm[set], 0));
   // grey, rectify, equalise as route_frame has planned them (the slabs they write are those the wait above has freed)
   HIP_TRY(c, prestage_enqueue(st, c->pre, c->rect.maps, c->eq, n, 2, c->buf.active));
+  // detection masks (kernels_mask.h): nothing while none is set
+  const bool masked = c->dmask.pending || c->dmask.stat[0] || c->dmask.stat[1];
+  if (masked) { if (const int rc = mask_prepare(c, st)) return rc; } else c->dmask.last = 0;
   const DevBuf bs = buf_set(c, set, c->img_override ? c->q0_frm : c->q0_img);
   dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, 2 * n);
   const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (coarse && c->timers) { e0 = ev_get(c); (void)hipEventRecord(e0, st); }
   { KernelTimer t(c, 0, st, true, !coarse); hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, st, c->cfg, bs); }
-  { KernelTimer t(c, 1, st, true, !coarse); hipLaunchKernelGGL(k_emit, dim3(n, 2), dim3(512), 0, st, c->cfg, bs, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 1); }
+  { KernelTimer t(c, 1, st, true, !coarse); if (masked) mask_enqueue(c, st, bs); hipLaunchKernelGGL(k_emit, dim3(n, 2), dim3(512), 0, st, c->cfg, bs, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 1); }
   if (e0) { e1 = ev_get(c); (void)hipEventRecord(e1, st); c->evrec.push_back({e0, e1, 0, true}); c->kern_n[1] += 1; }
   if (c->img_override && c->report && c->B == 1) {
     // stage path with a view reader: coordinates and scores leave for the host as soon as k_emit has written them, so that the caller

@@ -193,6 +193,19 @@ VS_API int vslam_rgbd_get_equalized(vslam_rgbd* r, int32_t stream, uint8_t* imag
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_equalized") : r->d.get_equalized(stream, image);
 }
+// ---- the static detection mask (kernels_mask.h): the device-resident loop only ----
+static int rgbd_mask_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes no detection mask; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_detection_mask(vslam_rgbd* r, const uint8_t* mask, int32_t row_stride, int32_t margin) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_detection_mask") : r->d.set_detection_mask(mask, row_stride, margin);
+}
+VS_API int vslam_rgbd_get_detection_mask(vslam_rgbd* r, uint64_t* words) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_get_detection_mask") : r->d.get_detection_mask(words);
+}
 // ---- CLAHE of the intensity image, the equalisation slot's second mode (kernels_clahe.h): the device-resident loop only ----
 VS_API int vslam_rgbd_set_clahe(vslam_rgbd* r, int on, double clip_limit, int tiles_x, int tiles_y) {
   if (!r) return VSLAM_ERR_INVALID;

@@ -299,6 +299,143 @@ static int launch_motion_prior(vslam_ctx* c) {
   guess_drop_pending(c);
   return VSLAM_OK;
 }
+// ---- detection masks (kernels_mask.h) ------------------------------------------------------------------------------
+// k_mask_pack on `n` streams of `sides` masks; fused when a.corner is set
+static void mask_pack_enqueue(hipStream_t st, const MaskPackArgs& a) {
+  hipLaunchKernelGGL(k_mask_pack, dim3((a.TX + VS_MASK_CW - 1) / VS_MASK_CW, (a.rows + VS_MASK_BR - 1) / VS_MASK_BR, a.n * a.sides), dim3(256), 0, st, a);
+}
+// what both setters refuse about a mask's geometry
+static int mask_args_check(vslam_ctx* c, const char* who, int32_t row_stride, int32_t margin) {
+  if (margin < 0 || margin > VS_MASK_MAX_MARGIN) return fail(c, VSLAM_ERR_INVALID, std::string(who) + ": margin outside 0 .. 64");
+  if (row_stride < c->cfg.c.cols) return fail(c, VSLAM_ERR_INVALID, std::string(who) + ": row stride smaller than image width");
+  return VSLAM_OK;
+}
+static void mask_static_free(vslam_ctx* c) {
+  c->dmask.stat_mem.release();
+  c->dmask.stat[0] = c->dmask.stat[1] = nullptr;
+}
+VS_API int vslam_set_detection_mask(vslam_ctx* c, const uint8_t* left, const uint8_t* right, int32_t row_stride, int32_t margin) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_detection_mask called inside a frame");
+  const bool off = !left && !right;
+  if (!off) if (int rc = mask_args_check(c, "vslam_set_detection_mask", row_stride, margin)) return rc;
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the old words
+  mask_static_free(c);
+  c->dmask.last = 0;               // no frame has run under the new setting
+  if (off) return VSLAM_OK;
+  vslam_ctx::DetMask& q = c->dmask;
+  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols, TX = c->cfg.TX;
+  const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
+  const uint8_t* const src[2] = {left, right};
+  uint8_t* tmp = nullptr;
+  hipError_t e = hipMalloc((void**)&tmp, bytes);
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    if (!src[k]) continue;
+    e = q.stat_mem.alloc(&q.stat[k], (size_t)rows * TX);
+    if (e == hipSuccess) e = hipMemcpy(tmp, src[k], bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    MaskPackArgs a{};
+    a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = rows; a.cols = cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
+    a.dst = q.stat[k];
+    active_all(a.active, 1);
+    mask_pack_enqueue(c->stream, a);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // tmp is refilled for the other side
+  }
+  if (tmp) (void)hipFree(tmp);
+  if (e != hipSuccess) { mask_static_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_detection_mask: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_set_frame_masks(vslam_ctx* c, const uint8_t* left, const uint8_t* right, int32_t row_stride, size_t image_stride, int32_t margin, int on_device) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_frame_masks called inside a frame");
+  vslam_ctx::DetMask& q = c->dmask;
+  if (!left && !right) { q.pending = false; return VSLAM_OK; }
+  if (int rc = mask_args_check(c, "vslam_set_frame_masks", row_stride, margin)) return rc;
+  if (c->B > 1 && image_stride < (size_t)(c->cfg.c.rows - 1) * row_stride + c->cfg.c.cols)
+    return fail(c, VSLAM_ERR_INVALID, "vslam_set_frame_masks: image stride smaller than one mask");
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  q.pending = true; q.on_device = on_device != 0;
+  q.src[0] = left; q.src[1] = right; q.row_stride = row_stride; q.image_stride = image_stride; q.margin = margin;
+  return VSLAM_OK;
+}
+// Ahead of k_fast_box: what the frame's mask launch needs that can fail — the effective words, and the host masks' copy into the slab on
+// the queue the launch goes to (the previous frame's launch, the slab's last reader, ran on the same queue or is ordered ahead of it by
+// launch_image_pipeline's own waits).  Consumes the pending set.
+static int mask_prepare(vslam_ctx* c, hipStream_t st) {
+  vslam_ctx::DetMask& q = c->dmask;
+  q.job_ready = false;
+  if (!q.pending) return VSLAM_OK;
+  q.pending = false;
+  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols, TX = c->cfg.TX, B = c->B;
+  if (!q.eff) HIP_TRY(c, q.eff_mem.alloc(&q.eff, (size_t)B * 2 * rows * TX));
+  const uint8_t* src[2] = {q.src[0], q.src[1]};
+  if (!q.on_device) {
+    const size_t one = (size_t)(rows - 1) * q.row_stride + cols, span = (size_t)(B - 1) * q.image_stride + one;
+    if (q.slab_bytes < span) {
+      sync_all(c);                 // the last frame's launch may still read the old slabs
+      q.slab_mem.release(); q.slab[0] = q.slab[1] = nullptr; q.slab_bytes = 0;
+      for (int k = 0; k < 2; ++k) HIP_TRY(c, q.slab_mem.alloc(&q.slab[k], span));
+      q.slab_bytes = span;
+    }
+    bool all_active = true;
+    for (int s = 0; s < B; ++s) all_active = all_active && ((c->buf.active[s >> 5] >> (s & 31)) & 1u);
+    for (int k = 0; k < 2; ++k) {
+      if (!src[k]) continue;
+      if (all_active) HIP_TRY(c, hipMemcpyAsync(q.slab[k], src[k], span, hipMemcpyHostToDevice, st));
+      else   // the mask of a switched-off stream is not read
+        for (int s = 0; s < B; ++s)
+          if ((c->buf.active[s >> 5] >> (s & 31)) & 1u)
+            HIP_TRY(c, hipMemcpyAsync(q.slab[k] + (size_t)s * q.image_stride, src[k] + (size_t)s * q.image_stride, one, hipMemcpyHostToDevice, st));
+      src[k] = q.slab[k];
+    }
+  }
+  MaskPackArgs& a = q.job;
+  a = MaskPackArgs{};
+  a.src[0] = src[0]; a.src[1] = src[1]; a.src_stream_stride = q.image_stride; a.src_row_stride = q.row_stride;
+  a.rows = rows; a.cols = cols; a.TX = TX; a.margin = q.margin; a.n = B; a.sides = 2;
+  a.dst = q.eff; a.stat[0] = q.stat[0]; a.stat[1] = q.stat[1];
+  q.job_ready = true;
+  return VSLAM_OK;
+}
+// Between k_fast_box and k_emit, on their queue: the frame masks' fused pack / erode / apply, else the static words' apply, else nothing.
+static void mask_enqueue(vslam_ctx* c, hipStream_t st, const DevBuf& bs) {
+  vslam_ctx::DetMask& q = c->dmask;
+  const bool stat = q.stat[0] || q.stat[1];
+  if (q.job_ready) {
+    q.job.corner = bs.mask;
+    std::memcpy(q.job.active, bs.active, sizeof q.job.active);
+    mask_pack_enqueue(st, q.job);
+    q.job_ready = false;
+    q.last = 2 | (stat ? 1 : 0);
+    std::memcpy(q.last_active, bs.active, sizeof q.last_active);
+  } else if (stat) {
+    MaskApplyArgs a{};
+    a.stat[0] = q.stat[0]; a.stat[1] = q.stat[1]; a.corner = bs.mask; a.nw = c->cfg.c.rows * c->cfg.TX; a.n = c->B; a.sides = 2;
+    std::memcpy(a.active, bs.active, sizeof a.active);
+    hipLaunchKernelGGL(k_mask_apply, dim3(((a.nw + 1) / 2 + 255) / 256, 2, (a.n + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, st, a);
+    q.last = 1;
+    std::memcpy(q.last_active, bs.active, sizeof q.last_active);
+  } else q.last = 0;
+}
+VS_API int vslam_get_detection_mask(vslam_ctx* c, int s, int side, uint64_t* words) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (side < 0 || side > 1 || !words) return fail(c, VSLAM_ERR_INVALID, "vslam_get_detection_mask: bad side or null output");
+  const vslam_ctx::DetMask& q = c->dmask;
+  if (!q.last) return fail(c, VSLAM_ERR_STATE, "vslam_get_detection_mask: the last frame used no mask");
+  if (!((q.last_active[s >> 5] >> (s & 31)) & 1u)) return fail(c, VSLAM_ERR_STATE, "vslam_get_detection_mask: the stream was switched off during the last frame");
+  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols, TX = c->cfg.TX;
+  const size_t nw = (size_t)rows * TX;
+  const unsigned long long* from = (q.last & 2) ? q.eff + ((size_t)s * 2 + side) * nw : q.stat[side];
+  if (from) { HIP_TRY(c, hipMemcpy(words, from, nw * sizeof(uint64_t), hipMemcpyDeviceToHost)); return VSLAM_OK; }
+  for (int r = 0; r < rows; ++r)     // a static mask on the other side only: this one is all-keep
+    for (int t = 0; t < TX; ++t) words[(size_t)r * TX + t] = mask_cols_word(t, cols);
+  return VSLAM_OK;
+}
+
 VS_API int vslam_get_pose_guess(vslam_ctx* c, int s, double guess[12], double guess_previous[12]) {
   const int rc = check_stream(c, s);
   if (rc != VSLAM_OK) return rc;

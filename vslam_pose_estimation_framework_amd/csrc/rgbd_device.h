@@ -127,6 +127,7 @@ public:
     eq.have_frame = false;                                                   // and so does the equalisation switch
     col.have_frame = false;                                                  // and the colour format
     bl.have_frame = false;                                                   // and the depth image's bilateral filter
+    dmask.have_frame = false;                                                // and the detection mask
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
     return VSLAM_OK;
   }
@@ -387,6 +388,47 @@ public:
     return fetched(planes_to_host(image, eq.dst, 0, stream, p.rows, p.cols));
   }
 
+  // ---- the static detection mask (kernels_mask.h): opt-in, its own allocation, nothing launched while dmask.words is null.  One image,
+  // shared by every sequence of a batch; k_mask_apply ANDs its eroded packed words into the corner words between k_fast_box and k_emit of
+  // every attempt (enqueue_attempt), inside the captured launch sequence as well.
+  int set_detection_mask(const uint8_t* mask, int32_t row_stride, int32_t margin) {
+    if (pending) { err = "vslam_rgbd_set_detection_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (mask && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_detection_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
+    if (mask && row_stride < p.cols) { err = "vslam_rgbd_set_detection_mask: row stride smaller than image width"; return VSLAM_ERR_INVALID; }
+    if (!mask && !dmask.words) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q); (void)hipStreamSynchronize(q2);
+    dmask_free();
+    drop_graph();                  // a captured launch sequence holds the launch, or lacks it
+    if (!mask) return VSLAM_OK;
+    const int TX = ic->cfg.TX;
+    const size_t bytes = (size_t)(p.rows - 1) * row_stride + p.cols;
+    uint8_t* tmp = nullptr;
+    hipError_t e = hipMalloc((void**)&tmp, bytes);
+    if (e == hipSuccess) e = dmask.mem.alloc(&dmask.words, (size_t)p.rows * TX);
+    if (e == hipSuccess) e = hipMemcpy(tmp, mask, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      MaskPackArgs a{};
+      a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = p.rows; a.cols = p.cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
+      a.dst = dmask.words;
+      active_all(a.active, 1);
+      mask_pack_enqueue(q, a);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipStreamSynchronize(q);
+    }
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) { dmask_free(); return hip_fail(e, "vslam_rgbd_set_detection_mask"); }
+    return VSLAM_OK;
+  }
+  // the eroded packed keep-mask the last finished frame used: rows * TX words
+  int get_detection_mask(uint64_t* words) {
+    if (int rc = readable(0)) return rc;
+    if (!dmask.words || !dmask.have_frame) { err = "vslam_rgbd_get_detection_mask: no frame has run under a mask since vslam_rgbd_set_detection_mask / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    if (!words) { err = "vslam_rgbd_get_detection_mask: null output"; return VSLAM_ERR_INVALID; }
+    (void)hipSetDevice(ic->device);
+    return fetched(hipMemcpy(words, dmask.words, (size_t)p.rows * ic->cfg.TX * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+
   // ---- bilateral filtering of the depth image (kernels_bilateral.h): opt-in, its own allocations, nothing launched while bl.on is false.
   // The three kernels read this frame's depth image (d_depth: the upload or the undistorted image; else the caller's device images) and
   // write bl.depth, which the space map's kernels read instead: caller memory and d_depth (vslam_rgbd_get_undistorted) are never written.
@@ -490,7 +532,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; bl.have_frame = bl.on; }
+    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; bl.have_frame = bl.on; dmask.have_frame = dmask.words != nullptr; }
     return rc;
   }
 
@@ -578,6 +620,9 @@ private:
   // bilateral filtering of the depth image: off while bl.on is false.  depth: the filtered images [B][rows * cols] the space map reads;
   // args: what the three kernels get but for this frame's source (sizes, scales, taps, the range cells [B][4] and the tables [B][4098])
   struct Bilateral { bool on = false, have_frame = false; double sigma_color = 0, sigma_space = 0; uint16_t* depth = nullptr; BilateralArgs args; DeviceStore mem; } bl;
+  // the static detection mask: off while words is null; [rows][TX] eroded packed words
+  struct DetMask { unsigned long long* words = nullptr; bool have_frame = false; DeviceStore mem; } dmask;
+  void dmask_free() { dmask.mem.release(); dmask.words = nullptr; dmask.have_frame = false; }
   PrePlan pre;                   // this frame's routing through the three stages (route_frame): pre.color is its colour source
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
@@ -670,6 +715,7 @@ private:
     eq_free();
     col_free();
     bl_free();
+    dmask_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (q2) { (void)hipStreamDestroy(q2); q2 = nullptr; }
     if (ev_depth) { (void)hipEventDestroy(ev_depth); ev_depth = nullptr; }
@@ -690,6 +736,12 @@ private:
     if (again) hipLaunchKernelGGL(k_rgbd_save_features, dim3(B), dim3(1024), 0, q, d, b, rb);
     hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, q, d, b);
     const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
+    if (dmask.words) {             // the detection mask: the keep words into every sequence's corner words, ahead of the count
+      MaskApplyArgs ma{};
+      ma.stat[0] = dmask.words; ma.corner = b.mask; ma.nw = d.c.rows * d.TX; ma.n = B; ma.sides = 1;
+      std::memcpy(ma.active, b.active, sizeof ma.active);
+      hipLaunchKernelGGL(k_mask_apply, dim3(((ma.nw + 1) / 2 + 255) / 256, 1, (B + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, q, ma);
+    }
     hipLaunchKernelGGL(k_emit, dim3(B, 1), dim3(512), 0, q, d, b, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 2);
     const dim3 g3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, B);
     if (orb) {

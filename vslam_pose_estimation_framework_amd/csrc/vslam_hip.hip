@@ -25,6 +25,7 @@
 #include "kernels_map.h"
 #include "kernels_obs.h"
 #include "kernels_map_color.h"
+#include "kernels_mask.h"      // detection masks: pack + erode, apply between k_fast_box and k_emit
 
 #define VS_API extern "C" __attribute__((visibility("default")))
 
