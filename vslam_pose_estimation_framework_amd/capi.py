@@ -982,13 +982,23 @@ class CApi(object):
                                            _p(ang, C.c_float)))
         return resp, ang
 
-    def orb_detect(self, image, nfeatures=5000, scale_factor=1.2, nlevels=8, edge_threshold=31, patch_size=31, fast_threshold=20, cap=20000):
-        """cv::ORB::detect (HARRIS_SCORE): rows of (x, y, size, angle, response, octave)."""
-        img = np.ascontiguousarray(image, np.uint8)
+    def orb_detect(self, image, nfeatures=5000, scale_factor=1.2, nlevels=8, edge_threshold=31, patch_size=31, fast_threshold=20, cap=20000,
+                   row_stride=None):
+        """cv::ORB::detect (HARRIS_SCORE): rows of (x, y, size, angle, response, octave).  row_stride: the image is a [rows, cols] uint8
+        view into padded rows (row stride row_stride bytes, unit column stride) and is passed where it lies, as the RGB-D tracker passes
+        a detector region; default: a dense copy, its own width."""
+        if row_stride is None:
+            img = np.ascontiguousarray(image, np.uint8)
+            stride = img.shape[1]
+        else:
+            img, stride = np.asarray(image), int(row_stride)
+            if img.dtype != np.uint8 or img.ndim != 2 or stride < img.shape[1] or (img.shape[1] > 1 and img.strides[1] != 1) or \
+                    (img.shape[0] > 1 and img.strides[0] != stride):
+                raise ValueError("orb_detect: with row_stride the image must be a [rows, cols] uint8 view whose rows lie row_stride bytes apart")
         out = np.zeros((cap, 6), np.float32)
         n = C.c_int32()
         self.check(self.fn("orb_detect")(*self._ctx_args(), _p(img, C.c_uint8), C.c_int32(img.shape[0]), C.c_int32(img.shape[1]),
-                                         C.c_int32(img.shape[1]), C.c_int32(int(nfeatures)), C.c_float(float(scale_factor)), C.c_int32(int(nlevels)),
+                                         C.c_int32(stride), C.c_int32(int(nfeatures)), C.c_float(float(scale_factor)), C.c_int32(int(nlevels)),
                                          C.c_int32(int(edge_threshold)), C.c_int32(int(patch_size)), C.c_int32(int(fast_threshold)),
                                          C.c_int32(cap), C.byref(n), _p(out, C.c_float)))
         return out[:n.value].copy()
