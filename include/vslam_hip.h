@@ -353,8 +353,23 @@ int vslam_gray_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols
  * vslam_mask_pack_u8: the pack kernel stand-alone on one host image of any size up to 32767 x 32767 (any alignment): `words` receives
  *   rows * ((cols + 63) / 64) words.  rows or cols 0: VSLAM_OK, nothing written.  VSLAM_ERR_INVALID, nothing written: null src / words, a
  *   negative size, a stride below cols, a margin outside 0 .. 64; the context stays usable.
- * Not built: frame masks in RGB-D mode, masks in the shim (the reference's generator has no mask argument), masks for the stand-alone
- * vslam_fast_detect / vslam_orb_detect entries. */
+ * The rectification maps' validity mask (k_map_valid in csrc/kernels_mask.h).  k_rectify fills every tap outside the raw
+ * image with 0, and FAST fires along the seam between picture and fill.  An output pixel is VALID iff every tap of non-zero weight of
+ * its map entry (x0, y0), ax = a & 31, ay = (a >> 5) & 31 lies inside the raw image:
+ *   x0 >= 0 and x0 + (ax > 0) <= raw_cols - 1 and y0 >= 0 and y0 + (ay > 0) <= raw_rows - 1
+ * (integers; not defined by the remap's result: a missing tap of weight <= 2/1024 rounds away).  Packed and eroded like any mask.
+ * vslam_set_rectification_mask: on != 0: the validity words of both sides, computed once from the maps the context holds, become part
+ *   of the context-wide keep-mask: static mask AND validity, per side, wherever the static mask applies (both launch sequences, the
+ *   stage entries, composed with frame masks); vslam_get_detection_mask returns the words including them, with validity as the only
+ *   mask as well.  New maps (vslam_set_rectification) recompute the words, switching rectification off switches this off; it survives
+ *   vslam_reset.  VSLAM_ERR_STATE without rectification maps or inside a frame, VSLAM_ERR_INVALID for a margin outside 0 .. 64; nothing
+ *   is changed by a refused call.  While off nothing is allocated or launched.  Synchronises the context.
+ * vslam_get_rectification_mask: the switch and its margin (0, 0 while off).
+ * vslam_map_validity_mask: the kernel stand-alone on one dense host map of rows x cols entries (map_xy [rows][cols][2], map_a [rows]
+ *   [cols]) over a raw image of raw_rows x raw_cols: `words` receives rows * ((cols + 63) / 64) words.  VSLAM_ERR_INVALID, nothing
+ *   written: a size outside 1 .. 32767, a margin outside 0 .. 64, a null pointer, a map_a value >= 1024; the context stays usable.
+ * Not built: masks in the shim (the reference's generator has no mask argument), masks for the stand-alone vslam_fast_detect /
+ * vslam_orb_detect entries, validity masks for fisheye maps (the maps themselves are refused). */
 #define VSLAM_MASK_MAX_MARGIN 64
 int vslam_set_detection_mask(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t row_stride_bytes, int32_t margin);
 int vslam_set_frame_masks(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t row_stride_bytes, size_t image_stride_bytes,
@@ -362,6 +377,10 @@ int vslam_set_frame_masks(vslam_ctx* ctx, const uint8_t* left, const uint8_t* ri
 int vslam_get_detection_mask(vslam_ctx* ctx, int stream, int side, uint64_t* words);
 int vslam_mask_pack_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride_bytes, int32_t margin,
                        uint64_t* words);
+int vslam_set_rectification_mask(vslam_ctx* ctx, int on, int32_t margin);
+int vslam_get_rectification_mask(vslam_ctx* ctx, int* on, int32_t* margin);
+int vslam_map_validity_mask(vslam_ctx* ctx, const int16_t* map_xy, const uint16_t* map_a, int32_t rows, int32_t cols, int32_t raw_rows,
+                            int32_t raw_cols, int32_t margin, uint64_t* words);
 /* Block until all queued work of the context is done; returns the sticky HIP error state (VSLAM_ERR_HIP once a runtime
  * call has failed, else VSLAM_OK; capacity overflows are reported in vslam_frame_info.error_flags, see VSLAM_ERR_CAPACITY). */
 int vslam_synchronize(vslam_ctx* ctx);
@@ -958,19 +977,46 @@ int vslam_rgbd_get_clahe_luts(vslam_rgbd* t, int32_t stream, uint8_t* luts);
 int vslam_rgbd_set_bilateral(vslam_rgbd* t, int on, double sigma_color, double sigma_space);
 int vslam_rgbd_get_bilateral(vslam_rgbd* t, int* on, double* sigma_color, double* sigma_space);
 int vslam_rgbd_get_filtered_depth(vslam_rgbd* t, int32_t stream, uint16_t* depth, float* lut4098);
-/* The static detection mask in this mode (opt-in; the definition above vslam_set_detection_mask; csrc/kernels_mask.h): one
+/* Detection masks in this mode (opt-in; the definition above vslam_set_detection_mask; csrc/kernels_mask.h): one
  * 8-bit image at the processed size (the undistorted image's coordinates while undistortion is set), shared by every sequence of a batch.
  * Its eroded packed words are ANDed into the corner words between k_fast_box and k_emit of EVERY attempt of a frame, re-registration
- * attempts included, inside the captured launch sequence as well; nothing is launched while it is off.  There are no per-frame masks in
- * this mode.  n_detected_left of the frame report is the masked count.
+ * attempts included, inside the captured launch sequence as well; nothing is launched while it is off.  n_detected_left of the frame
+ * report is the masked count.  The effective keep-mask of sequence s is (static mask AND undistortion validity AND frame mask of s),
+ * each eroded by its own margin, a missing one all-keep.
  * vslam_rgbd_set_detection_mask: host pointer, copied and packed before the call returns; NULL switches the mask off and frees it.  The
  *   mask survives vslam_rgbd_reset.  VSLAM_ERR_STATE with a frame in flight (between submit and wait), or on the host-driven loop
  *   (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature; VSLAM_ERR_INVALID (nothing changed) for a stride below cols
  *   or a margin outside 0 .. 64.
  * vslam_rgbd_get_detection_mask: the packed keep-mask (rows * ((cols + 63) / 64) words) the last finished frame used; VSLAM_ERR_STATE
- *   when off, before a frame, after vslam_rgbd_reset, or with a frame in flight. */
+ *   when off, before a frame, after vslam_rgbd_reset, or with a frame in flight.  These are the context-wide words: the static mask
+ *   AND the undistortion maps' validity (below); with validity as the only mask the call succeeds.
+ * vslam_rgbd_set_frame_masks: one mask per sequence of the batch for the NEXT submit only (a frame without a set behaves as if the call
+ *   did not exist): sequence s at masks + s * image_stride_bytes; NULL cancels a pending set.  "The next submit" is the next one that
+ *   is accepted: a submit refused for its arguments or its state (a frame in flight, a failed tracker) changes nothing and the set goes
+ *   on waiting; a submit that fails after it was accepted (VSLAM_ERR_HIP) drops the set with its frame.  That submit copies host masks
+ *   (on_device 0) on the frame's queue; device masks are read in place by its one k_mask_pack launch and never written.  The launch
+ *   runs on the tracker's own queue and waits for no other stream: whatever wrote the device masks must have finished before the
+ *   submit call (synchronise the producing stream first, as for the images of vslam_rgbd_submit_batch_device), and they must stay as
+ *   they are until that launch has run: vslam_rgbd_wait is the bound.  The launch packs and erodes every sequence's mask and ANDs the
+ *   context-wide words in, into effective words [B][rows][TX], ahead of the first detection; k_mask_apply ANDs a sequence's words into
+ *   its corner words in every attempt of that frame.  Under VSLAM_RGBD_GRAPH=1 the pack launch stays outside the captured sequence,
+ *   which is captured again when a frame with masks follows one without, or the reverse.  VSLAM_ERR_STATE with a frame in flight or on
+ *   the host-driven loop; VSLAM_ERR_INVALID for a stride below cols, a margin outside 0 .. 64, or, with more than one sequence, an
+ *   image stride smaller than one mask.  No refusal is sticky, and a refused call changes nothing.  vslam_rgbd_reset drops a pending set.
+ * vslam_rgbd_get_frame_detection_mask: the effective words the last finished frame of `stream` used (the context-wide words when it had
+ *   no frame mask); VSLAM_ERR_STATE when that frame used no mask of any kind, before a frame, after vslam_rgbd_reset, or with a frame
+ *   in flight.
+ * vslam_rgbd_set_undistortion_mask / vslam_rgbd_get_undistortion_mask: the undistortion maps' validity as part of the context-wide
+ *   keep-mask, as vslam_set_rectification_mask defines it: computed once per call and per new maps (vslam_rgbd_set_undistortion), off
+ *   with the maps, kept over vslam_rgbd_reset.  VSLAM_ERR_STATE without maps, with a frame in flight, or on the host-driven loop;
+ *   VSLAM_ERR_INVALID for a margin outside 0 .. 64. */
 int vslam_rgbd_set_detection_mask(vslam_rgbd* t, const uint8_t* mask, int32_t row_stride_bytes, int32_t margin);
 int vslam_rgbd_get_detection_mask(vslam_rgbd* t, uint64_t* words);
+int vslam_rgbd_set_frame_masks(vslam_rgbd* t, const uint8_t* masks, int32_t row_stride_bytes, size_t image_stride_bytes, int32_t margin,
+                               int on_device);
+int vslam_rgbd_get_frame_detection_mask(vslam_rgbd* t, int32_t stream, uint64_t* words);
+int vslam_rgbd_set_undistortion_mask(vslam_rgbd* t, int on, int32_t margin);
+int vslam_rgbd_get_undistortion_mask(vslam_rgbd* t, int* on, int32_t* margin);
 /* Colour input in this mode (opt-in; the definition and the VSLAM_PIXEL_* formats above vslam_set_color_input): while the format is not
  * VSLAM_PIXEL_GRAY8 the intensity image of every process / submit / batch entry, host or device, is interleaved colour at the size the
  * tracker otherwise expects; its row and stream strides are in BYTES (row stride >= channels * cols).  The depth image is untouched.

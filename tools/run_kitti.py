@@ -30,6 +30,10 @@ either side of the hot path; executables/test_stereo_frontend.cpp:106-111,256-31
                               a folder that mirrors the two image folders file name for file name (moving objects from a segmentation
                               network; a missing file: no mask for that frame).  Also with --chunks (every chunk its own frame's mask),
                               --rectify, --color, --equalize / --clahe, --map, --observations
+    python tools/run_kitti.py <sequence dir> --rectify --mask-invalid [N]   with --rectify: no keypoints on rectified pixels whose source lies partly
+                              outside the raw image (the seam between picture and black fill); the masks of both sides are computed from
+                              the rectification maps on the GPU (vslam_set_rectification_mask), N = 0 .. 64 widens them.  Also with --chunks,
+                              --mask, --frame-masks, --map, --observations
 
 The sequence runs in exact mode (one stream, whole sequence, bit-for-bit the reference port's arithmetic); images are
 uploaded frame by frame through vslam_process_host.  With --gt (KITTI 3x4 rows) the ATE-RMSE after rigid alignment is
@@ -51,7 +55,7 @@ MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a
 
 
 def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None):
+                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None, mask_invalid=None):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -62,6 +66,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
     api.create(cfg, device, len(plan))
     if rect is not None:
         api.set_rectification(rect)
+    if mask_invalid is not None:
+        api.set_rectification_mask(True, mask_invalid)
     if equalize:
         api.set_equalization(True)
     if clahe is not None:
@@ -111,8 +117,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
         chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8), map_color=False,
-        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, mask=None, mask_margin=0, frame_masks=None):
-    check_mask_args(mask, mask_margin, frame_masks, SystemExit)
+        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, mask=None, mask_margin=0, frame_masks=None, mask_invalid=None):
+    check_mask_args(mask, mask_margin, frame_masks, SystemExit, mask_invalid, rectify)
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -142,6 +148,10 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         rectify_mod.apply_to_config(cfg, rect)
         log("rectifying on the GPU: raw %dx%d -> %dx%d, f %.3f px, baseline %.4f m" % (
             rect.raw_rows, rect.raw_cols, rect.rows, rect.cols, rect.P1[0, 0], -rect.P2[0, 3] / rect.P1[0, 0]))
+        if mask_invalid is not None:
+            log("validity masks from the rectification maps on the GPU: %.1f / %.1f %% of the left / right pixels have every tap inside the raw image, margin %d px" % (
+                100.0 * float(rectify_mod.validity(rect.map_xy_left, rect.map_a_left, rect.raw_rows, rect.raw_cols).mean()),
+                100.0 * float(rectify_mod.validity(rect.map_xy_right, rect.map_a_right, rect.raw_rows, rect.raw_cols).mean()), mask_invalid))
     elif euroc:
         cal = seq.calibration()       # a rectified export may carry its P0 / P1; otherwise the EuRoC values of the default config
         if cal is not None:
@@ -178,7 +188,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
                                                 equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles, map_color=map_color,
-                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks)
+                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks, mask_invalid=mask_invalid)
         tracking = None
         dead_reckoned = None
     else:
@@ -186,6 +196,8 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         api.create(cfg, device, 1)
         if rect is not None:
             api.set_rectification(rect)
+        if mask_invalid is not None:
+            api.set_rectification_mask(True, mask_invalid)
         if equalize:
             api.set_equalization(True)
         if clahe is not None:
@@ -324,7 +336,7 @@ class DetectionMasks(object):
             api.set_frame_masks(sides[0], sides[1], self.margin)
 
 
-def check_mask_args(mask, mask_margin, frame_masks, error):
+def check_mask_args(mask, mask_margin, frame_masks, error, mask_invalid=None, rectify=True):
     """What --mask, --mask-margin and --frame-masks allow together (tools/run_rgbd.py takes the first two)."""
     if mask_margin < 0 or mask_margin > 64:
         raise error("--mask-margin: a whole number of pixels in 0 .. 64")
@@ -339,6 +351,10 @@ def check_mask_args(mask, mask_margin, frame_masks, error):
                 raise error("--mask: no such file: %s" % p)
     if frame_masks is not None and not os.path.isdir(frame_masks):
         raise error("--frame-masks: no such folder: %s" % frame_masks)
+    if mask_invalid is not None and not rectify:
+        raise error("--mask-invalid needs --rectify: the validity masks come from the rectification maps")
+    if mask_invalid is not None and (mask_invalid < 0 or mask_invalid > 64):
+        raise error("--mask-invalid: a whole number of pixels in 0 .. 64")
 
 
 MOTION_MODELS = {"constant-velocity": 0, "none": 1, "odometry": 2}     # enum vslam_motion_model
@@ -401,11 +417,13 @@ def parse_args(argv=None):
     ap.add_argument("--mask", default=None, metavar="LEFT.png[,RIGHT.png]", help="detection masks for the whole run: 8-bit PNGs at the processed size, "
                     "zero = no keypoints on that pixel (the bonnet, overlays, vignetted corners); one file masks the left image only")
     ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask / --frame-masks by N pixels (0 .. 64)")
+    ap.add_argument("--mask-invalid", nargs="?", type=int, const=0, default=None, metavar="N", help="with --rectify: no keypoints on pixels whose source lies "
+                    "partly outside the raw image (the seam between picture and black fill), computed from the maps on the GPU, both sides; N widens it (0 .. 64)")
     ap.add_argument("--frame-masks", default=None, metavar="DIR", help="per-frame detection masks: a folder that mirrors the sequence's two image folders "
                     "file name for file name; a missing file means no mask for that frame")
     a = ap.parse_args(argv)
     try:
-        check_mask_args(a.mask, a.mask_margin, a.frame_masks, ValueError)
+        check_mask_args(a.mask, a.mask_margin, a.frame_masks, ValueError, a.mask_invalid, a.rectify)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
@@ -421,7 +439,7 @@ def main(argv=None):
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
         rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
         map_color=a.map_color, motion_model=a.motion_model, odometry=a.odometry, dead_reckoning_limit=a.dead_reckoning_limit,
-        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks)
+        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ reference's TUM format (WorldMap::writeTrajectoryTUM, world_map.cpp:222-258).
                              [--depth-unit 0.0002] [--out traj.txt] [--max-frames N] [--descriptor ORB|BRIEF] [--detector FAST|ORB]
                              [--map map.ply] [--observations bundle.npz] [--undistort [k1,k2,p1,p2[,k3]]] [--equalize | -eh] [--color [--map-color]]
                              [--clahe [CLIP]] [--clahe-tiles X,Y] [--motion-model constant-velocity|none|odometry] [--odometry FILE]
-                             [--dead-reckoning-limit N] [--bilateral [SIGMA_COLOR,SIGMA_SPACE]] [--mask MASK.png [--mask-margin N]]
+                             [--dead-reckoning-limit N] [--bilateral [SIGMA_COLOR,SIGMA_SPACE]] [--mask MASK.png] [--frame-masks DIR] [--mask-margin N] [--mask-invalid [N]]
 
 --config picks the values of configurations/configuration_{icl,tum,xtion}.yaml the path reads (table below: detector grid and thresholds,
 tracking windows and descriptor distances, depth limits, bin size, triangulation of points without depth, landmark / aligner settings); the
@@ -36,7 +36,13 @@ row (without it one failed frame means dead reckoning for good: DESIGN.md 6j).  
 loops.
 --bilateral [SIGMA_COLOR,SIGMA_SPACE] smooths every depth image with the reference's bilateral filter on the GPU ahead of the space map
 (vslam_rgbd_set_bilateral: enable_bilateral_filtering, cv::bilateralFilter on the depth in metres; 2,2 without a value), behind --undistort:
-noisy depth streams.  The intensity image is untouched, so it combines with --color, --equalize and --clahe.  Device-resident loop only."""
+noisy depth streams.  The intensity image is untouched, so it combines with --color, --equalize and --clahe.  Device-resident loop only.
+--frame-masks DIR gives every frame a mask of its own (vslam_rgbd_set_frame_masks): a folder of 8-bit PNGs at the processed size named like
+the frames' files under rgb/; a missing file means no mask for that frame.  --mask-margin applies to --mask and --frame-masks.
+--mask-invalid [N] (with --undistort) keeps keypoints off the pixels whose source lies partly outside the raw frame, the seam between picture
+and black fill (vslam_rgbd_set_undistortion_mask: computed from the maps on the GPU); N = 0 .. 64 widens it.  Both compose with --mask,
+--map and --observations.  Device-resident loop only.
+"""
 import argparse
 import os
 import sys
@@ -119,8 +125,9 @@ def distortion_of(undistort, intrinsics):
 
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
         gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None, mask=None, mask_margin=0):
-    check_mask_args(mask, mask_margin, SystemExit)
+        map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None, mask=None, mask_margin=0,
+        frame_masks=None, mask_invalid=None):
+    check_mask_args(mask, mask_margin, SystemExit, frame_masks, mask_invalid, undistort)
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -182,6 +189,15 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
                 raise SystemExit("--mask: %s is %dx%d, the detector works on %dx%d images" % (mask, mk.shape[0], mk.shape[1], cfg.rows, cfg.cols))
             tr.set_detection_mask(mk, mask_margin)
             log("detection mask: %s, margin %d px (no keypoints on its zero pixels, every re-registration attempt included)" % (mask, mask_margin))
+        if mask_invalid is not None:
+            if dist is None:
+                raise SystemExit("--mask-invalid: nothing is undistorted, there are no maps to take a validity mask from")
+            tr.set_undistortion_mask(True, mask_invalid)
+            log("validity mask from the undistortion maps on the GPU: %.1f %% of the pixels have every tap inside the raw frame, margin %d px" % (
+                100.0 * float(rectify.validity(und.map_xy, und.map_a, und.raw_rows, und.raw_cols).mean()), mask_invalid))
+        if frame_masks:
+            log("frame masks: %s, margin %d px (a PNG named like the frame's rgb file; a frame without one has none)" % (frame_masks, mask_margin))
+        masked_frames = 0
         tr.set_motion_model(MOTION_MODELS[motion_model], dead_reckoning_limit)
         if want_map:
             tr.enable_map(MAP_ENTRIES_PER_FRAME * n)
@@ -202,6 +218,14 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
                     gray, depth = seq.frame(k)
             if guesses is not None and own[k]:
                 tr.set_pose_guess(guesses[k])
+            if frame_masks:
+                mpath = os.path.join(frame_masks, os.path.basename(seq.rgb[k]))
+                if os.path.isfile(mpath):
+                    mk = io_formats.read_png_gray8(mpath)
+                    if mk.shape != (int(cfg.rows), int(cfg.cols)):
+                        raise SystemExit("--frame-masks: %s is %dx%d, the detector works on %dx%d images" % (mpath, mk.shape[0], mk.shape[1], cfg.rows, cfg.cols))
+                    tr.set_frame_mask(mk, mask_margin)
+                    masked_frames += 1
             fi, n_temp = tr.process(gray, depth)
             dead_reckoned += int(motion_model == "odometry" and fi.fallback == 1)
             poses.append(np.array(fi.camera_left_to_world))
@@ -222,6 +246,9 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     poses = np.array(poses).reshape(-1, 3, 4)
     log("%d frames in %.2f s (%.1f frames/s incl. PNG decode and upload), error flags %d" % (n, dt, n / dt, flags))
     result = {"frames": n, "seconds": dt, "error_flags": flags, "poses": poses, "times": seq.times[:n], "tracking_frames": tracking}
+    if frame_masks:
+        result["masked_frames"] = masked_frames
+        log("%d of %d frames had a mask of their own" % (masked_frames, n))
     if motion_model == "odometry":
         result["dead_reckoned_frames"] = dead_reckoned     # frames whose pose was taken from the odometry
         if dead_reckoned:
@@ -331,10 +358,14 @@ def parse_args(argv=None):
                     "whose pose was taken from the odometry (0: never)")
     ap.add_argument("--mask", default=None, metavar="MASK.png", help="detection mask for the whole run: an 8-bit PNG at the processed size (the undistorted "
                     "one under --undistort), zero = no keypoints on that pixel (the robot's own body, overlays, vignetted corners)")
-    ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask by N pixels (0 .. 64)")
+    ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask and --frame-masks by N pixels (0 .. 64)")
+    ap.add_argument("--frame-masks", default=None, metavar="DIR", help="a mask per frame (a segmentation network's output): a folder of 8-bit PNGs at the "
+                    "processed size, named like the frames' files under rgb/; a frame without a file has no mask of its own")
+    ap.add_argument("--mask-invalid", nargs="?", type=int, const=0, default=None, metavar="N", help="with --undistort: no keypoints on pixels whose source "
+                    "lies partly outside the raw frame (the seam between picture and black fill), computed from the maps on the GPU; N widens it (0 .. 64)")
     a = ap.parse_args(argv)
     try:
-        check_mask_args(a.mask, a.mask_margin, ValueError)
+        check_mask_args(a.mask, a.mask_margin, ValueError, a.frame_masks, a.mask_invalid, a.undistort)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
@@ -345,14 +376,20 @@ def parse_args(argv=None):
     return a
 
 
-def check_mask_args(mask, mask_margin, error):
-    """What --mask and --mask-margin allow together."""
+def check_mask_args(mask, mask_margin, error, frame_masks=None, mask_invalid=None, undistort=None):
+    """What --mask, --frame-masks, --mask-margin and --mask-invalid allow together."""
     if mask_margin < 0 or mask_margin > 64:
         raise error("--mask-margin: a whole number of pixels in 0 .. 64")
-    if mask_margin and not mask:
-        raise error("--mask-margin needs --mask")
+    if mask_margin and not mask and not frame_masks:
+        raise error("--mask-margin needs --mask or --frame-masks")
     if mask is not None and not os.path.isfile(mask):
         raise error("--mask: no such file: %s" % mask)
+    if frame_masks is not None and not os.path.isdir(frame_masks):
+        raise error("--frame-masks: no such folder: %s" % frame_masks)
+    if mask_invalid is not None and undistort is None:
+        raise error("--mask-invalid needs --undistort: the validity mask comes from the undistortion maps")
+    if mask_invalid is not None and (mask_invalid < 0 or mask_invalid > 64):
+        raise error("--mask-invalid: a whole number of pixels in 0 .. 64")
 
 
 def main(argv=None):
@@ -360,7 +397,7 @@ def main(argv=None):
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
         map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles, motion_model=a.motion_model, odometry=a.odometry,
         dead_reckoning_limit=a.dead_reckoning_limit,
-        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin)
+        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid)
 
 
 if __name__ == "__main__":

@@ -272,6 +272,27 @@ class CApi(object):
                                                 _p(xr, C.c_int16), _p(ar, C.c_uint16)))
         self.rect = rect
 
+    def set_rectification_mask(self, on=True, margin=0):
+        """The rectification maps' validity (rectify.validity, eroded by margin) as part of the context-wide keep-mask of both sides."""
+        self.check(self.fn("set_rectification_mask")(self.ctx, C.c_int(1 if on else 0), C.c_int32(int(margin))))
+
+    def rectification_mask(self):
+        """(on, margin) in force."""
+        on, m = C.c_int(), C.c_int32()
+        self.check(self.fn("get_rectification_mask")(self.ctx, C.byref(on), C.byref(m)))
+        return bool(on.value), m.value
+
+    def map_validity_mask(self, map_xy, map_a, raw_rows, raw_cols, margin=0):
+        """vslam_map_validity_mask: the eroded packed validity words of one remap map -> uint64 [rows, (cols + 63) // 64]."""
+        mxy = np.ascontiguousarray(map_xy, np.int16)
+        ma = np.ascontiguousarray(map_a, np.uint16)
+        assert mxy.shape[:2] == ma.shape and mxy.shape[2] == 2
+        rows, cols = ma.shape
+        w = np.zeros((rows, (cols + 63) // 64), np.uint64)
+        self.check(self.fn("map_validity_mask")(*self._ctx_args(), _p(mxy, C.c_int16), _p(ma, C.c_uint16), C.c_int32(rows), C.c_int32(cols),
+                                                C.c_int32(int(raw_rows)), C.c_int32(int(raw_cols)), C.c_int32(int(margin)), _p(w, C.c_uint64)))
+        return w
+
     def rectified_images(self, stream=0):
         """The rectified pair the last submitted frame of `stream` was processed on."""
         rows, cols = int(self.cfg.rows), int(self.cfg.cols)
@@ -1228,9 +1249,57 @@ class _RgbdMaskApi(object):
         self._check(self.lib.vslam_rgbd_set_detection_mask(self.h, _p(m, C.c_uint8), C.c_int32(m.shape[1]), C.c_int32(int(margin))))
 
     def detection_mask(self):
-        """The packed keep-mask the last finished frame used: uint64 [rows, (cols + 63) // 64] (mask.unpack)."""
+        """The context-wide packed keep-mask (static mask AND undistortion validity) the last finished frame used: uint64 [rows,
+        (cols + 63) // 64] (mask.unpack)."""
         w = np.zeros((int(self.cfg.rows), (int(self.cfg.cols) + 63) // 64), np.uint64)
         self._check(self.lib.vslam_rgbd_get_detection_mask(self.h, _p(w, C.c_uint64)))
+        return w
+
+    def set_undistortion_mask(self, on=True, margin=0):
+        """The undistortion maps' validity (rectify.validity, eroded by margin) as part of the context-wide keep-mask."""
+        self._check(self.lib.vslam_rgbd_set_undistortion_mask(self.h, C.c_int(1 if on else 0), C.c_int32(int(margin))))
+
+    def undistortion_mask(self):
+        """(on, margin) in force."""
+        on, m = C.c_int(), C.c_int32()
+        self._check(self.lib.vslam_rgbd_get_undistortion_mask(self.h, C.byref(on), C.byref(m)))
+        return bool(on.value), m.value
+
+    def set_frame_masks(self, masks=None, margin=0):
+        """The next frame's masks, one per sequence: uint8 [n_streams, rows, stride] (or [rows, stride] with one sequence), a numpy array
+        (host, copied by the next submit) or a torch device tensor (read in place by that submit's pack launch; the caller keeps it as it
+        is until wait() has returned).  None cancels a pending set."""
+        n = int(getattr(self, "n", 1))
+        if masks is None:
+            self._check(self.lib.vslam_rgbd_set_frame_masks(self.h, None, C.c_int32(0), C.c_size_t(0), C.c_int32(0), C.c_int(0)))
+            self._frame_masks_alive = None
+            return
+        if hasattr(masks, "data_ptr"):
+            if str(masks.dtype) != "torch.uint8" or masks.stride(-1) != 1:
+                raise ValueError("set_frame_masks: a uint8 tensor with unit column stride is required")
+            shape, strides, addr, dev = tuple(masks.shape), tuple(masks.stride()), masks.data_ptr(), bool(masks.is_cuda)
+        else:
+            a = np.asarray(masks)
+            if a.dtype != np.uint8 or a.ndim < 2 or (a.shape[-1] > 1 and a.strides[-1] != 1) or a.strides[-2] < a.shape[-1]:
+                a = np.ascontiguousarray(masks, np.uint8)
+            masks, shape, strides, addr, dev = a, a.shape, a.strides, a.ctypes.data, False
+        if len(shape) == 2:
+            shape, strides = (1,) + tuple(shape), (0,) + tuple(strides)
+        if len(shape) != 3 or shape[0] != n or shape[1] != self.cfg.rows or shape[2] < self.cfg.cols:
+            raise ValueError("set_frame_masks: expected %d x %d x >= %d, got %s" % (n, self.cfg.rows, self.cfg.cols, tuple(shape)))
+        self._check(self.lib.vslam_rgbd_set_frame_masks(self.h, C.c_void_p(addr), C.c_int32(int(strides[1])), C.c_size_t(int(strides[0])),
+                                                        C.c_int32(int(margin)), C.c_int(1 if dev else 0)))
+        self._frame_masks_alive = masks
+
+    def set_frame_mask(self, mask, margin=0):
+        """set_frame_masks for a tracker of one sequence."""
+        self.set_frame_masks(mask, margin)
+
+    def frame_detection_mask(self, stream=0):
+        """The effective packed keep-mask (static AND validity AND frame mask) the last finished frame of `stream` used: uint64 [rows,
+        (cols + 63) // 64] (mask.unpack)."""
+        w = np.zeros((int(self.cfg.rows), (int(self.cfg.cols) + 63) // 64), np.uint64)
+        self._check(self.lib.vslam_rgbd_get_frame_detection_mask(self.h, C.c_int32(int(stream)), _p(w, C.c_uint64)))
         return w
 
 

@@ -112,7 +112,12 @@ struct vslam_ctx {
   // caller's pointers (null: that side has none), read in place on the device, copied into `slab` at the caller's strides when they are
   // host memory; eff [B][2][rows][TX]: the effective words of the last frame that had frame masks.  last: what the last frame used (bit 0
   // static, bit 1 frame masks) and on which streams (last_active).  Nothing of this is allocated, launched or copied while no mask is set.
-  struct DetMask { unsigned long long* stat[2] = {nullptr, nullptr}; DeviceStore stat_mem;
+  // The context-wide keep words are the user's static mask AND the rectification maps' validity (vslam_set_rectification_mask): user[side]
+  // and valid[side] hold either alone, stat[side] points at the one there is, or at comb[side] = both ANDed (mask_static_sync).
+  struct DetMask { unsigned long long* stat[2] = {nullptr, nullptr};
+                   unsigned long long* user[2] = {nullptr, nullptr}; DeviceStore user_mem;
+                   bool valid_on = false; int valid_margin = 0; unsigned long long* valid[2] = {nullptr, nullptr}; DeviceStore valid_mem;
+                   unsigned long long* comb[2] = {nullptr, nullptr}; DeviceStore comb_mem;
                    bool pending = false, on_device = false; const uint8_t* src[2] = {nullptr, nullptr}; int32_t row_stride = 0; size_t image_stride = 0; int margin = 0;
                    uint8_t* slab[2] = {nullptr, nullptr}; size_t slab_bytes = 0; DeviceStore slab_mem;
                    unsigned long long* eff = nullptr; DeviceStore eff_mem;
@@ -563,7 +568,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
   for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem}) m->release();     // the input stages' stores
-  for (DeviceStore* m : {&c->dmask.stat_mem, &c->dmask.slab_mem, &c->dmask.eff_mem}) m->release();    // detection masks
+  for (DeviceStore* m : {&c->dmask.user_mem, &c->dmask.valid_mem, &c->dmask.comb_mem, &c->dmask.slab_mem, &c->dmask.eff_mem}) m->release();    // detection masks
   c->guess.mem.release();
   for (int q = 0; q < 2; ++q) { if (c->guess.pin[q]) (void)hipHostFree(c->guess.pin[q]); if (c->guess.pin_ev[q]) (void)hipEventDestroy(c->guess.pin_ev[q]); }
   map_free(c);

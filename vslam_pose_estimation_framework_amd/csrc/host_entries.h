@@ -953,6 +953,32 @@ VS_API int vslam_mask_pack_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, in
   return k.finish();
 }
 
+// ---- the eroded packed validity words of one host remap map (kernels_mask.h, k_map_valid) -------------------------------
+VS_API int vslam_map_validity_mask(vslam_ctx* c, const int16_t* map_xy, const uint16_t* map_a, int32_t rows, int32_t cols, int32_t raw_rows,
+                                   int32_t raw_cols, int32_t margin, uint64_t* words) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 1 || cols < 1 || rows > 32767 || cols > 32767 || raw_rows < 1 || raw_cols < 1 || raw_rows > 32767 || raw_cols > 32767)
+    return fail(c, VSLAM_ERR_INVALID, "map_validity_mask: sizes outside 1 .. 32767");
+  if (margin < 0 || margin > VS_MASK_MAX_MARGIN) return fail(c, VSLAM_ERR_INVALID, "map_validity_mask: margin outside 0 .. 64");
+  if (!map_xy || !map_a || !words) return fail(c, VSLAM_ERR_INVALID, "map_validity_mask: null argument");
+  if (!rect_maps_ok(map_a, (size_t)rows * cols)) return fail(c, VSLAM_ERR_INVALID, "map_validity_mask: interpolation table index >= 1024");
+  Call k(c, c->stream);
+  RemapMaps m;
+  m.rows = rows; m.cols = cols; m.raw_rows = raw_rows; m.raw_cols = raw_cols;
+  m.stride = (cols + 3) & ~3;
+  std::vector<int16_t> pxy;
+  std::vector<uint16_t> pa;
+  rect_pad_maps(map_xy, map_a, rows, cols, m.stride, pxy, pa);
+  m.xy[0] = k.up(pxy.data(), pxy.size());
+  m.a[0] = k.up(pa.data(), pa.size());
+  const size_t nw = (size_t)rows * ((cols + 63) / 64);
+  unsigned long long* dw = k.dev<unsigned long long>(nw);
+  if (k.ok()) map_valid_enqueue(c->stream, m, 1, margin, dw);
+  k.launched();
+  k.down(reinterpret_cast<unsigned long long*>(words), dw, nw);
+  return k.finish();
+}
+
 // ---- cv::CLAHE::apply on one host image (kernels_clahe.h) -------------------------------------------------------------
 VS_API int vslam_clahe_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, double clip_limit, int32_t tiles_x,
                           int32_t tiles_y, uint8_t* dst, int32_t dst_row_stride, uint8_t* luts) {

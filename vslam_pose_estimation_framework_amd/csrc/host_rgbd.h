@@ -202,6 +202,23 @@ VS_API int vslam_rgbd_set_detection_mask(vslam_rgbd* r, const uint8_t* mask, int
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_detection_mask") : r->d.set_detection_mask(mask, row_stride, margin);
 }
+VS_API int vslam_rgbd_set_frame_masks(vslam_rgbd* r, const uint8_t* masks, int32_t row_stride, size_t image_stride, int32_t margin, int on_device) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_frame_masks") : r->d.set_frame_masks(masks, row_stride, image_stride, margin, on_device != 0);
+}
+VS_API int vslam_rgbd_get_frame_detection_mask(vslam_rgbd* r, int32_t stream, uint64_t* words) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_get_frame_detection_mask") : r->d.get_frame_detection_mask(stream, words);
+}
+VS_API int vslam_rgbd_set_undistortion_mask(vslam_rgbd* r, int on, int32_t margin) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_undistortion_mask") : r->d.set_undistortion_mask(on, margin);
+}
+VS_API int vslam_rgbd_get_undistortion_mask(vslam_rgbd* r, int* on, int32_t* margin) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (r->on_host) { if (on) *on = 0; if (margin) *margin = 0; return VSLAM_OK; }
+  return r->d.get_undistortion_mask(on, margin);
+}
 VS_API int vslam_rgbd_get_detection_mask(vslam_rgbd* r, uint64_t* words) {
   if (!r) return VSLAM_ERR_INVALID;
   return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_get_detection_mask") : r->d.get_detection_mask(words);

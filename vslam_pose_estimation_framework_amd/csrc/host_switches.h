@@ -63,6 +63,8 @@ static int pair_to_host(vslam_ctx* c, const ImgPlanes& x, int s, int rows, int c
 }
 
 // ---- rectification of raw input pairs ------------------------------------------------------------
+static void mask_valid_free(vslam_ctx* c);                       // the maps' validity mask (below, with the detection masks)
+static hipError_t mask_valid_build(vslam_ctx* c, int margin);
 VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_cols, const int16_t* xyL, const uint16_t* aL, const int16_t* xyR,
                                    const uint16_t* aR) {
   if (!c) return VSLAM_ERR_INVALID;
@@ -76,6 +78,9 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the old maps and raw slabs
   rect_free(c);
+  const bool valid_on = c->dmask.valid_on;       // the maps' validity mask: recomputed from new maps, off with them
+  const int valid_margin = c->dmask.valid_margin;
+  if (valid_on) { mask_valid_free(c); c->dmask.last = 0; }
   if (off) { (void)eq_keep_sync(c); return col_slab_sync(c) == hipSuccess ? VSLAM_OK : fail(c, VSLAM_ERR_HIP, "vslam_set_rectification: colour slabs"); }
   vslam_ctx::Rect& q = c->rect;
   q.raw_stride = (raw_cols + 63) & ~63;
@@ -87,7 +92,8 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   q.on = true;
   e = eq_keep_sync(c);
   if (e == hipSuccess) e = col_slab_sync(c);
-  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
+  if (e == hipSuccess && valid_on) e = mask_valid_build(c, valid_margin);
+  if (e != hipSuccess) { mask_valid_free(c); rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
   return VSLAM_OK;
 }
 VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
@@ -310,9 +316,92 @@ static int mask_args_check(vslam_ctx* c, const char* who, int32_t row_stride, in
   if (row_stride < c->cfg.c.cols) return fail(c, VSLAM_ERR_INVALID, std::string(who) + ": row stride smaller than image width");
   return VSLAM_OK;
 }
+// k_mask_apply: corner words [n][2][nw] &= stat (stat_stream_stride 0: shared by the streams, else the stream's own words [n][nw] of side 0)
+static void mask_apply_enqueue(hipStream_t st, const MaskApplyArgs& a) {
+  hipLaunchKernelGGL(k_mask_apply, dim3(((a.nw + 1) / 2 + 255) / 256, a.sides, (a.n + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, st, a);
+}
+// k_map_valid on `sides` maps of m: the eroded validity words [sides][rows][TX] into dst
+static void map_valid_enqueue(hipStream_t st, const RemapMaps& m, int sides, int margin, unsigned long long* dst) {
+  MapValidArgs v{};
+  for (int k = 0; k < sides; ++k) { v.map_xy[k] = m.xy[k]; v.map_a[k] = m.a[k]; }
+  v.map_stride = m.stride; v.raw_rows = m.raw_rows; v.raw_cols = m.raw_cols;
+  v.rows = m.rows; v.cols = m.cols; v.TX = (m.cols + 63) / 64; v.margin = margin; v.sides = sides; v.dst = dst;
+  hipLaunchKernelGGL(k_map_valid, dim3((v.TX + VS_MASK_CW - 1) / VS_MASK_CW, (v.rows + VS_MASK_BR - 1) / VS_MASK_BR, sides), dim3(256), 0, st, v);
+}
+// The context-wide keep words of `sides` images out of the user's words and the maps' validity words: the one there is, or both ANDed in
+// `comb` ([2][nw]: the validity words copied, the user's applied by k_mask_apply as to one stream's corner words).  Queues idle.
+static hipError_t mask_static_combine(hipStream_t st, int sides, size_t nw, unsigned long long* const* user, unsigned long long* const* valid,
+                                      DeviceStore& comb_mem, unsigned long long** comb, unsigned long long** stat) {
+  comb_mem.release();
+  comb[0] = comb[1] = nullptr;
+  bool both = false;
+  for (int k = 0; k < sides; ++k) { stat[k] = user[k] ? user[k] : valid[k]; both = both || (user[k] && valid[k]); }
+  if (!both) return hipSuccess;
+  unsigned long long* base = nullptr;
+  hipError_t e = comb_mem.alloc(&base, 2 * nw);
+  if (e != hipSuccess) return e;
+  MaskApplyArgs a{};
+  a.corner = base; a.nw = (int32_t)nw; a.n = 1; a.sides = sides;
+  active_all(a.active, 1);
+  for (int k = 0; k < sides && e == hipSuccess; ++k) {
+    if (!(user[k] && valid[k])) continue;
+    comb[k] = base + (size_t)k * nw;
+    e = hipMemcpyAsync(comb[k], valid[k], nw * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+    a.stat[k] = user[k];
+    stat[k] = comb[k];
+  }
+  if (e == hipSuccess) { mask_apply_enqueue(st, a); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+static hipError_t mask_static_sync(vslam_ctx* c) {
+  vslam_ctx::DetMask& q = c->dmask;
+  return mask_static_combine(c->stream, 2, (size_t)c->cfg.c.rows * c->cfg.TX, q.user, q.valid, q.comb_mem, q.comb, q.stat);
+}
 static void mask_static_free(vslam_ctx* c) {
-  c->dmask.stat_mem.release();
-  c->dmask.stat[0] = c->dmask.stat[1] = nullptr;
+  c->dmask.user_mem.release();
+  c->dmask.user[0] = c->dmask.user[1] = nullptr;
+  (void)mask_static_sync(c);     // what is left: the validity words, or nothing
+}
+static void mask_valid_free(vslam_ctx* c) {
+  c->dmask.valid_mem.release();
+  c->dmask.valid[0] = c->dmask.valid[1] = nullptr;
+  c->dmask.valid_on = false; c->dmask.valid_margin = 0;
+  (void)mask_static_sync(c);
+}
+// the validity words of the maps the context holds (queues idle, rectification on)
+static hipError_t mask_valid_build(vslam_ctx* c, int margin) {
+  vslam_ctx::DetMask& q = c->dmask;
+  const size_t nw = (size_t)c->cfg.c.rows * c->cfg.TX;
+  q.valid_mem.release();
+  q.valid[0] = q.valid[1] = nullptr;
+  unsigned long long* base = nullptr;
+  hipError_t e = q.valid_mem.alloc(&base, 2 * nw);
+  if (e == hipSuccess) { map_valid_enqueue(c->stream, c->rect.maps, 2, margin, base); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) { q.valid[0] = base; q.valid[1] = base + nw; q.valid_on = true; q.valid_margin = margin; e = mask_static_sync(c); }
+  return e;
+}
+VS_API int vslam_set_rectification_mask(vslam_ctx* c, int on, int32_t margin) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification_mask called inside a frame");
+  if (on && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification_mask: margin outside 0 .. 64");
+  if (on && !c->rect.on) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification_mask: no rectification maps are set (vslam_set_rectification)");
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  if (!on && !c->dmask.valid_on) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the old words
+  c->dmask.last = 0;               // no frame has run under the new setting
+  if (!on) { mask_valid_free(c); return VSLAM_OK; }
+  const hipError_t e = mask_valid_build(c, margin);
+  if (e != hipSuccess) { mask_valid_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification_mask: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_rectification_mask(vslam_ctx* c, int* on, int32_t* margin) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (on) *on = c->dmask.valid_on ? 1 : 0;
+  if (margin) *margin = c->dmask.valid_on ? c->dmask.valid_margin : 0;
+  return VSLAM_OK;
 }
 VS_API int vslam_set_detection_mask(vslam_ctx* c, const uint8_t* left, const uint8_t* right, int32_t row_stride, int32_t margin) {
   if (!c) return VSLAM_ERR_INVALID;
@@ -333,18 +422,19 @@ VS_API int vslam_set_detection_mask(vslam_ctx* c, const uint8_t* left, const uin
   hipError_t e = hipMalloc((void**)&tmp, bytes);
   for (int k = 0; k < 2 && e == hipSuccess; ++k) {
     if (!src[k]) continue;
-    e = q.stat_mem.alloc(&q.stat[k], (size_t)rows * TX);
+    e = q.user_mem.alloc(&q.user[k], (size_t)rows * TX);
     if (e == hipSuccess) e = hipMemcpy(tmp, src[k], bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) break;
     MaskPackArgs a{};
     a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = rows; a.cols = cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
-    a.dst = q.stat[k];
+    a.dst = q.user[k];
     active_all(a.active, 1);
     mask_pack_enqueue(c->stream, a);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // tmp is refilled for the other side
   }
   if (tmp) (void)hipFree(tmp);
+  if (e == hipSuccess) e = mask_static_sync(c);
   if (e != hipSuccess) { mask_static_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_detection_mask: ") + hipGetErrorString(e)); }
   return VSLAM_OK;
 }
@@ -396,7 +486,7 @@ static int mask_prepare(vslam_ctx* c, hipStream_t st) {
   a = MaskPackArgs{};
   a.src[0] = src[0]; a.src[1] = src[1]; a.src_stream_stride = q.image_stride; a.src_row_stride = q.row_stride;
   a.rows = rows; a.cols = cols; a.TX = TX; a.margin = q.margin; a.n = B; a.sides = 2;
-  a.dst = q.eff; a.stat[0] = q.stat[0]; a.stat[1] = q.stat[1];
+  a.dst = q.eff; a.stat[0] = q.stat[0]; a.stat[1] = q.stat[1]; a.corner_sides = 2;
   q.job_ready = true;
   return VSLAM_OK;
 }
@@ -415,7 +505,7 @@ static void mask_enqueue(vslam_ctx* c, hipStream_t st, const DevBuf& bs) {
     MaskApplyArgs a{};
     a.stat[0] = q.stat[0]; a.stat[1] = q.stat[1]; a.corner = bs.mask; a.nw = c->cfg.c.rows * c->cfg.TX; a.n = c->B; a.sides = 2;
     std::memcpy(a.active, bs.active, sizeof a.active);
-    hipLaunchKernelGGL(k_mask_apply, dim3(((a.nw + 1) / 2 + 255) / 256, 2, (a.n + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, st, a);
+    mask_apply_enqueue(st, a);
     q.last = 1;
     std::memcpy(q.last_active, bs.active, sizeof q.last_active);
   } else q.last = 0;

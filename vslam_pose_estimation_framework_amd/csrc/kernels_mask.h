@@ -16,7 +16,10 @@
 //                 streams (grid z = stream * sides + side).  With `corner` set it is the frame-mask path fused: the eroded word is ANDed
 //                 with the static word and into the corner word, and the effective word is kept for vslam_get_detection_mask — one pass
 //                 over the mask bytes, no intermediate buffer.
-//   k_mask_apply  corner_word &= static_word, two words (16 B) per lane, the static words loaded once per VS_MASK_SB streams.
+//   k_mask_apply  corner_word &= static_word, two words (16 B) per lane, the static words loaded once per VS_MASK_SB streams (or, with a
+//                 stream stride, every stream's own words: the RGB-D frame masks' effective words).
+//   k_map_valid   the validity of a remap map's output pixels (every tap of non-zero weight inside the raw image), packed and eroded by
+//                 k_mask_pack's own tile (mask_pack_tile) with the map entries as its pixel source.
 // A switched-off stream (DevBuf::active) is neither read nor written.  Integer logic only: bit-exact by construction.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -94,30 +97,48 @@ struct MaskPackArgs {
   int32_t margin;
   int32_t n, sides;           // streams 0 .. n - 1, grid z = n * sides
   unsigned long long* dst;    // [n][sides][rows][TX]; fused: the effective words [n][2][rows][TX]
-  const unsigned long long* stat[2];   // fused: the static words [rows][TX] of each side, null: none
-  unsigned long long* corner; // fused: DevBuf::mask [n][2][rows][TX]; null: plain pack
+  const unsigned long long* stat[2];   // the static words [rows][TX] of each side, ANDed into what is stored and applied; null: none
+  unsigned long long* corner; // fused: DevBuf::mask [n][corner_sides][rows][TX]; null: nothing is applied
+  int32_t corner_sides;       // images per stream of `corner`: 2 (DevBuf::mask), whichever `sides` are packed
   uint32_t active[VS_MAX_STREAMS / 32];
 };
 
-__global__ __launch_bounds__(256) void k_mask_pack(MaskPackArgs a) {
-  __shared__ unsigned long long raw[VS_MASK_BR + 2 * VS_MASK_MAX_MARGIN][VS_MASK_CW + 2];
-  __shared__ unsigned long long hor[VS_MASK_BR + 2 * VS_MASK_MAX_MARGIN][VS_MASK_CW];
+// The pixel source of k_mask_pack: an 8-bit image.  load4: the keep bytes (non-zero = keep) of the pixels x .. x + 3 of `row`, x any
+// multiple of four from -256 on; what it returns for a pixel outside the image (or with !row_ok) is overridden by the caller.
+struct MaskSrcU8 {
+  const uint8_t* src; int32_t row_stride;
+  __device__ __forceinline__ uint32_t load4(int row, int x, bool row_ok, int cols) const {
+    // one aligned 32-bit load when the row starts on a multiple of four bytes, two funnelled into one otherwise (a loaded word always
+    // holds a byte of the row, so it lies inside the caller's allocation)
+    const uint8_t* at = src + (size_t)(row_ok ? row : 0) * row_stride + x;
+    const int sh = (int)((uintptr_t)at & 3u);
+    const uint32_t* al = reinterpret_cast<const uint32_t*>(at - sh);
+    // pixels x .. x + 3 - sh come from the first aligned word, x + 4 - sh .. x + 3 from the second
+    const bool lo_ok = row_ok && x + 3 - sh >= 0 && x < cols;
+    const bool hi_ok = row_ok && sh > 0 && x + 3 >= 0 && x + 4 - sh < cols;
+    const uint32_t lo = lo_ok ? al[0] : 0u, hi = hi_ok ? al[1] : 0u;
+    return sh ? (lo >> (8 * sh)) | (hi << (32 - 8 * sh)) : lo;
+  }
+};
+
+typedef unsigned long long (*MaskRawRows)[VS_MASK_CW + 2];
+typedef unsigned long long (*MaskHorRows)[VS_MASK_CW];
+
+// One workgroup's tile of image (s, side): pack `from` (have: there is a source, workgroup-uniform; else all-keep), erode, AND with the
+// static words, apply and store.  Written once for every pixel source (k_mask_pack: 8-bit images, k_map_valid: remap map entries).
+template <class Src>
+__device__ __forceinline__ void mask_pack_tile(const MaskPackArgs& a, const Src& from, bool have, int s, int side, MaskRawRows raw, MaskHorRows hor) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int s = (int)blockIdx.z / a.sides, side = (int)blockIdx.z - s * a.sides;
-  if (!((a.active[s >> 5] >> (s & 31)) & 1u)) return;
   const int m = a.margin;
   const int t0 = blockIdx.x * VS_MASK_CW, r0 = blockIdx.y * VS_MASK_BR;
   const int cw = min(VS_MASK_CW, a.TX - t0), nout = min(VS_MASK_BR, a.rows - r0);
   const int nr = nout + 2 * m;                      // staged rows: r0 - m .. r0 + nout + m - 1
-  const uint8_t* src = a.src[side];
-  if (src) {                                        // workgroup-uniform
-    src += (size_t)s * a.src_stream_stride;
+  if (have) {                                       // workgroup-uniform
     // raw words, four at a time: item (j, g) = row r0 - m + j, words tb + 4 g .. tb + 4 g + 3, where tb = t0 - 1 (raw[j][0]) when the
-    // halo words matter (m > 0), else t0 (raw[j][1]).  Lane l takes the four pixels 64 (tb + 4 g) + 4 l .. + 3 of the 256: one aligned
-    // 32-bit load when the row starts on a multiple of four bytes, two funnelled into one otherwise (a loaded word always holds a byte
-    // of the row, so it lies inside the caller's allocation), four ballots give the bits pixel-interleaved, and lanes 0 .. 3 put one
-    // word each in order (mask_gather4).  Outside the image everything is kept.  VS_MASK_INFLIGHT items of a wave are loaded before the
-    // first ballot waits: the loop is bound by load latency otherwise.
+    // halo words matter (m > 0), else t0 (raw[j][1]).  Lane l takes the four pixels 64 (tb + 4 g) + 4 l .. + 3 of the 256 (Src::load4),
+    // four ballots give the bits pixel-interleaved, and lanes 0 .. 3 put one word each in order (mask_gather4).  Outside the image
+    // everything is kept.  VS_MASK_INFLIGHT items of a wave are loaded before the first ballot waits: the loop is bound by load latency
+    // otherwise.
     const int tb = m > 0 ? t0 - 1 : t0, k0 = m > 0 ? 0 : 1, nk = m > 0 ? cw + 2 : cw;
     const int ng = (nk + 3) >> 2, items = nr * ng;
     for (int i0 = wave; i0 < items; i0 += 4 * VS_MASK_INFLIGHT) {     // wave-uniform: every lane takes part in the ballots
@@ -128,14 +149,7 @@ __global__ __launch_bounds__(256) void k_mask_pack(MaskPackArgs a) {
         const int j = i / ng, g = i - j * ng;
         const int row = r0 - m + j, x = 64 * (tb + 4 * g) + 4 * lane;
         const bool row_ok = i < items && row >= 0 && row < a.rows;
-        const uint8_t* at = src + (size_t)(row_ok ? row : 0) * a.src_row_stride + x;
-        const int sh = (int)((uintptr_t)at & 3u);
-        const uint32_t* al = reinterpret_cast<const uint32_t*>(at - sh);
-        // pixels x .. x + 3 - sh come from the first aligned word, x + 4 - sh .. x + 3 from the second
-        const bool lo_ok = row_ok && x + 3 - sh >= 0 && x < a.cols;
-        const bool hi_ok = row_ok && sh > 0 && x + 3 >= 0 && x + 4 - sh < a.cols;
-        const uint32_t lo = lo_ok ? al[0] : 0u, hi = hi_ok ? al[1] : 0u;
-        uint32_t px = sh ? (lo >> (8 * sh)) | (hi << (32 - 8 * sh)) : lo;
+        uint32_t px = from.load4(row, x, row_ok, a.cols);
         // a pixel outside the image (or the row) counts as kept
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -161,21 +175,74 @@ __global__ __launch_bounds__(256) void k_mask_pack(MaskPackArgs a) {
   for (int i = tid; i < nout * cw; i += 256) {
     const int r = i / cw, k = i - r * cw;
     unsigned long long acc = ~0ull;
-    if (src)
+    if (have)
       for (int j = r; j <= r + 2 * m; ++j) acc &= hor[j][k];
     const int row = r0 + r, t = t0 + k;
     acc &= mask_cols_word(t, a.cols);
-    const size_t at = (((size_t)s * a.sides + side) * a.rows + row) * a.TX + t;
-    if (a.corner) {
-      if (a.stat[side]) acc &= a.stat[side][(size_t)row * a.TX + t];
-      a.corner[at] &= acc;
-    }
-    a.dst[at] = acc;
+    if (a.stat[side]) acc &= a.stat[side][(size_t)row * a.TX + t];
+    // the corner words lie [n][corner_sides][rows][TX]: DevBuf::mask keeps two images per stream whichever sides are in use
+    if (a.corner) a.corner[(((size_t)s * a.corner_sides + side) * a.rows + row) * a.TX + t] &= acc;
+    a.dst[(((size_t)s * a.sides + side) * a.rows + row) * a.TX + t] = acc;
   }
+}
+
+__global__ __launch_bounds__(256) void k_mask_pack(MaskPackArgs a) {
+  __shared__ unsigned long long raw[VS_MASK_BR + 2 * VS_MASK_MAX_MARGIN][VS_MASK_CW + 2];
+  __shared__ unsigned long long hor[VS_MASK_BR + 2 * VS_MASK_MAX_MARGIN][VS_MASK_CW];
+  const int s = (int)blockIdx.z / a.sides, side = (int)blockIdx.z - s * a.sides;
+  if (!((a.active[s >> 5] >> (s & 31)) & 1u)) return;
+  const uint8_t* src = a.src[side];
+  const MaskSrcU8 from{src ? src + (size_t)s * a.src_stream_stride : nullptr, a.src_row_stride};
+  mask_pack_tile(a, from, src != nullptr, s, side, raw, hor);
+}
+
+// ---- validity of a remap map's output pixels (kernels_rectify.h: BORDER_CONSTANT fills every tap outside the raw image with 0) -------
+// A map entry (x0, y0), ax = a & 31, ay = (a >> 5) & 31 is valid iff every tap of non-zero weight lies inside the raw image:
+//   x0 >= 0 and x0 + (ax > 0) <= raw_cols - 1 and y0 >= 0 and y0 + (ay > 0) <= raw_rows - 1.
+// k_map_valid packs that bit per entry and erodes it: k_mask_pack's tile with the map as its pixel source.  The loads are k_rectify's: one
+// lane takes four consecutive entries (16 B of map_xy, 8 B of map_a; rows padded to map_stride, a multiple of four, so that a load that
+// starts inside the image ends inside the row).  The padding entries are outside the image: they erode as kept and never become bits
+// (mask_cols_word).  Grid (word groups, row bands, sides); once per setter call, not per frame.
+struct MapValidArgs {
+  const int16_t* map_xy[2];   // [rows][map_stride][2]
+  const uint16_t* map_a[2];   // [rows][map_stride]
+  int32_t map_stride, raw_rows, raw_cols;
+  int32_t rows, cols, TX, margin, sides;
+  unsigned long long* dst;    // [sides][rows][TX]
+};
+struct MaskSrcMap {
+  const int16_t* xy; const uint16_t* fa; int32_t map_stride, raw_rows, raw_cols;
+  __device__ __forceinline__ uint32_t load4(int row, int x, bool row_ok, int cols) const {
+    if (!(row_ok && x >= 0 && x < cols)) return 0u;
+    const size_t m = (size_t)row * map_stride + x;
+    const int4 q = *reinterpret_cast<const int4*>(xy + 2 * m);
+    const uint2 fr = *reinterpret_cast<const uint2*>(fa + m);
+    const int xyw[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t fw[4] = {fr.x & 0xffffu, fr.x >> 16, fr.y & 0xffffu, fr.y >> 16};
+    uint32_t px = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x0 = (int)(int16_t)(xyw[k] & 0xffff), y0 = xyw[k] >> 16;      // as k_rectify unpacks them
+      const int ax = (int)(fw[k] & 31u), ay = (int)((fw[k] >> 5) & 31u);
+      const bool ok = x0 >= 0 && x0 + (ax > 0) <= raw_cols - 1 && y0 >= 0 && y0 + (ay > 0) <= raw_rows - 1;
+      px |= (ok ? 1u : 0u) << (8 * k);
+    }
+    return px;
+  }
+};
+__global__ __launch_bounds__(256) void k_map_valid(MapValidArgs v) {
+  __shared__ unsigned long long raw[VS_MASK_BR + 2 * VS_MASK_MAX_MARGIN][VS_MASK_CW + 2];
+  __shared__ unsigned long long hor[VS_MASK_BR + 2 * VS_MASK_MAX_MARGIN][VS_MASK_CW];
+  const int side = blockIdx.z;
+  MaskPackArgs a{};
+  a.rows = v.rows; a.cols = v.cols; a.TX = v.TX; a.margin = v.margin; a.n = 1; a.sides = v.sides; a.dst = v.dst;
+  const MaskSrcMap from{v.map_xy[side], v.map_a[side], v.map_stride, v.raw_rows, v.raw_cols};
+  mask_pack_tile(a, from, true, 0, side, raw, hor);
 }
 
 struct MaskApplyArgs {
   const unsigned long long* stat[2];   // static words [nw] of each side, null: the side is unmasked
+  size_t stat_stream_stride;           // words between the streams' own words [n][nw] (one side); 0: every stream shares stat[side]
   unsigned long long* corner;          // DevBuf::mask: image (s, side) at corner + (s * 2 + side) * nw
   int32_t nw;                          // rows * TX
   int32_t n, sides;                    // streams 0 .. n - 1; sides 1: the left image only (RGB-D)
@@ -197,6 +264,11 @@ __global__ __launch_bounds__(256) void k_mask_apply(MaskApplyArgs a) {
   const int j0 = blockIdx.z * VS_MASK_SB, j1 = min(a.n, j0 + VS_MASK_SB);
   for (int s = j0; s < j1; ++s) {
     if (!((a.active[s >> 5] >> (s & 31)) & 1u)) continue;
+    if (a.stat_stream_stride) {        // the stream's own words (uniform over the launch)
+      const unsigned long long* own = stat + (size_t)s * a.stat_stream_stride + i;
+      if (pair) sw = *reinterpret_cast<const u64x2*>(own);
+      else { sw.x = own[0]; sw.y = i + 1 < a.nw ? own[1] : ~0ull; }
+    }
     unsigned long long* cw = a.corner + ((size_t)s * 2 + side) * a.nw + i;
     if (pair) {
       u64x2 v = *reinterpret_cast<u64x2*>(cw);

@@ -127,7 +127,8 @@ public:
     eq.have_frame = false;                                                   // and so does the equalisation switch
     col.have_frame = false;                                                  // and the colour format
     bl.have_frame = false;                                                   // and the depth image's bilateral filter
-    dmask.have_frame = false;                                                // and the detection mask
+    dmask.have_frame = false;                                                // and the detection mask, with the maps' validity mask
+    dmask.fm_pending = false; dmask.fm_frame = false; dmask.fm_have = false;  // frame masks that waited for a frame belong to the sequence that ended
     if (mp.cap && map_clear() != hipSuccess) { err = "RGB-D reset: landmark map"; return VSLAM_ERR_HIP; }     // map and log start over, still enabled
     return VSLAM_OK;
   }
@@ -319,6 +320,9 @@ public:
     (void)hipStreamSynchronize(q2);
     und_free();
     drop_graph();                                   // a captured launch sequence holds the old maps and buffers (or none)
+    const bool valid_on = dmask.valid_on;           // the maps' validity mask: recomputed from new maps, off with them
+    const int valid_margin = dmask.valid_margin;
+    if (valid_on) dmask_valid_free();
     if (off) return VSLAM_OK;
     hipError_t e = remap_maps_upload(und_mem, und.maps, 1, raw_rows, raw_cols, p.rows, p.cols, &map_xy, &map_a);
     und.img.row_stride = und.maps.stride;           // k_rectify stores words: rows 4-byte aligned
@@ -329,6 +333,7 @@ public:
     if (e != hipSuccess) { und_free(); err = std::string("vslam_rgbd_set_undistortion: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
     und.img.p[0] = img;
     und.on = true;
+    if (valid_on && (e = dmask_valid_build(valid_margin)) != hipSuccess) { dmask_valid_free(); und_free(); return hip_fail(e, "vslam_rgbd_set_undistortion"); }
     return VSLAM_OK;
   }
   // the undistorted image and depth image the last finished frame of `stream` was processed on (dense; either may be null)
@@ -388,45 +393,90 @@ public:
     return fetched(planes_to_host(image, eq.dst, 0, stream, p.rows, p.cols));
   }
 
-  // ---- the static detection mask (kernels_mask.h): opt-in, its own allocation, nothing launched while dmask.words is null.  One image,
-  // shared by every sequence of a batch; k_mask_apply ANDs its eroded packed words into the corner words between k_fast_box and k_emit of
-  // every attempt (enqueue_attempt), inside the captured launch sequence as well.
+  // ---- detection masks (kernels_mask.h): opt-in, their own allocations, nothing launched while none is set.  The context-wide keep words
+  // dmask.stat[0] are the static mask (one image, shared by every sequence of a batch) AND the undistortion maps' validity
+  // (set_undistortion_mask); a frame mask per sequence (set_frame_masks) is packed, eroded and ANDed with them once per frame into
+  // dmask.eff [B][rows][TX], ahead of the first detection.  k_mask_apply ANDs the frame's words into the corner words between k_fast_box
+  // and k_emit of every attempt (enqueue_attempt), inside the captured launch sequence as well.
   int set_detection_mask(const uint8_t* mask, int32_t row_stride, int32_t margin) {
     if (pending) { err = "vslam_rgbd_set_detection_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if (mask && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_detection_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
     if (mask && row_stride < p.cols) { err = "vslam_rgbd_set_detection_mask: row stride smaller than image width"; return VSLAM_ERR_INVALID; }
-    if (!mask && !dmask.words) return VSLAM_OK;
+    if (!mask && !dmask.user[0]) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q); (void)hipStreamSynchronize(q2);
-    dmask_free();
+    dmask_user_free();
     drop_graph();                  // a captured launch sequence holds the launch, or lacks it
     if (!mask) return VSLAM_OK;
     const int TX = ic->cfg.TX;
     const size_t bytes = (size_t)(p.rows - 1) * row_stride + p.cols;
     uint8_t* tmp = nullptr;
     hipError_t e = hipMalloc((void**)&tmp, bytes);
-    if (e == hipSuccess) e = dmask.mem.alloc(&dmask.words, (size_t)p.rows * TX);
+    if (e == hipSuccess) e = dmask.mem.alloc(&dmask.user[0], (size_t)p.rows * TX);
     if (e == hipSuccess) e = hipMemcpy(tmp, mask, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
       MaskPackArgs a{};
       a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = p.rows; a.cols = p.cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
-      a.dst = dmask.words;
+      a.dst = dmask.user[0];
       active_all(a.active, 1);
       mask_pack_enqueue(q, a);
       e = hipGetLastError();
       if (e == hipSuccess) e = hipStreamSynchronize(q);
     }
     if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) { dmask_free(); return hip_fail(e, "vslam_rgbd_set_detection_mask"); }
+    if (e == hipSuccess) e = dmask_sync();
+    if (e != hipSuccess) { dmask_user_free(); return hip_fail(e, "vslam_rgbd_set_detection_mask"); }
     return VSLAM_OK;
   }
-  // the eroded packed keep-mask the last finished frame used: rows * TX words
+  // the context-wide eroded packed keep-mask (static AND validity) the last finished frame used: rows * TX words
   int get_detection_mask(uint64_t* words) {
     if (int rc = readable(0)) return rc;
-    if (!dmask.words || !dmask.have_frame) { err = "vslam_rgbd_get_detection_mask: no frame has run under a mask since vslam_rgbd_set_detection_mask / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    if (!dmask.stat[0] || !dmask.have_frame) { err = "vslam_rgbd_get_detection_mask: no frame has run under a mask since vslam_rgbd_set_detection_mask / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
     if (!words) { err = "vslam_rgbd_get_detection_mask: null output"; return VSLAM_ERR_INVALID; }
     (void)hipSetDevice(ic->device);
-    return fetched(hipMemcpy(words, dmask.words, (size_t)p.rows * ic->cfg.TX * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return fetched(hipMemcpy(words, dmask.stat[0], (size_t)p.rows * ic->cfg.TX * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+  // the undistortion maps' validity as part of the context-wide keep-mask (k_map_valid, once per call and per new maps)
+  int set_undistortion_mask(int on, int32_t margin) {
+    if (pending) { err = "vslam_rgbd_set_undistortion_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (on && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_undistortion_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
+    if (on && !und.on) { err = "vslam_rgbd_set_undistortion_mask: no undistortion maps are set (vslam_rgbd_set_undistortion)"; return VSLAM_ERR_STATE; }
+    if (!on && !dmask.valid_on) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q); (void)hipStreamSynchronize(q2);
+    drop_graph();                  // a captured launch sequence holds the launch on the old words, or lacks it
+    dmask.have_frame = false;
+    if (!on) { dmask_valid_free(); return VSLAM_OK; }
+    const hipError_t e = dmask_valid_build(margin);
+    if (e != hipSuccess) { dmask_valid_free(); return hip_fail(e, "vslam_rgbd_set_undistortion_mask"); }
+    return VSLAM_OK;
+  }
+  int get_undistortion_mask(int* on, int32_t* margin) const {
+    if (on) *on = dmask.valid_on ? 1 : 0;
+    if (margin) *margin = dmask.valid_on ? dmask.valid_margin : 0;
+    return VSLAM_OK;
+  }
+  // One mask per sequence for the next submit only: sequence s at masks + s * image_stride; null cancels a pending set.  Host masks are
+  // copied by that submit; device masks are read by its one pack launch and never written.
+  int set_frame_masks(const uint8_t* masks, int32_t row_stride, size_t image_stride, int32_t margin, bool on_device) {
+    if (pending) { err = "vslam_rgbd_set_frame_masks: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (!masks) { dmask.fm_pending = false; return VSLAM_OK; }
+    if (margin < 0 || margin > VS_MASK_MAX_MARGIN) { err = "vslam_rgbd_set_frame_masks: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
+    if (row_stride < p.cols) { err = "vslam_rgbd_set_frame_masks: row stride smaller than image width"; return VSLAM_ERR_INVALID; }
+    if (B > 1 && image_stride < (size_t)(p.rows - 1) * row_stride + p.cols) { err = "vslam_rgbd_set_frame_masks: image stride smaller than one mask"; return VSLAM_ERR_INVALID; }
+    dmask.fm_pending = true; dmask.fm_on_device = on_device;
+    dmask.fm_src = masks; dmask.fm_row_stride = row_stride; dmask.fm_image_stride = image_stride; dmask.fm_margin = margin;
+    return VSLAM_OK;
+  }
+  // the effective words (static AND validity AND frame mask) the last finished frame of `stream` used: rows * TX words
+  int get_frame_detection_mask(int stream, uint64_t* words) {
+    if (int rc = readable(stream)) return rc;
+    const bool stat = dmask.stat[0] && dmask.have_frame;
+    if (!dmask.fm_have && !stat) { err = "vslam_rgbd_get_frame_detection_mask: the last frame used no mask"; return VSLAM_ERR_STATE; }
+    if (!words) { err = "vslam_rgbd_get_frame_detection_mask: null output"; return VSLAM_ERR_INVALID; }
+    (void)hipSetDevice(ic->device);
+    const size_t nw = (size_t)p.rows * ic->cfg.TX;
+    return fetched(hipMemcpy(words, dmask.fm_have ? dmask.eff + (size_t)stream * nw : dmask.stat[0], nw * sizeof(uint64_t), hipMemcpyDeviceToHost));
   }
 
   // ---- bilateral filtering of the depth image (kernels_bilateral.h): opt-in, its own allocations, nothing launched while bl.on is false.
@@ -522,8 +572,10 @@ public:
     if (B > 1 && (left_stream_stride < (size_t)(in_rows() - 1) * lstride + in_bytes() || depth_stream_stride < (size_t)(in_rows() - 1) * dstride + in_cols())) {
       err = "RGB-D batch: stream strides smaller than an image"; return VSLAM_ERR_INVALID;
     }
+    // a submit refused above has changed nothing: frame masks that wait for a frame go on waiting.  From here on the set is this frame's: an
+    // accepted submit consumes it (frame_masks_prepare), and one that fails afterwards drops it with the frame
     const int rc = submit_frame(left, lstride, depth, dstride, left_stream_stride, depth_stream_stride, on_device);
-    if (rc != VSLAM_OK) { failed = true; failed_why = err; }
+    if (rc != VSLAM_OK) { failed = true; failed_why = err; dmask.fm_pending = false; dmask.fm_frame = false; }
     else pending = true;
     return rc;
   }
@@ -532,7 +584,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; bl.have_frame = bl.on; dmask.have_frame = dmask.words != nullptr; }
+    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; bl.have_frame = bl.on; dmask.have_frame = dmask.stat[0] != nullptr; dmask.fm_have = dmask.fm_frame; }
     return rc;
   }
 
@@ -587,12 +639,14 @@ private:
   // block's copy out) captured once into a hipGraph and replayed — two copies and ONE launch per frame instead of ~22.  Measured on MI355X /
   // ROCm 7.2 (tests/validation/rgbd_submit_time.py): submit() takes 80 us of host time either way (the two pageable copies; the runtime replays a
   // graph node by node) and the frame 0.31 against 0.30 ms: the frame is bound by its dependent kernels, not by their launches.  Kept as a
-  // tested switch, captured again when the image stride or buffer changes.
+  // tested switch, captured again when the image stride or buffer changes, or when a frame with frame masks follows one without (or the
+  // reverse): the pack launch stays outside, the sequence holds the apply launches on eff or on the context-wide words.
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   bool use_graph = false;
   int32_t graph_stride = -1;
   const uint8_t* graph_img = nullptr;
+  bool graph_fm = false;         // the captured sequence applies the frame masks' effective words (else the context-wide ones, or none)
   hipEvent_t ev_fork = nullptr;
   // the landmark map and the observation log (kernels_rgbd_map.h): off while cap / ocap == 0.  Allocations of their own, freed when the
   // store is turned off or replaced (the inner context's allocation list only grows until destroy)
@@ -620,9 +674,66 @@ private:
   // bilateral filtering of the depth image: off while bl.on is false.  depth: the filtered images [B][rows * cols] the space map reads;
   // args: what the three kernels get but for this frame's source (sizes, scales, taps, the range cells [B][4] and the tables [B][4098])
   struct Bilateral { bool on = false, have_frame = false; double sigma_color = 0, sigma_space = 0; uint16_t* depth = nullptr; BilateralArgs args; DeviceStore mem; } bl;
-  // the static detection mask: off while words is null; [rows][TX] eroded packed words
-  struct DetMask { unsigned long long* words = nullptr; bool have_frame = false; DeviceStore mem; } dmask;
-  void dmask_free() { dmask.mem.release(); dmask.words = nullptr; dmask.have_frame = false; }
+  // detection masks.  user / valid: the static mask's and the maps' validity's eroded packed words [rows][TX] (index 0; the pairs are
+  // what mask_static_combine takes), stat[0]: the context-wide words, the one there is or comb[0] = both ANDed; off while null.  The
+  // frame masks wait in fm_* for the next submit; slab: the device copy of host masks at the caller's strides; eff [B][rows][TX]: the
+  // effective words of the frame under way (fm_frame) / of the last finished frame (fm_have).
+  struct DetMask { unsigned long long* stat[2] = {nullptr, nullptr}; bool have_frame = false;
+                   unsigned long long* user[2] = {nullptr, nullptr}; DeviceStore mem;
+                   bool valid_on = false; int valid_margin = 0; unsigned long long* valid[2] = {nullptr, nullptr}; DeviceStore valid_mem;
+                   unsigned long long* comb[2] = {nullptr, nullptr}; DeviceStore comb_mem;
+                   bool fm_pending = false, fm_on_device = false; const uint8_t* fm_src = nullptr; int32_t fm_row_stride = 0; size_t fm_image_stride = 0; int fm_margin = 0;
+                   uint8_t* slab = nullptr; size_t slab_bytes = 0; DeviceStore slab_mem;
+                   unsigned long long* eff = nullptr; DeviceStore eff_mem;
+                   bool fm_frame = false, fm_have = false; } dmask;
+  hipError_t dmask_sync() { return mask_static_combine(q, 1, (size_t)p.rows * ic->cfg.TX, dmask.user, dmask.valid, dmask.comb_mem, dmask.comb, dmask.stat); }
+  void dmask_user_free() { dmask.mem.release(); dmask.user[0] = nullptr; dmask.have_frame = false; (void)dmask_sync(); }
+  void dmask_valid_free() { dmask.valid_mem.release(); dmask.valid[0] = nullptr; dmask.valid_on = false; dmask.valid_margin = 0; dmask.have_frame = false; (void)dmask_sync(); }
+  hipError_t dmask_valid_build(int margin) {
+    dmask.valid_mem.release();
+    dmask.valid[0] = nullptr;
+    unsigned long long* w = nullptr;
+    hipError_t e = dmask.valid_mem.alloc(&w, (size_t)p.rows * ic->cfg.TX);
+    if (e == hipSuccess) { map_valid_enqueue(q, und.maps, 1, margin, w); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    if (e == hipSuccess) { dmask.valid[0] = w; dmask.valid_on = true; dmask.valid_margin = margin; e = dmask_sync(); }
+    return e;
+  }
+  void dmask_free() {
+    for (DeviceStore* m : {&dmask.mem, &dmask.valid_mem, &dmask.comb_mem, &dmask.slab_mem, &dmask.eff_mem}) m->release();
+    dmask = DetMask{};
+  }
+  // Ahead of the frame's first launch (and outside a captured sequence, whose launches read eff at its fixed address): a pending set of
+  // frame masks is consumed — host masks copied into the slab on the frame's queue, then ONE k_mask_pack over all sequences packs, erodes
+  // and ANDs the context-wide words into eff.  The previous frame has been waited for: nothing reads slab or eff any more.
+  int frame_masks_prepare() {
+    dmask.fm_frame = false;
+    if (!dmask.fm_pending) return VSLAM_OK;
+    dmask.fm_pending = false;
+    const int TX = ic->cfg.TX;
+    hipError_t e = hipSuccess;
+    if (!dmask.eff) e = dmask.eff_mem.alloc(&dmask.eff, (size_t)B * p.rows * TX);
+    if (e != hipSuccess) return hip_fail(e, "frame masks");
+    const uint8_t* src = dmask.fm_src;
+    if (!dmask.fm_on_device) {
+      const size_t span = (size_t)(B - 1) * dmask.fm_image_stride + (size_t)(p.rows - 1) * dmask.fm_row_stride + p.cols;
+      if (dmask.slab_bytes < span) {
+        dmask.slab_mem.release(); dmask.slab = nullptr; dmask.slab_bytes = 0;
+        if ((e = dmask.slab_mem.alloc(&dmask.slab, span)) != hipSuccess) return hip_fail(e, "frame masks");
+        dmask.slab_bytes = span;
+      }
+      if ((e = hipMemcpyAsync(dmask.slab, src, span, hipMemcpyHostToDevice, q)) != hipSuccess) return hip_fail(e, "frame masks");
+      src = dmask.slab;
+    }
+    MaskPackArgs a{};
+    a.src[0] = src; a.src_stream_stride = dmask.fm_image_stride; a.src_row_stride = dmask.fm_row_stride;
+    a.rows = p.rows; a.cols = p.cols; a.TX = TX; a.margin = dmask.fm_margin; a.n = B; a.sides = 1;
+    a.dst = dmask.eff; a.stat[0] = dmask.stat[0];
+    active_all(a.active, B);
+    mask_pack_enqueue(q, a);
+    dmask.fm_frame = true;
+    return VSLAM_OK;
+  }
   PrePlan pre;                   // this frame's routing through the three stages (route_frame): pre.color is its colour source
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
@@ -736,11 +847,13 @@ private:
     if (again) hipLaunchKernelGGL(k_rgbd_save_features, dim3(B), dim3(1024), 0, q, d, b, rb);
     hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, q, d, b);
     const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
-    if (dmask.words) {             // the detection mask: the keep words into every sequence's corner words, ahead of the count
-      MaskApplyArgs ma{};
-      ma.stat[0] = dmask.words; ma.corner = b.mask; ma.nw = d.c.rows * d.TX; ma.n = B; ma.sides = 1;
+    if (dmask.fm_frame || dmask.stat[0]) {     // the detection mask: the keep words into every sequence's corner words, ahead of the count
+      MaskApplyArgs ma{};                       // (under frame masks: the sequence's own effective words, which hold the context-wide ones)
+      ma.corner = b.mask; ma.nw = d.c.rows * d.TX; ma.n = B; ma.sides = 1;
+      if (dmask.fm_frame) { ma.stat[0] = dmask.eff; ma.stat_stream_stride = (size_t)ma.nw; }
+      else ma.stat[0] = dmask.stat[0];
       std::memcpy(ma.active, b.active, sizeof ma.active);
-      hipLaunchKernelGGL(k_mask_apply, dim3(((ma.nw + 1) / 2 + 255) / 256, 1, (B + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, q, ma);
+      mask_apply_enqueue(q, ma);
     }
     hipLaunchKernelGGL(k_emit, dim3(B, 1), dim3(512), 0, q, d, b, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 2);
     const dim3 g3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, B);
@@ -779,6 +892,7 @@ private:
     src_on_device = on_device;
     if (on_device) {
       use_graph = false;                       // the captured graph holds the staging buffers' addresses
+      if (const int mrc = frame_masks_prepare()) return mrc;
       bs = buf_set(ic, 0, 0);
       // the first stage that is on (k_gray_u8, else the undistortion, else the equalisation) alone reads the caller's image
       if (const hipError_t ce = route_frame({{left, nullptr}, lstride, lss}, false)) return hip_fail(ce, "grey image");
@@ -827,11 +941,12 @@ private:
       }
     }
     if (e != hipSuccess) return hip_fail(e, "image / depth upload");
+    if (const int mrc = frame_masks_prepare()) return mrc;
     bs = buf_set(ic, 0, 0);
     if (const hipError_t ce = route_frame({{d_img, nullptr}, lstride, img_stream}, true)) return hip_fail(ce, "grey image");
     if (und.on) { raw_dep = und.raw_depth; raw_dep_stride = cols; raw_dep_stream = (size_t)rows * cols; }
     active_all(bs.active, B);
-    if (use_graph && (!graph_exec || graph_stride != lstride || graph_img != d_img)) capture_graph(lstride);
+    if (use_graph && (!graph_exec || graph_stride != lstride || graph_img != d_img || graph_fm != dmask.fm_frame)) capture_graph(lstride);
     if (use_graph && graph_exec) {
       e = hipGraphLaunch(graph_exec, q);
       if (e != hipSuccess) { ic->sticky = VSLAM_ERR_HIP; return hip_fail(e, "RGB-D frame (graph launch)"); }
@@ -912,7 +1027,7 @@ private:
     depth_pending = false;
     if (e == hipSuccess) e = hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0);
     if (e != hipSuccess || !graph_exec) { (void)hipGetLastError(); drop_graph(); use_graph = false; return; }
-    graph_stride = lstride; graph_img = d_img;
+    graph_stride = lstride; graph_img = d_img; graph_fm = dmask.fm_frame;
   }
 
   int finish_frame() {

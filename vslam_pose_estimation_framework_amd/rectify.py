@@ -199,6 +199,17 @@ def remap_u8(src, map_xy, map_a):
     return ((s + 16384) >> 15).astype(np.uint8)
 
 
+def validity(map_xy, map_a, raw_rows, raw_cols):
+    """bool [rows, cols]: the output pixels whose every tap of non-zero weight lies inside the raw image (integers, the rule above
+    vslam_set_rectification_mask): x0 >= 0, x0 + (ax > 0) <= raw_cols - 1, y0 >= 0, y0 + (ay > 0) <= raw_rows - 1.  remap_u8 fills the
+    other pixels' missing taps with 0.  The restatement of k_map_valid's bit; packed and eroded by mask.pack_bool / mask.erode."""
+    x0 = np.asarray(map_xy)[..., 0].astype(np.int64)
+    y0 = np.asarray(map_xy)[..., 1].astype(np.int64)
+    a = np.asarray(map_a).astype(np.int64)
+    ax, ay = a & 31, (a >> 5) & 31
+    return (x0 >= 0) & (x0 + (ax > 0) <= int(raw_cols) - 1) & (y0 >= 0) & (y0 + (ay > 0) <= int(raw_rows) - 1)
+
+
 def remap_nearest_u16(src, map_xy, map_a):
     """The depth kernel's arithmetic on 16-bit single-channel images: the nearest raw pixel of the 1/32-px source coordinate, ties up
     (this repository's own rule; depth is not interpolated): x = x0 + (ax >> 4), y = y0 + (ay >> 4), out = src[y][x] inside the raw image,
