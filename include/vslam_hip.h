@@ -848,7 +848,12 @@ int vslam_orb_describe(vslam_ctx* ctx, const uint8_t* image_host, int32_t rows, 
  * frame by frame: the device-resident loop (csrc/kernels_rgbd.h + csrc/rgbd_device.h, the default: framepoints, temporary points,
  * landmarks, history and the tracker's scalars live in HBM; a frame is two copies in, one launch sequence on two HIP streams and one
  * 1 KB state block out) and the host-driven loop over the stand-alone entry points above (csrc/rgbd_tracker.h: VSLAM_RGBD_HOST=1 in the
- * environment of vslam_rgbd_create; it also serves p->detector_type = VSLAM_DETECTOR_ORB).  One sequence per object, any detector
+ * environment of vslam_rgbd_create), kept as the cross-check.  Both serve p->detector_type = VSLAM_DETECTOR_FAST and _ORB: with the
+ * OrbDetector the device-resident loop runs every region's pyramid, FAST, the two retainBest selects, Harris and angles, the extractor
+ * (ORB::compute on the keypoint's own level and angle, or BRIEF at level 0) and a feature store of float keypoints on the frame's queue
+ * (csrc/kernels_rgbd_orb.h), so batches, the captured launch sequence, the map, the log, map colours and every input
+ * stage below work with it; the detection masks alone are refused in that mode (VSLAM_ERR_STATE, the context stays usable).  A detector
+ * grid above 2 x 2 with the OrbDetector (regions of different sizes) selects the host-driven loop.  One sequence per object, any detector
  * grid (configuration_icl.yaml: 2 x 2).  cfg carries the tracker / aligner / landmark / detector values, p the depth camera
  * (p->descriptor_type selects the extractor: the RGB-D configurations say "ORB-256").  A frame that fails (capacity, HIP error) leaves
  * the tracker refusing further frames until vslam_rgbd_reset (the reference throws out of compute() and the run ends, app.cpp:128).
@@ -901,8 +906,8 @@ int vslam_rgbd_get_points(vslam_rgbd* t, int32_t cap, int32_t* n, float* xy, dou
  * 16 in every frame that dropped one; neither stops the tracker.  vslam_rgbd_reset clears both and leaves them enabled; capacity 0 turns
  * the store off (vslam_rgbd_enable_map(0): map and log); the log needs the map (VSLAM_ERR_STATE otherwise).  Enabling between frames of a
  * running sequence is allowed: tracks that already carry a landmark get an id at their next update.  With a frame in flight (between
- * submit and wait) every call here returns VSLAM_ERR_STATE; so does every call on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type
- * ORB), which does not have the feature.  Any output pointer may be NULL; first_id / first read only what is new;
+ * submit and wait) every call here returns VSLAM_ERR_STATE; so does every call on the host-driven loop (VSLAM_RGBD_HOST=1),
+ * which does not have the feature.  Any output pointer may be NULL; first_id / first read only what is new;
  * vslam_rgbd_get_point_ids: the finished frame's ids in vslam_rgbd_get_points order (needs the map only). */
 int vslam_rgbd_enable_map(vslam_rgbd* t, int32_t capacity_per_stream);
 int vslam_rgbd_get_map_size(vslam_rgbd* t, int32_t stream, int32_t* n);
@@ -934,7 +939,7 @@ int vslam_rgbd_get_map_colors(vslam_rgbd* t, int32_t stream, int32_t first_id, i
  * downstream reports undistorted coordinates.  The maps survive vslam_rgbd_reset.
  * vslam_rgbd_set_undistortion: host pointers, copied before the call returns; both NULL turns it off and frees the storage.
  *   VSLAM_ERR_INVALID: one map only, map_a >= 1024, raw size outside 1 .. 32767.  VSLAM_ERR_STATE: a frame in flight, or the host-driven
- *   loop (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature.
+ *   loop (VSLAM_RGBD_HOST=1), which does not have the feature.
  * vslam_rgbd_get_undistorted: the image (rows*cols bytes) and depth image (rows*cols uint16) the last finished frame of `stream` was
  *   processed on, dense; either pointer may be NULL.  VSLAM_ERR_STATE when off, before a frame, or with a frame in flight.
  * vslam_remap_nearest_u16: the depth remap stand-alone on a host image, the counterpart of vslam_remap_u8 (src rows x cols <= 32767 with
@@ -945,8 +950,8 @@ int vslam_rgbd_get_undistorted(vslam_rgbd* t, int32_t stream, uint8_t* image, ui
  * untouched (slam_assembly.cpp:406-409).  On the image queue, behind the undistortion of the image when that is on and ahead of the
  * detector, once per frame (further registration attempts read the equalised image again), inside the captured launch sequence as well.
  * A caller's device image is read only: it is equalised into an image of the tracker's own.  The switch survives vslam_rgbd_reset.
- * vslam_rgbd_set_equalization: VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type
- *   ORB), which does not have the feature; VSLAM_ERR_INVALID above 2^24 pixels.
+ * vslam_rgbd_set_equalization: VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop (VSLAM_RGBD_HOST=1),
+ *   which does not have the feature; VSLAM_ERR_INVALID above 2^24 pixels.
  * vslam_rgbd_get_equalized: the image (rows*cols bytes, dense) the last finished frame of `stream` was processed on; VSLAM_ERR_STATE
  *   when off, before a frame, or with a frame in flight. */
 int vslam_rgbd_set_equalization(vslam_rgbd* t, int on);
@@ -969,7 +974,7 @@ int vslam_rgbd_get_clahe_luts(vslam_rgbd* t, int32_t stream, uint8_t* luts);
  * device depth image is read only, and vslam_rgbd_get_undistorted keeps returning the unfiltered depth.  depth_scale is
  * depth_scale_factor_intensity_to_meters.  The switch survives vslam_rgbd_reset.  Nothing is launched or allocated while it is off.
  * vslam_rgbd_set_bilateral: a sigma of 0 selects the reference's 2.  VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop
- *   (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature; VSLAM_ERR_INVALID for a negative or non-finite sigma, a
+ *   (VSLAM_RGBD_HOST=1), which does not have the feature; VSLAM_ERR_INVALID for a negative or non-finite sigma, a
  *   radius above VSLAM_BILATERAL_MAX_RADIUS, a depth scale <= 0 or more than 2^24 pixels.
  * vslam_rgbd_get_bilateral: the switch and the sigmas in force (any pointer may be NULL).
  * vslam_rgbd_get_filtered_depth: the depth image (rows*cols uint16, dense) the last finished frame of `stream` was mapped from, and its
@@ -983,9 +988,12 @@ int vslam_rgbd_get_filtered_depth(vslam_rgbd* t, int32_t stream, uint16_t* depth
  * attempts included, inside the captured launch sequence as well; nothing is launched while it is off.  n_detected_left of the frame
  * report is the masked count.  The effective keep-mask of sequence s is (static mask AND undistortion validity AND frame mask of s),
  * each eroded by its own margin, a missing one all-keep.
+ * With p->detector_type = VSLAM_DETECTOR_ORB no mask is built: cv::ORB::detect resizes its mask for every pyramid level and the library
+ * has no restatement of that.  The three setters return VSLAM_ERR_STATE with a message that says so (switching a mask off is accepted),
+ * nothing changes and the next frame runs as if the call had not been made.
  * vslam_rgbd_set_detection_mask: host pointer, copied and packed before the call returns; NULL switches the mask off and frees it.  The
  *   mask survives vslam_rgbd_reset.  VSLAM_ERR_STATE with a frame in flight (between submit and wait), or on the host-driven loop
- *   (VSLAM_RGBD_HOST=1, detector_type ORB), which does not have the feature; VSLAM_ERR_INVALID (nothing changed) for a stride below cols
+ *   (VSLAM_RGBD_HOST=1), which does not have the feature; VSLAM_ERR_INVALID (nothing changed) for a stride below cols
  *   or a margin outside 0 .. 64.
  * vslam_rgbd_get_detection_mask: the packed keep-mask (rows * ((cols + 63) / 64) words) the last finished frame used; VSLAM_ERR_STATE
  *   when off, before a frame, after vslam_rgbd_reset, or with a frame in flight.  These are the context-wide words: the static mask
@@ -1023,7 +1031,7 @@ int vslam_rgbd_get_undistortion_mask(vslam_rgbd* t, int* on, int32_t* margin);
  * k_gray_u8 runs on the image queue ahead of the undistortion, the equalisation and the detector, once per frame (further registration
  * attempts read the grey image again), inside the captured launch sequence as well.  A caller's device image is read only.  The switch
  * survives vslam_rgbd_reset.
- * vslam_rgbd_set_color_input: VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB),
+ * vslam_rgbd_set_color_input: VSLAM_ERR_STATE with a frame in flight, or on the host-driven loop (VSLAM_RGBD_HOST=1),
  *   which does not have the feature; VSLAM_ERR_INVALID for a format outside 0 .. 4.
  * vslam_rgbd_get_gray: the grey image (dense, at the input size: the raw size while undistortion maps are set) of the last finished
  *   frame of `stream`; VSLAM_ERR_STATE when off, before a frame, after vslam_rgbd_reset, or with a frame in flight.  With equalisation on

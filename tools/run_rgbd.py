@@ -16,7 +16,10 @@ Colour images are converted like cv::imread(IMREAD_GRAYSCALE).  With a groundtru
 trajectory_analyzer (executables/trajectory_analyzer.cpp, restated in evaluation.py) reports the RMSE after its alignment.
 --map writes every landmark of the run (world frame) as a binary PLY (x y z id first_frame last_frame updates); --observations writes
 trajectory + landmark map + which landmark was seen in which frame at which pixel and depth into one .npz (io_formats.read_bundle_rgbd;
-implies the map) and reports the residuals of the log against map and trajectory.  Both need the device-resident loop (FAST detector).
+implies the map) and reports the residuals of the log against map and trajectory.  Both need the device-resident loop.
+--detector ORB runs the reference's OrbDetector (cv::ORB as detector: float keypoints of up to eight pyramid levels) on the device-resident
+loop as well, so it combines with every flag below but the masks: --mask, --frame-masks and --mask-invalid are refused with the library's
+message (cv::ORB::detect resizes its mask per pyramid level; the library has no restatement of that).
 --undistort takes the folder's frames as RAW ones of a camera with radial-tangential lens distortion and undoes it on the GPU ahead of the
 detector (vslam_rgbd_set_undistortion: image bilinear, depth nearest, one map for both — the depth images are registered to the colour
 camera); without a value the coefficients are io_formats.TUM_DISTORTION[--intrinsics].  The output camera is --intrinsics' pinhole
@@ -54,7 +57,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, hip, io_formats  # noqa: E402
-from vslam_pose_estimation_framework_amd.capi import DepthParams, RgbdTracker  # noqa: E402
+from vslam_pose_estimation_framework_amd.capi import DepthParams, RgbdTracker, VslamError  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from run_kitti import MOTION_MODELS, check_motion_args  # noqa: E402  (--motion-model / --odometry / --dead-reckoning-limit: one set of rules)
@@ -158,6 +161,14 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             int(own.sum()), n, odometry, ", dead-reckoning limit %d" % dead_reckoning_limit if dead_reckoning_limit else ""))
     tr = RgbdTracker(api, cfg, p, device)
     poses, flags, tracking, dead_reckoned = [], 0, 0, 0
+
+    def refusable(set_mask):                     # --detector ORB takes no mask: the run ends with the library's own words
+        try:
+            set_mask()
+        except VslamError as e:
+            if detector != 1:
+                raise
+            raise SystemExit(str(e))
     want_map = bool(map_path or obs_path)        # the log's ids are the map's
     lm_map = obs = None
     t0 = time.perf_counter()
@@ -187,12 +198,12 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             mk = io_formats.read_png_gray8(mask)
             if mk.shape != (int(cfg.rows), int(cfg.cols)):
                 raise SystemExit("--mask: %s is %dx%d, the detector works on %dx%d images" % (mask, mk.shape[0], mk.shape[1], cfg.rows, cfg.cols))
-            tr.set_detection_mask(mk, mask_margin)
+            refusable(lambda: tr.set_detection_mask(mk, mask_margin))
             log("detection mask: %s, margin %d px (no keypoints on its zero pixels, every re-registration attempt included)" % (mask, mask_margin))
         if mask_invalid is not None:
             if dist is None:
                 raise SystemExit("--mask-invalid: nothing is undistorted, there are no maps to take a validity mask from")
-            tr.set_undistortion_mask(True, mask_invalid)
+            refusable(lambda: tr.set_undistortion_mask(True, mask_invalid))
             log("validity mask from the undistortion maps on the GPU: %.1f %% of the pixels have every tap inside the raw frame, margin %d px" % (
                 100.0 * float(rectify.validity(und.map_xy, und.map_a, und.raw_rows, und.raw_cols).mean()), mask_invalid))
         if frame_masks:
@@ -224,7 +235,7 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
                     mk = io_formats.read_png_gray8(mpath)
                     if mk.shape != (int(cfg.rows), int(cfg.cols)):
                         raise SystemExit("--frame-masks: %s is %dx%d, the detector works on %dx%d images" % (mpath, mk.shape[0], mk.shape[1], cfg.rows, cfg.cols))
-                    tr.set_frame_mask(mk, mask_margin)
+                    refusable(lambda: tr.set_frame_mask(mk, mask_margin))
                     masked_frames += 1
             fi, n_temp = tr.process(gray, depth)
             dead_reckoned += int(motion_model == "odometry" and fi.fallback == 1)

@@ -403,15 +403,8 @@ VS_API int vslam_orb_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int3
   if (!img || !n || nlevels < 1 || nlevels > 16 || nfeatures < 0 || patch < 3 || patch > 63 || cap < 0 || (cap && !keypoints) || row_stride < cols ||
       !(scale_factor > 1.f) || edge < patch / 2 + 1 || edge < 4 || rows < 2 * edge + 8 || cols < 2 * edge + 8 || rows > 32767 || cols > 32767)
     return fail(c, VSLAM_ERR_INVALID, "orb_detect: bad argument");
-  // features per level (orb.cpp computeKeyPoints), float arithmetic as upstream
-  std::vector<int> per(nlevels);
-  {
-    const float factor = (float)(1.0 / scale_factor);
-    float nd = nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
-    int sum = 0;
-    for (int l = 0; l < nlevels - 1; ++l) { per[l] = (int)std::lrint(nd); sum += per[l]; nd *= factor; }
-    per[nlevels - 1] = std::max(nfeatures - sum, 0);
-  }
+  // level sizes, scales and features per level (orb.cpp computeKeyPoints): orb_plan.h, shared with the device-resident RGB-D loop
+  const OrbPlan plan = orb_plan(rows, cols, nfeatures, scale_factor, nlevels, edge);
   const int half = patch / 2;
   const OrbUmax um = orb_umax_table(half);
   hipStream_t st = c->stream;
@@ -429,11 +422,10 @@ VS_API int vslam_orb_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int3
   }
   std::vector<vslam_ctx*> scratch;
   StreamState sst;
-  for (int l = 0; l < nlevels && k.ok() && rc == VSLAM_OK; ++l) {
-    const float sc = (float)std::pow((double)scale_factor, (double)l);
+  for (int l = 0; l < plan.n_levels && k.ok() && rc == VSLAM_OK; ++l) {
+    const float sc = plan.scale[l];
     if (l > 0) {
-      const int nr = (int)std::lrint(rows / sc), nc = (int)std::lrint(cols / sc);
-      if (nr < 2 * edge + 8 || nc < 2 * edge + 8) break;
+      const int nr = plan.rows[l], nc = plan.cols[l];
       const int ns = (nc + 63) & ~63;
       uint8_t* dl = k.dev<uint8_t>((size_t)nr * ns);
       if (!k.ok()) break;
@@ -458,9 +450,9 @@ VS_API int vslam_orb_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int3
     if (!k.ok()) break;
     launch_fast_box(t, st, 1);
     hipLaunchKernelGGL(k_emit, dim3(1, 1), dim3(512), 0, st, t->cfg, t->buf, edge, 0);                                  // runByImageBorder(edgeThreshold)
-    hipLaunchKernelGGL(k_orb_select<uint8_t>, dim3(1), dim3(1024), 0, st, t->buf.n_kp, t->buf.kp_xy, t->buf.kp_score, 2 * per[l], n1, xy1, r1, (int)N);   // retainBest(2 n) on the FAST score
+    hipLaunchKernelGGL(k_orb_select<uint8_t>, dim3(1), dim3(1024), 0, st, t->buf.n_kp, t->buf.kp_xy, t->buf.kp_score, 2 * plan.quota[l], n1, xy1, r1, (int)N);   // retainBest(2 n) on the FAST score
     hipLaunchKernelGGL(k_orb_harris, dim3(256), dim3(256), 0, st, lev, lstride, n1, xy1, rh);
-    hipLaunchKernelGGL(k_orb_select<float>, dim3(1), dim3(1024), 0, st, n1, xy1, rh, per[l], n2, xy2, r2, (int)N);            // retainBest(n) on the Harris response
+    hipLaunchKernelGGL(k_orb_select<float>, dim3(1), dim3(1024), 0, st, n1, xy1, rh, plan.quota[l], n2, xy2, r2, (int)N);            // retainBest(n) on the Harris response
     hipLaunchKernelGGL(k_orb_angle, dim3(256), dim3(256), 0, st, lev, lstride, n2, xy2, r2, half, um, (float*)nullptr, dout, dtotal, cap, sc, l, patch);
     hipLaunchKernelGGL(k_orb_advance, dim3(1), dim3(1), 0, st, dtotal, n2);
     k.launched();

@@ -3,6 +3,7 @@
 #pragma once
 // Two implementations behind the same entry points: the device-resident loop (csrc/rgbd_device.h + kernels_rgbd.h; the default) and the
 // host-driven loop over the library's own stand-alone entry points (csrc/rgbd_tracker.h; VSLAM_RGBD_HOST=1), kept as the cross-check.
+// Both serve detector_type FAST and ORB.
 #include "rgbd_tracker.h"
 #include "rgbd_device.h"
 struct vslam_rgbd {
@@ -18,11 +19,11 @@ static int rgbd_create(const vslam_config* cfg, const vslam_depth_params* p, int
   if (!cfg || !p || !out) { g_rgbd_error = "vslam_rgbd_create: null argument"; return VSLAM_ERR_INVALID; }
   vslam_rgbd* r = new vslam_rgbd;
   if (const char* e = std::getenv("VSLAM_RGBD_HOST")) r->on_host = std::atoi(e) != 0;
-  // detector_type ORB (no shipped configuration): the OrbDetector is a host-driven sequence of per-level kernels (vslam_orb_detect) and several
-  // features can share a pixel — the device-resident loop's image pipeline is FAST's; the host-driven loop serves this mode
-  if (p->detector_type == VSLAM_DETECTOR_ORB) r->on_host = true;
+  // detector_type ORB: the device-resident loop runs the OrbDetector on its own queue (kernels_rgbd_orb.h) for detector grids whose regions
+  // all have one size (up to 2 x 2: every shipped configuration); a larger grid keeps the host-driven loop, with its refusals
+  if (p->detector_type == VSLAM_DETECTOR_ORB) { if (!vs_rgbd::DeviceTracker::orb_grid_supported(*cfg)) r->on_host = true; }
   else if (p->detector_type != VSLAM_DETECTOR_FAST) { g_rgbd_error = "vslam_rgbd_create: unknown detector_type"; delete r; return VSLAM_ERR_INVALID; }
-  if (r->on_host && n_streams != 1) { g_rgbd_error = "vslam_rgbd_create_batch: the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) tracks one sequence per object"; delete r; return VSLAM_ERR_INVALID; }
+  if (r->on_host && n_streams != 1) { g_rgbd_error = "vslam_rgbd_create_batch: the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB on a grid above 2 x 2) tracks one sequence per object"; delete r; return VSLAM_ERR_INVALID; }
   const int rc = r->on_host ? r->t.create(*cfg, *p, device) : r->d.create(*cfg, *p, device, n_streams);
   if (rc != VSLAM_OK) { g_rgbd_error = r->err(); delete r; return rc; }
   *out = r;
@@ -124,7 +125,7 @@ VS_API int vslam_rgbd_get_points_stream(vslam_rgbd* r, int32_t stream, int32_t c
 }
 // ---- the RGB-D landmark map and observation log (kernels_rgbd_map.h): the device-resident loop only ----
 static int rgbd_map_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) keeps no landmark map or observation log; use the device-resident loop";
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) keeps no landmark map or observation log; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
 VS_API int vslam_rgbd_enable_map(vslam_rgbd* r, int32_t cap) {
@@ -169,7 +170,7 @@ VS_API int vslam_rgbd_get_map_colors(vslam_rgbd* r, int32_t stream, int32_t firs
 }
 // ---- undistortion of raw frames (kernels_undistort.h): the device-resident loop only ----
 static int rgbd_undistort_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes undistorted frames only; use the device-resident loop";
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) takes undistorted frames only; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
 VS_API int vslam_rgbd_set_undistortion(vslam_rgbd* r, int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a) {
@@ -182,7 +183,7 @@ VS_API int vslam_rgbd_get_undistorted(vslam_rgbd* r, int32_t stream, uint8_t* im
 }
 // ---- histogram equalisation of the intensity image (kernels_equalize.h): the device-resident loop only ----
 static int rgbd_equalize_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) does not equalise; use the device-resident loop";
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not equalise; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
 VS_API int vslam_rgbd_set_equalization(vslam_rgbd* r, int on) {
@@ -195,7 +196,7 @@ VS_API int vslam_rgbd_get_equalized(vslam_rgbd* r, int32_t stream, uint8_t* imag
 }
 // ---- the static detection mask (kernels_mask.h): the device-resident loop only ----
 static int rgbd_mask_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes no detection mask; use the device-resident loop";
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) takes no detection mask; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
 VS_API int vslam_rgbd_set_detection_mask(vslam_rgbd* r, const uint8_t* mask, int32_t row_stride, int32_t margin) {
@@ -234,7 +235,7 @@ VS_API int vslam_rgbd_get_clahe_luts(vslam_rgbd* r, int32_t stream, uint8_t* lut
 }
 // ---- bilateral filtering of the depth image (kernels_bilateral.h): the device-resident loop only ----
 static int rgbd_bilateral_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) does not filter the depth image; use the device-resident loop";
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not filter the depth image; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
 VS_API int vslam_rgbd_set_bilateral(vslam_rgbd* r, int on, double sigma_color, double sigma_space) {
@@ -252,7 +253,7 @@ VS_API int vslam_rgbd_get_filtered_depth(vslam_rgbd* r, int32_t stream, uint16_t
 }
 // ---- colour input (kernels_gray.h): the device-resident loop only ----
 static int rgbd_color_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB) takes grey frames only; use the device-resident loop";
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) takes grey frames only; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
 VS_API int vslam_rgbd_set_color_input(vslam_rgbd* r, int format) {
@@ -281,7 +282,7 @@ static int rgbd_set_guess(vslam_rgbd* r, int32_t stream, const double* T, bool o
   if (!r->on_host) return r->d.set_pose_guess(stream, T, on_device);
   if (!T) { r->t.err = "vslam_rgbd_set_pose_guess: null pose"; return VSLAM_ERR_INVALID; }
   if (stream > 0) { r->t.err = "stream index out of range"; return VSLAM_ERR_INVALID; }
-  if (on_device) { r->t.err = "vslam_rgbd_set_pose_guesses: device memory on the host-driven loop (VSLAM_RGBD_HOST=1, detector_type ORB)"; return VSLAM_ERR_STATE; }
+  if (on_device) { r->t.err = "vslam_rgbd_set_pose_guesses: device memory on the host-driven loop (VSLAM_RGBD_HOST=1)"; return VSLAM_ERR_STATE; }
   if (r->host_pending) { r->t.err = "RGB-D tracker: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
   std::memcpy(r->t.guess, T, 96);
   return VSLAM_OK;

@@ -85,6 +85,9 @@ struct RgbdBuf {
   int16_t* a_kxy; uint8_t* a_desc; uint8_t* a_score; int32_t* a_rowcell; int32_t* a_order; uint8_t* a_vis;
   int16_t* t_kxy; uint8_t* t_desc; uint8_t* t_score; int32_t* t_order; int32_t* m_rank;
   uint8_t* fvis;
+  // detector_type ORB (kernels_rgbd_orb.h): the float keypoint and the pyramid level of every feature of the store, beside the lattice pixel in
+  // the inner context's kp_xy; null with the FAST detector, whose keypoint is its pixel
+  float* fkxy; uint8_t* flvl;
   int32_t ncsr;               // rows * (CW + 1): entries of a row / cell CSR
   // space map
   const uint16_t* depth; unsigned long long* dkey; int32_t* dlast; float* space; int16_t* row_map; int16_t* col_map;
@@ -121,6 +124,7 @@ __device__ __forceinline__ RgbdBuf rgbd_stream(const RgbdBuf& a, int stream) {
   r.order += s * N; r.matched += s * N;
   r.a_kxy += s * N * 2; r.a_desc += s * N * 32; r.a_score += s * N; r.a_rowcell += s * (size_t)a.ncsr; r.a_order += s * N; r.a_vis += s * N;
   r.t_kxy += s * N * 2; r.t_desc += s * N * 32; r.t_score += s * N; r.t_order += s * N; r.m_rank += s * N * 2; r.fvis += s * N;
+  if (r.fkxy) { r.fkxy += s * N * 2; r.flvl += s * N; }
   r.depth += s * X; r.dkey += s * X; r.dlast += s * X; r.space += s * X * 3; r.row_map += s * X; r.col_map += s * X;
   r.hold += s * N * 2; r.pick += s * P; r.cand += s * P * (VS_DT_K + 1); r.out2 += s * P * 2; r.xyz += s * P * 3; r.temp2 += s * P * 2; r.lost_raw += s * P;
   r.lost += s * P; r.lost_has += s * P; r.lost_lm += s * P * 3; r.lost_desc += s * P * 32;
@@ -145,6 +149,8 @@ __device__ __forceinline__ RgbdList rgbd_pick(const RgbdBuf& r, bool second) {
 __device__ __forceinline__ RgbdList rgbd_cur(const RgbdBuf& r) { return rgbd_pick(r, (r.st->frame_count & 1) != 0); }
 __device__ __forceinline__ RgbdList rgbd_prev(const RgbdBuf& r) { return rgbd_pick(r, (r.st->frame_count & 1) == 0); }
 
+// coordinate e (2 * feature + axis) of a feature's keypoint: the OrbDetector's float keypoint, else the FAST corner's pixel
+__device__ __forceinline__ float rgbd_kp(const RgbdBuf& r, const int16_t* kxy, int e) { return r.fkxy ? r.fkxy[e] : (float)kxy[e]; }
 __device__ __forceinline__ void rgbd_copy_desc(uint8_t* dst, const uint8_t* src) {
   const uint4 a = reinterpret_cast<const uint4*>(src)[0], b = reinterpret_cast<const uint4*>(src)[1];
   reinterpret_cast<uint4*>(dst)[0] = a; reinterpret_cast<uint4*>(dst)[1] = b;
@@ -386,7 +392,7 @@ __global__ __launch_bounds__(1024) void k_rgbd_track(const DevCfg c, const DevBu
   // frame->points().clear(); one framepoint per tracked point (Frame::createFramepoint + setPrevious, frame_point.cpp:43-55)
   for (int u = tid; u < nt; u += NT) {
     const int i = r.out2[2 * u], f = r.out2[2 * u + 1];
-    cur.xy[2 * u] = (float)kxy[2 * f]; cur.xy[2 * u + 1] = (float)kxy[2 * f + 1];
+    cur.xy[2 * u] = rgbd_kp(r, kxy, 2 * f); cur.xy[2 * u + 1] = rgbd_kp(r, kxy, 2 * f + 1);
     rgbd_copy_desc(cur.desc + (size_t)32 * u, a.desc + (size_t)32 * f);
     for (int k = 0; k < 3; ++k) cur.cam[3 * (size_t)u + k] = r.xyz[3 * (size_t)u + k];
     const int fl = pv.flags[i];
@@ -400,7 +406,7 @@ __global__ __launch_bounds__(1024) void k_rgbd_track(const DevCfg c, const DevBu
   // matches on pixels without a depth measurement: temporary points (:247-256); they are NOT cleared between registration attempts
   for (int u = tid; u < ntmp; u += NT) {
     const int i = r.temp2[2 * u], f = r.temp2[2 * u + 1], j = t0 + u;
-    tp.xy[2 * j] = (float)kxy[2 * f]; tp.xy[2 * j + 1] = (float)kxy[2 * f + 1];
+    tp.xy[2 * j] = rgbd_kp(r, kxy, 2 * f); tp.xy[2 * j + 1] = rgbd_kp(r, kxy, 2 * f + 1);
     rgbd_copy_desc(tp.desc + (size_t)32 * j, a.desc + (size_t)32 * f);
     for (int k = 0; k < 3; ++k) tp.cam[3 * (size_t)j + k] = 0.0;
     const int fl = pv.flags[i];
@@ -874,7 +880,7 @@ __global__ __launch_bounds__(1024) void k_rgbd_finish(const DevCfg c, const DevB
   const int n_all = min(nT + nn + t0 + nq, c.MAXP);
   for (int k = tid; k < nn; k += NT) {
     const int g = r.remf[r.new_feat[k]], j = nT + k;
-    cur.xy[2 * j] = (float)kxy[2 * g]; cur.xy[2 * j + 1] = (float)kxy[2 * g + 1];
+    cur.xy[2 * j] = rgbd_kp(r, kxy, 2 * g); cur.xy[2 * j + 1] = rgbd_kp(r, kxy, 2 * g + 1);
     rgbd_copy_desc(cur.desc + (size_t)32 * j, kdesc + (size_t)32 * g);
     for (int q = 0; q < 3; ++q) { cur.cam[3 * (size_t)j + q] = r.new_xyz[3 * (size_t)k + q]; cur.lmw[3 * (size_t)j + q] = 0; }
     cur.prev[j] = -1; cur.tlen[j] = 0; cur.flags[j] = 0; cur.lmu[j] = 0; cur.lmm[j] = 0;
@@ -884,7 +890,7 @@ __global__ __launch_bounds__(1024) void k_rgbd_finish(const DevCfg c, const DevB
   for (int u = tid; u < t0 && np + u < c.MAXP; u += NT) { RgbdPoint q; rgbd_load(tp, u, q); rgbd_store(cur, np + u, q); }
   for (int k = tid; k < nq; k += NT) {
     const int g = r.remf[r.temp_feat[k]], j = np + t0 + k;
-    cur.xy[2 * j] = (float)kxy[2 * g]; cur.xy[2 * j + 1] = (float)kxy[2 * g + 1];
+    cur.xy[2 * j] = rgbd_kp(r, kxy, 2 * g); cur.xy[2 * j + 1] = rgbd_kp(r, kxy, 2 * g + 1);
     rgbd_copy_desc(cur.desc + (size_t)32 * j, kdesc + (size_t)32 * g);
     for (int q = 0; q < 3; ++q) { cur.cam[3 * (size_t)j + q] = r.temp_xyz[3 * (size_t)k + q]; cur.lmw[3 * (size_t)j + q] = 0; }
     cur.prev[j] = -1; cur.tlen[j] = 0; cur.flags[j] = RGBD_F_UNREL; cur.lmu[j] = 0; cur.lmm[j] = 0;

@@ -7,11 +7,14 @@
 // workgroup per sequence in the single-workgroup kernels, a grid dimension in the wide ones —, a step takes the time of its slowest sequence.  When
 // the registration asks for another attempt (RgbdState::done still 0 after the tail skipped itself: pose_tracker_3d.cpp:333-418, a lost
 // track), the block image pipeline .. aligner .. tail is enqueued again, at most twice.
+// detector_type ORB (kernels_rgbd_orb.h): the image pipeline of an attempt is enqueue_orb_detect instead — the OrbDetector of every region on
+// pyramids of the region's view, the extractor on the whole image, k_orbd_install — and the rest of the frame is the same launches.
 #pragma once
 #include "kernels_rgbd.h"
 #include "kernels_rgbd_map.h"
 #include "kernels_undistort.h"
 #include "kernels_bilateral.h"
+#include "kernels_rgbd_orb.h"
 
 namespace vs_rgbd {
 
@@ -28,6 +31,9 @@ public:
   std::string failed_why;
 
   ~DeviceTracker() { release(); }
+  // detector_type ORB on this loop: every region of the grid has the size of the first (grids of up to two rows and two columns: all shipped
+  // RGB-D configurations)
+  static bool orb_grid_supported(const vslam_config& cfg) { return cfg.det_rows <= 2 && cfg.det_cols <= 2; }
 
   int create(const vslam_config& c, const vslam_depth_params& dp, int device, int n_streams = 1) {
     cfg = c; p = dp; B = n_streams;
@@ -79,6 +85,7 @@ public:
     if (const char* g = std::getenv("VSLAM_RGBD_GRAPH")) use_graph = std::atoi(g) != 0;
     if (e != hipSuccess) { err = std::string("RGB-D mode: ") + hipGetErrorString(e); release(); return VSLAM_ERR_HIP; }
     rb.depth = d_depth;
+    if (p.detector_type == VSLAM_DETECTOR_ORB) { rc = orb_create(); if (rc != VSLAM_OK) { release(); return rc; } }
     {   // the premise of k_depth_direct, as kernels_depth.h depth_source tests it
       const double* Ki = p.K_right_inverse; const double* K = p.K_left; const double* T = p.right_to_left;
       depth_plain = Ki[1] == 0 && Ki[3] == 0 && Ki[6] == 0 && Ki[7] == 0 && Ki[8] == 1 && K[1] == 0 && K[3] == 0 && K[6] == 0 && K[7] == 0 && K[8] == 1 &&
@@ -398,7 +405,14 @@ public:
   // (set_undistortion_mask); a frame mask per sequence (set_frame_masks) is packed, eroded and ANDed with them once per frame into
   // dmask.eff [B][rows][TX], ahead of the first detection.  k_mask_apply ANDs the frame's words into the corner words between k_fast_box
   // and k_emit of every attempt (enqueue_attempt), inside the captured launch sequence as well.
+  // detector_type ORB: cv::ORB::detect resizes its mask for every pyramid level, and nothing here restates that: masks are refused, the context
+  // stays as it was
+  int orb_mask_refusal(const char* what) {
+    err = std::string(what) + ": detection masks are not built for detector_type ORB (cv::ORB::detect resizes its mask per pyramid level; the library has no restatement of that)";
+    return VSLAM_ERR_STATE;
+  }
   int set_detection_mask(const uint8_t* mask, int32_t row_stride, int32_t margin) {
+    if (orbdet && mask) return orb_mask_refusal("vslam_rgbd_set_detection_mask");
     if (pending) { err = "vslam_rgbd_set_detection_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if (mask && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_detection_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
     if (mask && row_stride < p.cols) { err = "vslam_rgbd_set_detection_mask: row stride smaller than image width"; return VSLAM_ERR_INVALID; }
@@ -438,6 +452,7 @@ public:
   }
   // the undistortion maps' validity as part of the context-wide keep-mask (k_map_valid, once per call and per new maps)
   int set_undistortion_mask(int on, int32_t margin) {
+    if (orbdet && on) return orb_mask_refusal("vslam_rgbd_set_undistortion_mask");
     if (pending) { err = "vslam_rgbd_set_undistortion_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if (on && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_undistortion_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
     if (on && !und.on) { err = "vslam_rgbd_set_undistortion_mask: no undistortion maps are set (vslam_rgbd_set_undistortion)"; return VSLAM_ERR_STATE; }
@@ -459,6 +474,7 @@ public:
   // One mask per sequence for the next submit only: sequence s at masks + s * image_stride; null cancels a pending set.  Host masks are
   // copied by that submit; device masks are read by its one pack launch and never written.
   int set_frame_masks(const uint8_t* masks, int32_t row_stride, size_t image_stride, int32_t margin, bool on_device) {
+    if (orbdet && masks) return orb_mask_refusal("vslam_rgbd_set_frame_masks");
     if (pending) { err = "vslam_rgbd_set_frame_masks: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if (!masks) { dmask.fm_pending = false; return VSLAM_OK; }
     if (margin < 0 || margin > VS_MASK_MAX_MARGIN) { err = "vslam_rgbd_set_frame_masks: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
@@ -844,6 +860,7 @@ private:
   void enqueue_attempt(const DevBuf& b, bool again = false) {
     const DevCfg& d = ic->cfg;
     const dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, B);
+    if (orbdet) { enqueue_orb_detect(b, again); enqueue_registration(b); return; }
     if (again) hipLaunchKernelGGL(k_rgbd_save_features, dim3(B), dim3(1024), 0, q, d, b, rb);
     hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, q, d, b);
     const bool orb = d.c.descriptor_type == VSLAM_DESCRIPTOR_ORB;
@@ -865,10 +882,137 @@ private:
       hipLaunchKernelGGL(k_brief, g3, dim3(256), 0, q, d, b);
     }
     if (again) hipLaunchKernelGGL(k_rgbd_merge_features, dim3(B), dim3(1024), 0, q, d, b, rb);
+    enqueue_registration(b);
+  }
+  void enqueue_registration(const DevBuf& b) {
+    const DevCfg& d = ic->cfg;
     if (depth_pending) { (void)hipStreamWaitEvent(q, ev_depth, 0); depth_pending = false; }     // the space map is first read here
     hipLaunchKernelGGL(k_rgbd_track_candidates, dim3(std::max(8, std::min(256, 4096 / B)), B), dim3(256), 0, q, d, b, rb);
     hipLaunchKernelGGL(k_rgbd_track, dim3(B), dim3(wg1), 0, q, d, b, rb);
     hipLaunchKernelGGL(k_rgbd_align, dim3(B), dim3(VS_WG), 0, q, d, b, rb);
+  }
+
+  // ---- detector_type ORB (kernels_rgbd_orb.h) ------------------------------------------------------------------------------------------------
+  // Launches of one attempt, whatever the batch size and the detector grid (L <= 8: the levels a region holds): 1 (level 0, thresholds)
+  // + (L - 1) resizes + 2 L (k_fast_box, k_emit per level) + 5 (two selects, Harris, control, angle) + the extractor's + 1 (install).
+  // The ORB extractor adds k_gauss7, (L - 1) resizes of the whole image, (L - 1) Gaussians and the describe kernel = 2 L (one region that
+  // is the whole image: the pyramid is the detector's, L + 1); BRIEF adds k_fast_box for the box image and its describe kernel = 2.
+  // Together 5 L + 6 (ORB extractor on a grid), 4 L + 7 (ORB extractor, one region), 3 L + 8 (BRIEF), then the three registration launches.
+  bool orbdet = false;
+  OrbDet od{};
+  OrbDet* d_od = nullptr;
+  std::vector<DevCfg> lcfg;      // the level contexts: what k_fast_box / k_emit take, level-sized, their streams the (sequence, region) pairs
+  std::vector<DevBuf> lbuf;
+  bool walias = false;           // one region that is the whole image: the extractor's pyramid is the detector's
+  std::vector<uint8_t*> wraw;    // else the whole image's levels 1 .. L - 1, [B][wrows * wstride]
+  int orb_create() {
+    const DevCfg& d = ic->cfg;
+    const int R = d.n_regions, BR = B * R;
+    for (int r = 1; r < R; ++r)
+      if (d.regions[r].w != d.regions[0].w || d.regions[r].h != d.regions[0].h) { err = "RGB-D mode, detector_type ORB: detector regions of different sizes"; return VSLAM_ERR_INVALID; }
+    if (BR > VS_MAX_STREAMS) { err = "RGB-D mode, detector_type ORB: more than 4096 (sequence, region) pairs"; return VSLAM_ERR_INVALID; }
+    const int rr = d.regions[0].h, rc = d.regions[0].w;
+    if (rr < 2 * VS_ORBD_EDGE + 8 || rc < 2 * VS_ORBD_EDGE + 8) { err = "RGB-D mode, detector_type ORB: a detector region smaller than 70 pixels"; return VSLAM_ERR_INVALID; }
+    const OrbPlan plan = orb_plan(rr, rc, VS_ORBD_FEATURES, 1.2f, VS_ORBD_LEVELS, VS_ORBD_EDGE);
+    const OrbPlan whole = orb_plan(p.rows, p.cols, VS_ORBD_FEATURES, 1.2f, VS_ORBD_LEVELS, VS_ORBD_EDGE);
+    const int L = plan.n_levels;
+    const bool orb_ext = p.descriptor_type == VSLAM_DESCRIPTOR_ORB;
+    walias = R == 1 && rr == p.rows && rc == p.cols;
+    std::memset(&od, 0, sizeof od);
+    od.L = L; od.R = R; od.B = B; od.NMAX = d.NMAX;
+    for (int r = 0; r < R; ++r) { od.rx[r] = d.regions[r].x; od.ry[r] = d.regions[r].y; }
+    od.um = orb_umax_table(VS_ORBD_PATCH / 2);
+    hipError_t e = hipSuccess;
+    auto A = [&](auto** ptr, size_t count) {          // zeroed: counts, tickets and level states start from nothing
+      if (e == hipSuccess) e = dalloc(ic, ptr, count);
+      if (e == hipSuccess) e = hipMemset(*ptr, 0, std::max<size_t>(count, 1) * sizeof(**ptr));
+    };
+    lcfg.assign(L, DevCfg{}); lbuf.assign(L, DevBuf{}); wraw.assign(L, nullptr);
+    const size_t nBR = (size_t)BR, S2 = 2 * nBR, nB = (size_t)B, N = (size_t)d.NMAX;
+    for (int l = 0; l < L; ++l) {
+      OrbdLevel& v = od.lv[l];
+      v.rows = plan.rows[l]; v.cols = plan.cols[l]; v.stride = (v.cols + 63) & ~63; v.quota = plan.quota[l]; v.sc = plan.scale[l];
+      // corners that survive the strict 3 x 3 maximum never touch: one per 2 x 2 block at most; 65535 is the detector's own bound
+      v.nmax = (int32_t)std::max<size_t>(64, std::min<size_t>(65535, (size_t)((v.rows + 1) / 2) * ((v.cols + 1) / 2)));
+      vslam_config lc = d.c;
+      lc.rows = v.rows; lc.cols = v.cols; lc.det_rows = 1; lc.det_cols = 1; lc.max_keypoints = v.nmax;
+      lc.descriptor_type = VSLAM_DESCRIPTOR_ORB;      // no box image at the levels
+      derive_cfg(lc, BR, &lcfg[l]);
+      lcfg[l].mono = 1;
+      DevBuf& lb = lbuf[l];
+      std::memset(&lb, 0, sizeof lb);
+      const DevCfg& c = lcfg[l];
+      const size_t n = (size_t)v.nmax;
+      A(&v.pyr, nBR * v.rows * v.stride);
+      A(&lb.score8, S2 * v.rows * c.bstride); A(&lb.mask, S2 * v.rows * c.TX); A(&lb.kp_xy, S2 * n * 2); A(&lb.kp_score, S2 * n); A(&lb.n_kp, S2);
+      A(&lb.rowcell, S2 * v.rows * (c.CW + 1)); A(&lb.used, S2 * n); A(&lb.iinfo, nBR); A(&lb.st, nBR);
+      lb.img[0] = lb.img[1] = v.pyr; lb.img_row_stride = v.stride; lb.img_stream_stride = (size_t)v.rows * v.stride;
+      v.kp_xy = lb.kp_xy; v.kp_score = lb.kp_score; v.n_kp = lb.n_kp; v.st = lb.st;
+      A(&v.xy1, nBR * n * 2); A(&v.xy2, nBR * n * 2); A(&v.r1, nBR * n); A(&v.rh, nBR * n); A(&v.r2, nBR * n); A(&v.n1, nBR); A(&v.n2, nBR);
+      v.wrows = l ? whole.rows[l] : p.rows; v.wcols = l ? whole.cols[l] : p.cols; v.wstride = (v.wcols + 63) & ~63;
+      if (orb_ext && l > 0) {
+        if (walias) wraw[l] = v.pyr;
+        else A(&wraw[l], nB * v.wrows * v.wstride);
+        uint8_t* blur = nullptr;
+        A(&blur, nB * v.wrows * v.wstride);
+        v.wblur = blur;
+      }
+    }
+    A(&od.base, nB * (size_t)(R * L + 1)); A(&od.n_new, nB); A(&od.kp, nB * N * 4); A(&od.keep, nB * N); A(&od.kdesc, nB * N * 32);
+    A(&od.v_key, nB * N); A(&od.v_vp, nB * N); A(&od.v_lvl, nB * N); A(&od.v_fxy, nB * N * 2); A(&od.v_desc, nB * N * 32); A(&od.s_key, nB * N);
+    A(&od.bucket, nB * N); A(&od.row_start, nB * (size_t)(p.rows + 1)); A(&od.row_fill, nB * (size_t)(p.rows + 1));
+    A(&rb.fkxy, nB * N * 2); A(&rb.flvl, nB * N);
+    A(&d_od, 1);
+    if (e == hipSuccess) e = hipMemcpy(d_od, &od, sizeof od, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { err = std::string("RGB-D mode, detector_type ORB: ") + hipGetErrorString(e); return VSLAM_ERR_HIP; }
+    orbdet = true;
+    return VSLAM_OK;
+  }
+  void enqueue_orb_detect(const DevBuf& b, bool again) {
+    const DevCfg& d = ic->cfg;
+    const int R = od.R, L = od.L, BR = B * R;
+    uint32_t act[VS_MAX_STREAMS / 32];
+    std::memset(act, 0, sizeof act);
+    for (int s = 0; s < B; ++s)
+      if ((b.active[s >> 5] >> (s & 31)) & 1u) for (int r = 0; r < R; ++r) { const int z = s * R + r; act[z >> 5] |= 1u << (z & 31); }
+    const OrbdLevel& l0 = od.lv[0];
+    hipLaunchKernelGGL(k_orbd_begin, dim3((l0.cols + 255) / 256, l0.rows, BR), dim3(256), 0, q, d, b, d_od);
+    for (int l = 1; l < L; ++l) {
+      const OrbdLevel& u = od.lv[l - 1]; const OrbdLevel& v = od.lv[l];
+      hipLaunchKernelGGL(k_orbd_resize, dim3((v.cols + 255) / 256, v.rows, BR), dim3(256), 0, q, b, R, u.pyr, u.rows, u.cols, u.stride, (size_t)u.rows * u.stride,
+                         v.pyr, v.rows, v.cols, v.stride, (size_t)v.rows * v.stride);
+    }
+    for (int l = 0; l < L; ++l) {
+      std::memcpy(lbuf[l].active, act, sizeof act);
+      hipLaunchKernelGGL(k_fast_box, dim3(lcfg[l].TX, (lcfg[l].c.rows + VS_TILE_H - 1) / VS_TILE_H, BR), dim3(256), VS_FB_DYN_LDS, q, lcfg[l], lbuf[l]);
+      hipLaunchKernelGGL(k_emit, dim3(BR, 1), dim3(512), 0, q, lcfg[l], lbuf[l], (int)VS_ORBD_EDGE, 0);        // runByImageBorder(edgeThreshold)
+    }
+    hipLaunchKernelGGL(k_orbd_select_fast, dim3(BR, L), dim3(1024), 0, q, b, d_od);
+    const int gk = std::max(4, std::min(64, 8192 / (BR * L)));       // blocks of four wavefronts per (sequence, region, level) list
+    hipLaunchKernelGGL(k_orbd_harris, dim3(gk, BR, L), dim3(256), 0, q, b, d_od);
+    hipLaunchKernelGGL(k_orbd_select_harris, dim3(BR, L), dim3(1024), 0, q, b, d_od);
+    hipLaunchKernelGGL(k_orbd_control, dim3(B), dim3(64), 0, q, d, b, d_od);
+    hipLaunchKernelGGL(k_orbd_angle, dim3(gk, BR, L), dim3(256), 0, q, b, d_od);
+    const dim3 g1(d.TX, (d.c.rows + VS_TILE_H - 1) / VS_TILE_H, B);
+    const dim3 gd(std::max(4, std::min(64, 1024 / B)), B);
+    if (p.descriptor_type == VSLAM_DESCRIPTOR_ORB) {
+      Gauss7 g7; for (int i = 0; i < 4; ++i) g7.k[i] = d.gauss7[i];
+      hipLaunchKernelGGL(k_gauss7, g1, dim3(256), 0, q, d, b, g7);          // level 0's Gaussian: the image the recovery samples as well
+      const uint8_t* src = b.img[0]; int srows = d.c.rows, scols = d.c.cols, sstride = b.img_row_stride; size_t sstream = b.img_stream_stride;
+      for (int l = 1; l < L; ++l) {
+        const OrbdLevel& v = od.lv[l];
+        const size_t ws = (size_t)v.wrows * v.wstride;
+        if (!walias) hipLaunchKernelGGL(k_orbd_resize, dim3((v.wcols + 255) / 256, v.wrows, B), dim3(256), 0, q, b, 1, src, srows, scols, sstride, sstream, wraw[l], v.wrows, v.wcols, v.wstride, ws);
+        hipLaunchKernelGGL(k_orbd_gauss7, dim3((v.wcols + VS_TILE_W - 1) / VS_TILE_W, (v.wrows + VS_TILE_H - 1) / VS_TILE_H, B), dim3(256), 0, q, b, (const uint8_t*)wraw[l], v.wstride,
+                           v.wrows, v.wcols, ws, g7, const_cast<uint8_t*>(v.wblur), v.wstride, ws);
+        src = wraw[l]; srows = v.wrows; scols = v.wcols; sstride = v.wstride; sstream = ws;
+      }
+      hipLaunchKernelGGL(k_orbd_describe, gd, dim3(256), 0, q, d, b, d_od);
+    } else {
+      hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, q, d, b);       // the whole frame's box image (BRIEF here, and at the recovery)
+      hipLaunchKernelGGL(k_orbd_brief, gd, dim3(256), 0, q, d, b, d_od);
+    }
+    hipLaunchKernelGGL(k_orbd_install, dim3(B), dim3(1024), 0, q, d, b, rb, d_od, again ? 1 : 0);
   }
   void enqueue_tail(const DevBuf& b) {
     const DevCfg& d = ic->cfg;

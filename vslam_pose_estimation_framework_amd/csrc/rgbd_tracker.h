@@ -1,12 +1,13 @@
-// rgbd_tracker.h — WHY IT SHIPS IN THE PRODUCT LIBRARY: it is the only RGB-D loop that serves detector_type ORB (the device-resident
-// loop of rgbd_device.h runs the FAST detector grid only) and the independent second implementation the device loop is fuzzed against.
+// rgbd_tracker.h — WHY IT SHIPS IN THE PRODUCT LIBRARY: it is the independent second implementation the device-resident loop of
+// rgbd_device.h is compared with, for both detector types (VSLAM_RGBD_HOST=1); it also serves detector_type ORB on detector grids above
+// 2 x 2, whose regions differ in size.
 // RGB-D mode: PoseTracker3D with a DepthFramePointGenerator and a UVDAligner plugged in
 // (slam_assembly.cpp _createDepthTracker; pose_tracker_3d.cpp:32-566; depth_framepoint_generator.cpp:24-407; uvd_aligner.cpp),
 // as a HOST-DRIVEN loop: the tracker's control flow and the object bookkeeping (framepoints, links, temporary points, landmarks)
 // run here in C++, every data-parallel step is one of the library's own device entry points (vslam_depth_space_map /
 // _compute / _track / _recover, vslam_fast_detect, vslam_brief_describe | vslam_orb_describe, vslam_align_points_uvd,
 // vslam_landmark_update, vslam_point_in_camera).  The device-resident version of this loop is csrc/rgbd_device.h + kernels_rgbd.h (the
-// default behind vslam_rgbd_*); this one is its cross-check (VSLAM_RGBD_HOST=1) and serves detector_type ORB.  Detector grids of any shape (configuration_icl.yaml:57-58 runs 2 x 2; tum and
+// default behind vslam_rgbd_*); this one is its cross-check (VSLAM_RGBD_HOST=1).  Detector grids of any shape (configuration_icl.yaml:57-58 runs 2 x 2; tum and
 // xtion 1 x 1): one FAST detection, one threshold and one controller per region, keypoints in region-major order.
 //
 // Re-registration attempts of a frame ACCUMULATE its keypoints, as upstream: detectKeypoints appends to frame_->keypointsLeft(), which is
