@@ -320,6 +320,70 @@ int vslam_set_color_input(vslam_ctx* ctx, int format);
 int vslam_get_gray_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
 int vslam_gray_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride_bytes, int format,
                   uint8_t* dst /* dense */);
+/* ---- integer-factor reduction of images and depth images (csrc/kernels_downscale.h, downscale.py) ------------------------
+ * The project's own definition, all integer.  Factor f is 2, 3 or 4.  A full image of full_rows x full_cols gives full_rows / f x
+ * full_cols / f (integer division); the full_rows % f bottom rows and full_cols % f right columns are never read.  Both full sizes lie
+ * in 1 .. 32767 and give at least 1 x 1.
+ *   8 bit:  out[y][x] = (sum of the f x f block at (f y, f x) + f f / 2) / (f f), round half up.  At f = 2 that is (a + b + c + d + 2) >> 2,
+ *           which cv::resize(INTER_AREA) computes at an integer factor of 2 [recalled]; at 3 and 4 OpenCV goes through a float reciprocal
+ *           and may differ on ties.  Parity with OpenCV is not pinned.
+ *   depth:  the values are never blended (a mix across a depth edge invents a surface, as for the nearest-neighbour depth remap): the v
+ *           non-zero values of the block in ascending order, out = the element at index (v - 1) / 2, the lower median; 0 when v == 0.
+ * Calibration of the reduced image (the caller's arithmetic, downscale.py: scale_intrinsics / scale_projection; the library does not
+ * touch K): output pixel x covers full pixels f x .. f x + f - 1, so fx' = fx / f, fy' = fy / f, cx' = (cx + 0.5) / f - 0.5, cy'
+ * likewise, a projection matrix's P[0][3] is divided by f; baseline, distortion coefficients and depth scale are unchanged.
+ * vslam_downscale_u8 / vslam_downscale_depth_u16: the kernels (k_downscale_u8, k_downscale_depth_u16) stand-alone on one host image:
+ *   src is rows x cols (the FULL size) with row_stride bytes / elements per row, dst is rows / factor x cols / factor with
+ *   dst_row_stride, each at any alignment (2-byte for depth); what lies beyond the reduced width in a dst row is neither read nor written.
+ *   rows == 0 or cols == 0: VSLAM_OK, nothing written.  VSLAM_ERR_INVALID, nothing written: a factor outside 2 .. 4, null src / dst, a
+ *   negative size, row_stride < cols, dst_row_stride < cols / factor, a full size above 32767 or one that gives a 0-row or 0-column
+ *   result; the context stays usable.
+ * The stage (opt-in, the stereo context): colour -> grey -> DOWNSCALE -> rectify (when set) -> equalise / CLAHE (when set) -> detect.  One
+ * kernel (k_downscale_u8) per frame on the image pipeline's queue, all streams and both sides in one launch, under the fused entries and
+ * the stage path (vslam_frame_begin) alike.
+ * vslam_set_downscale: while factor is not 1, vslam_process_host, vslam_process_device and vslam_frame_begin take images of full_rows x
+ *   full_cols — colour images (vslam_set_color_input) of that size too.  full / factor must equal what the next stage expects: raw_rows x
+ *   raw_cols while rectification is set (the maps then address the REDUCED raw image; the maps' validity mask needs no change), else the
+ *   context's rows x cols; else VSLAM_ERR_INVALID, not sticky, nothing changed.  vslam_set_rectification makes the same check while this
+ *   switch is on, so the pair of setters is consistent in either order: with maps whose raw size differs from rows x cols, set the maps
+ *   first.  The context is created at the reduced size with the reduced calibration (downscale.py: apply_to_config); the library does
+ *   not touch K.  Detection masks stay at the processed size.  Host images are copied to full-size slabs of the stage's own (two
+ *   parities); device images are READ by this kernel only (colour ones by k_gray_u8, and by k_map_color while map colours are on) and
+ *   never written.  The reduced pair is written where the next stage reads.  A switched-off stream is neither read nor written.
+ *   Synchronises the context; VSLAM_ERR_STATE between vslam_frame_begin and the end of that frame; VSLAM_ERR_INVALID for a factor outside
+ *   1 .. 4 or a full size outside 1 .. 32767.  The switch survives vslam_reset and vslam_reset_stream(s).  factor 1 (the sizes are then
+ *   ignored) turns it off and frees its allocations; nothing is launched or allocated while off.
+ *   Map colours under the switch: k_map_color reads the caller's full-size colour image; each tap is the per-channel block average with
+ *   the rounding above, through the remap's four taps when rectification is on, each of them such an average.
+ * vslam_get_downscale: the switch in force; factor 1, sizes 0 while off.
+ * vslam_get_downscaled_images: the reduced pair of the last submitted frame of `stream` (full / factor, dense); VSLAM_ERR_STATE when the
+ *   switch is off or no frame has been submitted since it was set.  Synchronises.  With equalisation on and rectification off the pair
+ *   is equalised in place afterwards: this getter then returns the equalised pair, like vslam_get_equalized_images.  While the switch is
+ *   on, vslam_get_gray_images returns the full-size grey pair, which no later stage touches. */
+int vslam_set_downscale(vslam_ctx* ctx, int32_t factor, int32_t full_rows, int32_t full_cols);
+int vslam_get_downscale(vslam_ctx* ctx, int32_t* factor, int32_t* full_rows, int32_t* full_cols);
+int vslam_get_downscaled_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
+/* The same stage in RGB-D mode (the device-resident loop; the vslam_rgbd type is declared with that mode below).  The image: colour ->
+ * grey -> DOWNSCALE -> undistort -> equalise / CLAHE -> detect (the ORB detector of that loop included, which sits behind the stage).  The
+ * depth image, by the depth rule above: on the space map's queue behind the upload and ahead of the depth undistortion and the bilateral
+ * filter, once per frame, inside the captured launch sequence (VSLAM_RGBD_GRAPH=1) as well; toggling drops the captured sequence.
+ * vslam_rgbd_set_downscale: as vslam_set_downscale, with vslam_rgbd_set_undistortion in the place of vslam_set_rectification (the same
+ *   size check in both setters); the frame entries then take image AND depth image of full_rows x full_cols.  Host frames are copied to
+ *   full-size staging of the stage's own; caller device images are only read (depth images of a batch need no dense stream stride while
+ *   the switch is on).  VSLAM_ERR_STATE with a frame in flight, and on the host-driven loop (VSLAM_RGBD_HOST=1), which does not get the
+ *   feature.  The switch survives vslam_rgbd_reset.
+ * vslam_rgbd_get_downscale: the switch in force; factor 1, sizes 0 while off (and on the host-driven loop).
+ * vslam_rgbd_get_downscaled: the reduced image and depth image of the last finished frame of `stream` (dense, full / factor; either may
+ *   be NULL); VSLAM_ERR_STATE when off, before a frame, after a reset, with a frame in flight.  With equalisation on and undistortion off
+ *   the image is equalised in place afterwards and this getter returns the equalised image. */
+struct vslam_rgbd;
+int vslam_rgbd_set_downscale(struct vslam_rgbd* t, int32_t factor, int32_t full_rows, int32_t full_cols);
+int vslam_rgbd_get_downscale(struct vslam_rgbd* t, int32_t* factor, int32_t* full_rows, int32_t* full_cols);
+int vslam_rgbd_get_downscaled(struct vslam_rgbd* t, int32_t stream, uint8_t* image /* may be NULL */, uint16_t* depth /* may be NULL */);
+int vslam_downscale_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int32_t factor, uint8_t* dst,
+                       int32_t dst_row_stride);
+int vslam_downscale_depth_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride /* elements */,
+                              int32_t factor, uint16_t* dst, int32_t dst_row_stride);
 /* ---- detection masks: keep keypoints off masked pixels (opt-in; csrc/kernels_mask.h, mask.py) ----------------------------
  * cv::Feature2D::detect(image, keypoints, mask) [recalled]: the detector and its non-maximum suppression run on the whole image, and
  * every keypoint whose pixel reads 0 in the mask is dropped afterwards (KeyPointsFilter::runByPixelsMask), ahead of the count the

@@ -48,14 +48,14 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, hip, io_formats  # noqa: E402
+from vslam_pose_estimation_framework_amd import color as color_mod, downscale as downscale_mod, evaluation, hip, io_formats  # noqa: E402
 
 
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
 
 
 def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None, mask_invalid=None):
+                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None, mask_invalid=None, downscale=None):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -66,6 +66,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
     api.create(cfg, device, len(plan))
     if rect is not None:
         api.set_rectification(rect)
+    if downscale is not None:
+        api.set_downscale(*downscale)
     if mask_invalid is not None:
         api.set_rectification_mask(True, mask_invalid)
     if equalize:
@@ -83,7 +85,7 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
     api.set_motion_model(motion_model, dead_reckoning_limit)
     if masks is not None:
         masks.set_static(api)
-    rows, cols = (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
+    rows, cols = downscale[1:] if downscale is not None else (rect.raw_rows, rect.raw_cols) if rect is not None else (int(cfg.rows), int(cfg.cols))
     Lb = np.zeros((len(plan), rows, cols) + ((3,) if color else ()), np.uint8)
     Rb = np.zeros_like(Lb)
     live = [True] * len(plan)
@@ -117,8 +119,10 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
         chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8), map_color=False,
-        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, mask=None, mask_margin=0, frame_masks=None, mask_invalid=None):
+        motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, mask=None, mask_margin=0, frame_masks=None, mask_invalid=None,
+        downscale=1):
     check_mask_args(mask, mask_margin, frame_masks, SystemExit, mask_invalid, rectify)
+    check_downscale_arg(downscale, SystemExit)
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -137,13 +141,22 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     api = hip.load()
     cfg = api.default_config("euroc" if euroc and which == "kitti" else which)
     rect = None
+    ds = None                          # (factor, full rows, full cols) under --downscale
+    if downscale != 1:
+        try:
+            downscale_mod.output_size(left.shape[0], left.shape[1], downscale)
+        except ValueError as e:
+            raise SystemExit("--downscale: %s" % e)
+        ds = (int(downscale), int(left.shape[0]), int(left.shape[1]))
     if rectify:
         from vslam_pose_estimation_framework_amd import rectify as rectify_mod
         raw = seq.raw_calibration()
         if raw is None:
             raise SystemExit("--rectify: no mav0/cam0/sensor.yaml and mav0/cam1/sensor.yaml under %s" % seq_dir)
-        if (raw[0].rows, raw[0].cols) != left.shape:
+        if (raw[0].rows, raw[0].cols) != left.shape[:2]:
             raise SystemExit("--rectify: sensor.yaml says %dx%d, the images are %dx%d" % (raw[0].rows, raw[0].cols, left.shape[0], left.shape[1]))
+        if ds is not None:             # the raw cameras of the reduced images: the maps are built over them
+            raw = tuple(rectify_mod.CameraModel(downscale_mod.scale_intrinsics(c.K, ds[0]), c.dist, c.rows // ds[0], c.cols // ds[0]) for c in raw[:2]) + tuple(raw[2:])
         rect = rectify_mod.rectification(*raw)
         rectify_mod.apply_to_config(cfg, rect)
         log("rectifying on the GPU: raw %dx%d -> %dx%d, f %.3f px, baseline %.4f m" % (
@@ -166,6 +179,11 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
                 log("note: sensor.yaml describes distorted raw cameras and there is no calib.txt; --rectify rectifies them on the GPU")
     else:
         io_formats.apply_calib(cfg, seq.K, seq.baseline, left.shape[0], left.shape[1])
+    if ds is not None:
+        if rect is None:
+            downscale_mod.apply_to_config(cfg, ds[0])
+        log("downscaling on the GPU by %d: %dx%d -> %dx%d, ahead of %s; calibration scaled (f %.3f px, c %.3f %.3f)" % (
+            ds[0], ds[1], ds[2], ds[1] // ds[0], ds[2] // ds[0], "the rectification" if rect is not None else "the detector", cfg.K[0], cfg.K[2], cfg.K[5]))
     if color:
         log("colour cameras (image_2 / image_3, calibration P2 / P3): RGB -> grey on the GPU, ahead of %s" % ("the equalisation" if equalize else "CLAHE" if clahe is not None else "the detector"))
     if equalize:
@@ -188,7 +206,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
                                                 equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles, map_color=map_color,
-                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks, mask_invalid=mask_invalid)
+                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks, mask_invalid=mask_invalid, downscale=ds)
         tracking = None
         dead_reckoned = None
     else:
@@ -196,6 +214,8 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
         api.create(cfg, device, 1)
         if rect is not None:
             api.set_rectification(rect)
+        if ds is not None:
+            api.set_downscale(*ds)
         if mask_invalid is not None:
             api.set_rectification_mask(True, mask_invalid)
         if equalize:
@@ -360,6 +380,11 @@ def check_mask_args(mask, mask_margin, frame_masks, error, mask_invalid=None, re
 MOTION_MODELS = {"constant-velocity": 0, "none": 1, "odometry": 2}     # enum vslam_motion_model
 
 
+def check_downscale_arg(downscale, error):
+    if isinstance(downscale, bool) or not isinstance(downscale, int) or downscale < 1 or downscale > 4:
+        raise error("--downscale: a whole factor in 1 .. 4 (1: off)")
+
+
 def check_motion_args(motion_model, odometry, dead_reckoning_limit, error):
     """What --motion-model, --odometry and --dead-reckoning-limit allow together (tools/run_rgbd.py takes the same flags)."""
     if motion_model not in MOTION_MODELS:
@@ -419,11 +444,15 @@ def parse_args(argv=None):
     ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask / --frame-masks by N pixels (0 .. 64)")
     ap.add_argument("--mask-invalid", nargs="?", type=int, const=0, default=None, metavar="N", help="with --rectify: no keypoints on pixels whose source lies "
                     "partly outside the raw image (the seam between picture and black fill), computed from the maps on the GPU, both sides; N widens it (0 .. 64)")
+    ap.add_argument("--downscale", type=int, default=1, metavar="N", help="reduce every image by the whole factor N (2, 3 or 4) on the GPU ahead of everything but "
+                    "the colour conversion: rounded block averages; the folder's calibration is scaled and the tracker runs at the reduced size "
+                    "(masks are given at that size); combines with every other switch")
     ap.add_argument("--frame-masks", default=None, metavar="DIR", help="per-frame detection masks: a folder that mirrors the sequence's two image folders "
                     "file name for file name; a missing file means no mask for that frame")
     a = ap.parse_args(argv)
     try:
         check_mask_args(a.mask, a.mask_margin, a.frame_masks, ValueError, a.mask_invalid, a.rectify)
+        check_downscale_arg(a.downscale, ValueError)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
@@ -439,7 +468,7 @@ def main(argv=None):
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
         rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
         map_color=a.map_color, motion_model=a.motion_model, odometry=a.odometry, dead_reckoning_limit=a.dead_reckoning_limit,
-        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid)
+        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid, downscale=a.downscale)
 
 
 if __name__ == "__main__":

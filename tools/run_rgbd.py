@@ -56,7 +56,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from vslam_pose_estimation_framework_amd import color as color_mod, evaluation, hip, io_formats  # noqa: E402
+from vslam_pose_estimation_framework_amd import color as color_mod, downscale as downscale_mod, evaluation, hip, io_formats  # noqa: E402
 from vslam_pose_estimation_framework_amd.capi import DepthParams, RgbdTracker, VslamError  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -129,8 +129,10 @@ def distortion_of(undistort, intrinsics):
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
         gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
         map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None, mask=None, mask_margin=0,
-        frame_masks=None, mask_invalid=None):
+        frame_masks=None, mask_invalid=None, downscale=1):
     check_mask_args(mask, mask_margin, SystemExit, frame_masks, mask_invalid, undistort)
+    if isinstance(downscale, bool) or not isinstance(downscale, int) or downscale < 1 or downscale > 4:
+        raise SystemExit("--downscale: a whole factor in 1 .. 4 (1: off)")
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
     if map_color and not (color and (map_path or obs_path)):
         raise SystemExit("--map-color needs --color and --map or --observations")
@@ -146,7 +148,15 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     else:
         gray, depth = seq.frame(0)
     api = hip.load()
-    cfg, p = configure(api, which, gray.shape[0], gray.shape[1], K, depth_unit, descriptor, detector, depth_scale)
+    full_rows, full_cols = int(gray.shape[0]), int(gray.shape[1])
+    rows, cols = full_rows, full_cols
+    if downscale != 1:                           # the camera of the reduced frames: tracker, depth parameters and undistortion maps are built on it
+        try:
+            rows, cols = downscale_mod.output_size(full_rows, full_cols, downscale)
+        except ValueError as e:
+            raise SystemExit("--downscale: %s" % e)
+        K = downscale_mod.scale_intrinsics(K, downscale)
+    cfg, p = configure(api, which, rows, cols, K, depth_unit, descriptor, detector, depth_scale)
     dist = distortion_of(undistort, intrinsics)
     if dist is None and any(io_formats.TUM_DISTORTION.get(intrinsics, ())):
         log("note: the %s camera has lens distortion (k1 %g, k2 %g, ...) and the frames are used as they are; --undistort undoes it on the GPU" % (
@@ -175,10 +185,15 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
     try:
         if dist is not None:
             from vslam_pose_estimation_framework_amd import rectify
-            und = rectify.undistortion(rectify.CameraModel(K, dist, gray.shape[0], gray.shape[1]))
+            und = rectify.undistortion(rectify.CameraModel(K, dist, rows, cols))
             tr.set_undistortion(und)
             log("undistorting on the GPU: %dx%d, k1 %g k2 %g p1 %g p2 %g k3 %g, %.1f %% of the pixels have a source inside the raw frame" % (
                 (und.rows, und.cols) + tuple(dist) + (100.0 * float(np.mean(rectify.remap_nearest_u16(np.ones((und.raw_rows, und.raw_cols), np.uint16), und.map_xy, und.map_a))),)))
+        if downscale != 1:
+            tr.set_downscale(downscale, full_rows, full_cols)
+            log("downscaling on the GPU by %d: %dx%d -> %dx%d (image: rounded block averages; depth: lower median of the valid values), ahead of %s; "
+                "calibration scaled (f %.3f px, c %.3f %.3f)" % (downscale, full_rows, full_cols, rows, cols, "the undistortion" if dist is not None else "the detector",
+                                                               K[0, 0], K[0, 2], K[1, 2]))
         if fmt != color_mod.GRAY8:
             tr.set_color_input(fmt)
             log("colour frames (%s): converted to grey on the GPU, ahead of %s" % (color_mod.NAMES[fmt], "the undistortion" if dist is not None else "the detector"))
@@ -370,6 +385,9 @@ def parse_args(argv=None):
     ap.add_argument("--mask", default=None, metavar="MASK.png", help="detection mask for the whole run: an 8-bit PNG at the processed size (the undistorted "
                     "one under --undistort), zero = no keypoints on that pixel (the robot's own body, overlays, vignetted corners)")
     ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask and --frame-masks by N pixels (0 .. 64)")
+    ap.add_argument("--downscale", type=int, default=1, metavar="N", help="reduce every image and depth image by the whole factor N (2, 3 or 4) on the GPU ahead "
+                    "of everything but the colour conversion: rounded block averages, and for depth the lower median of a block's valid values; the "
+                    "intrinsics are scaled and the tracker runs at the reduced size (masks are given at that size); combines with every other switch")
     ap.add_argument("--frame-masks", default=None, metavar="DIR", help="a mask per frame (a segmentation network's output): a folder of 8-bit PNGs at the "
                     "processed size, named like the frames' files under rgb/; a frame without a file has no mask of its own")
     ap.add_argument("--mask-invalid", nargs="?", type=int, const=0, default=None, metavar="N", help="with --undistort: no keypoints on pixels whose source "
@@ -380,6 +398,8 @@ def parse_args(argv=None):
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
+    if a.downscale < 1 or a.downscale > 4:
+        ap.error("--downscale: a whole factor in 1 .. 4 (1: off)")
     if a.clahe is not None and a.equalize:
         ap.error("--clahe and --equalize exclude each other: one equalisation ahead of the detector")
     if a.map_color and not (a.color and (a.map or a.observations)):
@@ -408,7 +428,7 @@ def main(argv=None):
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
         map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles, motion_model=a.motion_model, odometry=a.odometry,
         dead_reckoning_limit=a.dead_reckoning_limit,
-        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid)
+        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid, downscale=a.downscale)
 
 
 if __name__ == "__main__":

@@ -189,6 +189,7 @@ class CApi(object):
         self.cfg = cfg.copy()
         self.n_streams = n_streams
         self.rect = None
+        self._ds_state = None
         self.color = 0
         return self
 
@@ -235,17 +236,15 @@ class CApi(object):
                 left, right = left[None], right[None]
             assert left.ndim == 4 and left.shape[3] == ch, (left.shape, ch)
             n, rows, cols = left.shape[:3]
-            want = (self.rect.raw_rows, self.rect.raw_cols) if getattr(self, "rect", None) is not None else (self.cfg.rows, self.cfg.cols)
+            want = self._incoming_size()
             assert left.shape == right.shape and n == self.n_streams and (rows, cols) == want, (left.shape, right.shape, want)
             self.check(self.fn("process_host")(self.ctx, _p(left, C.c_uint8), _p(right, C.c_uint8), C.c_int32(cols * ch), C.c_size_t(rows * cols * ch)))
             return
         if left.ndim == 2:
             left, right = left[None], right[None]
         assert left.shape == right.shape and left.shape[0] == self.n_streams
-        if getattr(self, "rect", None) is not None:      # rectifying context: raw images
-            assert left.shape[1] == self.rect.raw_rows and left.shape[2] >= self.rect.raw_cols, (left.shape, self.rect.raw_rows, self.rect.raw_cols)
-        else:
-            assert left.shape[1] == self.cfg.rows and left.shape[2] >= self.cfg.cols
+        want = self._incoming_size()                      # downscaling context: full images; rectifying context: raw images
+        assert left.shape[1] == want[0] and left.shape[2] >= want[1], (left.shape, want)
         stride = left.shape[2]
         self.check(self.fn("process_host")(self.ctx, _p(left, C.c_uint8), _p(right, C.c_uint8),
                                            C.c_int32(stride), C.c_size_t(left.shape[1] * stride)))
@@ -256,6 +255,37 @@ class CApi(object):
 
     def synchronize(self):
         self.check(self.fn("synchronize")(self.ctx))
+
+    def _incoming_size(self):
+        """(rows, cols) of the frames the frame entries take: the full size while downscaling, else the raw size of a rectifying context,
+        else the context's own."""
+        ds = getattr(self, "_ds_state", None)
+        if ds is not None:
+            return ds[1], ds[2]
+        rect = getattr(self, "rect", None)
+        return (int(rect.raw_rows), int(rect.raw_cols)) if rect is not None else (int(self.cfg.rows), int(self.cfg.cols))
+
+    # -- integer-factor reduction of the incoming frames (vslam_set_downscale; definition: downscale.py) -----------------------
+    def set_downscale(self, factor, full_rows=0, full_cols=0):
+        """factor 2 .. 4: the frame entries take images of full_rows x full_cols (colour images too) and reduce them on the device ahead
+        of rectification; full // factor must be the raw size of a rectifying context, else the context's own.  factor 1: off."""
+        self.check(self.fn("set_downscale")(self.ctx, C.c_int32(int(factor)), C.c_int32(int(full_rows)), C.c_int32(int(full_cols))))
+        self._ds_state = None if int(factor) == 1 else (int(factor), int(full_rows), int(full_cols))
+
+    def downscale(self):
+        """(factor, full_rows, full_cols) in force; (1, 0, 0) while off."""
+        f, r, c_ = C.c_int32(), C.c_int32(), C.c_int32()
+        self.check(self.fn("get_downscale")(self.ctx, C.byref(f), C.byref(r), C.byref(c_)))
+        return f.value, r.value, c_.value
+
+    def downscaled_images(self, stream=0):
+        """The reduced pair the last submitted frame of `stream` was downscaled to (full // factor)."""
+        f, r, c_ = self.downscale()
+        rows, cols = (r // f, c_ // f) if f > 1 else (int(self.cfg.rows), int(self.cfg.cols))
+        L = np.zeros((rows, cols), np.uint8)
+        R = np.zeros((rows, cols), np.uint8)
+        self.check(self.fn("get_downscaled_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
+        return L, R
 
     # -- rectification of raw pairs (vslam_set_rectification) ---------------------------------------------------------
     def set_rectification(self, rect):
@@ -338,8 +368,7 @@ class CApi(object):
 
     def gray_images(self, stream=0):
         """The grey pair the last submitted frame of `stream` was converted to, at the input size (the raw size of a rectifying context)."""
-        rect = getattr(self, "rect", None)
-        rows, cols = (int(rect.raw_rows), int(rect.raw_cols)) if rect is not None else (int(self.cfg.rows), int(self.cfg.cols))
+        rows, cols = self._incoming_size()
         L = np.zeros((rows, cols), np.uint8)
         R = np.zeros((rows, cols), np.uint8)
         self.check(self.fn("get_gray_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
@@ -942,6 +971,37 @@ class CApi(object):
                                       _p(dst, C.c_uint8)))
         return dst
 
+    def _downscale(self, name, dtype, image, factor, out, row_stride, dst_row_stride):
+        size = np.dtype(dtype).itemsize
+        img = np.asarray(image)
+
+        def plain(a):
+            return a.dtype == dtype and a.ndim == 2 and (a.shape[1] <= 1 or a.strides[1] == size) and \
+                (a.shape[0] <= 1 or (a.strides[0] >= size * a.shape[1] and a.strides[0] % size == 0))
+        if not plain(img):
+            raise ValueError("%s: a 2-D %s array with unit column stride is required" % (name, np.dtype(dtype).name))
+        rows, cols = img.shape
+        f = int(factor)
+        orows, ocols = (rows // f, cols // f) if f > 0 else (0, 0)
+        dst = np.zeros((orows, ocols), dtype) if out is None else out
+        if not plain(dst) or dst.shape != (orows, ocols):
+            raise ValueError("%s: out is not a 2-D %s array of %d x %d with unit column stride" % (name, np.dtype(dtype).name, orows, ocols))
+        stride = lambda a: a.strides[0] // size if a.shape[0] > 1 else max(a.shape[1], 1)
+        self.check(self.fn(name)(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(cols),
+                                 C.c_int32(stride(img) if row_stride is None else int(row_stride)), C.c_int32(f), C.c_void_p(dst.ctypes.data),
+                                 C.c_int32(stride(dst) if dst_row_stride is None else int(dst_row_stride))))
+        return dst
+
+    def downscale_u8(self, image, factor, out=None, row_stride=None, dst_row_stride=None):
+        """vslam_downscale_u8: image (and out, when given) is a 2-D uint8 array or view with unit column stride; row strides and alignments
+        are passed on as they are.  out=None: a dense result.  row_stride / dst_row_stride (bytes) override the arrays' own, for the
+        refusal tests.  -> uint8 [rows // factor, cols // factor]."""
+        return self._downscale("downscale_u8", np.uint8, image, factor, out, row_stride, dst_row_stride)
+
+    def downscale_depth_u16(self, depth, factor, out=None, row_stride=None, dst_row_stride=None):
+        """vslam_downscale_depth_u16: as downscale_u8 on 2-D uint16 arrays or views; the strides are in elements."""
+        return self._downscale("downscale_depth_u16", np.uint16, depth, factor, out, row_stride, dst_row_stride)
+
     def sample_color_u8(self, image, fmt, xy, maps=None, cols=None):
         """vslam_sample_color_u8: image as in gray_u8 ([rows, cols, channels], or [rows, bytes] with cols, strides and alignment passed on);
         xy int16 [n, 2] (x, y); maps None or (map_xy int16 [R, C, 2], map_a uint16 [R, C]) -> uint8 [n, 3] (r, g, b)."""
@@ -1312,10 +1372,34 @@ class _RgbdColorApi(object):
 
     def gray(self, stream=0):
         """The grey image the last finished frame of `stream` was converted to, at the input size (the raw size while undistorting)."""
-        rows, cols = getattr(self, "_raw_size", None) or (int(self.cfg.rows), int(self.cfg.cols))
+        rows, cols = getattr(self, "_full_size", None) or getattr(self, "_raw_size", None) or (int(self.cfg.rows), int(self.cfg.cols))
         img = np.zeros((rows, cols), np.uint8)
         self._check(self.lib.vslam_rgbd_get_gray(self.h, C.c_int32(stream), _p(img, C.c_uint8)))
         return img
+
+
+class _RgbdDownscaleApi(object):
+    """vslam_rgbd_set_downscale / _get_downscale / _get_downscaled (the device-resident loop only), shared by RgbdTracker and RgbdBatch.
+    While the factor is not 1, process / submit take image and depth image of full_rows x full_cols."""
+
+    def set_downscale(self, factor, full_rows=0, full_cols=0):
+        self._check(self.lib.vslam_rgbd_set_downscale(self.h, C.c_int32(int(factor)), C.c_int32(int(full_rows)), C.c_int32(int(full_cols))))
+        self._full_size = None if int(factor) == 1 else (int(full_rows), int(full_cols))
+
+    def downscale(self):
+        """(factor, full_rows, full_cols) in force; (1, 0, 0) while off."""
+        f, r, c_ = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.vslam_rgbd_get_downscale(self.h, C.byref(f), C.byref(r), C.byref(c_)))
+        return f.value, r.value, c_.value
+
+    def downscaled(self, stream=0):
+        """(image, depth) the last finished frame of `stream` was downscaled to (full // factor)."""
+        f, r, c_ = self.downscale()
+        rows, cols = (r // f, c_ // f) if f > 1 else (int(self.cfg.rows), int(self.cfg.cols))
+        img = np.zeros((rows, cols), np.uint8)
+        dep = np.zeros((rows, cols), np.uint16)
+        self._check(self.lib.vslam_rgbd_get_downscaled(self.h, C.c_int32(stream), _p(img, C.c_uint8), _p(dep, C.c_uint16)))
+        return img, dep
 
 
 class _RgbdMotionApi(object):
@@ -1351,7 +1435,7 @@ def _row_bytes(left, image_ndim):
     return int(left.shape[-1]) if left.ndim == image_ndim else int(left.shape[-2] * left.shape[-1])
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdMotionApi):
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdDownscaleApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -1408,7 +1492,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilater
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdMotionApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdDownscaleApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

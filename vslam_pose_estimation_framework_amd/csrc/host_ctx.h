@@ -89,7 +89,12 @@ struct vslam_ctx {
   struct Col { int format = 0; bool have_frame = false; int slab_rows = 0, slab_cols = 0, stride = 0; size_t stream_stride = 0;
                uint8_t* slab[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
                DeviceStore mem; } col;
-  // this frame's routing through the three stages (route_frame, host_frame.h): the colour pair (a slab or the caller's device memory) and
+  // integer-factor reduction of the incoming frames (vslam_set_downscale, kernels_downscale.h): off while factor == 1.  full[step parity]
+  // [left/right]: the full-size grey slabs (B x full_rows x stride each) host frames are copied into and k_gray_u8 writes.
+  struct Ds { int factor = 1, full_rows = 0, full_cols = 0, stride = 0; size_t stream_stride = 0; bool have_frame = false;
+              uint8_t* full[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+              DeviceStore mem; } ds;
+  // this frame's routing through the input stages (route_frame, host_frame.h): the colour pair (a slab or the caller's device memory) and
   // where k_gray_u8 writes the grey pair, so where vslam_get_gray_images reads it; the raw pair k_rectify reads and the pair it writes
   PrePlan pre;
   // the landmark map (vslam_enable_map, kernels_map.h): off while cap == 0; its own allocations, freed by vslam_enable_map(0) and destroy
@@ -567,7 +572,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (auto& e : c->scratch) vslam_destroy(e.t);
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
-  for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem}) m->release();     // the input stages' stores
+  for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem, &c->ds.mem}) m->release();     // the input stages' stores
   for (DeviceStore* m : {&c->dmask.user_mem, &c->dmask.valid_mem, &c->dmask.comb_mem, &c->dmask.slab_mem, &c->dmask.eff_mem}) m->release();    // detection masks
   c->guess.mem.release();
   for (int q = 0; q < 2; ++q) { if (c->guess.pin[q]) (void)hipHostFree(c->guess.pin[q]); if (c->guess.pin_ev[q]) (void)hipEventDestroy(c->guess.pin_ev[q]); }

@@ -1051,6 +1051,59 @@ VS_API int vslam_gray_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t
   return k.finish();
 }
 
+// ---- integer-factor reduction of one host image / depth image (kernels_downscale.h) -------------------------------------
+// the checks the two entries share; *empty: a zero-size call, nothing to do
+static int downscale_entry_check(vslam_ctx* c, const char* who, const void* src, int32_t rows, int32_t cols, int32_t row_stride, int32_t factor, const void* dst,
+                                 int32_t dst_row_stride, bool* empty) {
+  *empty = false;
+  const std::string w(who);
+  if (rows < 0 || cols < 0) return fail(c, VSLAM_ERR_INVALID, w + ": negative size");
+  if (!ds_factor_ok(factor)) return fail(c, VSLAM_ERR_INVALID, w + ": factor outside 2 .. 4");
+  if (rows == 0 || cols == 0) { *empty = true; return VSLAM_OK; }
+  if (!ds_size_ok(rows, cols, factor)) return fail(c, VSLAM_ERR_INVALID, w + ": full size outside 1 .. 32767 or below one block");
+  if (!src || !dst || row_stride < cols || dst_row_stride < ds_out(cols, factor)) return fail(c, VSLAM_ERR_INVALID, w + ": bad argument");
+  return VSLAM_OK;
+}
+VS_API int vslam_downscale_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int32_t factor, uint8_t* dst,
+                              int32_t dst_row_stride) {
+  if (int rc = entry_begin(c)) return rc;
+  bool empty;
+  if (int rc = downscale_entry_check(c, "downscale_u8", src, rows, cols, row_stride, factor, dst, dst_row_stride, &empty)) return rc;
+  if (empty) return VSLAM_OK;
+  const int orows = ds_out(rows, factor), ocols = ds_out(cols, factor);
+  Call k(c, c->stream);
+  // the device copies keep the caller's alignment: rows start where they would in place.  Only what the blocks cover is copied.
+  const size_t bytes = (size_t)(orows * factor - 1) * row_stride + (size_t)ocols * factor, nd = (size_t)(orows - 1) * dst_row_stride + ocols;
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16) + (size_t)((uintptr_t)src & 15u);
+  k.up_to(ds, src, bytes);
+  uint8_t* dd = k.dev<uint8_t>(nd + 16) + (size_t)((uintptr_t)dst & 15u);
+  DownscaleArgs da{};
+  place(da, ds, row_stride, dd, dst_row_stride, orows, ocols);
+  da.factor = factor;
+  if (k.ok()) k.note(downscale_enqueue(c->stream, da));
+  if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)dst_row_stride, dd, (size_t)dst_row_stride, (size_t)ocols, (size_t)orows, hipMemcpyDeviceToHost, c->stream));
+  return k.finish();
+}
+VS_API int vslam_downscale_depth_u16(vslam_ctx* c, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride, int32_t factor, uint16_t* dst,
+                                     int32_t dst_row_stride) {
+  if (int rc = entry_begin(c)) return rc;
+  bool empty;
+  if (int rc = downscale_entry_check(c, "downscale_depth_u16", src, rows, cols, row_stride, factor, dst, dst_row_stride, &empty)) return rc;
+  if (empty) return VSLAM_OK;
+  const int orows = ds_out(rows, factor), ocols = ds_out(cols, factor);
+  Call k(c, c->stream);
+  // the device copies keep the caller's 4-byte phase: the kernel chooses its loads by it
+  const size_t ne = (size_t)(orows * factor - 1) * row_stride + (size_t)ocols * factor, nd = (size_t)(orows - 1) * dst_row_stride + ocols;
+  uint16_t* ds = k.dev<uint16_t>(ne + 2) + (((uintptr_t)src & 3u) >> 1);
+  k.up_to(ds, src, ne);
+  uint16_t* dd = k.dev<uint16_t>(nd + 2) + (((uintptr_t)dst & 3u) >> 1);
+  DownscaleDepthArgs da{};
+  da.src = ds; da.src_row_stride = row_stride; da.dst = dd; da.dst_row_stride = dst_row_stride; da.rows = orows; da.cols = ocols; da.n = 1; da.factor = factor;
+  if (k.ok()) k.note(downscale_depth_enqueue(c->stream, da));
+  if (k.ok()) k.note(hipMemcpy2DAsync(dst, (size_t)dst_row_stride * 2, dd, (size_t)dst_row_stride * 2, (size_t)ocols * 2, (size_t)orows, hipMemcpyDeviceToHost, c->stream));
+  return k.finish();
+}
+
 // ---- the colour of n pixels of one host image, direct or through a remap map pair (kernels_map_color.h) --------------
 VS_API int vslam_sample_color_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int format, const int16_t* map_xy,
                                  const uint16_t* map_a, int32_t map_rows, int32_t map_cols, const int16_t* xy, int32_t n, uint8_t* rgb) {

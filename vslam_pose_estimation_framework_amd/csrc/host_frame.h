@@ -68,6 +68,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
   if (c->rect.on) c->rect.have_frame = true;
   if (c->eq.on) c->eq.have_frame = true;
   if (c->col.format != VSLAM_PIXEL_GRAY8) c->col.have_frame = true;
+  if (c->ds.factor > 1) c->ds.have_frame = true;
   return VSLAM_OK;
 }
 static int frame_done(vslam_ctx* c) {
@@ -83,9 +84,12 @@ static int frame_done(vslam_ctx* c) {
 static int cand_blocks(int n_streams) { return std::max(4, std::min(128, 7040 / std::max(n_streams, 1))); }
 // blocks per stream of k_recover_brief (four wavefronts each, one lost point per wavefront)
 static int recover_blocks(int n_streams) { return std::max(4, std::min(64, 1024 / std::max(n_streams, 1))); }
-// this frame's left colour image as k_map_color reads it: the raw image behind the left rectification map while rectifying
+// this frame's left colour image as k_map_color reads it: the raw image behind the left rectification map while rectifying; while
+// downscaling the full-size image, tapped by block averages at the reduced size
 static ColorSrc map_color_src(const vslam_ctx* c) {
-  return color_src(c->pre.color, c->pre.in_rows, c->pre.in_cols, c->col.format, c->rect.on ? &c->rect.maps : nullptr);
+  const PrePlan& p = c->pre;
+  const bool ds = p.factor > 1;
+  return color_src(p.color, ds ? p.red_rows : p.in_rows, ds ? p.red_cols : p.in_cols, c->col.format, c->rect.on ? &c->rect.maps : nullptr, p.factor);
 }
 static int launch_frame(vslam_ctx* c) {
   const int n = c->B;
@@ -196,12 +200,16 @@ static void route_frame(vslam_ctx* c, const ImgPlanes& in) {
   const int set = c->parity;
   const ImgPlanes up = upload_planes(c, set);
   PrePlan& p = c->pre;
-  p.format = c->col.format; p.remap = c->rect.on;
+  p.format = c->col.format; p.remap = c->rect.on; p.factor = c->ds.factor;
   p.rows = c->cfg.c.rows; p.cols = c->cfg.c.cols;
-  p.in_rows = p.remap ? c->rect.maps.raw_rows : p.rows; p.in_cols = p.remap ? c->rect.maps.raw_cols : p.cols;
+  p.red_rows = p.remap ? c->rect.maps.raw_rows : p.rows; p.red_cols = p.remap ? c->rect.maps.raw_cols : p.cols;
+  p.in_rows = p.factor > 1 ? c->ds.full_rows : p.red_rows; p.in_cols = p.factor > 1 ? c->ds.full_cols : p.red_cols;
   ImgPlanes cur = in;                                  // where the pair lies behind the stages so far
   const vslam_ctx::Rect& r = c->rect;
-  if (p.format != VSLAM_PIXEL_GRAY8) { p.color = cur; p.gray = p.remap ? ImgPlanes{{r.raw[set][0], r.raw[set][1]}, r.raw_stride, r.raw_stream_stride} : up; cur = p.gray; }
+  const vslam_ctx::Ds& d = c->ds;
+  const ImgPlanes raw_slab = p.remap ? ImgPlanes{{r.raw[set][0], r.raw[set][1]}, r.raw_stride, r.raw_stream_stride} : up;     // what the remap, else the detector reads
+  if (p.format != VSLAM_PIXEL_GRAY8) { p.color = cur; p.gray = p.factor > 1 ? ImgPlanes{{d.full[set][0], d.full[set][1]}, d.stride, d.stream_stride} : raw_slab; cur = p.gray; }
+  if (p.factor > 1) { p.full = cur; p.reduced = raw_slab; cur = p.reduced; }
   if (p.remap) { p.raw = cur; p.mapped = rectified_planes(c, set); cur = p.mapped; }
   // equalised pair in upload[set]: in place when the input is already there (a host upload keeps the caller's strides), written there
   // from the rectified pair's own slabs or from the caller's device images, which these kernels alone read
@@ -209,15 +217,16 @@ static void route_frame(vslam_ctx* c, const ImgPlanes& in) {
   buf_set_planes(c->buf, cur);
 }
 // A frame's input pair.  Host images go to the slabs of this step's parity that the first stage reads — the colour slabs (upload_to with
-// the byte width as cols), the rectifier's raw slabs, else upload[parity]; device images are read in place, by the first stage alone
+// the byte width as cols), the downscale's full-size slabs, the rectifier's raw slabs, else upload[parity]; device images are read in place, by the first stage alone
 // (and, colour, by k_map_color behind the frame's last launch while map colours are on).
 static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
-  const bool colour = c->col.format != VSLAM_PIXEL_GRAY8, raw = c->rect.on;
-  const int rows = raw ? c->rect.maps.raw_rows : c->cfg.c.rows, cols = raw ? c->rect.maps.raw_cols : c->cfg.c.cols;
+  const bool colour = c->col.format != VSLAM_PIXEL_GRAY8, full = c->ds.factor > 1, raw = c->rect.on;
+  int rows, cols;
+  incoming_size(c, &rows, &cols);
   const int wb = colour ? gray_channels(c->col.format) * cols : cols;
   if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");  // stereo_framepoint_generator.cpp:75-78
   if (row_stride < wb)
-    return fail(c, VSLAM_ERR_INVALID, colour ? "row stride smaller than channels * image width" : raw ? "row stride smaller than the raw image width" : "row stride smaller than image width");
+    return fail(c, VSLAM_ERR_INVALID, colour ? "row stride smaller than channels * image width" : full ? "row stride smaller than the full image width" : raw ? "row stride smaller than the raw image width" : "row stride smaller than image width");
   ImgPlanes in = {{L, R}, row_stride, image_stride};
   if (!on_device) {
     // map colours: k_map_color read this parity's slab on the FRAME queue two steps ago, and the upload below is issued ahead of the wait in
@@ -231,6 +240,7 @@ static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t 
     }
     const int p = c->parity;
     const int rc = colour ? upload_to(c, L, R, row_stride, image_stride, rows, wb, c->col.slab[p], c->col.stride, c->col.stream_stride, &in)
+                   : full ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->ds.full[p], c->ds.stride, c->ds.stream_stride, &in)
                    : raw  ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->rect.raw[p], c->rect.raw_stride, c->rect.raw_stream_stride, &in)
                           : upload_to(c, L, R, row_stride, image_stride, rows, cols, c->upload[p], c->up_stride, c->up_stream_stride, &in);
     if (rc != VSLAM_OK) return rc;

@@ -1,5 +1,5 @@
 // host_prestage.h — the input stages ahead of the detector, written once for the stereo context and the RGB-D tracker: colour to grey
-// (kernels_gray.h), remap (rectification / undistortion, kernels_rectify.h) and the equalisation slot (global or CLAHE,
+// (kernels_gray.h), integer-factor reduction (kernels_downscale.h), remap (rectification / undistortion, kernels_rectify.h) and the equalisation slot (global or CLAHE,
 // kernels_equalize.h / kernels_clahe.h).  Where an image pair lies (ImgPlanes), the one filler of the kernels' argument blocks (place),
 // the slot (EqSlot), the intake of remap maps, the per-frame plan (PrePlan) with its one enqueue, the plane read-out of the getters and the
 // colour source of the map's colours.  Owner-independent host code: no context, no tracker; errors come back as hipError_t or as text.
@@ -178,30 +178,43 @@ struct EqSlot {
 //
 // Stereo (the final pair is always in upload[parity], except an untouched caller device pair):
 //   stage     reads                                                              writes
-//   grey      colour slab[parity] (host) or caller memory (device)               rect.raw[parity] if rectifying, else upload[parity]
-//   rectify   rect.raw[parity] (host or grey output) or caller memory            eq.keep if equalising, else upload[parity]
+//   grey      colour slab[parity] (host) or caller memory (device)               ds.full[parity] if downscaling, else rect.raw[parity] if
+//                                                                                rectifying, else upload[parity]
+//   downscale ds.full[parity] (host or grey output) or caller memory             rect.raw[parity] if rectifying, else upload[parity]
+//   rectify   rect.raw[parity] (host, grey or downscale output) or caller memory eq.keep if equalising, else upload[parity]
 //   equalise  eq.keep if rectifying, else DevBuf::img (in place when that        upload[parity]
 //             already is upload[parity])
 // RGB-D (single buffers; caller memory is never written):
 //   grey      d_img (host) or caller memory                                      col.gray
+//   downscale previous                                                           ds.img (the depth image: on the space map's queue)
 //   undistort previous                                                           und.img
 //   equalise  previous                                                           in place if the image is ours (host frame, grey,
 //                                                                                undistorted), else eq.img
 struct PrePlan {
   int format = 0;               // VSLAM_PIXEL_*: the grey stage runs unless GRAY8
   bool remap = false;
-  int in_rows = 0, in_cols = 0; // the frames that come in (the raw size while remapping)
+  int factor = 1;               // the downscale stage runs unless 1
+  int in_rows = 0, in_cols = 0; // the frames that come in (the full size while downscaling, else the raw size while remapping)
+  int red_rows = 0, red_cols = 0; // downscale: the reduced size (the raw size while remapping, else rows x cols)
   int rows = 0, cols = 0;       // the size the detector works on
   ImgPlanes color, gray;        // grey stage: source, result (in_rows x in_cols)
+  ImgPlanes full, reduced;      // downscale: source (in_rows x in_cols), result (red_rows x red_cols)
   ImgPlanes raw, mapped;        // remap: source (in_rows x in_cols), result (rows x cols)
 };
-// grey, then remap, then equalise, on one queue
+// grey, then downscale, then remap, then equalise, on one queue
 static hipError_t prestage_enqueue(hipStream_t st, const PrePlan& pl, const RemapMaps& maps, const EqSlot& eq, int n, int sides, const uint32_t* active) {
   if (pl.format != VSLAM_PIXEL_GRAY8) {
     GrayArgs ga{};
     place(ga, pl.color, pl.gray, pl.in_rows, pl.in_cols, n, sides, active);
     ga.format = pl.format;
     const hipError_t e = gray_enqueue(st, ga);
+    if (e != hipSuccess) return e;
+  }
+  if (pl.factor > 1) {
+    DownscaleArgs da{};
+    place(da, pl.full, pl.reduced, pl.red_rows, pl.red_cols, n, sides, active);
+    da.factor = pl.factor;
+    const hipError_t e = downscale_enqueue(st, da);
     if (e != hipSuccess) return e;
   }
   if (pl.remap) remap_enqueue(st, maps, pl.raw, pl.mapped, n, sides, active);
@@ -213,10 +226,13 @@ static hipError_t prestage_enqueue(hipStream_t st, const PrePlan& pl, const Rema
 static hipError_t planes_to_host(uint8_t* out, const ImgPlanes& x, int side, int s, int rows, int cols) {
   return hipMemcpy2D(out, (size_t)cols, x.p[side] + (size_t)s * x.stream_stride, (size_t)x.row_stride, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost);
 }
-// a frame's left colour image as the map-colour kernels read it: through the left map while remapping (maps non-null)
-static ColorSrc color_src(const ImgPlanes& colour, int rows, int cols, int format, const RemapMaps* maps) {
+// a frame's left colour image as the map-colour kernels read it: through the left map while remapping (maps non-null).  rows x cols: the
+// grid the taps are addressed in — the image's own size, or, while downscaling (factor > 1), the reduced size: a tap is then the rounded
+// average of its factor x factor block of the full-size colour image
+static ColorSrc color_src(const ImgPlanes& colour, int rows, int cols, int format, const RemapMaps* maps, int factor = 1) {
   ColorSrc s{};
   s.img = colour.p[0]; s.stream_stride = colour.stream_stride; s.row_stride = colour.row_stride; s.rows = rows; s.cols = cols; s.format = format;
+  s.factor = factor;
   if (maps) { s.map_xy = maps->xy[0]; s.map_a = maps->a[0]; s.map_stride = maps->stride; s.map_rows = maps->rows; s.map_cols = maps->cols; }
   return s;
 }

@@ -265,6 +265,28 @@ VS_API int vslam_rgbd_get_gray(vslam_rgbd* r, int32_t stream, uint8_t* image) {
   return r->on_host ? rgbd_color_host_refusal(r, "vslam_rgbd_get_gray") : r->d.get_gray(stream, image);
 }
 
+// ---- downscale of the incoming frames (the definition above vslam_downscale_u8) -------------------------------------------
+static int rgbd_downscale_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not downscale; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_downscale(vslam_rgbd* r, int32_t factor, int32_t full_rows, int32_t full_cols) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_downscale_host_refusal(r, "vslam_rgbd_set_downscale") : r->d.set_downscale(factor, full_rows, full_cols);
+}
+VS_API int vslam_rgbd_get_downscale(vslam_rgbd* r, int32_t* factor, int32_t* full_rows, int32_t* full_cols) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (!r->on_host) { r->d.get_downscale(factor, full_rows, full_cols); return VSLAM_OK; }
+  if (factor) *factor = 1;
+  if (full_rows) *full_rows = 0;
+  if (full_cols) *full_cols = 0;
+  return VSLAM_OK;
+}
+VS_API int vslam_rgbd_get_downscaled(vslam_rgbd* r, int32_t stream, uint8_t* image, uint16_t* depth) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_downscale_host_refusal(r, "vslam_rgbd_get_downscaled") : r->d.get_downscaled(stream, image, depth);
+}
+
 // ---- motion models (the definition above vslam_set_motion_model) ---------------------------------------------------------
 VS_API int vslam_rgbd_set_motion_model(vslam_rgbd* r, int model, int32_t dead_reckoning_limit) {
   if (!r) return VSLAM_ERR_INVALID;

@@ -1,5 +1,5 @@
 // host_switches.h — the stereo context's input-stage switches and their getters: rectification (vslam_set_rectification), the equalisation
-// slot (vslam_set_equalization, vslam_set_clahe) and colour input (vslam_set_color_input), the stores behind them, and the stand-alone
+// slot (vslam_set_equalization, vslam_set_clahe), colour input (vslam_set_color_input) and the downscale (vslam_set_downscale), the stores behind them, and the stand-alone
 // vslam_remap_u8; behind them the motion model and the pose guesses of CAMERA_ODOMETRY (vslam_set_motion_model, vslam_set_pose_guess*),
 // with launch_motion_prior, the head of the frame's launch sequence.  What the switches share with the RGB-D tracker is host_prestage.h; a frame's routing through the stages is route_frame
 // in host_frame.h.  Host code, included by vslam_hip.hip after host_ctx.h and ahead of host_frame.h.
@@ -31,12 +31,23 @@ static void col_free(vslam_ctx* c) {
   c->col.mem.release();
   c->col = vslam_ctx::Col();
 }
-// the colour slabs exist while the switch is on, at the size of the frames that come in: the raw size while rectification is set (called by
-// both setters, queues idle)
+static void ds_free(vslam_ctx* c) {
+  c->ds.mem.release();
+  c->ds = vslam_ctx::Ds();
+}
+// the size of the frames that come in: the full size while downscaling, else the raw size while rectification is set, else rows x cols
+static void incoming_size(const vslam_ctx* c, int* rows, int* cols) {
+  if (c->ds.factor > 1) { *rows = c->ds.full_rows; *cols = c->ds.full_cols; }
+  else if (c->rect.on) { *rows = c->rect.maps.raw_rows; *cols = c->rect.maps.raw_cols; }
+  else { *rows = c->cfg.c.rows; *cols = c->cfg.c.cols; }
+}
+// the colour slabs exist while the switch is on, at the size of the frames that come in (called by the three setters that change it,
+// queues idle)
 static hipError_t col_slab_sync(vslam_ctx* c) {
   vslam_ctx::Col& q = c->col;
   const int fmt = q.format;
-  const int rows = c->rect.on ? c->rect.maps.raw_rows : c->cfg.c.rows, cols = c->rect.on ? c->rect.maps.raw_cols : c->cfg.c.cols;
+  int rows, cols;
+  incoming_size(c, &rows, &cols);
   const int wb = fmt == VSLAM_PIXEL_GRAY8 ? 0 : gray_channels(fmt) * cols;
   if (fmt != 0 && q.slab[0][0] && q.slab_rows == rows && q.slab_cols == wb) return hipSuccess;
   col_free(c);
@@ -75,6 +86,13 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   bool off = false;
   std::string why;
   if (const int rc = remap_maps_check("vslam_set_rectification", 2, raw_rows, raw_cols, rows, cols, xy, a, &off, &why)) return fail(c, rc, why);
+  // while downscaling, the maps address the reduced raw image: full / factor is what this stage is handed
+  if (c->ds.factor > 1) {
+    const int want_rows = off ? rows : raw_rows, want_cols = off ? cols : raw_cols;
+    if (ds_out(c->ds.full_rows, c->ds.factor) != want_rows || ds_out(c->ds.full_cols, c->ds.factor) != want_cols)
+      return fail(c, VSLAM_ERR_INVALID, off ? "vslam_set_rectification: the downscaled frames (vslam_set_downscale) do not have the context's size"
+                                            : "vslam_set_rectification: the raw size is not the size of the downscaled frames (vslam_set_downscale)");
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the old maps and raw slabs
   rect_free(c);
@@ -210,6 +228,51 @@ VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* ri
   if (c->col.format == VSLAM_PIXEL_GRAY8 || !c->col.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_gray_images: no frame has been converted since vslam_set_color_input");
   if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_gray_images: null output");
   return pair_to_host(c, c->pre.gray, s, c->pre.in_rows, c->pre.in_cols, left, right);
+}
+
+// ---- integer-factor reduction of the incoming frames (kernels_downscale.h) ----------------------------------------
+VS_API int vslam_set_downscale(vslam_ctx* c, int32_t factor, int32_t full_rows, int32_t full_cols) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_downscale called inside a frame");
+  if (factor != 1) {
+    if (!ds_factor_ok(factor)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_downscale: factor outside 1 .. 4");
+    if (!ds_size_ok(full_rows, full_cols, factor)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_downscale: full size outside 1 .. 32767 or below one block");
+    const int want_rows = c->rect.on ? c->rect.maps.raw_rows : c->cfg.c.rows, want_cols = c->rect.on ? c->rect.maps.raw_cols : c->cfg.c.cols;
+    if (ds_out(full_rows, factor) != want_rows || ds_out(full_cols, factor) != want_cols)
+      return fail(c, VSLAM_ERR_INVALID, c->rect.on ? "vslam_set_downscale: full size / factor is not the raw size of the rectification maps"
+                                                   : "vslam_set_downscale: full size / factor is not the context's image size");
+  }
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  const vslam_ctx::Ds& q = c->ds;
+  if (factor == 1 ? q.factor == 1 : (q.factor == factor && q.full_rows == full_rows && q.full_cols == full_cols)) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the slabs
+  ds_free(c);
+  hipError_t e = hipSuccess;
+  if (factor != 1) {
+    vslam_ctx::Ds& d = c->ds;
+    d.factor = factor; d.full_rows = full_rows; d.full_cols = full_cols;
+    d.stride = (full_cols + 63) & ~63;
+    d.stream_stride = (size_t)full_rows * d.stride;
+    for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = d.mem.alloc(&d.full[p][k], (size_t)c->B * d.stream_stride);
+  }
+  if (e == hipSuccess) e = col_slab_sync(c);     // colour frames come in at the new size
+  if (e != hipSuccess) { ds_free(c); (void)col_slab_sync(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_downscale: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_downscale(vslam_ctx* c, int32_t* factor, int32_t* full_rows, int32_t* full_cols) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (factor) *factor = c->ds.factor;
+  if (full_rows) *full_rows = c->ds.factor > 1 ? c->ds.full_rows : 0;
+  if (full_cols) *full_cols = c->ds.factor > 1 ? c->ds.full_cols : 0;
+  return VSLAM_OK;
+}
+VS_API int vslam_get_downscaled_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (c->ds.factor == 1 || !c->ds.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_downscaled_images: no frame has been downscaled since vslam_set_downscale");
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_downscaled_images: null output");
+  return pair_to_host(c, c->pre.reduced, s, c->pre.red_rows, c->pre.red_cols, left, right);
 }
 
 // ---- motion models and the pose guesses of CAMERA_ODOMETRY (kernels_motion.h) --------------------------------------

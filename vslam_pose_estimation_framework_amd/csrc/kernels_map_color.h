@@ -30,6 +30,7 @@
 #include "kernels_frame.h"
 #include "kernels_map.h"
 #include "kernels_rgbd_map.h"
+#include "downscale_geometry.h"   // ds_round: a tap's block average while the frames are downscaled
 
 #define VS_MAP_COLOR_WG 1024
 
@@ -37,16 +38,28 @@
 struct ColorSrc {
   const uint8_t* img;
   size_t stream_stride;
-  int32_t row_stride, rows, cols;     // bytes per row; pixels
+  int32_t row_stride, rows, cols;     // bytes per row; pixels of the grid the taps are addressed in (the reduced size while factor > 1)
   int32_t format;                     // VSLAM_PIXEL_BGR8 .. VSLAM_PIXEL_RGBA8
   const int16_t* map_xy;              // [map_rows][map_stride][2], null: direct
   const uint16_t* map_a;              // [map_rows][map_stride], values < 1024
   int32_t map_stride, map_rows, map_cols;
+  int32_t factor;                     // > 1: img is the full-size image, a tap is the rounded average of its factor x factor block
 };
 
 // the three colour bytes of pixel (x, y) in file order, byte k in bits 8k .. 8k + 7; 0 outside the image (nothing is read then)
 __device__ __forceinline__ uint32_t color_tap(const uint8_t* __restrict__ img, const ColorSrc& s, int ch, int x, int y) {
   if ((unsigned)x >= (unsigned)s.cols || (unsigned)y >= (unsigned)s.rows) return 0u;
+  if (s.factor > 1) {               // the downscale stage's arithmetic (kernels_downscale.h), per channel, on the full-size image
+    const int f = s.factor;
+    const uint8_t* p = img + (size_t)y * f * (size_t)s.row_stride + (size_t)x * f * ch;
+    uint32_t sum[3] = {0u, 0u, 0u};
+    for (int k = 0; k < f; ++k)
+      for (int j = 0; j < f; ++j) {
+        const uint8_t* q = p + (size_t)k * (size_t)s.row_stride + (size_t)j * ch;
+        sum[0] += q[0]; sum[1] += q[1]; sum[2] += q[2];
+      }
+    return ds_round(sum[0], f) | (ds_round(sum[1], f) << 8) | (ds_round(sum[2], f) << 16);
+  }
   const uint8_t* p = img + (size_t)y * (size_t)s.row_stride + (size_t)x * ch;
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
 }

@@ -133,6 +133,7 @@ public:
     und.have_frame = false;                                                  // the maps stay (like the rig of a rectifying context)
     eq.have_frame = false;                                                   // and so does the equalisation switch
     col.have_frame = false;                                                  // and the colour format
+    ds.have_frame = false;                                                   // and the downscale
     bl.have_frame = false;                                                   // and the depth image's bilateral filter
     dmask.have_frame = false;                                                // and the detection mask, with the maps' validity mask
     dmask.fm_pending = false; dmask.fm_frame = false; dmask.fm_have = false;  // frame masks that waited for a frame belong to the sequence that ended
@@ -315,13 +316,22 @@ public:
   }
 
   // ---- undistortion of raw frames (kernels_undistort.h): opt-in, its own allocations, nothing launched while und.on is false ----
-  // size of the frames the submit entries take: the raw camera's while the maps are set
-  int in_rows() const { return und.on ? und.maps.raw_rows : p.rows; }
-  int in_cols() const { return und.on ? und.maps.raw_cols : p.cols; }
+  // size of the frames the submit entries take: the full size while downscaling (set_downscale), else the raw camera's while the maps are
+  // set; red_*: what the undistortion, else the detector and the space map work on (the downscale's result)
+  int red_rows() const { return und.on ? und.maps.raw_rows : p.rows; }
+  int red_cols() const { return und.on ? und.maps.raw_cols : p.cols; }
+  int in_rows() const { return ds.factor > 1 ? ds.full_rows : red_rows(); }
+  int in_cols() const { return ds.factor > 1 ? ds.full_cols : red_cols(); }
   int set_undistortion(int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a) {
     bool off = false;
     if (const int rc = remap_maps_check("vslam_rgbd_set_undistortion", 1, raw_rows, raw_cols, p.rows, p.cols, &map_xy, &map_a, &off, &err)) return rc;
     if (pending) { err = "vslam_rgbd_set_undistortion: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    // while downscaling, the maps address the reduced raw image: full / factor is what this stage is handed
+    if (ds.factor > 1 && (ds_out(ds.full_rows, ds.factor) != (off ? p.rows : raw_rows) || ds_out(ds.full_cols, ds.factor) != (off ? p.cols : raw_cols))) {
+      err = off ? "vslam_rgbd_set_undistortion: the downscaled frames (vslam_rgbd_set_downscale) do not have the tracker's size"
+                : "vslam_rgbd_set_undistortion: the raw size is not the size of the downscaled frames (vslam_rgbd_set_downscale)";
+      return VSLAM_ERR_INVALID;
+    }
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
     (void)hipStreamSynchronize(q2);
@@ -544,6 +554,55 @@ public:
     return fetched(e);
   }
 
+  // ---- downscale of the incoming frames (kernels_downscale.h): opt-in, its own allocations, nothing launched while ds.factor is 1.  The
+  // image: behind the grey stage and ahead of the undistortion, on the image queue, into ds.img.  The depth image: on the space map's
+  // queue behind the upload and ahead of the depth undistortion and the bilateral filter, from the full-size staging (host frames) or the
+  // caller's device images into what the next stage reads — und.raw_depth while undistorting, else d_depth.  Caller memory is only read.
+  int set_downscale(int32_t factor, int32_t full_rows, int32_t full_cols) {
+    if (pending) { err = "vslam_rgbd_set_downscale: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (factor != 1) {
+      if (!ds_factor_ok(factor)) { err = "vslam_rgbd_set_downscale: factor outside 1 .. 4"; return VSLAM_ERR_INVALID; }
+      if (!ds_size_ok(full_rows, full_cols, factor)) { err = "vslam_rgbd_set_downscale: full size outside 1 .. 32767 or below one block"; return VSLAM_ERR_INVALID; }
+      if (ds_out(full_rows, factor) != red_rows() || ds_out(full_cols, factor) != red_cols()) {
+        err = und.on ? "vslam_rgbd_set_downscale: full size / factor is not the raw size of the undistortion maps" : "vslam_rgbd_set_downscale: full size / factor is not the tracker's image size";
+        return VSLAM_ERR_INVALID;
+      }
+    }
+    if (factor == 1 ? ds.factor == 1 : (ds.factor == factor && ds.full_rows == full_rows && ds.full_cols == full_cols)) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    (void)hipStreamSynchronize(q2);
+    ds_free();
+    drop_graph();                                   // a captured launch sequence holds the kernels and buffers (or lacks them)
+    if (factor == 1) return VSLAM_OK;
+    const int rr = red_rows(), rc = red_cols();
+    ds.img.row_stride = (rc + 15) & ~15;
+    ds.img.stream_stride = (size_t)rr * ds.img.row_stride;
+    uint8_t* img = nullptr;
+    hipError_t e = ds.mem.alloc(&img, ds.img.stream_stride * (size_t)B + 64);
+    if (e == hipSuccess) e = ds.mem.alloc(&ds.full_depth, (size_t)B * full_rows * full_cols);
+    if (e != hipSuccess) { ds_free(); return hip_fail(e, "vslam_rgbd_set_downscale"); }
+    ds.img.p[0] = img;
+    ds.factor = factor; ds.full_rows = full_rows; ds.full_cols = full_cols;
+    return VSLAM_OK;
+  }
+  void get_downscale(int32_t* factor, int32_t* full_rows, int32_t* full_cols) const {
+    if (factor) *factor = ds.factor;
+    if (full_rows) *full_rows = ds.factor > 1 ? ds.full_rows : 0;
+    if (full_cols) *full_cols = ds.factor > 1 ? ds.full_cols : 0;
+  }
+  // the reduced image and depth image of the last finished frame of `stream` (dense, full / factor; either may be null)
+  int get_downscaled(int stream, uint8_t* image, uint16_t* depth) {
+    if (int rc = readable(stream)) return rc;
+    if (ds.factor == 1 || !ds.have_frame) { err = "vslam_rgbd_get_downscaled: no frame has been downscaled since vslam_rgbd_set_downscale / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    (void)hipSetDevice(ic->device);
+    const int rr = red_rows(), rc = red_cols();
+    hipError_t e = image ? planes_to_host(image, ds.img, 0, stream, rr, rc) : hipSuccess;
+    const uint16_t* reduced = und.on ? und.raw_depth : d_depth;
+    if (e == hipSuccess && depth) e = hipMemcpy(depth, reduced + (size_t)stream * rr * rc, (size_t)rr * rc * 2, hipMemcpyDeviceToHost);
+    return fetched(e);
+  }
+
   // ---- colour input (kernels_gray.h): opt-in, its own allocation, nothing launched while col.format is VSLAM_PIXEL_GRAY8.  The intensity
   // image of every entry is interleaved colour then (strides in bytes); k_gray_u8 converts it into col.gray, an image of the tracker's own at
   // the input size, which everything behind it reads — the undistortion, else the equalisation (in place) and the detector.  The caller's
@@ -581,10 +640,10 @@ public:
   // read them where they are; the depth images must then be dense per sequence (depth_stream_stride == rows * depth_row_stride)
   int submit(const uint8_t* left, int32_t lstride, const uint16_t* depth, int32_t dstride, size_t left_stream_stride = 0, size_t depth_stream_stride = 0, bool on_device = false) {
     if (!left || !depth) { err = "called with empty frame"; return VSLAM_ERR_INVALID; }
-    if (on_device && !und.on && B > 1 && depth_stream_stride != (size_t)p.rows * dstride) { err = "RGB-D batch on device images: depth images must be dense per sequence"; return VSLAM_ERR_INVALID; }
+    if (on_device && !und.on && ds.factor == 1 && B > 1 && depth_stream_stride != (size_t)p.rows * dstride) { err = "RGB-D batch on device images: depth images must be dense per sequence"; return VSLAM_ERR_INVALID; }
     if (failed) { err = "RGB-D tracker: an earlier frame failed (" + failed_why + "); reset() before the next frame"; return VSLAM_ERR_STATE; }
     if (pending) { err = "RGB-D tracker: the previous frame has not been waited for"; return VSLAM_ERR_STATE; }
-    if (und.on && (size_t)und.maps.raw_rows * (size_t)dstride > 0x7fffffffu) { err = "RGB-D frame: raw depth row stride too large"; return VSLAM_ERR_INVALID; }   // k_undistort_depth's 32-bit tap offsets
+    if (und.on && ds.factor == 1 && (size_t)und.maps.raw_rows * (size_t)dstride > 0x7fffffffu) { err = "RGB-D frame: raw depth row stride too large"; return VSLAM_ERR_INVALID; }   // k_undistort_depth's 32-bit tap offsets
     if (B > 1 && (left_stream_stride < (size_t)(in_rows() - 1) * lstride + in_bytes() || depth_stream_stride < (size_t)(in_rows() - 1) * dstride + in_cols())) {
       err = "RGB-D batch: stream strides smaller than an image"; return VSLAM_ERR_INVALID;
     }
@@ -600,7 +659,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; bl.have_frame = bl.on; dmask.have_frame = dmask.stat[0] != nullptr; dmask.fm_have = dmask.fm_frame; }
+    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; ds.have_frame = ds.factor > 1; bl.have_frame = bl.on; dmask.have_frame = dmask.stat[0] != nullptr; dmask.fm_have = dmask.fm_frame; }
     return rc;
   }
 
@@ -687,6 +746,10 @@ private:
   // at that size)
   struct Colour { int format = 0; bool have_frame = false; ImgPlanes gray; int32_t rows = 0, cols = 0; } col;
   DeviceStore col_mem;
+  // downscale of the incoming frames: off while factor is 1.  img: the reduced images [B]; full_depth: the full-size depth images of a host
+  // frame [B][full_rows * full_cols], re-packed.  full_dep*: where this frame's full-size depth images are (the staging or caller memory)
+  struct Down { int factor = 1, full_rows = 0, full_cols = 0; bool have_frame = false; ImgPlanes img; uint16_t* full_depth = nullptr; DeviceStore mem; } ds;
+  const uint16_t* full_dep = nullptr; int32_t full_dep_stride = 0; size_t full_dep_stream = 0;
   // bilateral filtering of the depth image: off while bl.on is false.  depth: the filtered images [B][rows * cols] the space map reads;
   // args: what the three kernels get but for this frame's source (sizes, scales, taps, the range cells [B][4] and the tables [B][4098])
   struct Bilateral { bool on = false, have_frame = false; double sigma_color = 0, sigma_space = 0; uint16_t* depth = nullptr; BilateralArgs args; DeviceStore mem; } bl;
@@ -750,7 +813,7 @@ private:
     dmask.fm_frame = true;
     return VSLAM_OK;
   }
-  PrePlan pre;                   // this frame's routing through the three stages (route_frame): pre.color is its colour source
+  PrePlan pre;                   // this frame's routing through the input stages (route_frame): pre.color is its colour source
   const uint16_t* raw_dep = nullptr; int32_t raw_dep_stride = 0; size_t raw_dep_stream = 0;
   bool src_on_device = false;    // this frame's images are the caller's device memory: q2 is ordered behind q before it reads them
 
@@ -771,12 +834,16 @@ private:
     col_mem.release();
     col = Colour{};
   }
+  void ds_free() {
+    ds.mem.release();
+    ds = Down{};
+  }
   // This frame's routing through the input stages (the table: host_prestage.h, PrePlan), from which switches are on: `in` is
   // the intensity image that came in (the staged copy or the caller's device memory), own: it is ours to overwrite.  Fills pre and the
   // slot's src / dst and points bs at what the detector reads.  The grey image is allocated here, with the first frame at its size.
   hipError_t route_frame(ImgPlanes in, bool own) {
-    pre.format = col.format; pre.remap = und.on;
-    pre.in_rows = in_rows(); pre.in_cols = in_cols(); pre.rows = p.rows; pre.cols = p.cols;
+    pre.format = col.format; pre.remap = und.on; pre.factor = ds.factor;
+    pre.in_rows = in_rows(); pre.in_cols = in_cols(); pre.red_rows = red_rows(); pre.red_cols = red_cols(); pre.rows = p.rows; pre.cols = p.cols;
     if (col.format) {
       if (!col.gray.p[0] || col.rows != pre.in_rows || col.cols != pre.in_cols) {
         (void)hipStreamSynchronize(q);
@@ -792,6 +859,7 @@ private:
       }
       pre.color = in; pre.gray = col.gray; in = col.gray; own = true;
     }
+    if (ds.factor > 1) { pre.full = in; pre.reduced = ds.img; in = ds.img; own = true; }
     if (und.on) { pre.raw = in; pre.mapped = und.img; in = und.img; own = true; }
     if (eq.on) { eq.src = in; eq.dst = own ? in : eq.img; in = eq.dst; }
     buf_set_planes(bs, in);
@@ -808,7 +876,11 @@ private:
   // this frame's colour image as k_rgbd_map_color reads it (pre.color: the staged copy of a host frame, which the next submit overwrites, or the
   // caller's device memory, which must stay as it is until wait() has returned: further attempts colour the frame from there); the raw
   // image behind the undistortion map while undistorting
-  ColorSrc map_color_src() const { return color_src(pre.color, col.rows, col.cols, col.format, und.on ? &und.maps : nullptr); }
+  // while downscaling: the full-size image, tapped by block averages at the reduced size
+  ColorSrc map_color_src() const {
+    const bool down = ds.factor > 1;
+    return color_src(pre.color, down ? red_rows() : col.rows, down ? red_cols() : col.cols, col.format, und.on ? &und.maps : nullptr, ds.factor);
+  }
   void map_free() {
     obs_free();
     mapcol_free();                                  // the colours are indexed by the map's ids
@@ -841,6 +913,7 @@ private:
     und_free();
     eq_free();
     col_free();
+    ds_free();
     bl_free();
     dmask_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
@@ -1040,7 +1113,11 @@ private:
       bs = buf_set(ic, 0, 0);
       // the first stage that is on (k_gray_u8, else the undistortion, else the equalisation) alone reads the caller's image
       if (const hipError_t ce = route_frame({{left, nullptr}, lstride, lss}, false)) return hip_fail(ce, "grey image");
-      if (und.on) {                            // k_undistort_depth is the only reader of the caller's depth images
+      if (ds.factor > 1) {                     // k_downscale_depth_u16 is the only reader of the caller's depth images
+        full_dep = depth; full_dep_stride = dstride; full_dep_stream = dss;
+        raw_dep = und.raw_depth; raw_dep_stride = red_cols(); raw_dep_stream = (size_t)red_rows() * red_cols();
+        depth_src = d_depth; depth_src_stride = p.cols;
+      } else if (und.on) {                     // k_undistort_depth is the only reader of the caller's depth images
         raw_dep = depth; raw_dep_stride = dstride; raw_dep_stream = dss;
         depth_src = d_depth; depth_src_stride = p.cols;
       } else {
@@ -1054,7 +1131,7 @@ private:
       return VSLAM_OK;
     }
     depth_src = d_depth; depth_src_stride = p.cols;
-    uint16_t* const depth_up = und.on ? und.raw_depth : d_depth;     // where the depth images are copied to, re-packed
+    uint16_t* const depth_up = ds.factor > 1 ? ds.full_depth : und.on ? und.raw_depth : d_depth;     // where the depth images are copied to, re-packed
     // inputs: the caller's row stride kept on the device for the image, the depth image re-packed
     const size_t ib = (size_t)(rows - 1) * lstride + in_bytes();           // bytes of one image the caller owns
     // device bytes per sequence: the caller's own stream stride when the images lie in one (nearly) dense block — then ONE copy brings all of
@@ -1088,7 +1165,8 @@ private:
     if (const int mrc = frame_masks_prepare()) return mrc;
     bs = buf_set(ic, 0, 0);
     if (const hipError_t ce = route_frame({{d_img, nullptr}, lstride, img_stream}, true)) return hip_fail(ce, "grey image");
-    if (und.on) { raw_dep = und.raw_depth; raw_dep_stride = cols; raw_dep_stream = (size_t)rows * cols; }
+    if (ds.factor > 1) { full_dep = ds.full_depth; full_dep_stride = cols; full_dep_stream = (size_t)rows * cols; }
+    if (und.on) { raw_dep = und.raw_depth; raw_dep_stride = red_cols(); raw_dep_stream = (size_t)red_rows() * red_cols(); }
     active_all(bs.active, B);
     if (use_graph && (!graph_exec || graph_stride != lstride || graph_img != d_img || graph_fm != dmask.fm_frame)) capture_graph(lstride);
     if (use_graph && graph_exec) {
@@ -1115,6 +1193,15 @@ private:
     std::memcpy(&f0_bits, &f0, 4);
     const dim3 grid((cols + 255) / 256, rows, B);
     if (src_on_device) { (void)hipEventRecord(ev_fork, q); (void)hipStreamWaitEvent(q2, ev_fork, 0); }   // device images: whatever wrote them was ordered before q
+    // full-size depth -> reduced depth on the space map's queue, behind the depth upload and ahead of the undistortion: into the raw depth
+    // images while undistorting, else into d_depth
+    if (ds.factor > 1) {
+      DownscaleDepthArgs da{};
+      da.src = full_dep; da.src_stream_stride = full_dep_stream; da.src_row_stride = full_dep_stride;
+      da.rows = red_rows(); da.cols = red_cols(); da.n = B; da.factor = ds.factor;
+      da.dst = und.on ? und.raw_depth : d_depth; da.dst_row_stride = da.cols; da.dst_stream_stride = (size_t)da.rows * da.cols;
+      (void)downscale_depth_enqueue(q2, da);
+    }
     // raw depth -> undistorted depth on the space map's queue, behind the depth upload and ahead of the map's first kernel
     if (und.on) {
       UndistortDepthArgs ua{};

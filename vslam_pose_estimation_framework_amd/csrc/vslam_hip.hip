@@ -22,6 +22,7 @@
 #include "kernels_clahe.h"
 #include "kernels_bilateral.h"
 #include "kernels_gray.h"
+#include "kernels_downscale.h" // integer-factor reduction of images and depth images (stand-alone entries)
 #include "kernels_map.h"
 #include "kernels_obs.h"
 #include "kernels_map_color.h"
