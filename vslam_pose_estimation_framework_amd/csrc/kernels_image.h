@@ -114,34 +114,50 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ s16x2 pk_min(s16x2 a, s16x2 b) { return __builtin_elementwise_min(a, b); }
 __device__ __forceinline__ s16x2 pk_max(s16x2 a, s16x2 b) { return __builtin_elementwise_max(a, b); }
 
-// FAST-9/16 without branches, two pixels per lane in packed i16 (v_pk_sub/min/max_i16): with
-// A = max over the 16 nine-arcs of min(d), Bm = min over arcs of max(d) (d = centre - ring pixel), the pixel is
-// a corner iff A > t or -Bm > t, and cornerScore = max(t, A, -Bm) - 1 — one sliding min/max table gives both.
+// three-input packed half-precision min / max of gfx950 (v_pk_minimum3_f16 / v_pk_maximum3_f16: the nested builtins fuse)
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ h16x2 pk_min3(h16x2 a, h16x2 b, h16x2 c) { return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c); }
+__device__ __forceinline__ h16x2 pk_max3(h16x2 a, h16x2 b, h16x2 c) { return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c); }
+
+// FAST-9/16 without branches, two pixels per lane, on the ring pixels themselves: a pixel p in 0..255 ORed with 0x6400 is the
+// half-precision number 1024 + p (exact, normal, ordered like p), so min and max of three ring pixels are one packed
+// instruction each and nothing is ever rounded.  With M = min over the 16 nine-arcs of max(p), m = max over arcs of min(p) and
+// centre v, the pixel is a corner iff v - M > t or m - v > t, and cornerScore = max(t, v - M, m - v) - 1.  A sliding 3-window,
+// then the windows at offsets 0, 3, 6 of it, are the 16 nine-arcs: 32 + 32 operations, 16 more reduce the arcs to M and m.
 __device__ __forceinline__ void fast_pair_scores(const uint8_t (*t)[80], int ly0, int lx0, int ly1, int lx1, int thr0, int thr1,
                                                  int* s0, int* s1) {
   const int dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
   const int dy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
-  const s16x2 v = {(short)t[ly0][lx0], (short)t[ly1][lx1]};
-  s16x2 d[16];
+  h16x2 p[16];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const s16x2 p = {(short)t[ly0 + dy[k]][lx0 + dx[k]], (short)t[ly1 + dy[k]][lx1 + dx[k]]};
-    d[k] = v - p;
-  }
-  s16x2 mn2[16], mx2[16], mn4[16], mx4[16];
+  for (int k = 0; k < 16; ++k)
+    p[k] = __builtin_bit_cast(h16x2, (uint32_t)t[ly0 + dy[k]][lx0 + dx[k]] | ((uint32_t)t[ly1 + dy[k]][lx1 + dx[k]] << 16) | 0x64006400u);
+  h16x2 mn3[16], mx3[16], amn[16], amx[16];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) { mn2[k] = pk_min(d[k], d[(k + 1) & 15]); mx2[k] = pk_max(d[k], d[(k + 1) & 15]); }
+  for (int k = 0; k < 16; ++k) { mn3[k] = pk_min3(p[k], p[(k + 1) & 15], p[(k + 2) & 15]); mx3[k] = pk_max3(p[k], p[(k + 1) & 15], p[(k + 2) & 15]); }
 #pragma unroll
-  for (int k = 0; k < 16; ++k) { mn4[k] = pk_min(mn2[k], mn2[(k + 2) & 15]); mx4[k] = pk_max(mx2[k], mx2[(k + 2) & 15]); }
-  s16x2 A = {-1000, -1000}, Bm = {1000, 1000};
+  for (int k = 0; k < 16; ++k) { amn[k] = pk_min3(mn3[k], mn3[(k + 3) & 15], mn3[(k + 6) & 15]); amx[k] = pk_max3(mx3[k], mx3[(k + 3) & 15], mx3[(k + 6) & 15]); }
+  // 16 -> 6 -> 2 -> 1
+  h16x2 M6[6], m6[6];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    A = pk_max(A, pk_min(pk_min(mn4[k], mn4[(k + 4) & 15]), d[(k + 8) & 15]));
-    Bm = pk_min(Bm, pk_max(pk_max(mx4[k], mx4[(k + 4) & 15]), d[(k + 8) & 15]));
-  }
-  const int a0 = A.x, b0 = -Bm.x, a1 = A.y, b1 = -Bm.y;
+  for (int k = 0; k < 5; ++k) { M6[k] = pk_min3(amx[3 * k], amx[3 * k + 1], amx[3 * k + 2]); m6[k] = pk_max3(amn[3 * k], amn[3 * k + 1], amn[3 * k + 2]); }
+  M6[5] = amx[15]; m6[5] = amn[15];
+  const h16x2 M2 = pk_min3(pk_min3(M6[0], M6[1], M6[2]), pk_min3(M6[3], M6[4], M6[5]), M6[5]);
+  const h16x2 m2 = pk_max3(pk_max3(m6[0], m6[1], m6[2]), pk_max3(m6[3], m6[4], m6[5]), m6[5]);
+  const uint32_t Mb = __builtin_bit_cast(uint32_t, M2), mb = __builtin_bit_cast(uint32_t, m2);   // low 10 bits of a half: the pixel
+  const int v0 = t[ly0][lx0], v1 = t[ly1][lx1];
+  const int a0 = v0 - (int)(Mb & 0x3ffu), b0 = (int)(mb & 0x3ffu) - v0, a1 = v1 - (int)((Mb >> 16) & 0x3ffu), b1 = (int)((mb >> 16) & 0x3ffu) - v1;
   *s0 = (thr0 >= 0 && (a0 > thr0 || b0 > thr0)) ? max(thr0, max(a0, b0)) - 1 : 0;
   *s1 = (thr1 >= 0 && (a1 > thr1 || b1 > thr1)) ? max(thr1, max(a1, b1)) - 1 : 0;
+}
+
+// One lane's fetch-and-add on a word of LDS.  atomicAdd with a wave-uniform operand goes through the compiler's wave reduction
+// (two mbcnt, a compare, a multiply and a multiply-add per call) although a single lane calls it; the instruction itself does not.
+__device__ __forceinline__ int lds_fetch_add(int* word, int v) {
+  const uint32_t addr = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) int*)word);
+  int old;
+  asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(old) : "v"(addr), "v"(v) : "memory");
+  return old;
 }
 
 // The candidate queue is DYNAMIC shared memory (VS_FB_DYN_LDS bytes at every launch): with all 22.6 KB declared statically the
@@ -150,16 +166,14 @@ __device__ __forceinline__ void fast_pair_scores(const uint8_t (*t)[80], int ly0
 // of another kernel in when one workgroup leaves).
 #define VS_FB_QCAP ((VS_TILE_H + 2) * 66)
 #define VS_FB_HS_BYTES ((VS_TILE_H + 8) * VS_TILE_W * 2)
-#define VS_FB_DYN_LDS (((VS_FB_QCAP + 256) * 2) > VS_FB_HS_BYTES ? ((VS_FB_QCAP + 256) * 2) : VS_FB_HS_BYTES)
+#define VS_FB_DYN_LDS ((VS_FB_QCAP * 2) > VS_FB_HS_BYTES ? (VS_FB_QCAP * 2) : VS_FB_HS_BYTES)
 __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBuf b) {
   extern __shared__ __align__(16) unsigned char fb_dyn[];
   __shared__ __align__(16) uint8_t tile[VS_TILE_H + 8][80];
   __shared__ __align__(4) uint8_t sc[VS_TILE_H + 2][68];
   __shared__ int32_t s_thr[VSLAM_MAX_REGIONS];
   // candidate queue of the tile (packed: the scoring pass fills whole wavefronts — per-wavefront queues were measured slower,
-  // they leave every wavefront a partly filled scoring pass); the 256 slots behind it take the stores of lanes without a
-  // candidate, so that the four queue writes of a pretest pass need no exec-mask branches
-  constexpr int QCAP = VS_FB_QCAP;
+  // they leave every wavefront a partly filled scoring pass)
   uint16_t* queue = reinterpret_cast<uint16_t*>(fb_dyn);
   // the horizontal 9-sums of the box pass live in the SAME memory: the queue is dead once the NMS has read it, the sums are built after
   // that (one more barrier, 7-9 KB less LDS).  With that a 64-row tile costs 20 052 B, 8 workgroups = 32 wavefronts still share a CU, and the
@@ -234,7 +248,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
   // ---- FAST on the 66 x (H+2) score region (tile + 1 px NMS halo), two passes:
   //  A) every pixel: the high-speed test (a 9-arc of 16 contains two ADJACENT compass points, i.e. one of {N,S} and one
   //     of {E,W}, on the dark or on the bright side) -> ~1 pixel in 8 survives, queued in LDS (one atomic per wave-row)
-  //  B) queued pixels only, two per lane in packed i16: exact corner test + cornerScore
+  //  B) queued pixels only, two per lane in packed half precision (fast_pair_scores): exact corner test + cornerScore
   auto pretest = [&](int r, int cc, bool valid = true) {
     const int thr = !valid ? -1 : (uni_full ? uni_thr : region_threshold(c, s_thr, x0 - 1 + cc, y0 - 1 + r));
     bool cand = false;
@@ -249,7 +263,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
     const unsigned long long m = __ballot(cand);
     if (m) {
       int base = 0;
-      if (lane == 0) base = atomicAdd(&qn, __popcll(m));
+      if (lane == 0) base = lds_fetch_add(&qn, __popcll(m));
       base = __builtin_amdgcn_readfirstlane(base);
       if (cand) queue[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)((r << 8) | cc);
     }
@@ -258,18 +272,28 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
     // uniform threshold (the usual tile): four pixels per lane from aligned dwords, the compass differences in packed
     // i16 (v_perm_b32 unpacks, v_pk_sub/min/max_i16).  16 lanes per region row (dwords 1..16 = region columns 1..64), four rows
     // per wavefront and pass: no division in the index arithmetic.  The four candidate predicates are the sign bits of the packed
-    // differences, balloted as they are (v_cmp_lt_i16 / _i32): one queue reservation per wave-pass.
+    // differences; each is balloted once, and that one compare also counts the group and masks its store: one queue reservation
+    // per wave-pass, the four groups of a pass behind one another in the queue at wave-uniform offsets.
     const s16x2 thr2 = {(short)uni_thr, (short)uni_thr};
     // Tile heights that are a multiple of 16: the H tile rows (region rows 1 .. H) are whole passes of every wavefront, and the
     // NMS halo ring (region rows 0 and H + 1, region columns 0 and 65) goes through the one-pixel test, spread over all lanes.
     constexpr bool RING = (VS_TILE_H % 16) == 0;
     constexpr int RBASE = RING ? 1 : 0, RCOUNT = RING ? VS_TILE_H : VS_TILE_H + 2;
+    // The clipped validity rectangle of a border tile: its rows bound the rows a lane tests, its columns are masks of the predicates'
+    // sign bits for the lane's four columns 4q-3 .. 4q (loop-invariant; all set in an interior tile)
+    const int rlo = max(RBASE, vy0), rhi = min(RBASE + RCOUNT, vy1);
+    uint32_t cm0 = 0x80008000u, cm1 = 0x80008000u;
+    if (!uni_full) {
+      const int c0 = 4 * ((tid & 15) + 1) - 3;
+      cm0 = (c0 >= vx0 && c0 < vx1 ? 0x8000u : 0u) | (c0 + 1 >= vx0 && c0 + 1 < vx1 ? 0x80000000u : 0u);
+      cm1 = (c0 + 2 >= vx0 && c0 + 2 < vx1 ? 0x8000u : 0u) | (c0 + 3 >= vx0 && c0 + 3 < vx1 ? 0x80000000u : 0u);
+    }
 #pragma unroll 1
     for (int pass = 0; pass < (RCOUNT + 15) / 16; ++pass) {
-      if (pass * 16 + w * 4 >= RCOUNT) continue;          // wave-uniform: nothing of this wavefront in the pass
+      if (RCOUNT % 16 != 0 && pass * 16 + w * 4 >= RCOUNT) continue;   // wave-uniform: nothing of this wavefront in the pass
       const int r = RBASE + pass * 16 + (tid >> 4), q = (tid & 15) + 1;
       uint32_t ng0 = 0, ng1 = 0;
-      if (r < RBASE + RCOUNT) {
+      if ((unsigned)(r - rlo) < (unsigned)(rhi - rlo)) {
         const uint32_t* rowp = reinterpret_cast<const uint32_t*>(&tile[r + 3][0]);
         const uint32_t C = rowp[q], C0 = rowp[q - 1], C2 = rowp[q + 1];
         const uint32_t N = reinterpret_cast<const uint32_t*>(&tile[r][0])[q], S = reinterpret_cast<const uint32_t*>(&tile[r + 6][0])[q];
@@ -285,34 +309,32 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
           const s16x2 e = __builtin_bit_cast(s16x2, ee), w_ = __builtin_bit_cast(s16x2, ww);
           const s16x2 lo = pk_max(pk_min(n, s_), pk_min(e, w_)), hi = pk_min(pk_max(n, s_), pk_max(e, w_));
           const uint32_t neg = __builtin_bit_cast(uint32_t, (s16x2)(lo - (v - thr2))) | __builtin_bit_cast(uint32_t, (s16x2)((v + thr2) - hi));
-          if (half) ng1 = neg; else ng0 = neg;
+          if (half) ng1 = neg & cm1; else ng0 = neg & cm0;
         }
       }
-      bool p0 = (short)(ng0 & 0xffffu) < 0, p1 = (int)ng0 < 0, p2 = (short)(ng1 & 0xffffu) < 0, p3 = (int)ng1 < 0;
-      if (!uni_full) {   // clipped validity rectangle (wave-uniform branch): region columns 4q-3 .. 4q of region row r
-        const bool rok = r >= vy0 && r < vy1;
-        const int c0 = 4 * q - 3;
-        p0 = p0 && rok && c0 >= vx0 && c0 < vx1;         p1 = p1 && rok && c0 + 1 >= vx0 && c0 + 1 < vx1;
-        p2 = p2 && rok && c0 + 2 >= vx0 && c0 + 2 < vx1; p3 = p3 && rok && c0 + 3 >= vx0 && c0 + 3 < vx1;
-      }
+      // the predicates as sign bits of 32-bit words: one shift for the low halves, and each compare serves ballot and store alike
+      uint32_t lo0 = ng0 << 16, lo1 = ng1 << 16;
+      asm("" : "+v"(lo0), "+v"(lo1));   // keeps the shifts: as bit tests the low predicates are evaluated twice, two instructions each time
+      const bool p0 = (int)lo0 < 0, p1 = (int)ng0 < 0, p2 = (int)lo1 < 0, p3 = (int)ng1 < 0;
       const unsigned long long m0 = __ballot(p0), m1 = __ballot(p1), m2 = __ballot(p2), m3 = __ballot(p3);
       const int n0 = __popcll(m0), n1 = __popcll(m1), n2 = __popcll(m2), n3 = __popcll(m3);
       if (n0 + n1 + n2 + n3) {
         int base = 0;
-        if (lane == 0) base = atomicAdd(&qn, n0 + n1 + n2 + n3);
+        if (lane == 0) base = lds_fetch_add(&qn, n0 + n1 + n2 + n3);
         base = __builtin_amdgcn_readfirstlane(base);
-        const int ent = (r << 8) | (4 * q - 3);
+        const int ent = (r << 8) + (4 * q - 3);
         auto below = [&](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
-        const int trash = QCAP + tid;
-        queue[p0 ? base + below(m0) : trash] = (uint16_t)ent;
-        queue[p1 ? base + n0 + below(m1) : trash] = (uint16_t)(ent + 1);
-        queue[p2 ? base + n0 + n1 + below(m2) : trash] = (uint16_t)(ent + 2);
-        queue[p3 ? base + n0 + n1 + n2 + below(m3) : trash] = (uint16_t)(ent + 3);
+        // one store per predicate under its own ballot as the exec mask; the offsets of the four groups are wave-uniform (SALU)
+        if (p0) queue[base + below(m0)] = (uint16_t)ent;
+        if (p1) queue[base + n0 + below(m1)] = (uint16_t)(ent + 1);
+        if (p2) queue[base + n0 + n1 + below(m2)] = (uint16_t)(ent + 2);
+        if (p3) queue[base + n0 + n1 + n2 + below(m3)] = (uint16_t)(ent + 3);
       }
     }
     if (RING) {
       constexpr int NRING = 2 * 66 + 2 * VS_TILE_H;
       for (int i0 = 0; i0 < NRING; i0 += 256) {
+        if (i0 + 64 * w >= NRING) continue;               // wave-uniform: the second trip is four pixels of wavefront 0
         const int i = i0 + tid;
         int r = 0, cc = 0;
         if (i < 66) { r = 0; cc = i; }
