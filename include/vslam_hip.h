@@ -384,6 +384,48 @@ int vslam_downscale_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t
                        int32_t dst_row_stride);
 int vslam_downscale_depth_u16(vslam_ctx* ctx, const uint16_t* src, int32_t rows, int32_t cols, int32_t row_stride /* elements */,
                               int32_t factor, uint16_t* dst, int32_t dst_row_stride);
+/* ---- smoothing of the intensity image: Gaussian and median (opt-in; csrc/kernels_smooth.h, smooth.py) --------------------
+ * Noise suppression on the 8-bit grey image ahead of the equalisation slot and the detector.  All integer, bit-exact by definition:
+ *   VSLAM_SMOOTH_GAUSSIAN, ksize 3, 5 or 7: taps K in 1/256 — {64,128,64}, {16,64,96,64,16}, {8,28,56,72,56,28,8} —
+ *     out = (sum_i sum_j K_i K_j p(y+i-r, x+j-r) + 32768) >> 16, r = ksize / 2, rows and columns reflected without edge duplication
+ *     (index -1 -> 1).  This is cv::GaussianBlur(src, dst, Size(k, k), 0) on CV_8UC1 with BORDER_REFLECT_101 [recalled; parity with OpenCV
+ *     is not pinned, the integer definition is].  It needs rows > r and cols > r.
+ *   VSLAM_SMOOTH_MEDIAN, ksize 3 or 5: element k k / 2 of the sorted k x k window, the border replicated (cv::medianBlur [recalled]); any
+ *     size from 1 x 1.
+ * The chain: colour -> grey -> downscale -> rectify -> SMOOTH -> equalise / CLAHE -> detect.  The histogram and the CLAHE tables are
+ * built from the smoothed pair; masks, FAST, the descriptors, the recovery and the ORB extractor read the smoothed (then equalised) pair;
+ * map colours keep sampling the colour source.  One launch (k_smooth) per frame on the image pipeline's queue, all streams and both sides;
+ * a switched-off stream is neither read nor written; a caller's device pair is only read.  The stage never works in place.
+ * vslam_set_smoothing: mode VSLAM_SMOOTH_OFF frees the stage's buffers (ksize is then ignored).  VSLAM_ERR_INVALID for an unknown mode,
+ *   a ksize the mode does not have (nothing changes; the Gaussian's size refusal can only be met through vslam_smooth_u8: a context is
+ *   never that small); VSLAM_ERR_STATE inside a frame
+ *   of the stage path.  Nothing is allocated or launched while off.  The switch survives vslam_reset.
+ * vslam_get_smoothing: the switch in force; ksize 0 while off.
+ * vslam_get_smoothed_images: the smoothed pair of the last submitted frame of `stream` (rows x cols, dense), ahead of the equalisation;
+ *   VSLAM_ERR_STATE while off, before a frame has run under the switch, after vslam_reset.  Synchronises.  While the switch is on,
+ *   vslam_get_rectified_images / _downscaled_images / _gray_images return the pair ahead of the smoothing: no later stage touches it.
+ * vslam_smooth_u8: the kernel stand-alone on one host image, dense dst (rows x cols).  rows or cols 0: VSLAM_OK, nothing written.
+ *   VSLAM_ERR_INVALID as above, for a null pointer and for row_stride < cols. */
+#define VSLAM_SMOOTH_OFF 0
+#define VSLAM_SMOOTH_GAUSSIAN 1
+#define VSLAM_SMOOTH_MEDIAN 2
+int vslam_set_smoothing(vslam_ctx* ctx, int mode, int32_t ksize);
+int vslam_get_smoothing(vslam_ctx* ctx, int* mode, int32_t* ksize);
+int vslam_get_smoothed_images(vslam_ctx* ctx, int stream, uint8_t* left, uint8_t* right);
+int vslam_smooth_u8(vslam_ctx* ctx, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int mode, int32_t ksize, uint8_t* dst);
+/* The same stage in RGB-D mode (the device-resident loop): colour -> grey -> downscale -> undistort -> SMOOTH -> equalise / CLAHE ->
+ * detect (the ORB detector of that loop included: its pyramid is built from the smoothed, equalised image).  Only the intensity image is
+ * smoothed; the depth image is untouched.  Once per frame on the image queue (further registration attempts read the smoothed image
+ * again), inside the captured launch sequence (VSLAM_RGBD_GRAPH=1) as well; toggling drops the captured sequence.
+ * vslam_rgbd_set_smoothing: as vslam_set_smoothing; VSLAM_ERR_STATE with a frame in flight, and on the host-driven loop
+ *   (VSLAM_RGBD_HOST=1), which does not get the stage.  The switch survives vslam_rgbd_reset.
+ * vslam_rgbd_get_smoothing: the switch in force; OFF and 0 on the host-driven loop.
+ * vslam_rgbd_get_smoothed: the smoothed image of the last finished frame of `stream` (dense); VSLAM_ERR_STATE when off, before a frame,
+ *   after a reset, with a frame in flight.  With the equalisation slot on the image is equalised in place afterwards and this getter
+ *   returns the equalised image, like vslam_rgbd_get_undistorted. */
+int vslam_rgbd_set_smoothing(struct vslam_rgbd* t, int mode, int32_t ksize);
+int vslam_rgbd_get_smoothing(struct vslam_rgbd* t, int* mode, int32_t* ksize);
+int vslam_rgbd_get_smoothed(struct vslam_rgbd* t, int32_t stream, uint8_t* image);
 /* ---- detection masks: keep keypoints off masked pixels (opt-in; csrc/kernels_mask.h, mask.py) ----------------------------
  * cv::Feature2D::detect(image, keypoints, mask) [recalled]: the detector and its non-maximum suppression run on the whole image, and
  * every keypoint whose pixel reads 0 in the mask is dropped afterwards (KeyPointsFilter::runByPixelsMask), ahead of the count the

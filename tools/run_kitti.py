@@ -48,14 +48,14 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from vslam_pose_estimation_framework_amd import color as color_mod, downscale as downscale_mod, evaluation, hip, io_formats  # noqa: E402
+from vslam_pose_estimation_framework_amd import color as color_mod, downscale as downscale_mod, evaluation, hip, io_formats, smooth as smooth_mod  # noqa: E402
 
 
 MAP_ENTRIES_PER_FRAME = 200     # map capacity per stream and processed frame (a KITTI frame creates ~30-60 landmarks)
 
 
 def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, want_map=False, want_obs=False, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
-                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None, mask_invalid=None, downscale=None):
+                map_color=False, motion_model=0, dead_reckoning_limit=0, guesses=None, masks=None, mask_invalid=None, downscale=None, smooth=None):
     """Frame-sharded mode (bench.py's headline mode) on a recorded sequence: `n_chunks` contiguous chunks, each
     started `overlap` frames early, run side by side as the streams of one context; the chunk trajectories are chained at the seams
     (sharding.assemble_trajectory).  Approximate at the seams — DESIGN.md section 9 has the accuracy study."""
@@ -70,6 +70,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
         api.set_downscale(*downscale)
     if mask_invalid is not None:
         api.set_rectification_mask(True, mask_invalid)
+    if smooth is not None:
+        api.set_smoothing(*smooth)
     if equalize:
         api.set_equalization(True)
     if clahe is not None:
@@ -120,7 +122,8 @@ def run_chunked(api, cfg, seq, n, n_chunks, overlap, device, log, rect=None, wan
 def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="kitti", device=0, log=print, layout="kitti", asl_gt=None,
         chunks=0, overlap=6, rectify=False, map_path=None, obs_path=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8), map_color=False,
         motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, mask=None, mask_margin=0, frame_masks=None, mask_invalid=None,
-        downscale=1):
+        downscale=1, smooth=None):
+    smooth = smooth_mod.argument(smooth, SystemExit)
     check_mask_args(mask, mask_margin, frame_masks, SystemExit, mask_invalid, rectify)
     check_downscale_arg(downscale, SystemExit)
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
@@ -184,6 +187,9 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             downscale_mod.apply_to_config(cfg, ds[0])
         log("downscaling on the GPU by %d: %dx%d -> %dx%d, ahead of %s; calibration scaled (f %.3f px, c %.3f %.3f)" % (
             ds[0], ds[1], ds[2], ds[1] // ds[0], ds[2] // ds[0], "the rectification" if rect is not None else "the detector", cfg.K[0], cfg.K[2], cfg.K[5]))
+    if smooth is not None:
+        log("smoothing on the GPU (%s %d x %d on every image, ahead of %s)" % (
+            "Gaussian" if smooth[0] == smooth_mod.GAUSSIAN else "median", smooth[1], smooth[1], "the equalisation" if equalize else "CLAHE" if clahe is not None else "the detector"))
     if color:
         log("colour cameras (image_2 / image_3, calibration P2 / P3): RGB -> grey on the GPU, ahead of %s" % ("the equalisation" if equalize else "CLAHE" if clahe is not None else "the detector"))
     if equalize:
@@ -206,7 +212,7 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
     if chunks > 1:
         poses, flags, lm_map, obs = run_chunked(api, cfg, seq, n, chunks, overlap, device, log, rect, want_map=want_map, want_obs=bool(obs_path),
                                                 equalize=equalize, color=color, clahe=clahe, clahe_tiles=clahe_tiles, map_color=map_color,
-                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks, mask_invalid=mask_invalid, downscale=ds)
+                                                motion_model=model, dead_reckoning_limit=dead_reckoning_limit, guesses=guesses, masks=masks, mask_invalid=mask_invalid, downscale=ds, smooth=smooth)
         tracking = None
         dead_reckoned = None
     else:
@@ -218,6 +224,8 @@ def run(seq_dir, out_path=None, fmt="kitti", gt_path=None, max_frames=0, which="
             api.set_downscale(*ds)
         if mask_invalid is not None:
             api.set_rectification_mask(True, mask_invalid)
+        if smooth is not None:
+            api.set_smoothing(*smooth)
         if equalize:
             api.set_equalization(True)
         if clahe is not None:
@@ -444,6 +452,8 @@ def parse_args(argv=None):
     ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask / --frame-masks by N pixels (0 .. 64)")
     ap.add_argument("--mask-invalid", nargs="?", type=int, const=0, default=None, metavar="N", help="with --rectify: no keypoints on pixels whose source lies "
                     "partly outside the raw image (the seam between picture and black fill), computed from the maps on the GPU, both sides; N widens it (0 .. 64)")
+    ap.add_argument("--smooth", default=None, metavar="MODE[:K]", help="smooth every grey image on the GPU ahead of the equalisation and the detector: "
+                    "gaussian[:3|5|7] (default gaussian:5) or median[:3|5] (default median:3)")
     ap.add_argument("--downscale", type=int, default=1, metavar="N", help="reduce every image by the whole factor N (2, 3 or 4) on the GPU ahead of everything but "
                     "the colour conversion: rounded block averages; the folder's calibration is scaled and the tracker runs at the reduced size "
                     "(masks are given at that size); combines with every other switch")
@@ -453,6 +463,7 @@ def parse_args(argv=None):
     try:
         check_mask_args(a.mask, a.mask_margin, a.frame_masks, ValueError, a.mask_invalid, a.rectify)
         check_downscale_arg(a.downscale, ValueError)
+        smooth_mod.argument(a.smooth, ValueError)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
     except ValueError as e:
         ap.error(str(e))
@@ -468,7 +479,7 @@ def main(argv=None):
     run(a.sequence, a.out, a.format, a.gt, a.max_frames, a.config, a.device, layout=a.layout, asl_gt=a.asl_gt, chunks=a.chunks, overlap=a.overlap,
         rectify=a.rectify, map_path=a.map, obs_path=a.observations, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles,
         map_color=a.map_color, motion_model=a.motion_model, odometry=a.odometry, dead_reckoning_limit=a.dead_reckoning_limit,
-        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid, downscale=a.downscale)
+        mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid, downscale=a.downscale, smooth=a.smooth)
 
 
 if __name__ == "__main__":

@@ -56,7 +56,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from vslam_pose_estimation_framework_amd import color as color_mod, downscale as downscale_mod, evaluation, hip, io_formats  # noqa: E402
+from vslam_pose_estimation_framework_amd import color as color_mod, downscale as downscale_mod, evaluation, hip, io_formats, smooth as smooth_mod  # noqa: E402
 from vslam_pose_estimation_framework_amd.capi import DepthParams, RgbdTracker, VslamError  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -129,8 +129,9 @@ def distortion_of(undistort, intrinsics):
 def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_DEPTH_UNIT_M, out_path=None, max_frames=0, descriptor=1, detector=0,
         gt_path=None, device=0, depth_scale=1.0, log=print, map_path=None, obs_path=None, undistort=None, equalize=False, color=False, clahe=None, clahe_tiles=(8, 8),
         map_color=False, motion_model="constant-velocity", odometry=None, dead_reckoning_limit=0, bilateral=None, mask=None, mask_margin=0,
-        frame_masks=None, mask_invalid=None, downscale=1):
+        frame_masks=None, mask_invalid=None, downscale=1, smooth=None):
     check_mask_args(mask, mask_margin, SystemExit, frame_masks, mask_invalid, undistort)
+    smooth = smooth_mod.argument(smooth, SystemExit)
     if isinstance(downscale, bool) or not isinstance(downscale, int) or downscale < 1 or downscale > 4:
         raise SystemExit("--downscale: a whole factor in 1 .. 4 (1: off)")
     check_motion_args(motion_model, odometry, dead_reckoning_limit, SystemExit)
@@ -199,6 +200,10 @@ def run(folder, which="tum", intrinsics="freiburg1", depth_unit=io_formats.TUM_D
             log("colour frames (%s): converted to grey on the GPU, ahead of %s" % (color_mod.NAMES[fmt], "the undistortion" if dist is not None else "the detector"))
         elif color:
             log("--color: the folder's images are grey already, nothing to convert")
+        if smooth is not None:
+            tr.set_smoothing(*smooth)
+            log("smoothing on the GPU (%s %d x %d on every intensity image, ahead of %s; the depth image is untouched)" % (
+                "Gaussian" if smooth[0] == smooth_mod.GAUSSIAN else "median", smooth[1], smooth[1], "the equalisation" if equalize else "CLAHE" if clahe is not None else "the detector"))
         if equalize:
             tr.set_equalization(True)
             log("equalising histograms on the GPU (cv::equalizeHist on every intensity image%s)" % (", behind the undistortion" if dist is not None else ""))
@@ -385,6 +390,8 @@ def parse_args(argv=None):
     ap.add_argument("--mask", default=None, metavar="MASK.png", help="detection mask for the whole run: an 8-bit PNG at the processed size (the undistorted "
                     "one under --undistort), zero = no keypoints on that pixel (the robot's own body, overlays, vignetted corners)")
     ap.add_argument("--mask-margin", type=int, default=0, metavar="N", help="widen every masked region of --mask and --frame-masks by N pixels (0 .. 64)")
+    ap.add_argument("--smooth", default=None, metavar="MODE[:K]", help="smooth every intensity image on the GPU ahead of the equalisation and the detector: "
+                    "gaussian[:3|5|7] (default gaussian:5) or median[:3|5] (default median:3); the depth image is untouched")
     ap.add_argument("--downscale", type=int, default=1, metavar="N", help="reduce every image and depth image by the whole factor N (2, 3 or 4) on the GPU ahead "
                     "of everything but the colour conversion: rounded block averages, and for depth the lower median of a block's valid values; the "
                     "intrinsics are scaled and the tracker runs at the reduced size (masks are given at that size); combines with every other switch")
@@ -396,6 +403,7 @@ def parse_args(argv=None):
     try:
         check_mask_args(a.mask, a.mask_margin, ValueError, a.frame_masks, a.mask_invalid, a.undistort)
         check_motion_args(a.motion_model, a.odometry, a.dead_reckoning_limit, ValueError)
+        smooth_mod.argument(a.smooth, ValueError)
     except ValueError as e:
         ap.error(str(e))
     if a.downscale < 1 or a.downscale > 4:
@@ -428,7 +436,7 @@ def main(argv=None):
     run(a.folder, a.config, a.intrinsics, a.depth_unit, a.out, a.max_frames, 1 if a.descriptor == "ORB" else 0, 1 if a.detector == "ORB" else 0, a.gt, a.device,
         map_path=a.map, obs_path=a.observations, undistort=a.undistort, equalize=a.equalize, color=a.color, clahe=a.clahe, clahe_tiles=a.clahe_tiles, motion_model=a.motion_model, odometry=a.odometry,
         dead_reckoning_limit=a.dead_reckoning_limit,
-        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid, downscale=a.downscale)
+        map_color=a.map_color, bilateral=a.bilateral, mask=a.mask, mask_margin=a.mask_margin, frame_masks=a.frame_masks, mask_invalid=a.mask_invalid, downscale=a.downscale, smooth=a.smooth)
 
 
 if __name__ == "__main__":

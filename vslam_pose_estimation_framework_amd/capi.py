@@ -287,6 +287,24 @@ class CApi(object):
         self.check(self.fn("get_downscaled_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
         return L, R
 
+    # -- smoothing of the grey pair ahead of the equalisation slot (vslam_set_smoothing; definition: smooth.py) ------------------
+    def set_smoothing(self, mode, ksize=0):
+        """mode smooth.GAUSSIAN (ksize 3 / 5 / 7) or smooth.MEDIAN (3 / 5); smooth.OFF frees the stage's buffers."""
+        self.check(self.fn("set_smoothing")(self.ctx, C.c_int(int(mode)), C.c_int32(int(ksize))))
+
+    def smoothing(self):
+        """(mode, ksize) in force; (0, 0) while off."""
+        m, k = C.c_int(), C.c_int32()
+        self.check(self.fn("get_smoothing")(self.ctx, C.byref(m), C.byref(k)))
+        return m.value, k.value
+
+    def smoothed_images(self, stream=0):
+        """The smoothed pair of the last submitted frame of `stream`, ahead of the equalisation."""
+        L = np.zeros((int(self.cfg.rows), int(self.cfg.cols)), np.uint8)
+        R = np.zeros_like(L)
+        self.check(self.fn("get_smoothed_images")(self.ctx, C.c_int(stream), _p(L, C.c_uint8), _p(R, C.c_uint8)))
+        return L, R
+
     # -- rectification of raw pairs (vslam_set_rectification) ---------------------------------------------------------
     def set_rectification(self, rect):
         """rect: rectify.Rectification (its maps at the context's rows x cols), or None to switch rectification off."""
@@ -1002,6 +1020,20 @@ class CApi(object):
         """vslam_downscale_depth_u16: as downscale_u8 on 2-D uint16 arrays or views; the strides are in elements."""
         return self._downscale("downscale_depth_u16", np.uint16, depth, factor, out, row_stride, dst_row_stride)
 
+    def smooth_u8(self, image, mode, ksize, row_stride=None):
+        """vslam_smooth_u8: image is a 2-D uint8 array or view with unit column stride; its row stride and alignment are passed on as
+        they are (row_stride, bytes, overrides the array's own, for the refusal tests) -> a dense uint8 [rows, cols]."""
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 2 or (img.shape[1] > 1 and img.strides[1] != 1) or (img.shape[0] > 1 and img.strides[0] < img.shape[1]):
+            raise ValueError("smooth_u8: a 2-D uint8 array with unit column stride is required")
+        rows, cols = img.shape
+        stride = img.strides[0] if rows > 1 else max(cols, 1)
+        dst = np.zeros((rows, cols), np.uint8)
+        self.check(self.fn("smooth_u8")(*self._ctx_args(), C.c_void_p(img.ctypes.data), C.c_int32(rows), C.c_int32(cols),
+                                        C.c_int32(stride if row_stride is None else int(row_stride)), C.c_int(int(mode)), C.c_int32(int(ksize)),
+                                        C.c_void_p(dst.ctypes.data)))
+        return dst
+
     def sample_color_u8(self, image, fmt, xy, maps=None, cols=None):
         """vslam_sample_color_u8: image as in gray_u8 ([rows, cols, channels], or [rows, bytes] with cols, strides and alignment passed on);
         xy int16 [n, 2] (x, y); maps None or (map_xy int16 [R, C, 2], map_a uint16 [R, C]) -> uint8 [n, 3] (r, g, b)."""
@@ -1402,6 +1434,25 @@ class _RgbdDownscaleApi(object):
         return img, dep
 
 
+class _RgbdSmoothApi(object):
+    """vslam_rgbd_set_smoothing / _get_smoothing / _get_smoothed (the device-resident loop only), shared by RgbdTracker and RgbdBatch."""
+
+    def set_smoothing(self, mode, ksize=0):
+        self._check(self.lib.vslam_rgbd_set_smoothing(self.h, C.c_int(int(mode)), C.c_int32(int(ksize))))
+
+    def smoothing(self):
+        """(mode, ksize) in force; (0, 0) while off."""
+        m, k = C.c_int(), C.c_int32()
+        self._check(self.lib.vslam_rgbd_get_smoothing(self.h, C.byref(m), C.byref(k)))
+        return m.value, k.value
+
+    def smoothed(self, stream=0):
+        """The smoothed image of the last finished frame of `stream` (equalised in place afterwards while the slot is on)."""
+        img = np.zeros((int(self.cfg.rows), int(self.cfg.cols)), np.uint8)
+        self._check(self.lib.vslam_rgbd_get_smoothed(self.h, C.c_int32(stream), _p(img, C.c_uint8)))
+        return img
+
+
 class _RgbdMotionApi(object):
     """vslam_rgbd_set_motion_model / _set_pose_guess(es), shared by RgbdTracker and RgbdBatch (both loops)."""
 
@@ -1435,7 +1486,7 @@ def _row_bytes(left, image_ndim):
     return int(left.shape[-1]) if left.ndim == image_ndim else int(left.shape[-2] * left.shape[-1])
 
 
-class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdDownscaleApi, _RgbdMotionApi):
+class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdDownscaleApi, _RgbdSmoothApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_* (RGB-D mode end to end inside libvslam_hip.so: the device-resident loop, or the host-driven loop over the
     stand-alone entry points when VSLAM_RGBD_HOST=1 is set while the tracker is created)."""
 
@@ -1492,7 +1543,7 @@ class RgbdTracker(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilater
             self.h = None
 
 
-class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdDownscaleApi, _RgbdMotionApi):
+class RgbdBatch(_RgbdMapApi, _RgbdUndistortApi, _RgbdEqualizeApi, _RgbdBilateralApi, _RgbdMaskApi, _RgbdColorApi, _RgbdDownscaleApi, _RgbdSmoothApi, _RgbdMotionApi):
     """ctypes view of vslam_rgbd_create_batch / _process_batch_host: n_streams sequences of one camera and configuration in one context."""
 
     def __init__(self, api, cfg, params, n_streams, device=0):

@@ -94,6 +94,13 @@ struct vslam_ctx {
   struct Ds { int factor = 1, full_rows = 0, full_cols = 0, stride = 0; size_t stream_stride = 0; bool have_frame = false;
               uint8_t* full[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
               DeviceStore mem; } ds;
+  // smoothing of the grey pair ahead of the equalisation slot (vslam_set_smoothing, kernels_smooth.h): off while mode == VSLAM_SMOOTH_OFF.
+  // The stage cannot work in place: in[step parity][left/right] (B x up_stream_stride each, rows up_stride apart) take what would have
+  // gone to upload[parity] — the host upload, the grey pair, the reduced pair, the rectified pair; out[left/right]: with the equalisation
+  // slot on as well the smoothed pair goes here and the equalised one to upload[parity], else the smoothed pair goes to upload[parity].
+  struct Sm { int mode = 0, ksize = 0; bool have_frame = false;
+              uint8_t* in[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; uint8_t* out[2] = {nullptr, nullptr};
+              DeviceStore mem, out_mem; } sm;
   // this frame's routing through the input stages (route_frame, host_frame.h): the colour pair (a slab or the caller's device memory) and
   // where k_gray_u8 writes the grey pair, so where vslam_get_gray_images reads it; the raw pair k_rectify reads and the pair it writes
   PrePlan pre;
@@ -572,7 +579,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (auto& e : c->scratch) vslam_destroy(e.t);
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
-  for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem, &c->ds.mem}) m->release();     // the input stages' stores
+  for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem, &c->ds.mem, &c->sm.mem, &c->sm.out_mem}) m->release();     // the input stages' stores
   for (DeviceStore* m : {&c->dmask.user_mem, &c->dmask.valid_mem, &c->dmask.comb_mem, &c->dmask.slab_mem, &c->dmask.eff_mem}) m->release();    // detection masks
   c->guess.mem.release();
   for (int q = 0; q < 2; ++q) { if (c->guess.pin[q]) (void)hipHostFree(c->guess.pin[q]); if (c->guess.pin_ev[q]) (void)hipEventDestroy(c->guess.pin_ev[q]); }
@@ -590,6 +597,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
 VS_API int vslam_reset(vslam_ctx* c) {
   if (!c) return VSLAM_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
+  c->sm.have_frame = false;        // the smoothing switch stays; what its getter would read belongs to the sequence that ended
   return init_state(c);
 }
 // check a scratch context of configuration `cfg` out of the parent's pool (fresh stream state, pristine DevCfg) / back in

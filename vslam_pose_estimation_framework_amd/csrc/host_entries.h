@@ -1104,6 +1104,30 @@ VS_API int vslam_downscale_depth_u16(vslam_ctx* c, const uint16_t* src, int32_t 
   return k.finish();
 }
 
+// ---- Gaussian / median smoothing of one host image (kernels_smooth.h): dense dst ----------------------------------------
+VS_API int vslam_smooth_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int mode, int32_t ksize, uint8_t* dst) {
+  if (int rc = entry_begin(c)) return rc;
+  if (rows < 0 || cols < 0) return fail(c, VSLAM_ERR_INVALID, "smooth_u8: negative size");
+  if (mode != VSLAM_SMOOTH_GAUSSIAN && mode != VSLAM_SMOOTH_MEDIAN) return fail(c, VSLAM_ERR_INVALID, "smooth_u8: unknown mode");
+  if (!smooth_mode_ok(mode, ksize)) return fail(c, VSLAM_ERR_INVALID, "smooth_u8: a ksize the mode does not have");
+  if (rows == 0 || cols == 0) return VSLAM_OK;
+  std::string why;
+  if (const int rc = smooth_check("smooth_u8", mode, ksize, rows, cols, &why)) return fail(c, rc, why);
+  if (!src || !dst || row_stride < cols) return fail(c, VSLAM_ERR_INVALID, "smooth_u8: bad argument");
+  Call k(c, c->stream);
+  // the device copies keep the caller's alignment: source rows and destination dwords start where they would in place
+  const size_t bytes = (size_t)(rows - 1) * row_stride + (size_t)cols;
+  uint8_t* ds = k.dev<uint8_t>(bytes + 16) + (size_t)((uintptr_t)src & 15u);
+  k.up_to(ds, src, bytes);
+  uint8_t* dd = k.dev<uint8_t>((size_t)rows * cols + 16) + (size_t)((uintptr_t)dst & 15u);
+  SmoothArgs sa{};
+  place(sa, ds, row_stride, dd, cols, rows, cols);
+  sa.mode = mode; sa.ksize = ksize;
+  if (k.ok()) k.note(smooth_enqueue(c->stream, sa));
+  k.down(dst, dd, (size_t)rows * cols);
+  return k.finish();
+}
+
 // ---- the colour of n pixels of one host image, direct or through a remap map pair (kernels_map_color.h) --------------
 VS_API int vslam_sample_color_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, int format, const int16_t* map_xy,
                                  const uint16_t* map_a, int32_t map_rows, int32_t map_cols, const int16_t* xy, int32_t n, uint8_t* rgb) {

@@ -69,6 +69,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
   if (c->eq.on) c->eq.have_frame = true;
   if (c->col.format != VSLAM_PIXEL_GRAY8) c->col.have_frame = true;
   if (c->ds.factor > 1) c->ds.have_frame = true;
+  if (c->sm.mode) c->sm.have_frame = true;
   return VSLAM_OK;
 }
 static int frame_done(vslam_ctx* c) {
@@ -207,17 +208,21 @@ static void route_frame(vslam_ctx* c, const ImgPlanes& in) {
   ImgPlanes cur = in;                                  // where the pair lies behind the stages so far
   const vslam_ctx::Rect& r = c->rect;
   const vslam_ctx::Ds& d = c->ds;
-  const ImgPlanes raw_slab = p.remap ? ImgPlanes{{r.raw[set][0], r.raw[set][1]}, r.raw_stride, r.raw_stream_stride} : up;     // what the remap, else the detector reads
+  p.smooth_mode = c->sm.mode; p.smooth_ksize = c->sm.ksize;
+  // what the remap, else the smoothing, else the detector reads
+  const ImgPlanes raw_slab = p.remap ? ImgPlanes{{r.raw[set][0], r.raw[set][1]}, r.raw_stride, r.raw_stream_stride} : p.smooth_mode ? unsmoothed_planes(c, set) : up;
   if (p.format != VSLAM_PIXEL_GRAY8) { p.color = cur; p.gray = p.factor > 1 ? ImgPlanes{{d.full[set][0], d.full[set][1]}, d.stride, d.stream_stride} : raw_slab; cur = p.gray; }
   if (p.factor > 1) { p.full = cur; p.reduced = raw_slab; cur = p.reduced; }
   if (p.remap) { p.raw = cur; p.mapped = rectified_planes(c, set); cur = p.mapped; }
+  // smoothed pair: never in place — its input lies in sm.in[set] or in the caller's device memory; into upload[set] as the last stage
+  if (p.smooth_mode) { p.unsmoothed = cur; p.smoothed = c->eq.on ? ImgPlanes{{c->sm.out[0], c->sm.out[1]}, c->up_stride, c->up_stream_stride} : up; cur = p.smoothed; }
   // equalised pair in upload[set]: in place when the input is already there (a host upload keeps the caller's strides), written there
   // from the rectified pair's own slabs or from the caller's device images, which these kernels alone read
   if (c->eq.on) { c->eq.src = cur; c->eq.dst = cur.p[0] == up.p[0] ? cur : up; cur = c->eq.dst; }
   buf_set_planes(c->buf, cur);
 }
 // A frame's input pair.  Host images go to the slabs of this step's parity that the first stage reads — the colour slabs (upload_to with
-// the byte width as cols), the downscale's full-size slabs, the rectifier's raw slabs, else upload[parity]; device images are read in place, by the first stage alone
+// the byte width as cols), the downscale's full-size slabs, the rectifier's raw slabs, the smoothing's input slabs, else upload[parity]; device images are read in place, by the first stage alone
 // (and, colour, by k_map_color behind the frame's last launch while map colours are on).
 static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
   const bool colour = c->col.format != VSLAM_PIXEL_GRAY8, full = c->ds.factor > 1, raw = c->rect.on;
@@ -242,6 +247,7 @@ static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t 
     const int rc = colour ? upload_to(c, L, R, row_stride, image_stride, rows, wb, c->col.slab[p], c->col.stride, c->col.stream_stride, &in)
                    : full ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->ds.full[p], c->ds.stride, c->ds.stream_stride, &in)
                    : raw  ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->rect.raw[p], c->rect.raw_stride, c->rect.raw_stream_stride, &in)
+                   : c->sm.mode ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->sm.in[p], c->up_stride, c->up_stream_stride, &in)
                           : upload_to(c, L, R, row_stride, image_stride, rows, cols, c->upload[p], c->up_stride, c->up_stream_stride, &in);
     if (rc != VSLAM_OK) return rc;
   }

@@ -1,6 +1,6 @@
 // host_prestage.h — the input stages ahead of the detector, written once for the stereo context and the RGB-D tracker: colour to grey
-// (kernels_gray.h), integer-factor reduction (kernels_downscale.h), remap (rectification / undistortion, kernels_rectify.h) and the equalisation slot (global or CLAHE,
-// kernels_equalize.h / kernels_clahe.h).  Where an image pair lies (ImgPlanes), the one filler of the kernels' argument blocks (place),
+// (kernels_gray.h), integer-factor reduction (kernels_downscale.h), remap (rectification / undistortion, kernels_rectify.h), smoothing
+// (Gaussian / median, kernels_smooth.h) and the equalisation slot (global or CLAHE, kernels_equalize.h / kernels_clahe.h).  Where an image pair lies (ImgPlanes), the one filler of the kernels' argument blocks (place),
 // the slot (EqSlot), the intake of remap maps, the per-frame plan (PrePlan) with its one enqueue, the plane read-out of the getters and the
 // colour source of the map's colours.  Owner-independent host code: no context, no tracker; errors come back as hipError_t or as text.
 // Included by vslam_hip.hip ahead of host_ctx.h (the context holds these types); rgbd_device.h uses it too.
@@ -21,7 +21,7 @@ static void active_all(uint32_t* active, int n) {
 }
 
 // ---- the one argument filler -----------------------------------------------------------------------
-// what GrayArgs, EqArgs, ClaheArgs and RectArgs have in common
+// what GrayArgs, DownscaleArgs, SmoothArgs, EqArgs, ClaheArgs and RectArgs have in common
 template <class A>
 static void place(A& a, const ImgPlanes& src, const ImgPlanes& dst, int rows, int cols, int n, int sides, const uint32_t* active) {
   for (int k = 0; k < 2; ++k) { a.src[k] = src.p[k]; a.dst[k] = const_cast<uint8_t*>(dst.p[k]); }
@@ -182,14 +182,21 @@ struct EqSlot {
 //                                                                                rectifying, else upload[parity]
 //   downscale ds.full[parity] (host or grey output) or caller memory             rect.raw[parity] if rectifying, else upload[parity]
 //   rectify   rect.raw[parity] (host, grey or downscale output) or caller memory eq.keep if equalising, else upload[parity]
-//   equalise  eq.keep if rectifying, else DevBuf::img (in place when that        upload[parity]
-//             already is upload[parity])
+//   smooth    previous or caller memory; never upload[parity]: while smoothing,  sm.out if equalising, else upload[parity]
+//             every stage above (and the host upload) writes sm.in[parity] where
+//             it would have written upload[parity] or eq.keep
+//   equalise  sm.out if smoothing, else eq.keep if rectifying, else DevBuf::img  upload[parity]
+//             (in place when that already is upload[parity])
+// The getters read where a stage wrote: vslam_get_gray_images / _downscaled_images / _rectified_images the slabs above (sm.in[parity]
+// while smoothing, which nothing later overwrites), vslam_get_smoothed_images sm.out, or upload[parity] when smoothing is the last stage.
 // RGB-D (single buffers; caller memory is never written):
 //   grey      d_img (host) or caller memory                                      col.gray
 //   downscale previous                                                           ds.img (the depth image: on the space map's queue)
 //   undistort previous                                                           und.img
+//   smooth    previous                                                           sm.img
 //   equalise  previous                                                           in place if the image is ours (host frame, grey,
-//                                                                                undistorted), else eq.img
+//                                                                                undistorted, smoothed), else eq.img
+// (so vslam_rgbd_get_smoothed, like vslam_rgbd_get_undistorted, returns the equalised image while the slot is on: it works in place)
 struct PrePlan {
   int format = 0;               // VSLAM_PIXEL_*: the grey stage runs unless GRAY8
   bool remap = false;
@@ -200,8 +207,10 @@ struct PrePlan {
   ImgPlanes color, gray;        // grey stage: source, result (in_rows x in_cols)
   ImgPlanes full, reduced;      // downscale: source (in_rows x in_cols), result (red_rows x red_cols)
   ImgPlanes raw, mapped;        // remap: source (in_rows x in_cols), result (rows x cols)
+  int smooth_mode = 0, smooth_ksize = 0;   // VSLAM_SMOOTH_*: the smoothing stage runs unless OFF
+  ImgPlanes unsmoothed, smoothed;          // smoothing: source, result (rows x cols); never the same memory
 };
-// grey, then downscale, then remap, then equalise, on one queue
+// grey, then downscale, then remap, then smooth, then equalise, on one queue
 static hipError_t prestage_enqueue(hipStream_t st, const PrePlan& pl, const RemapMaps& maps, const EqSlot& eq, int n, int sides, const uint32_t* active) {
   if (pl.format != VSLAM_PIXEL_GRAY8) {
     GrayArgs ga{};
@@ -218,6 +227,13 @@ static hipError_t prestage_enqueue(hipStream_t st, const PrePlan& pl, const Rema
     if (e != hipSuccess) return e;
   }
   if (pl.remap) remap_enqueue(st, maps, pl.raw, pl.mapped, n, sides, active);
+  if (pl.smooth_mode) {
+    SmoothArgs sa{};
+    place(sa, pl.unsmoothed, pl.smoothed, pl.rows, pl.cols, n, sides, active);
+    sa.mode = pl.smooth_mode; sa.ksize = pl.smooth_ksize;
+    const hipError_t e = smooth_enqueue(st, sa);
+    if (e != hipSuccess) return e;
+  }
   return eq.on ? eq.enqueue(st, pl.rows, pl.cols, n, sides, active) : hipSuccess;
 }
 

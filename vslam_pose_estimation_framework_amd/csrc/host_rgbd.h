@@ -287,6 +287,27 @@ VS_API int vslam_rgbd_get_downscaled(vslam_rgbd* r, int32_t stream, uint8_t* ima
   return r->on_host ? rgbd_downscale_host_refusal(r, "vslam_rgbd_get_downscaled") : r->d.get_downscaled(stream, image, depth);
 }
 
+// ---- smoothing of the intensity image (the definition above vslam_set_smoothing) ------------------------------------------
+static int rgbd_smoothing_host_refusal(vslam_rgbd* r, const char* what) {
+  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not smooth; use the device-resident loop";
+  return VSLAM_ERR_STATE;
+}
+VS_API int vslam_rgbd_set_smoothing(vslam_rgbd* r, int mode, int32_t ksize) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_smoothing_host_refusal(r, "vslam_rgbd_set_smoothing") : r->d.set_smoothing(mode, ksize);
+}
+VS_API int vslam_rgbd_get_smoothing(vslam_rgbd* r, int* mode, int32_t* ksize) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (!r->on_host) { r->d.get_smoothing(mode, ksize); return VSLAM_OK; }
+  if (mode) *mode = VSLAM_SMOOTH_OFF;
+  if (ksize) *ksize = 0;
+  return VSLAM_OK;
+}
+VS_API int vslam_rgbd_get_smoothed(vslam_rgbd* r, int32_t stream, uint8_t* image) {
+  if (!r) return VSLAM_ERR_INVALID;
+  return r->on_host ? rgbd_smoothing_host_refusal(r, "vslam_rgbd_get_smoothed") : r->d.get_smoothed(stream, image);
+}
+
 // ---- motion models (the definition above vslam_set_motion_model) ---------------------------------------------------------
 VS_API int vslam_rgbd_set_motion_model(vslam_rgbd* r, int model, int32_t dead_reckoning_limit) {
   if (!r) return VSLAM_ERR_INVALID;

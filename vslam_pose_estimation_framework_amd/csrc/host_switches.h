@@ -1,5 +1,5 @@
 // host_switches.h — the stereo context's input-stage switches and their getters: rectification (vslam_set_rectification), the equalisation
-// slot (vslam_set_equalization, vslam_set_clahe), colour input (vslam_set_color_input) and the downscale (vslam_set_downscale), the stores behind them, and the stand-alone
+// slot (vslam_set_equalization, vslam_set_clahe), colour input (vslam_set_color_input), the downscale (vslam_set_downscale) and smoothing (vslam_set_smoothing), the stores behind them, and the stand-alone
 // vslam_remap_u8; behind them the motion model and the pose guesses of CAMERA_ODOMETRY (vslam_set_motion_model, vslam_set_pose_guess*),
 // with launch_motion_prior, the head of the frame's launch sequence.  What the switches share with the RGB-D tracker is host_prestage.h; a frame's routing through the stages is route_frame
 // in host_frame.h.  Host code, included by vslam_hip.hip after host_ctx.h and ahead of host_frame.h.
@@ -15,10 +15,11 @@ static void eq_free(vslam_ctx* c) {
   c->eq.keep_mem.release();
   c->eq.keep[0] = c->eq.keep[1] = nullptr;
 }
-// the rectified pair's own slabs exist exactly while rectification and equalisation are both on (called by both setters, queues idle)
+// the rectified pair's own slabs exist exactly while rectification and equalisation are both on and smoothing, which then takes the
+// rectified pair into sm.in, is off (called by the three setters, queues idle)
 static hipError_t eq_keep_sync(vslam_ctx* c) {
   vslam_ctx::Eq& q = c->eq;
-  const bool want = q.on && c->rect.on;
+  const bool want = q.on && c->rect.on && !c->sm.mode;
   if (want == (q.keep[0] != nullptr)) return hipSuccess;
   q.keep_mem.release();
   q.keep[0] = q.keep[1] = nullptr;
@@ -30,6 +31,23 @@ static hipError_t eq_keep_sync(vslam_ctx* c) {
 static void col_free(vslam_ctx* c) {
   c->col.mem.release();
   c->col = vslam_ctx::Col();
+}
+static void sm_free(vslam_ctx* c) {
+  c->sm.mem.release();
+  c->sm.out_mem.release();
+  c->sm = vslam_ctx::Sm();
+}
+// the smoothed pair's own slabs exist exactly while smoothing and equalisation are both on (called by the setters of both, queues idle)
+static hipError_t sm_out_sync(vslam_ctx* c) {
+  vslam_ctx::Sm& q = c->sm;
+  const bool want = q.mode && c->eq.on;
+  if (want == (q.out[0] != nullptr)) return hipSuccess;
+  q.out_mem.release();
+  q.out[0] = q.out[1] = nullptr;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && want && e == hipSuccess; ++k) e = q.out_mem.alloc(&q.out[k], (size_t)c->B * c->up_stream_stride);
+  if (e != hipSuccess) { q.out_mem.release(); q.out[0] = q.out[1] = nullptr; }
+  return e;
 }
 static void ds_free(vslam_ctx* c) {
   c->ds.mem.release();
@@ -64,7 +82,9 @@ static hipError_t col_slab_sync(vslam_ctx* c) {
 // the slabs of the context as image pairs: upload[set], and where k_rectify writes the pair of product set `set` (with equalisation on as
 // well: in slabs of its own, the equalised pair goes to upload[set])
 static ImgPlanes upload_planes(const vslam_ctx* c, int set) { return {{c->upload[set][0], c->upload[set][1]}, c->up_stride, c->up_stream_stride}; }
+static ImgPlanes unsmoothed_planes(const vslam_ctx* c, int set) { return {{c->sm.in[set][0], c->sm.in[set][1]}, c->up_stride, c->up_stream_stride}; }
 static ImgPlanes rectified_planes(const vslam_ctx* c, int set) {
+  if (c->sm.mode) return unsmoothed_planes(c, set);
   return c->eq.keep[0] ? ImgPlanes{{c->eq.keep[0], c->eq.keep[1]}, c->up_stride, c->up_stream_stride} : upload_planes(c, set);
 }
 // both sides of stream s of a pair, rows x cols, dense
@@ -163,7 +183,8 @@ static int eq_switch(vslam_ctx* c, bool on, const ClaheArgs* geo, double clip_li
   std::string why;
   const int rc = c->eq.switch_to(on, geo, clip_limit, c->B, 2, names, &why,
                                  [&] { (void)hipSetDevice(c->device); sync_all(c); eq_free(c); },     // the frames in flight still read the tables and the slabs
-                                 [&] { return eq_keep_sync(c); });
+                                 [&] { const hipError_t e = eq_keep_sync(c); return e == hipSuccess ? sm_out_sync(c) : e; });
+  if (!c->eq.on) (void)sm_out_sync(c);      // switched off: the smoothed pair goes to upload[parity] again (this can only free)
   return rc ? fail(c, rc, why) : VSLAM_OK;
 }
 VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
@@ -273,6 +294,54 @@ VS_API int vslam_get_downscaled_images(vslam_ctx* c, int s, uint8_t* left, uint8
   if (c->ds.factor == 1 || !c->ds.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_downscaled_images: no frame has been downscaled since vslam_set_downscale");
   if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_downscaled_images: null output");
   return pair_to_host(c, c->pre.reduced, s, c->pre.red_rows, c->pre.red_cols, left, right);
+}
+
+// ---- smoothing of the grey pair ahead of the equalisation slot (kernels_smooth.h) ------------------------------------
+static_assert(VSLAM_SMOOTH_OFF == VS_SMOOTH_OFF && VSLAM_SMOOTH_GAUSSIAN == VS_SMOOTH_GAUSSIAN && VSLAM_SMOOTH_MEDIAN == VS_SMOOTH_MEDIAN, "smoothing modes");
+// what both setters and the stand-alone entry refuse: 0, or VSLAM_ERR_INVALID with *why filled
+static int smooth_check(const char* who, int mode, int32_t ksize, int rows, int cols, std::string* why) {
+  const char* what = nullptr;
+  if (mode != VSLAM_SMOOTH_GAUSSIAN && mode != VSLAM_SMOOTH_MEDIAN) what = ": unknown mode";
+  else if (!smooth_mode_ok(mode, ksize)) what = mode == VSLAM_SMOOTH_GAUSSIAN ? ": a Gaussian has ksize 3, 5 or 7" : ": a median has ksize 3 or 5";
+  else if (!smooth_size_ok(mode, ksize, rows, cols)) what = ": a Gaussian needs rows and cols above ksize / 2";
+  if (!what) return VSLAM_OK;
+  *why = std::string(who) + what;
+  return VSLAM_ERR_INVALID;
+}
+VS_API int vslam_set_smoothing(vslam_ctx* c, int mode, int32_t ksize) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_smoothing called inside a frame");
+  std::string why;
+  if (mode != VSLAM_SMOOTH_OFF)
+    if (const int rc = smooth_check("vslam_set_smoothing", mode, ksize, c->cfg.c.rows, c->cfg.c.cols, &why)) return fail(c, rc, why);
+  if (c->sticky != VSLAM_OK) return c->sticky;
+  vslam_ctx::Sm& q = c->sm;
+  if (mode == VSLAM_SMOOTH_OFF ? q.mode == VSLAM_SMOOTH_OFF : (q.mode == mode && q.ksize == ksize)) return VSLAM_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  sync_all(c);                     // the frames in flight still read the slabs
+  if (mode != VSLAM_SMOOTH_OFF && q.mode != VSLAM_SMOOTH_OFF) { q.mode = mode; q.ksize = ksize; q.have_frame = false; return VSLAM_OK; }     // the slabs stay
+  sm_free(c);
+  hipError_t e = hipSuccess;
+  if (mode != VSLAM_SMOOTH_OFF) {
+    for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = q.mem.alloc(&q.in[p][k], (size_t)c->B * c->up_stream_stride);
+    if (e == hipSuccess) { q.mode = mode; q.ksize = ksize; e = sm_out_sync(c); }
+  }
+  if (e == hipSuccess) e = eq_keep_sync(c);
+  if (e != hipSuccess) { sm_free(c); (void)eq_keep_sync(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_smoothing: ") + hipGetErrorString(e)); }
+  return VSLAM_OK;
+}
+VS_API int vslam_get_smoothing(vslam_ctx* c, int* mode, int32_t* ksize) {
+  if (!c) return VSLAM_ERR_INVALID;
+  if (mode) *mode = c->sm.mode;
+  if (ksize) *ksize = c->sm.mode ? c->sm.ksize : 0;
+  return VSLAM_OK;
+}
+VS_API int vslam_get_smoothed_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
+  const int rc = check_stream(c, s);
+  if (rc != VSLAM_OK) return rc;
+  if (!c->sm.mode || !c->sm.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_smoothed_images: no frame has been smoothed since vslam_set_smoothing / vslam_reset");
+  if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_smoothed_images: null output");
+  return pair_to_host(c, c->pre.smoothed, s, c->cfg.c.rows, c->cfg.c.cols, left, right);
 }
 
 // ---- motion models and the pose guesses of CAMERA_ODOMETRY (kernels_motion.h) --------------------------------------

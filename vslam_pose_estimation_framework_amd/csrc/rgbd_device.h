@@ -134,6 +134,7 @@ public:
     eq.have_frame = false;                                                   // and so does the equalisation switch
     col.have_frame = false;                                                  // and the colour format
     ds.have_frame = false;                                                   // and the downscale
+    sm.have_frame = false;                                                   // and the smoothing
     bl.have_frame = false;                                                   // and the depth image's bilateral filter
     dmask.have_frame = false;                                                // and the detection mask, with the maps' validity mask
     dmask.fm_pending = false; dmask.fm_frame = false; dmask.fm_have = false;  // frame masks that waited for a frame belong to the sequence that ended
@@ -603,6 +604,43 @@ public:
     return fetched(e);
   }
 
+  // ---- smoothing of the intensity image (kernels_smooth.h): opt-in, its own allocation, nothing launched while sm.mode is OFF.  Behind
+  // the undistortion and ahead of the equalisation slot, on the image queue, once per frame, from wherever the image lies (the staged copy,
+  // the grey / reduced / undistorted image, the caller's device memory: only read) into sm.img, which the slot then equalises in place
+  // and the detector reads.  The depth image is untouched.
+  int set_smoothing(int mode, int32_t ksize) {
+    if (pending) { err = "vslam_rgbd_set_smoothing: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
+    if (mode != VSLAM_SMOOTH_OFF)
+      if (const int rc = smooth_check("vslam_rgbd_set_smoothing", mode, ksize, p.rows, p.cols, &err)) return rc;
+    if (mode == VSLAM_SMOOTH_OFF ? sm.mode == VSLAM_SMOOTH_OFF : (sm.mode == mode && sm.ksize == ksize)) return VSLAM_OK;
+    (void)hipSetDevice(ic->device);
+    (void)hipStreamSynchronize(q);
+    (void)hipStreamSynchronize(q2);
+    drop_graph();                                   // a captured launch sequence holds the kernel and its buffer (or lacks them)
+    if (mode != VSLAM_SMOOTH_OFF && sm.mode != VSLAM_SMOOTH_OFF) { sm.mode = mode; sm.ksize = ksize; sm.have_frame = false; return VSLAM_OK; }   // the image stays
+    sm_free();
+    if (mode == VSLAM_SMOOTH_OFF) return VSLAM_OK;
+    const int32_t stride = (p.cols + 15) & ~15;
+    uint8_t* img = nullptr;
+    const hipError_t e = sm.mem.alloc(&img, (size_t)p.rows * stride * (size_t)B);
+    if (e != hipSuccess) { sm_free(); return hip_fail(e, "vslam_rgbd_set_smoothing"); }
+    sm.img = {{img, nullptr}, stride, (size_t)p.rows * stride};
+    sm.mode = mode; sm.ksize = ksize;
+    return VSLAM_OK;
+  }
+  void get_smoothing(int* mode, int32_t* ksize) const {
+    if (mode) *mode = sm.mode;
+    if (ksize) *ksize = sm.mode ? sm.ksize : 0;
+  }
+  // the smoothed image of the last finished frame of `stream` (dense); equalised in place afterwards while the slot is on
+  int get_smoothed(int stream, uint8_t* image) {
+    if (int rc = readable(stream)) return rc;
+    if (!sm.mode || !sm.have_frame) { err = "vslam_rgbd_get_smoothed: no frame has been smoothed since vslam_rgbd_set_smoothing / vslam_rgbd_reset"; return VSLAM_ERR_STATE; }
+    if (!image) { err = "vslam_rgbd_get_smoothed: null output"; return VSLAM_ERR_INVALID; }
+    (void)hipSetDevice(ic->device);
+    return fetched(planes_to_host(image, sm.img, 0, stream, p.rows, p.cols));
+  }
+
   // ---- colour input (kernels_gray.h): opt-in, its own allocation, nothing launched while col.format is VSLAM_PIXEL_GRAY8.  The intensity
   // image of every entry is interleaved colour then (strides in bytes); k_gray_u8 converts it into col.gray, an image of the tracker's own at
   // the input size, which everything behind it reads — the undistortion, else the equalisation (in place) and the detector.  The caller's
@@ -659,7 +697,7 @@ public:
     pending = false;
     const int rc = finish_frame();
     if (rc != VSLAM_OK) { failed = true; failed_why = err; }
-    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; ds.have_frame = ds.factor > 1; bl.have_frame = bl.on; dmask.have_frame = dmask.stat[0] != nullptr; dmask.fm_have = dmask.fm_frame; }
+    else { und.have_frame = und.on; eq.have_frame = eq.on; col.have_frame = col.format != VSLAM_PIXEL_GRAY8; ds.have_frame = ds.factor > 1; sm.have_frame = sm.mode != 0; bl.have_frame = bl.on; dmask.have_frame = dmask.stat[0] != nullptr; dmask.fm_have = dmask.fm_frame; }
     return rc;
   }
 
@@ -750,6 +788,8 @@ private:
   // frame [B][full_rows * full_cols], re-packed.  full_dep*: where this frame's full-size depth images are (the staging or caller memory)
   struct Down { int factor = 1, full_rows = 0, full_cols = 0; bool have_frame = false; ImgPlanes img; uint16_t* full_depth = nullptr; DeviceStore mem; } ds;
   const uint16_t* full_dep = nullptr; int32_t full_dep_stride = 0; size_t full_dep_stream = 0;
+  // smoothing of the intensity image: off while mode is VSLAM_SMOOTH_OFF.  img: the smoothed images [B]
+  struct Smooth { int mode = 0, ksize = 0; bool have_frame = false; ImgPlanes img; DeviceStore mem; } sm;
   // bilateral filtering of the depth image: off while bl.on is false.  depth: the filtered images [B][rows * cols] the space map reads;
   // args: what the three kernels get but for this frame's source (sizes, scales, taps, the range cells [B][4] and the tables [B][4098])
   struct Bilateral { bool on = false, have_frame = false; double sigma_color = 0, sigma_space = 0; uint16_t* depth = nullptr; BilateralArgs args; DeviceStore mem; } bl;
@@ -838,6 +878,10 @@ private:
     ds.mem.release();
     ds = Down{};
   }
+  void sm_free() {
+    sm.mem.release();
+    sm = Smooth{};
+  }
   // This frame's routing through the input stages (the table: host_prestage.h, PrePlan), from which switches are on: `in` is
   // the intensity image that came in (the staged copy or the caller's device memory), own: it is ours to overwrite.  Fills pre and the
   // slot's src / dst and points bs at what the detector reads.  The grey image is allocated here, with the first frame at its size.
@@ -861,6 +905,8 @@ private:
     }
     if (ds.factor > 1) { pre.full = in; pre.reduced = ds.img; in = ds.img; own = true; }
     if (und.on) { pre.raw = in; pre.mapped = und.img; in = und.img; own = true; }
+    pre.smooth_mode = sm.mode; pre.smooth_ksize = sm.ksize;
+    if (sm.mode) { pre.unsmoothed = in; pre.smoothed = sm.img; in = sm.img; own = true; }
     if (eq.on) { eq.src = in; eq.dst = own ? in : eq.img; in = eq.dst; }
     buf_set_planes(bs, in);
     return hipSuccess;
@@ -914,6 +960,7 @@ private:
     eq_free();
     col_free();
     ds_free();
+    sm_free();
     bl_free();
     dmask_free();
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }

@@ -23,6 +23,7 @@
 #include "kernels_bilateral.h"
 #include "kernels_gray.h"
 #include "kernels_downscale.h" // integer-factor reduction of images and depth images (stand-alone entries)
+#include "kernels_smooth.h"    // Gaussian / median smoothing of the intensity image
 #include "kernels_map.h"
 #include "kernels_obs.h"
 #include "kernels_map_color.h"
