@@ -116,7 +116,9 @@ struct StreamState {
 struct ImgInfo {
   int32_t thr_after[VSLAM_MAX_REGIONS];   // thresholds after adjustDetectorThresholds of this frame
   int32_t raw_count[2][VSLAM_MAX_REGIONS];
-  int32_t ticket;                         // k_emit: arrival counter of the stream's two per-image workgroups
+  int32_t ticket;                         // k_emit: arrival counter of the stream's sides x bands workgroups
+  int32_t raw_acc[2][VSLAM_MAX_REGIONS];  // k_emit: the bands' raw counts add up here; like the ticket, zero between launches (the last arrival
+                                          // of a launch moves the sums into raw_count and clears them, so no launch relies on another's memset)
 };
 
 #define VS_MAX_STREAMS 4096   // streams per context (one bit each in DevBuf::active)

@@ -449,7 +449,7 @@ VS_API int vslam_orb_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int3
     int32_t* n1 = k.dev<int32_t>(1); int32_t* n2 = k.dev<int32_t>(1);
     if (!k.ok()) break;
     launch_fast_box(t, st, 1);
-    hipLaunchKernelGGL(k_emit, dim3(1, 1), dim3(512), 0, st, t->cfg, t->buf, edge, 0);                                  // runByImageBorder(edgeThreshold)
+    launch_emit(st, t->cfg, t->buf, 1, 1, edge, 0);                                  // runByImageBorder(edgeThreshold)
     hipLaunchKernelGGL(k_orb_select<uint8_t>, dim3(1), dim3(1024), 0, st, t->buf.n_kp, t->buf.kp_xy, t->buf.kp_score, 2 * plan.quota[l], n1, xy1, r1, (int)N);   // retainBest(2 n) on the FAST score
     hipLaunchKernelGGL(k_orb_harris, dim3(256), dim3(256), 0, st, lev, lstride, n1, xy1, rh);
     hipLaunchKernelGGL(k_orb_select<float>, dim3(1), dim3(1024), 0, st, n1, xy1, rh, plan.quota[l], n2, xy2, r2, (int)N);            // retainBest(n) on the Harris response
@@ -487,7 +487,7 @@ VS_API int vslam_fast_detect(vslam_ctx* c, const uint8_t* img, int32_t rows, int
   rc = k.ok() ? set_inputs(t, img, img, stride, 0, false) : k.status();
   if (rc == VSLAM_OK) {
     launch_fast_box(t, t->stream_img, 2);
-    hipLaunchKernelGGL(k_emit, dim3(1, 2), dim3(512), 0, t->stream_img, t->cfg, t->buf, 0, 0);
+    launch_emit(t->stream_img, t->cfg, t->buf, 1, 2, 0, 0);
     int32_t cnt = 0;
     rc = vslam_get_keypoints(t, 0, 0, cap, &cnt, xy, score, nullptr);
     *n = cnt;

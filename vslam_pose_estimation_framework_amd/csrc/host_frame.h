@@ -41,7 +41,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (coarse && c->timers) { e0 = ev_get(c); (void)hipEventRecord(e0, st); }
   { KernelTimer t(c, 0, st, true, !coarse); hipLaunchKernelGGL(k_fast_box, g1, dim3(256), VS_FB_DYN_LDS, st, c->cfg, bs); }
-  { KernelTimer t(c, 1, st, true, !coarse); if (masked) mask_enqueue(c, st, bs); hipLaunchKernelGGL(k_emit, dim3(n, 2), dim3(512), 0, st, c->cfg, bs, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 1); }
+  { KernelTimer t(c, 1, st, true, !coarse); if (masked) mask_enqueue(c, st, bs); launch_emit(st, c->cfg, bs, n, 2, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 1); }
   if (e0) { e1 = ev_get(c); (void)hipEventRecord(e1, st); c->evrec.push_back({e0, e1, 0, true}); c->kern_n[1] += 1; }
   if (c->img_override && c->report && c->B == 1) {
     // stage path with a view reader: coordinates and scores leave for the host as soon as k_emit has written them, so that the caller

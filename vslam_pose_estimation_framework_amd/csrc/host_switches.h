@@ -642,6 +642,12 @@ static void mask_enqueue(vslam_ctx* c, hipStream_t st, const DevBuf& bs) {
     std::memcpy(q.last_active, bs.active, sizeof q.last_active);
   } else q.last = 0;
 }
+// k_emit over `streams` streams of `sides` images each (kernels_image.h): one workgroup per band of VS_EMIT_BAND mask words.
+// run_controller: 0 none, 1 over a stream's two images, 2 over its one image.
+static void launch_emit(hipStream_t st, const DevCfg& cfg, const DevBuf& buf, int streams, int sides, int border, int run_controller) {
+  const int bands = (cfg.c.rows * cfg.TX + VS_EMIT_BAND - 1) / VS_EMIT_BAND;
+  hipLaunchKernelGGL(k_emit, dim3(streams, sides, bands), dim3(VS_EMIT_THREADS), 0, st, cfg, buf, border, run_controller);
+}
 VS_API int vslam_get_detection_mask(vslam_ctx* c, int s, int side, uint64_t* words) {
   const int rc = check_stream(c, s);
   if (rc != VSLAM_OK) return rc;

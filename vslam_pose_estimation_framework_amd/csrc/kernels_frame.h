@@ -245,7 +245,7 @@ __device__ __forceinline__ void candidates_wave(const DevCfg& c, const DevBuf& b
 // XCD-aware labels for (blocks-per-stream, streams) grids: workgroups are dealt round-robin over the 8 XCDs, so with the plain
 // grid the blocks of ONE stream land on all eight and every L2 fetches that stream's descriptors, keypoints and row / cell CSR.
 // Re-labelled, the gridDim.x blocks of stream s all run on XCD s mod 8 — the XCD its frame workgroup (block s of k_frame) and
-// its two k_emit workgroups run on, whose L2 then already holds / will want the same lines.  Speed only, never correctness.
+// its k_emit workgroups run on, whose L2 then already holds / will want the same lines.  Speed only, never correctness.
 __device__ __forceinline__ void xcd_stream_block(int* bx, int* sy, int rot = 0) {
   const int gx = gridDim.x, ns = gridDim.y;
   const int lin = blockIdx.y * gx + blockIdx.x, per = (ns >> 3) * gx;      // blocks per XCD among the first 8 * (ns / 8) streams

@@ -427,186 +427,248 @@ __global__ __launch_bounds__(256, 8) void k_fast_box(const DevCfg c, const DevBu
 }
 
 // ==============================================================================================
-// K2: one workgroup per stream.  Scans the corner masks of both images in (row, x) order, applies
-// the descriptor border filter (KeyPointsFilter::runByImageBorder(28)), writes keypoints
-// row-major, builds the row/cell CSR, counts raw detections per detector region, then runs the
+// K2: corner masks -> keypoints.  Scans the corner masks of both images in (row, x) order, applies
+// the descriptor border filter (KeyPointsFilter::runByImageBorder(28)), writes keypoints and their
+// scores row-major, builds the row/cell CSR, counts raw detections per detector region, then runs the
 // threshold controller + adjustDetectorThresholds and the triangulation-distance rule
 // (stereo_framepoint_generator.cpp:109-125).  `border` = 28 in the pipeline, 0 for stand-alone FAST.
-// run_controller: 0 none, 1 over the stream's two images (stereo: grid (streams, 2)), 2 over ONE image (RGB-D mode, grid
-// (streams, 1): adjustDetectorThresholds averages a single detection, depth_framepoint_generator.cpp:24-44).
+// run_controller: 0 none, 1 over the stream's two images (stereo: sides = 2), 2 over ONE image (RGB-D mode, sides = 1:
+// adjustDetectorThresholds averages a single detection, depth_framepoint_generator.cpp:24-44).
+//
+// Grid (streams, sides, bands), 256 threads: an image's mask words are cut into bands of VS_EMIT_BAND consecutive words and
+// workgroup (s, side, k) emits the keypoints of band k alone.  Where its keypoints start in the list it counts itself, from the
+// words [0, k * VS_EMIT_BAND) under the same border filter: no workgroup waits for another, so nothing can hang, and the words
+// read twice come from L2.  One barrier per workgroup: the block sum of the prefix count and the scan of the band's own words
+// go through it together.  launch_emit (host_switches.h) derives the grid.
 // ==============================================================================================
 __device__ __forceinline__ unsigned long long col_mask(int lo, int hi, int wx0) {
-  // bits of a 64-px word starting at column wx0 whose column lies in [lo, hi)
-  int a = max(lo - wx0, 0), e = min(hi - wx0, 64);
-  if (e <= a) return 0ull;
-  const unsigned long long hi_m = (e >= 64) ? ~0ull : ((1ull << e) - 1ull);
-  return hi_m & ~((1ull << a) - 1ull);
+  // bits of a 64-px word starting at column wx0 whose column lies in [lo, hi); without a branch: bits a and up AND bits below e
+  const int a = min(max(lo - wx0, 0), 64), e = min(max(hi - wx0, 0), 64);
+  const unsigned long long from_a = a >= 64 ? 0ull : (~0ull << a), below_e = e >= 64 ? ~0ull : ~(~0ull << e);
+  return from_a & below_e;
 }
 
+// inclusive prefix sum over the 64 lanes on the DPP network (no LDS round trip): three shifts by one lane, the shifts by 4 and 8
+// inside a row of 16, then lane 15 into the next row and lane 31 into the upper half.  All 64 lanes must be active.
+__device__ __forceinline__ int wave_scan_incl(int x) {
+  int s = x;
+  s += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1
+  s += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);   // row_shr:2
+  s += __builtin_amdgcn_update_dpp(0, x, 0x113, 0xf, 0xf, false);   // row_shr:3
+  s += __builtin_amdgcn_update_dpp(0, s, 0x114, 0xf, 0xe, false);   // row_shr:4, lanes 4 .. 15 of a row
+  s += __builtin_amdgcn_update_dpp(0, s, 0x118, 0xf, 0xc, false);   // row_shr:8, lanes 8 .. 15 of a row
+  s += __builtin_amdgcn_update_dpp(0, s, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+  s += __builtin_amdgcn_update_dpp(0, s, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+  return s;
+}
+__device__ __forceinline__ int wave_sum(int x) { return __builtin_amdgcn_readlane(wave_scan_incl(x), 63); }
+
 #ifndef VS_EMIT_WPT
-#define VS_EMIT_WPT 4    // mask words a thread keeps in registers per pass (one pass = 512 * 4 words = 131072 px; 96 VGPRs, no scratch).  Measured (round 4,
-                         // 157 streams, alone on the chip): 4 -> 58 us, 8 -> 67 us, 16 -> 73 us: the kernel is bound by the per-lane emission loops, not by its four passes
+#define VS_EMIT_WPT 4    // mask words of the band a thread keeps in registers.  Measured (157 streams, in situ, six runs each): 4 -> 60 us, 2 -> 70 us
 #endif
-__global__ __launch_bounds__(512, VS_EMIT_WPT > 8 ? 2 : 4) void k_emit(const DevCfg c, const DevBuf b, int border, int run_controller) {
-  __shared__ int sh_wave[8], sh_total;
-  __shared__ int sh_cnt[VSLAM_MAX_REGIONS];
-  __shared__ int sh_last;
-  // block (i, side) is the (side * gridDim.x + i)-th of the launch: both images of stream s on physical XCD s % 8 (dev_types.h xcd_rot)
-  const int s = b.s0 + xcd_local_stream(blockIdx.x, gridDim.x, (b.xcd_rot + blockIdx.y * gridDim.x) & 7), tid = threadIdx.x;
+#define VS_EMIT_THREADS 256
+#define VS_EMIT_BAND (VS_EMIT_THREADS * VS_EMIT_WPT)   // mask words per band
+#define VS_EMIT_PF 8     // words of the prefix count a thread has in flight at a time (16: the same time, and 40 B of scratch)
+#define VS_EMIT_HEAD 2   // keypoints per word whose score loads are in flight together
+__global__ __launch_bounds__(VS_EMIT_THREADS, 8) void k_emit(const DevCfg c, const DevBuf b, int border, int run_controller) {
+  __shared__ int sh_pre[VS_EMIT_THREADS / 64], sh_own[VS_EMIT_THREADS / 64];
+  __shared__ int sh_cnt[VS_EMIT_THREADS / 64][VSLAM_MAX_REGIONS];
+  // block (i, side, z) is the ((z * sides + side) * gridDim.x + i)-th of the launch: all workgroups of stream s on physical XCD s % 8
+  // (dev_types.h xcd_rot).  The last band, whose prefix count is the longest, starts first.
+  const int side = blockIdx.y, band = (int)gridDim.z - 1 - (int)blockIdx.z, tid = threadIdx.x;
+  const int s = b.s0 + xcd_local_stream(blockIdx.x, gridDim.x, (int)((b.xcd_rot + (side + gridDim.y * blockIdx.z) * gridDim.x) & 7));
   if (!vs_active(b, s)) return;
   const int rows = c.c.rows, cols = c.c.cols, TX = c.TX, CW = c.CW;
   StreamState& st = b.st[s];
-  if (tid < VSLAM_MAX_REGIONS) sh_cnt[tid] = 0;
-  __syncthreads();
   const int nwords = rows * TX;
-  // one 512-thread workgroup per image (blockIdx.y = side).
-  // Word order = keypoint order.  A pass covers 512 * VS_EMIT_WPT consecutive mask words: wave w owns 64 * VS_EMIT_WPT of them, [256 w, 256 w + 256)
-  // of the pass, lane l its words l, l + 64, ... — every load and store of a wave covers consecutive words (coalesced),
-  // and the prefix over the words is 8 wave scans + one 8-entry scan across waves.
-  const int side = blockIdx.y, lane = tid & 63, w = tid >> 6;
+  // Word order = keypoint order.  Wave w owns 64 * VS_EMIT_WPT consecutive words of the band, lane l its words l, l + 64, ... — every
+  // load and store of a wave covers consecutive words (coalesced), and the prefix over the band's words is one scan per wave and word
+  // slot + a sum across the four waves.
+  const int lane = tid & 63, w = tid >> 6;
+  const unsigned long long* mask = mask_of(c, b, s, side);
+  const uint8_t* score8 = score_of(c, b, s, side);
+  int16_t* kxy = kpxy_of(c, b, s, side);
+  uint8_t* ksc = kpscore_of(c, b, s, side);
+  int32_t* rowcell = rowcell_of(c, b, s, side);
+  uint8_t* used = used_of(c, b, s, side);
+  // the border filter, for the prefix count and the emission alike: the rows of the top and bottom strips lose everything, the others
+  // what col_keep takes from their first and last words
+  auto col_keep = [&](int t) -> unsigned long long { return col_mask(border, cols - border, t * 64); };
+  auto filtered = [&](unsigned long long m, int row, int t) -> unsigned long long {
+    return (row >= border && row < rows - border) ? (m & col_keep(t)) : 0ull;
+  };
+  const int w0 = band * VS_EMIT_BAND;                 // the band's first word
+  const int wbase = w0 + w * 64 * VS_EMIT_WPT + lane;
+  const int row_b = wbase / TX, t_b = wbase - row_b * TX;
+  const int q64 = 64 / TX, r64 = 64 - q64 * TX;       // (row, word-in-row) of word + 64 without a division
+  unsigned long long mw[VS_EMIT_WPT];
+#pragma unroll
+  for (int j = 0; j < VS_EMIT_WPT; ++j) mw[j] = (wbase + 64 * j < nwords) ? mask[wbase + 64 * j] : 0ull;
+  // Keypoints of the bands before this one, filtered(): the words [0, w0) of the rows [border, rows - border) — the strips hold no
+  // keypoint and are not loaded.  A sweep of the workgroup covers whole rows, so a thread stays on one word column and col_keep is one
+  // constant to it: a word costs its load, an AND and a population count.
+  int pre = 0;
   {
-    const unsigned long long* mask = mask_of(c, b, s, side);
-    const uint8_t* score8 = score_of(c, b, s, side);
-    int16_t* kxy = kpxy_of(c, b, s, side);
-    uint8_t* ksc = kpscore_of(c, b, s, side);
-    int32_t* rowcell = rowcell_of(c, b, s, side);
-    uint8_t* used = used_of(c, b, s, side);
-    auto filtered = [&](unsigned long long m, int row, int t) -> unsigned long long {
-      const bool row_ok = row >= border && row < rows - border;
-      return row_ok ? (m & col_mask(border, cols - border, t * 64)) : 0ull;
-    };
-    int done = 0;   // keypoints of earlier passes
-    const int q64 = 64 / TX, r64 = 64 - q64 * TX;   // (row, word-in-row) of word + 64 without a division
-    for (int p0 = 0; p0 < nwords; p0 += 512 * VS_EMIT_WPT) {
-      const int wbase = p0 + w * 64 * VS_EMIT_WPT + lane;
-      const int row_b = wbase / TX, t_b = wbase - row_b * TX;
-      unsigned long long mw[VS_EMIT_WPT];
+    const int pe = min(w0, (rows - border) * TX);
+    const int lt = min(TX, VS_EMIT_THREADS), rps = VS_EMIT_THREADS / lt;   // threads along a row, rows per sweep
+    const int r_off = tid / lt, t_in = tid - r_off * lt;
+    const int step = rps * TX;
+    for (int t = t_in; t < TX; t += lt) {     // one trip unless a row has more words than the workgroup threads
+      const unsigned long long keep = col_keep(t);
+      for (int i = r_off < rps ? (border + r_off) * TX + t : pe; i < pe; i += step * VS_EMIT_PF) {
+        unsigned long long pw[VS_EMIT_PF];
 #pragma unroll
-      for (int j = 0; j < VS_EMIT_WPT; ++j) mw[j] = (wbase + 64 * j < nwords) ? mask[wbase + 64 * j] : 0ull;
-      // raw detections per region (controller input): every corner bit lies in exactly one region
-      for (int r = 0; r < c.n_regions; ++r) {
-        const DevRegion& R = c.regions[r];
-        int n = 0, row = row_b, t = t_b;
+        for (int u = 0; u < VS_EMIT_PF; ++u) pw[u] = mask[i + step * u < pe ? i + step * u : i];   // word i itself where the sweep is past the end
 #pragma unroll
-        for (int j = 0; j < VS_EMIT_WPT; ++j) {
-          if (row >= R.y + 3 && row < R.y + R.h - 3) n += __popcll(mw[j] & col_mask(R.x + 3, R.x + R.w - 3, t * 64));
-          t += r64; row += q64; if (t >= TX) { t -= TX; ++row; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-        if (lane == 0 && n) atomicAdd(&sh_cnt[r], n);
+        for (int u = 0; u < VS_EMIT_PF; ++u) pre += (i + step * u < pe) ? __popcll(pw[u] & keep) : 0;
       }
-      // exclusive prefix of the filtered counts in word order
-      int ex[VS_EMIT_WPT];
-      int carry = 0;
-      int row = row_b, t = t_b;
-#pragma unroll
-      for (int j = 0; j < VS_EMIT_WPT; ++j) {
-        const int wd = wbase + 64 * j;
-        mw[j] = wd < nwords ? filtered(mw[j], row, t) : 0ull;   // from here on only the border-filtered bits matter
-        t += r64; row += q64; if (t >= TX) { t -= TX; ++row; }
-        const int cnt = __popcll(mw[j]);
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(inc, o, 64); if (lane >= o) inc += up; }
-        ex[j] = carry + inc - cnt;
-        carry += __shfl(inc, 63, 64);
-      }
-      __syncthreads();   // sh_wave / sh_total of the previous pass are consumed
-      if (lane == 0) sh_wave[w] = carry;
-      __syncthreads();
-      if (tid == 0) { int acc = 0; for (int i = 0; i < 8; ++i) { const int v = sh_wave[i]; sh_wave[i] = acc; acc += v; } sh_total = acc; }
-      __syncthreads();
-      const int wave_off = done + sh_wave[w];
-      // keypoints (x, row) in row-major order + the row/cell CSR: stores only, consecutive lanes -> consecutive addresses
-      row = row_b; t = t_b;
-#pragma unroll
-      for (int j = 0; j < VS_EMIT_WPT; ++j) {
-        const int wd = wbase + 64 * j;
-        if (wd < nwords) {
-          unsigned long long f = mw[j];
-          int off = wave_off + ex[j];
-          int32_t* rc = rowcell + (size_t)row * (CW + 1) + t * 4;
-          rc[0] = min(off, c.NMAX);
-          rc[1] = min(off + __popcll(f & 0xFFFFull), c.NMAX);
-          rc[2] = min(off + __popcll(f & 0xFFFFFFFFull), c.NMAX);
-          rc[3] = min(off + __popcll(f & 0xFFFFFFFFFFFFull), c.NMAX);
-          if (t == TX - 1) rc[4] = min(off + __popcll(f), c.NMAX);
-          while (f) {
-            const int bit = __ffsll((long long)f) - 1;
-            f &= f - 1;
-            if (off < c.NMAX) {
-              *reinterpret_cast<int32_t*>(kxy + 2 * off) = (t * 64 + bit) | (row << 16);
-              used[off] = 0;
-            }
-            ++off;
-          }
-        }
-        t += r64; row += q64; if (t >= TX) { t -= TX; ++row; }
-      }
-      done += sh_total;
     }
-    const int total = done;
-    if (total > c.NMAX) { if (tid == 0) atomicOr(&st.error_flags, 1); }
-    if (tid == 0) b.n_kp[s * 2 + side] = min(total, c.NMAX);
-    __syncthreads();   // the workgroup's keypoint stores are visible to its own loads below
-    // scores: one keypoint per thread, four gathers in flight
-    const int nk = min(total, c.NMAX);
-    for (int i0 = tid; i0 < nk; i0 += 4 * 512) {
-      int px[4];
-      uint8_t v[4];
+    pre = wave_sum(pre);
+  }
+  // raw detections per region (controller input): every corner bit lies in exactly one region
+  for (int r = 0; r < c.n_regions; ++r) {
+    const DevRegion& R = c.regions[r];
+    int n = 0, row = row_b, t = t_b;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + 512 * u;
-        px[u] = (i < nk) ? *reinterpret_cast<const int32_t*>(kxy + 2 * i) : 0;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = (i0 + 512 * u < nk) ? score8[(size_t)(px[u] >> 16) * c.bstride + (px[u] & 0xFFFF)] : 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) if (i0 + 512 * u < nk) ksc[i0 + 512 * u] = v[u];
+    for (int j = 0; j < VS_EMIT_WPT; ++j) {
+      if (row >= R.y + 3 && row < R.y + R.h - 3) n += __popcll(mw[j] & col_mask(R.x + 3, R.x + R.w - 3, t * 64));
+      t += r64; row += q64; if (t >= TX) { t -= TX; ++row; }
     }
-    __syncthreads();
+    n = wave_sum(n);
+    if (lane == 0) sh_cnt[w][r] = n;
   }
-  // the second of the stream's two workgroups to get here runs the controller on both images' counts
-  if (tid == 0) {
-    for (int r = 0; r < c.n_regions; ++r) b.iinfo[s].raw_count[side][r] = sh_cnt[r];
-    __threadfence();
-    const int last_ticket = (int)gridDim.y - 1;
-    const int ticket = atomicAdd(&b.iinfo[s].ticket, 1);
-    sh_last = ticket == last_ticket;
-    if (ticket == last_ticket) { __threadfence(); b.iinfo[s].ticket = 0; }
+  // exclusive prefix of the filtered counts in word order
+  int ex[VS_EMIT_WPT];
+  int carry = 0;
+  {
+    int row = row_b, t = t_b;
+#pragma unroll
+    for (int j = 0; j < VS_EMIT_WPT; ++j) {
+      mw[j] = filtered(mw[j], row, t);   // from here on only the border-filtered bits matter (words past the image are zero)
+      t += r64; row += q64; if (t >= TX) { t -= TX; ++row; }
+      const int cnt = __popcll(mw[j]);
+      const int inc = wave_scan_incl(cnt);
+      ex[j] = carry + inc - cnt;
+      asm volatile("" : "+v"(ex[j]));    // one register from here on: otherwise the terms of the scan are kept apart, live across the barrier
+      carry += __builtin_amdgcn_readlane(inc, 63);
+    }
   }
+  if (lane == 0) { sh_pre[w] = pre; sh_own[w] = carry; }
   __syncthreads();
-  if (tid == 0 && sh_last) {
-    const int (*cnt)[VSLAM_MAX_REGIONS] = b.iinfo[s].raw_count;
-    if (run_controller) {
-      // detectKeypoints controller (base_framepoint_generator.cpp:382-415) for L then R with the
-      // thresholds that were in effect, then adjustDetectorThresholds (:440-459)
-      const double tol = c.c.target_number_of_keypoints_tolerance, maxchg = c.c.detector_threshold_maximum_change;
-      const double tmin = c.c.detector_threshold_minimum, tmax = c.c.detector_threshold_maximum;
-      const double target = (double)c.target_per_detector;
-      const int n_sides = run_controller == 2 ? 1 : 2;
-      for (int r = 0; r < c.n_regions; ++r) {
-        double acc = 0;
-        for (int sd = 0; sd < n_sides; ++sd) {
-          double t = (double)st.thr[r];
-          const double delta = ((double)__hip_atomic_load(&cnt[sd][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) / target;
-          if (delta < -tol) {
-            const double change = fmax(delta, -maxchg);
-            t = t + fmin(change * t, -1.0);
-            if (t < tmin) t = tmin;
-          } else if (delta > tol) {
-            const double change = fmin(delta, maxchg);
-            t += fmax(change * t, 1.0);
-            if (t > tmax) t = tmax;
-          }
-          acc += t;
-        }
-        st.thr[r] = (int)rint(acc / n_sides);
+  int done = 0, own = 0, wave_off = 0;   // keypoints of earlier bands, of this band, of this band's earlier waves
+#pragma unroll
+  for (int i = 0; i < VS_EMIT_THREADS / 64; ++i) { done += sh_pre[i]; if (i < w) wave_off += sh_own[i]; own += sh_own[i]; }
+  wave_off += done;
+  // keypoints (x, row) in row-major order, their scores + the row/cell CSR: consecutive lanes -> consecutive addresses.  The first
+  // VS_EMIT_HEAD keypoints of every word of the thread go together, their score loads in flight before the first store; words with more
+  // follow in pairs.
+  auto pick = [&](unsigned long long& f, int t) -> int {
+    if (!f) return -1;
+    const int x = t * 64 + __ffsll((long long)f) - 1;
+    f &= f - 1;
+    return x;
+  };
+  auto put = [&](int off, int pos, uint8_t v) {
+    *reinterpret_cast<int32_t*>(kxy + 2 * off) = pos;
+    used[off] = 0;
+    ksc[off] = v;
+  };
+  auto score_at = [&](int pos) -> uint8_t { return score8[(size_t)(pos >> 16) * c.bstride + (pos & 0xFFFF)]; };
+  int pp[VS_EMIT_WPT][VS_EMIT_HEAD], po[VS_EMIT_WPT], prt[VS_EMIT_WPT];   // x | row << 16 or -1; first offset; t | row << 16
+  {
+    int row = row_b, t = t_b;
+#pragma unroll
+    for (int j = 0; j < VS_EMIT_WPT; ++j) {
+      const int off = wave_off + ex[j];
+      if (wbase + 64 * j < nwords) {
+        const unsigned long long f = mw[j];
+        int32_t* rc = rowcell + (size_t)row * (CW + 1) + t * 4;
+        rc[0] = min(off, c.NMAX);
+        rc[1] = min(off + __popcll(f & 0xFFFFull), c.NMAX);
+        rc[2] = min(off + __popcll(f & 0xFFFFFFFFull), c.NMAX);
+        rc[3] = min(off + __popcll(f & 0xFFFFFFFFFFFFull), c.NMAX);
+        if (t == TX - 1) rc[4] = min(off + __popcll(f), c.NMAX);
       }
+      po[j] = off; prt[j] = t | (row << 16);
+#pragma unroll
+      for (int u = 0; u < VS_EMIT_HEAD; ++u) { const int x = pick(mw[j], t); pp[j][u] = (x >= 0 && off + u < c.NMAX) ? (x | (row << 16)) : -1; }
+      t += r64; row += q64; if (t >= TX) { t -= TX; ++row; }
     }
-    for (int r = 0; r < c.n_regions; ++r) b.iinfo[s].thr_after[r] = st.thr[r];
   }
+  uint8_t pv[VS_EMIT_WPT][VS_EMIT_HEAD];
+#pragma unroll
+  for (int j = 0; j < VS_EMIT_WPT; ++j)
+#pragma unroll
+    for (int u = 0; u < VS_EMIT_HEAD; ++u) pv[j][u] = pp[j][u] >= 0 ? score_at(pp[j][u]) : 0;
+#pragma unroll
+  for (int j = 0; j < VS_EMIT_WPT; ++j)
+#pragma unroll
+    for (int u = 0; u < VS_EMIT_HEAD; ++u) if (pp[j][u] >= 0) put(po[j] + u, pp[j][u], pv[j][u]);
+#pragma unroll
+  for (int j = 0; j < VS_EMIT_WPT; ++j) {
+    unsigned long long f = mw[j];
+    const int t = prt[j] & 0xFFFF, rowbits = prt[j] & ~0xFFFF;
+    for (int off = po[j] + VS_EMIT_HEAD; f; off += 2) {
+      const int x0 = pick(f, t), x1 = pick(f, t);
+      const bool k0 = off < c.NMAX, k1 = x1 >= 0 && off + 1 < c.NMAX;
+      const uint8_t v0 = k0 ? score_at(x0 | rowbits) : 0, v1 = k1 ? score_at(x1 | rowbits) : 0;
+      if (k0) put(off, x0 | rowbits, v0);
+      if (k1) put(off + 1, x1 | rowbits, v1);
+    }
+  }
+  if (tid != 0) return;
+  if (band == (int)gridDim.z - 1) {     // the last band knows the image's total
+    const int total = done + own;
+    if (total > c.NMAX) atomicOr(&st.error_flags, 1);
+    b.n_kp[s * 2 + side] = min(total, c.NMAX);
+  }
+  // Raw counts: the bands add theirs into ImgInfo::raw_acc, and the last of the stream's sides * bands workgroups to get here moves the
+  // sums into raw_count, leaves raw_acc and the ticket zero for the next launch (whatever its grid) and runs the controller on them.
+  // Counts and ticket are device-scope read-modify-writes and nothing else: they are carried out where all XCDs see them, and a
+  // workgroup takes its ticket only after its additions have RETURNED, so the last arrival's exchanges find every sum.  No fence: a fence
+  // here writes the XCD's L2 back, once per workgroup (measured: 0.21 ms a launch with the two fences the one-workgroup-per-image form had).
+  ImgInfo& ii = b.iinfo[s];
+  int dep = 0;
+  for (int r = 0; r < c.n_regions; ++r) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < VS_EMIT_THREADS / 64; ++i) n += sh_cnt[i][r];
+    if (n) dep += __hip_atomic_fetch_add(&ii.raw_acc[side][r], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(dep) : : "memory");   // the additions have returned; the compiler moves no memory operation across
+  const int last_ticket = (int)(gridDim.y * gridDim.z) - 1;
+  if (__hip_atomic_fetch_add(&ii.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != last_ticket) return;
+  for (int sd = 0; sd < (int)gridDim.y; ++sd)
+    for (int r = 0; r < c.n_regions; ++r) ii.raw_count[sd][r] = __hip_atomic_exchange(&ii.raw_acc[sd][r], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&ii.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int (*cnt)[VSLAM_MAX_REGIONS] = ii.raw_count;
+  if (run_controller) {
+    // detectKeypoints controller (base_framepoint_generator.cpp:382-415) for L then R with the
+    // thresholds that were in effect, then adjustDetectorThresholds (:440-459)
+    const double tol = c.c.target_number_of_keypoints_tolerance, maxchg = c.c.detector_threshold_maximum_change;
+    const double tmin = c.c.detector_threshold_minimum, tmax = c.c.detector_threshold_maximum;
+    const double target = (double)c.target_per_detector;
+    const int n_sides = run_controller == 2 ? 1 : 2;
+    for (int r = 0; r < c.n_regions; ++r) {
+      double acc = 0;
+      for (int sd = 0; sd < n_sides; ++sd) {
+        double t = (double)st.thr[r];
+        const double delta = ((double)cnt[sd][r] - target) / target;
+        if (delta < -tol) {
+          const double change = fmax(delta, -maxchg);
+          t = t + fmin(change * t, -1.0);
+          if (t < tmin) t = tmin;
+        } else if (delta > tol) {
+          const double change = fmin(delta, maxchg);
+          t += fmax(change * t, 1.0);
+          if (t > tmax) t = tmax;
+        }
+        acc += t;
+      }
+      st.thr[r] = (int)rint(acc / n_sides);
+    }
+  }
+  for (int r = 0; r < c.n_regions; ++r) ii.thr_after[r] = st.thr[r];
 }
 
 // ==============================================================================================

@@ -992,7 +992,7 @@ private:
       std::memcpy(ma.active, b.active, sizeof ma.active);
       mask_apply_enqueue(q, ma);
     }
-    hipLaunchKernelGGL(k_emit, dim3(B, 1), dim3(512), 0, q, d, b, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 2);
+    launch_emit(q, d, b, B, 1, orb ? (int)VSLAM_ORB_BORDER : (int)VSLAM_BRIEF_BORDER, 2);
     const dim3 g3((d.c.cols + VS_BT_W - 1) / VS_BT_W, (d.c.rows + VS_BT_H - 1) / VS_BT_H, B);
     if (orb) {
       Gauss7 gk; for (int i = 0; i < 4; ++i) gk.k[i] = d.gauss7[i];
@@ -1105,7 +1105,7 @@ private:
     for (int l = 0; l < L; ++l) {
       std::memcpy(lbuf[l].active, act, sizeof act);
       hipLaunchKernelGGL(k_fast_box, dim3(lcfg[l].TX, (lcfg[l].c.rows + VS_TILE_H - 1) / VS_TILE_H, BR), dim3(256), VS_FB_DYN_LDS, q, lcfg[l], lbuf[l]);
-      hipLaunchKernelGGL(k_emit, dim3(BR, 1), dim3(512), 0, q, lcfg[l], lbuf[l], (int)VS_ORBD_EDGE, 0);        // runByImageBorder(edgeThreshold)
+      launch_emit(q, lcfg[l], lbuf[l], BR, 1, (int)VS_ORBD_EDGE, 0);        // runByImageBorder(edgeThreshold)
     }
     hipLaunchKernelGGL(k_orbd_select_fast, dim3(BR, L), dim3(1024), 0, q, b, d_od);
     const int gk = std::max(4, std::min(64, 8192 / (BR * L)));       // blocks of four wavefronts per (sequence, region, level) list
