@@ -73,34 +73,24 @@ struct vslam_ctx {
   int split = 0;   // launch sequence of the frame: 0 one fused k_frame launch; 4 phase launches around the wide recovery kernel, the landmark
                    // refinement in workgroups of its own inside the last one (fastest up to VS_SPLIT4_MAX_STREAMS streams)
   bool lm_published = false;                            // vslam_prune_recover has published the frame's history (one stream): vslam_compute runs the landmark refinement beside the stereo stage
-  // rectification of raw input pairs (vslam_set_rectification): maps at the rectified size, padded to map_stride entries per row, and
-  // the raw slabs [step parity][left/right] host images are copied into (B x raw_rows x raw_stride each).  k_rectify writes the rectified
-  // pair into upload[parity], so everything downstream, and the two-parity lifetime of the image slabs, is unchanged.
-  struct Rect { bool on = false, have_frame = false; RemapMaps maps; int raw_stride = 0; size_t raw_stream_stride = 0;
-                uint8_t* raw[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-                DeviceStore mem; } rect;
+  // The input stages ahead of the detector.  Every slab a stage reads or writes besides upload[parity] lives in `slabs`; which of them exist,
+  // at which geometry, and how a frame is routed through them is decided by stage_plan.h alone, from the switches below (stage_switches,
+  // host_switches.h).  All B x rows x stride bytes per image: COLOR / FULL / RAW [step parity][left/right] take the host frames that come in
+  // (colour, full-size, raw) and the stage outputs at those sizes; SM_IN [step parity][left/right] takes what would have gone to
+  // upload[parity] while smoothing, which cannot work in place; KEEP and SM_OUT (one pair: their only readers are the same frame's kernels on
+  // the same queue and a getter) hold the rectified / smoothed pair while the equalisation slot writes upload[parity] behind them.
+  StageSlabs<DeviceStore> slabs;
+  // rectification of raw input pairs (vslam_set_rectification): maps at the rectified size, padded to map_stride entries per row
+  struct Rect { bool on = false, have_frame = false; RemapMaps maps; DeviceStore mem; } rect;
   // the equalisation slot of the input pair (vslam_set_equalization / vslam_set_clahe: EqSlot, host_prestage.h), its tables [stream][side];
-  // dst: where the pair the last frame was processed on lies (inside upload[last_set]).  keep[left/right]: with rectification on as well,
-  // k_rectify writes here and the equalised pair goes to upload[parity], so that vslam_get_rectified_images still returns the rectified
-  // pair; one pair suffices, its only readers are the same frame's two kernels on the same queue and a getter.
-  struct Eq : EqSlot { uint8_t* keep[2] = {nullptr, nullptr}; DeviceStore keep_mem; } eq;
-  // colour input (vslam_set_color_input, kernels_gray.h): off while format == VSLAM_PIXEL_GRAY8.  slab[step parity][left/right]: what host
-  // colour images are copied into (B x in_rows x stride bytes each, at the size of the frames that come in).
-  struct Col { int format = 0; bool have_frame = false; int slab_rows = 0, slab_cols = 0, stride = 0; size_t stream_stride = 0;
-               uint8_t* slab[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-               DeviceStore mem; } col;
-  // integer-factor reduction of the incoming frames (vslam_set_downscale, kernels_downscale.h): off while factor == 1.  full[step parity]
-  // [left/right]: the full-size grey slabs (B x full_rows x stride each) host frames are copied into and k_gray_u8 writes.
-  struct Ds { int factor = 1, full_rows = 0, full_cols = 0, stride = 0; size_t stream_stride = 0; bool have_frame = false;
-              uint8_t* full[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-              DeviceStore mem; } ds;
-  // smoothing of the grey pair ahead of the equalisation slot (vslam_set_smoothing, kernels_smooth.h): off while mode == VSLAM_SMOOTH_OFF.
-  // The stage cannot work in place: in[step parity][left/right] (B x up_stream_stride each, rows up_stride apart) take what would have
-  // gone to upload[parity] — the host upload, the grey pair, the reduced pair, the rectified pair; out[left/right]: with the equalisation
-  // slot on as well the smoothed pair goes here and the equalised one to upload[parity], else the smoothed pair goes to upload[parity].
-  struct Sm { int mode = 0, ksize = 0; bool have_frame = false;
-              uint8_t* in[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; uint8_t* out[2] = {nullptr, nullptr};
-              DeviceStore mem, out_mem; } sm;
+  // dst: where the pair the last frame was processed on lies (inside upload[last_set])
+  EqSlot eq;
+  // colour input (vslam_set_color_input, kernels_gray.h): off while format == VSLAM_PIXEL_GRAY8
+  struct Col { int format = 0; bool have_frame = false; } col;
+  // integer-factor reduction of the incoming frames (vslam_set_downscale, kernels_downscale.h): off while factor == 1
+  struct Ds : DownscaleSwitch { bool have_frame = false; } ds;
+  // smoothing of the grey pair ahead of the equalisation slot (vslam_set_smoothing, kernels_smooth.h): off while mode == VSLAM_SMOOTH_OFF
+  struct Sm : SmoothSwitch { bool have_frame = false; } sm;
   // this frame's routing through the input stages (route_frame, host_frame.h): the colour pair (a slab or the caller's device memory) and
   // where k_gray_u8 writes the grey pair, so where vslam_get_gray_images reads it; the raw pair k_rectify reads and the pair it writes
   PrePlan pre;
@@ -499,7 +489,7 @@ static int create_internal(const vslam_config* cfg, int device, int n_streams, v
   }
   if (e == hipSuccess) b.iinfo = c->sets[0].iinfo;
   c->up_stride = d.bstride;
-  c->up_stream_stride = (size_t)rows * d.bstride;
+  c->up_stream_stride = (size_t)rows * d.bstride;       // rows * up_stride: stage_plan.h sizes SM_IN, KEEP and SM_OUT by that product (stage_switches asserts it)
   for (int q = 0; q < 2; ++q)
     for (int d2 = 0; d2 < 2; ++d2)
       if (e == hipSuccess) e = dalloc(c, &c->upload[q][d2], B * c->up_stream_stride);
@@ -579,7 +569,7 @@ VS_API void vslam_destroy(vslam_ctx* c) {
   for (auto& e : c->scratch) vslam_destroy(e.t);
   c->scratch.clear();
   for (void* p : c->allocs) (void)hipFree(p);
-  for (DeviceStore* m : {&c->rect.mem, &c->eq.mem, &c->eq.keep_mem, &c->col.mem, &c->ds.mem, &c->sm.mem, &c->sm.out_mem}) m->release();     // the input stages' stores
+  c->slabs.release(); c->rect.mem.release(); c->eq.mem.release();     // the input stages' stores
   for (DeviceStore* m : {&c->dmask.user_mem, &c->dmask.valid_mem, &c->dmask.comb_mem, &c->dmask.slab_mem, &c->dmask.eff_mem}) m->release();    // detection masks
   c->guess.mem.release();
   for (int q = 0; q < 2; ++q) { if (c->guess.pin[q]) (void)hipHostFree(c->guess.pin[q]); if (c->guess.pin_ev[q]) (void)hipEventDestroy(c->guess.pin_ev[q]); }

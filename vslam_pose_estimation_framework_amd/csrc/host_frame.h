@@ -1,5 +1,5 @@
 // host_frame.h — one frame on a context: where its input images come from (device pointers, host uploads through pinned staging), its
-// routing through the input stages (route_frame), the image pipeline and the frame's launch sequence, and the fused entries
+// routing through the input stages (route_frame, from the route of stage_plan.h), the image pipeline and the frame's launch sequence, and the fused entries
 // vslam_process_*.  Host code, included by vslam_hip.hip after host_switches.h.
 #pragma once
 
@@ -30,7 +30,7 @@ static int launch_image_pipeline(vslam_ctx* c) {
   // the image products of this set were last read by the frame kernel two steps ago; the detector thresholds come
   // from the controller in k_emit of the previous step (same queue)
   if (c->frm_pending[set] && st != c->stream) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_frm[set], 0));
-  // grey, rectify, equalise as route_frame has planned them (the slabs they write are those the wait above has freed)
+  // the input stages as route_frame has laid them out (the slabs they write are those the wait above has freed)
   HIP_TRY(c, prestage_enqueue(st, c->pre, c->rect.maps, c->eq, n, 2, c->buf.active));
   // detection masks (kernels_mask.h): nothing while none is set
   const bool masked = c->dmask.pending || c->dmask.stat[0] || c->dmask.stat[1];
@@ -194,44 +194,44 @@ static int upload_to(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t r
   *out = {{dst[0], dst[1]}, dst_stride, dst_stream_stride};
   return VSLAM_OK;
 }
-// This frame's routing through the input stages, from which switches are on and where the incoming pair `in` lies (a slab the upload
-// filled, or the caller's device memory): c->pre, the slot's src / dst, and DevBuf::img, which the detector reads.  The one place that
-// decides it (the table: host_prestage.h, PrePlan).
-static void route_frame(vslam_ctx* c, const ImgPlanes& in) {
+// This frame's routing through the input stages: the plan's route (stage_plan.h, which alone decides it) turned into c->pre,
+// the slot's src / dst, and DevBuf::img, which the detector reads.  `in`: where the incoming pair lies — the slab the upload filled, at the
+// strides upload_to left it with, or the caller's device memory.  Every stage reads where the one before it left the pair.
+static void route_frame(vslam_ctx* c, const StageSwitches& sw, const StageRoute& r, const ImgPlanes& in) {
   const int set = c->parity;
-  const ImgPlanes up = upload_planes(c, set);
   PrePlan& p = c->pre;
-  p.format = c->col.format; p.remap = c->rect.on; p.factor = c->ds.factor;
-  p.rows = c->cfg.c.rows; p.cols = c->cfg.c.cols;
-  p.red_rows = p.remap ? c->rect.maps.raw_rows : p.rows; p.red_cols = p.remap ? c->rect.maps.raw_cols : p.cols;
-  p.in_rows = p.factor > 1 ? c->ds.full_rows : p.red_rows; p.in_cols = p.factor > 1 ? c->ds.full_cols : p.red_cols;
-  ImgPlanes cur = in;                                  // where the pair lies behind the stages so far
-  const vslam_ctx::Rect& r = c->rect;
-  const vslam_ctx::Ds& d = c->ds;
+  p.format = c->col.format; p.remap = sw.remap; p.factor = sw.factor;
+  p.rows = sw.rows; p.cols = sw.cols;
+  p.red_rows = sw.remap ? sw.raw_rows : sw.rows; p.red_cols = sw.remap ? sw.raw_cols : sw.cols;
+  stage_in_size(sw, &p.in_rows, &p.in_cols);
   p.smooth_mode = c->sm.mode; p.smooth_ksize = c->sm.ksize;
-  // what the remap, else the smoothing, else the detector reads
-  const ImgPlanes raw_slab = p.remap ? ImgPlanes{{r.raw[set][0], r.raw[set][1]}, r.raw_stride, r.raw_stream_stride} : p.smooth_mode ? unsmoothed_planes(c, set) : up;
-  if (p.format != VSLAM_PIXEL_GRAY8) { p.color = cur; p.gray = p.factor > 1 ? ImgPlanes{{d.full[set][0], d.full[set][1]}, d.stride, d.stream_stride} : raw_slab; cur = p.gray; }
-  if (p.factor > 1) { p.full = cur; p.reduced = raw_slab; cur = p.reduced; }
-  if (p.remap) { p.raw = cur; p.mapped = rectified_planes(c, set); cur = p.mapped; }
-  // smoothed pair: never in place — its input lies in sm.in[set] or in the caller's device memory; into upload[set] as the last stage
-  if (p.smooth_mode) { p.unsmoothed = cur; p.smoothed = c->eq.on ? ImgPlanes{{c->sm.out[0], c->sm.out[1]}, c->up_stride, c->up_stream_stride} : up; cur = p.smoothed; }
-  // equalised pair in upload[set]: in place when the input is already there (a host upload keeps the caller's strides), written there
-  // from the rectified pair's own slabs or from the caller's device images, which these kernels alone read
-  if (c->eq.on) { c->eq.src = cur; c->eq.dst = cur.p[0] == up.p[0] ? cur : up; cur = c->eq.dst; }
+  ImgPlanes cur = in;                                  // where the pair lies behind the stages so far
+  auto hop = [&](const StageHop& h, ImgPlanes& src, ImgPlanes& dst) {
+    if (!h.on) return;
+    src = cur;
+    dst = h.src == h.dst ? cur : slab_planes(c, h.dst, set);     // in place (the slot alone): a host upload keeps the caller's strides
+    cur = dst;
+  };
+  hop(r.gray, p.color, p.gray);
+  hop(r.down, p.full, p.reduced);
+  hop(r.remap, p.raw, p.mapped);
+  hop(r.smooth, p.unsmoothed, p.smoothed);
+  hop(r.slot, c->eq.src, c->eq.dst);
   buf_set_planes(c->buf, cur);
 }
-// A frame's input pair.  Host images go to the slabs of this step's parity that the first stage reads — the colour slabs (upload_to with
-// the byte width as cols), the downscale's full-size slabs, the rectifier's raw slabs, the smoothing's input slabs, else upload[parity]; device images are read in place, by the first stage alone
-// (and, colour, by k_map_color behind the frame's last launch while map colours are on).
+// A frame's input pair.  Host images go to the slab of this step's parity that the plan names (the colour slabs take channels * width
+// bytes per row); device images are read in place, by the first stage alone (and, colour, by k_map_color behind the frame's last launch
+// while map colours are on).
 static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t row_stride, size_t image_stride, bool on_device) {
-  const bool colour = c->col.format != VSLAM_PIXEL_GRAY8, full = c->ds.factor > 1, raw = c->rect.on;
+  const StageSwitches sw = stage_switches(c);
+  const StageRoute r = stage_route(sw, on_device);
+  const bool colour = sw.channels != 0;
   int rows, cols;
-  incoming_size(c, &rows, &cols);
-  const int wb = colour ? gray_channels(c->col.format) * cols : cols;
+  stage_in_size(sw, &rows, &cols);
+  const int wb = colour ? sw.channels * cols : cols;
   if (!L || !R) return fail(c, VSLAM_ERR_INVALID, "called with empty frame");  // stereo_framepoint_generator.cpp:75-78
   if (row_stride < wb)
-    return fail(c, VSLAM_ERR_INVALID, colour ? "row stride smaller than channels * image width" : full ? "row stride smaller than the full image width" : raw ? "row stride smaller than the raw image width" : "row stride smaller than image width");
+    return fail(c, VSLAM_ERR_INVALID, colour ? "row stride smaller than channels * image width" : sw.factor > 1 ? "row stride smaller than the full image width" : sw.remap ? "row stride smaller than the raw image width" : "row stride smaller than image width");
   ImgPlanes in = {{L, R}, row_stride, image_stride};
   if (!on_device) {
     // map colours: k_map_color read this parity's slab on the FRAME queue two steps ago, and the upload below is issued ahead of the wait in
@@ -243,15 +243,11 @@ static int set_inputs(vslam_ctx* c, const uint8_t* L, const uint8_t* R, int32_t 
       for (int k = 0; k < 2; ++k)
         if (up[k] != c->stream && (k == 0 || up[k] != up[0])) HIP_TRY(c, hipStreamWaitEvent(up[k], c->ev_frm[c->parity], 0));
     }
-    const int p = c->parity;
-    const int rc = colour ? upload_to(c, L, R, row_stride, image_stride, rows, wb, c->col.slab[p], c->col.stride, c->col.stream_stride, &in)
-                   : full ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->ds.full[p], c->ds.stride, c->ds.stream_stride, &in)
-                   : raw  ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->rect.raw[p], c->rect.raw_stride, c->rect.raw_stream_stride, &in)
-                   : c->sm.mode ? upload_to(c, L, R, row_stride, image_stride, rows, cols, c->sm.in[p], c->up_stride, c->up_stream_stride, &in)
-                          : upload_to(c, L, R, row_stride, image_stride, rows, cols, c->upload[p], c->up_stride, c->up_stream_stride, &in);
-    if (rc != VSLAM_OK) return rc;
+    const ImgPlanes to = slab_planes(c, r.upload, c->parity);
+    uint8_t* const dst[2] = {const_cast<uint8_t*>(to.p[0]), const_cast<uint8_t*>(to.p[1])};
+    if (const int rc = upload_to(c, L, R, row_stride, image_stride, rows, wb, dst, to.row_stride, to.stream_stride, &in)) return rc;
   }
-  route_frame(c, in);
+  route_frame(c, sw, r, in);
   return VSLAM_OK;
 }
 

@@ -1,8 +1,9 @@
 // host_prestage.h — the input stages ahead of the detector, written once for the stereo context and the RGB-D tracker: colour to grey
 // (kernels_gray.h), integer-factor reduction (kernels_downscale.h), remap (rectification / undistortion, kernels_rectify.h), smoothing
 // (Gaussian / median, kernels_smooth.h) and the equalisation slot (global or CLAHE, kernels_equalize.h / kernels_clahe.h).  Where an image pair lies (ImgPlanes), the one filler of the kernels' argument blocks (place),
-// the slot (EqSlot), the intake of remap maps, the per-frame plan (PrePlan) with its one enqueue, the plane read-out of the getters and the
-// colour source of the map's colours.  Owner-independent host code: no context, no tracker; errors come back as hipError_t or as text.
+// the slot (EqSlot), the intake of remap maps, what the switches' setters refuse (one check each, worded by the owner's vocabulary), the
+// per-frame plan (PrePlan) with its one enqueue, the plane read-out of the getters, the colour source of the map's colours and the
+// detection masks' launches, static upload and validity words.  Owner-independent host code: no context, no tracker; errors come back as hipError_t or as text.
 // Included by vslam_hip.hip ahead of host_ctx.h (the context holds these types); rgbd_device.h uses it too.
 #pragma once
 
@@ -105,6 +106,75 @@ static void remap_enqueue(hipStream_t st, const RemapMaps& m, const ImgPlanes& s
   hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, st, ra);
 }
 
+// ---- what the switches' setters refuse, written once --------------------------------------------------
+// Each check returns 0, or the status with *why filled.  The owner's vocabulary keeps every message what it is for that owner.
+struct OwnerWords { const char* prefix; const char* owner; const char* remap; };
+static const OwnerWords VS_CONTEXT_WORDS = {"vslam_", "context", "rectification"};
+static const OwnerWords VS_TRACKER_WORDS = {"vslam_rgbd_", "tracker", "undistortion"};
+static int refuse(std::string* why, int status, const std::string& text) { *why = text; return status; }
+// the downscale switch as both owners hold it: off while factor == 1
+struct DownscaleSwitch {
+  int factor = 1, full_rows = 0, full_cols = 0;
+  bool is(int f, int rows, int cols) const { return f == 1 ? factor == 1 : (factor == f && full_rows == rows && full_cols == cols); }
+  void get(int32_t* f, int32_t* rows, int32_t* cols) const {
+    if (f) *f = factor;
+    if (rows) *rows = factor > 1 ? full_rows : 0;
+    if (cols) *cols = factor > 1 ? full_cols : 0;
+  }
+};
+// the downscale setter: full / factor must be red_rows x red_cols, what the next stage takes (the raw size while remapping, else the processed size)
+static int downscale_check(const OwnerWords& w, int factor, int full_rows, int full_cols, bool remap, int red_rows, int red_cols, std::string* why) {
+  if (factor == 1) return VSLAM_OK;
+  const std::string who = std::string(w.prefix) + "set_downscale: ";
+  if (!ds_factor_ok(factor)) return refuse(why, VSLAM_ERR_INVALID, who + "factor outside 1 .. 4");
+  if (!ds_size_ok(full_rows, full_cols, factor)) return refuse(why, VSLAM_ERR_INVALID, who + "full size outside 1 .. 32767 or below one block");
+  if (ds_out(full_rows, factor) == red_rows && ds_out(full_cols, factor) == red_cols) return VSLAM_OK;
+  return refuse(why, VSLAM_ERR_INVALID, who + "full size / factor is not the " + (remap ? std::string("raw size of the ") + w.remap + " maps" : std::string(w.owner) + "'s image size"));
+}
+// the remap setter while downscaling: the maps address the reduced raw image, full / factor is what this stage is handed (off: the detector)
+static int remap_downscale_check(const OwnerWords& w, const DownscaleSwitch& ds, bool off, int raw_rows, int raw_cols, int rows, int cols, std::string* why) {
+  if (ds.factor == 1 || (ds_out(ds.full_rows, ds.factor) == (off ? rows : raw_rows) && ds_out(ds.full_cols, ds.factor) == (off ? cols : raw_cols))) return VSLAM_OK;
+  const std::string who = std::string(w.prefix) + "set_" + w.remap, ds_name = std::string(" (") + w.prefix + "set_downscale)";
+  return refuse(why, VSLAM_ERR_INVALID, off ? who + ": the downscaled frames" + ds_name + " do not have the " + w.owner + "'s size"
+                                            : who + ": the raw size is not the size of the downscaled frames" + ds_name);
+}
+static int color_format_check(const OwnerWords& w, int format, std::string* why) {
+  return format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8 ? refuse(why, VSLAM_ERR_INVALID, std::string(w.prefix) + "set_color_input: unknown pixel format") : VSLAM_OK;
+}
+static int equalization_size_check(const OwnerWords& w, int rows, int cols, std::string* why) {
+  return (size_t)rows * cols > (size_t)VS_EQ_MAX_PIXELS ? refuse(why, VSLAM_ERR_INVALID, std::string(w.prefix) + "set_equalization: more than 2^24 pixels per image") : VSLAM_OK;
+}
+// the smoothing switch as both owners hold it: off while mode == VSLAM_SMOOTH_OFF
+static_assert(VSLAM_SMOOTH_OFF == VS_SMOOTH_OFF && VSLAM_SMOOTH_GAUSSIAN == VS_SMOOTH_GAUSSIAN && VSLAM_SMOOTH_MEDIAN == VS_SMOOTH_MEDIAN, "smoothing modes");
+struct SmoothSwitch {
+  int mode = 0, ksize = 0;
+  bool is(int m, int k) const { return m == VSLAM_SMOOTH_OFF ? mode == VSLAM_SMOOTH_OFF : (mode == m && ksize == k); }
+  void get(int* m, int32_t* k) const {
+    if (m) *m = mode;
+    if (k) *k = mode ? ksize : 0;
+  }
+};
+// what both setters and the stand-alone entry refuse about a mode that is not OFF
+static int smooth_check(const char* who, int mode, int32_t ksize, int rows, int cols, std::string* why) {
+  const char* what = nullptr;
+  if (mode != VSLAM_SMOOTH_GAUSSIAN && mode != VSLAM_SMOOTH_MEDIAN) what = ": unknown mode";
+  else if (!smooth_mode_ok(mode, ksize)) what = mode == VSLAM_SMOOTH_GAUSSIAN ? ": a Gaussian has ksize 3, 5 or 7" : ": a median has ksize 3 or 5";
+  else if (!smooth_size_ok(mode, ksize, rows, cols)) what = ": a Gaussian needs rows and cols above ksize / 2";
+  return what ? refuse(why, VSLAM_ERR_INVALID, std::string(who) + what) : VSLAM_OK;
+}
+// the mask setters (`who`: the entry's name): the margin; a static mask's rows; a set of frame masks, one per stream image_stride apart
+static int mask_margin_check(const char* who, int32_t margin, std::string* why) {
+  return margin < 0 || margin > VS_MASK_MAX_MARGIN ? refuse(why, VSLAM_ERR_INVALID, std::string(who) + ": margin outside 0 .. 64") : VSLAM_OK;
+}
+static int mask_args_check(const char* who, int cols, int32_t row_stride, int32_t margin, std::string* why) {
+  if (const int rc = mask_margin_check(who, margin, why)) return rc;
+  return row_stride < cols ? refuse(why, VSLAM_ERR_INVALID, std::string(who) + ": row stride smaller than image width") : VSLAM_OK;
+}
+static int frame_masks_check(const char* who, int n, int rows, int cols, int32_t row_stride, size_t image_stride, int32_t margin, std::string* why) {
+  if (const int rc = mask_args_check(who, cols, row_stride, margin, why)) return rc;
+  return n > 1 && image_stride < (size_t)(rows - 1) * row_stride + cols ? refuse(why, VSLAM_ERR_INVALID, std::string(who) + ": image stride smaller than one mask") : VSLAM_OK;
+}
+
 // ---- the equalisation slot -------------------------------------------------------------------------
 // Global equalisation (k_hist_u8, k_equalize_apply: the count table [image][256], zeroed and refilled every frame) or CLAHE (k_clahe_lut,
 // k_clahe_apply: the tables [image][tilesY][tilesX][256], geo holding what clahe_geometry made of the switch's arguments), image = stream *
@@ -174,21 +244,11 @@ struct EqSlot {
 
 // ---- a frame's plan and its enqueue ----------------------------------------------------------------
 // Which stage runs on this frame and where it reads and writes; the slot's part is EqSlot::on / src / dst.  Each owner fills it in ONE
-// function (route_frame in host_frame.h and in rgbd_device.h), from which switches are on and whether the frame is the caller's device memory.
+// function (route_frame in host_frame.h, which reads the route from stage_plan.h, and in rgbd_device.h), from which switches are on and whether the
+// frame is the caller's device memory.
 //
-// Stereo (the final pair is always in upload[parity], except an untouched caller device pair):
-//   stage     reads                                                              writes
-//   grey      colour slab[parity] (host) or caller memory (device)               ds.full[parity] if downscaling, else rect.raw[parity] if
-//                                                                                rectifying, else upload[parity]
-//   downscale ds.full[parity] (host or grey output) or caller memory             rect.raw[parity] if rectifying, else upload[parity]
-//   rectify   rect.raw[parity] (host, grey or downscale output) or caller memory eq.keep if equalising, else upload[parity]
-//   smooth    previous or caller memory; never upload[parity]: while smoothing,  sm.out if equalising, else upload[parity]
-//             every stage above (and the host upload) writes sm.in[parity] where
-//             it would have written upload[parity] or eq.keep
-//   equalise  sm.out if smoothing, else eq.keep if rectifying, else DevBuf::img  upload[parity]
-//             (in place when that already is upload[parity])
-// The getters read where a stage wrote: vslam_get_gray_images / _downscaled_images / _rectified_images the slabs above (sm.in[parity]
-// while smoothing, which nothing later overwrites), vslam_get_smoothed_images sm.out, or upload[parity] when smoothing is the last stage.
+// Stereo: stage_route of stage_plan.h is the table (the final pair is always in upload[parity], except an untouched caller device pair;
+// smoothing never works in place, the slot does when the pair already lies in upload[parity]).  The getters read where a stage wrote.
 // RGB-D (single buffers; caller memory is never written):
 //   grey      d_img (host) or caller memory                                      col.gray
 //   downscale previous                                                           ds.img (the depth image: on the space map's queue)
@@ -251,4 +311,82 @@ static ColorSrc color_src(const ImgPlanes& colour, int rows, int cols, int forma
   s.factor = factor;
   if (maps) { s.map_xy = maps->xy[0]; s.map_a = maps->a[0]; s.map_stride = maps->stride; s.map_rows = maps->rows; s.map_cols = maps->cols; }
   return s;
+}
+
+// ---- detection masks (kernels_mask.h) ------------------------------------------------------------------
+// k_mask_pack on `n` streams of `sides` masks; fused when a.corner is set
+static void mask_pack_enqueue(hipStream_t st, const MaskPackArgs& a) {
+  hipLaunchKernelGGL(k_mask_pack, dim3((a.TX + VS_MASK_CW - 1) / VS_MASK_CW, (a.rows + VS_MASK_BR - 1) / VS_MASK_BR, a.n * a.sides), dim3(256), 0, st, a);
+}
+// k_mask_apply: corner words [n][2][nw] &= stat (stat_stream_stride 0: shared by the streams, else the stream's own words [n][nw] of side 0)
+static void mask_apply_enqueue(hipStream_t st, const MaskApplyArgs& a) {
+  hipLaunchKernelGGL(k_mask_apply, dim3(((a.nw + 1) / 2 + 255) / 256, a.sides, (a.n + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, st, a);
+}
+// k_map_valid on `sides` maps of m: the eroded validity words [sides][rows][TX] into dst
+static void map_valid_enqueue(hipStream_t st, const RemapMaps& m, int sides, int margin, unsigned long long* dst) {
+  MapValidArgs v{};
+  for (int k = 0; k < sides; ++k) { v.map_xy[k] = m.xy[k]; v.map_a[k] = m.a[k]; }
+  v.map_stride = m.stride; v.raw_rows = m.raw_rows; v.raw_cols = m.raw_cols;
+  v.rows = m.rows; v.cols = m.cols; v.TX = (m.cols + 63) / 64; v.margin = margin; v.sides = sides; v.dst = dst;
+  hipLaunchKernelGGL(k_map_valid, dim3((v.TX + VS_MASK_CW - 1) / VS_MASK_CW, (v.rows + VS_MASK_BR - 1) / VS_MASK_BR, sides), dim3(256), 0, st, v);
+}
+// A static mask's host images src[side] (null: that side has none; rows x cols, row_stride bytes apart) -> their eroded packed words
+// user[side] [rows][TX], allocated from mem; one after the other through one device copy, st synchronised behind each.  Queues idle.
+static hipError_t mask_static_upload(hipStream_t st, int sides, const uint8_t* const* src, int32_t row_stride, int rows, int cols, int TX, int margin,
+                                     DeviceStore& mem, unsigned long long** user) {
+  const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
+  uint8_t* tmp = nullptr;
+  hipError_t e = hipMalloc((void**)&tmp, bytes);
+  for (int k = 0; k < sides && e == hipSuccess; ++k) {
+    if (!src[k]) continue;
+    e = mem.alloc(&user[k], (size_t)rows * TX);
+    if (e == hipSuccess) e = hipMemcpy(tmp, src[k], bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    MaskPackArgs a{};
+    a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = rows; a.cols = cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
+    a.dst = user[k];
+    active_all(a.active, 1);
+    mask_pack_enqueue(st, a);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);     // tmp is refilled for the other side
+  }
+  if (tmp) (void)hipFree(tmp);
+  return e;
+}
+// the validity words of `sides` maps of m, nw words each, in one block of mem: valid[side] (what mem held before is released).  Queues idle.
+static hipError_t mask_valid_words(hipStream_t st, const RemapMaps& m, int sides, int margin, size_t nw, DeviceStore& mem, unsigned long long** valid) {
+  mem.release();
+  valid[0] = valid[1] = nullptr;
+  unsigned long long* base = nullptr;
+  hipError_t e = mem.alloc(&base, sides * nw);
+  if (e == hipSuccess) { map_valid_enqueue(st, m, sides, margin, base); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (int k = 0; k < sides && e == hipSuccess; ++k) valid[k] = base + (size_t)k * nw;
+  return e;
+}
+// The context-wide keep words of `sides` images out of the user's words and the maps' validity words: the one there is, or both ANDed in
+// `comb` ([2][nw]: the validity words copied, the user's applied by k_mask_apply as to one stream's corner words).  Queues idle.
+static hipError_t mask_static_combine(hipStream_t st, int sides, size_t nw, unsigned long long* const* user, unsigned long long* const* valid,
+                                      DeviceStore& comb_mem, unsigned long long** comb, unsigned long long** stat) {
+  comb_mem.release();
+  comb[0] = comb[1] = nullptr;
+  bool both = false;
+  for (int k = 0; k < sides; ++k) { stat[k] = user[k] ? user[k] : valid[k]; both = both || (user[k] && valid[k]); }
+  if (!both) return hipSuccess;
+  unsigned long long* base = nullptr;
+  hipError_t e = comb_mem.alloc(&base, 2 * nw);
+  if (e != hipSuccess) return e;
+  MaskApplyArgs a{};
+  a.corner = base; a.nw = (int32_t)nw; a.n = 1; a.sides = sides;
+  active_all(a.active, 1);
+  for (int k = 0; k < sides && e == hipSuccess; ++k) {
+    if (!(user[k] && valid[k])) continue;
+    comb[k] = base + (size_t)k * nw;
+    e = hipMemcpyAsync(comb[k], valid[k], nw * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+    a.stat[k] = user[k];
+    stat[k] = comb[k];
+  }
+  if (e == hipSuccess) { mask_apply_enqueue(st, a); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
 }

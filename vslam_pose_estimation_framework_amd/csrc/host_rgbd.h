@@ -123,189 +123,133 @@ VS_API int vslam_rgbd_get_points_stream(vslam_rgbd* r, int32_t stream, int32_t c
   if (r->on_host) return stream == 0 ? vslam_rgbd_get_points(r, cap, n, xy, cam, meta4, desc) : VSLAM_ERR_INVALID;
   return r->d.get_points(stream, cap, n, xy, cam, meta4, desc);
 }
-// ---- the RGB-D landmark map and observation log (kernels_rgbd_map.h): the device-resident loop only ----
-static int rgbd_map_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) keeps no landmark map or observation log; use the device-resident loop";
+// ---- entries of the device-resident loop only ----------------------------------------------------------------------------------------
+// What the host-driven loop lacks, by feature: the phrase of its refusal.
+static const char* const RGBD_HOST_NO_MAP = "keeps no landmark map or observation log";       // kernels_rgbd_map.h
+static const char* const RGBD_HOST_NO_UNDISTORT = "takes undistorted frames only";            // kernels_undistort.h
+static const char* const RGBD_HOST_NO_EQUALIZE = "does not equalise";                         // kernels_equalize.h, kernels_clahe.h
+static const char* const RGBD_HOST_NO_MASK = "takes no detection mask";                       // kernels_mask.h
+static const char* const RGBD_HOST_NO_BILATERAL = "does not filter the depth image";          // kernels_bilateral.h
+static const char* const RGBD_HOST_NO_COLOR = "takes grey frames only";                       // kernels_gray.h
+static const char* const RGBD_HOST_NO_DOWNSCALE = "does not downscale";                       // the definition above vslam_downscale_u8; DESIGN.md 6o
+static const char* const RGBD_HOST_NO_SMOOTHING = "does not smooth";                          // the definition above vslam_set_smoothing; DESIGN.md 6p
+// entry `name`: call(the device-resident tracker), or on the host-driven loop the refusal with `phrase`
+template <class Call>
+static int rgbd_device_only(vslam_rgbd* r, const char* name, const char* phrase, Call&& call) {
+  if (!r) return VSLAM_ERR_INVALID;
+  if (!r->on_host) return call(r->d);
+  r->t.err = std::string(name) + ": the host-driven loop (VSLAM_RGBD_HOST=1) " + phrase + "; use the device-resident loop";
   return VSLAM_ERR_STATE;
 }
+using RgbdDev = vs_rgbd::DeviceTracker;
 VS_API int vslam_rgbd_enable_map(vslam_rgbd* r, int32_t cap) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_enable_map") : r->d.enable_map(cap);
+  return rgbd_device_only(r, "vslam_rgbd_enable_map", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.enable_map(cap); });
 }
 VS_API int vslam_rgbd_get_map_size(vslam_rgbd* r, int32_t stream, int32_t* n) {
-  if (!r) return VSLAM_ERR_INVALID;
-  if (r->on_host) return rgbd_map_host_refusal(r, "vslam_rgbd_get_map_size");
-  if (!n) { r->d.err = "vslam_rgbd_get_map_size: null output"; return VSLAM_ERR_INVALID; }
-  return r->d.map_ready(stream, false, n);
+  return rgbd_device_only(r, "vslam_rgbd_get_map_size", RGBD_HOST_NO_MAP, [&](RgbdDev& d) {
+    if (!n) { d.err = "vslam_rgbd_get_map_size: null output"; return (int)VSLAM_ERR_INVALID; }
+    return d.map_ready(stream, false, n);
+  });
 }
 VS_API int vslam_rgbd_get_map(vslam_rgbd* r, int32_t stream, int32_t first_id, int32_t cap, int32_t* n, double* xyz, int32_t* info3, uint8_t* desc) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_map") : r->d.get_map(stream, first_id, cap, n, xyz, info3, desc);
+  return rgbd_device_only(r, "vslam_rgbd_get_map", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.get_map(stream, first_id, cap, n, xyz, info3, desc); });
 }
 VS_API int vslam_rgbd_enable_observations(vslam_rgbd* r, int32_t cap) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_enable_observations") : r->d.enable_observations(cap);
+  return rgbd_device_only(r, "vslam_rgbd_enable_observations", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.enable_observations(cap); });
 }
 VS_API int vslam_rgbd_get_observation_count(vslam_rgbd* r, int32_t stream, int32_t* n) {
-  if (!r) return VSLAM_ERR_INVALID;
-  if (r->on_host) return rgbd_map_host_refusal(r, "vslam_rgbd_get_observation_count");
-  if (!n) { r->d.err = "vslam_rgbd_get_observation_count: null output"; return VSLAM_ERR_INVALID; }
-  return r->d.map_ready(stream, true, n);
+  return rgbd_device_only(r, "vslam_rgbd_get_observation_count", RGBD_HOST_NO_MAP, [&](RgbdDev& d) {
+    if (!n) { d.err = "vslam_rgbd_get_observation_count: null output"; return (int)VSLAM_ERR_INVALID; }
+    return d.map_ready(stream, true, n);
+  });
 }
 VS_API int vslam_rgbd_get_observations(vslam_rgbd* r, int32_t stream, int32_t first, int32_t cap, int32_t* n, int32_t* id_frame2, float* xy, double* cam) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_observations") : r->d.get_observations(stream, first, cap, n, id_frame2, xy, cam);
+  return rgbd_device_only(r, "vslam_rgbd_get_observations", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.get_observations(stream, first, cap, n, id_frame2, xy, cam); });
 }
 VS_API int vslam_rgbd_get_point_ids(vslam_rgbd* r, int32_t stream, int32_t cap, int32_t* n, int32_t* ids) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_point_ids") : r->d.get_point_ids(stream, cap, n, ids);
+  return rgbd_device_only(r, "vslam_rgbd_get_point_ids", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.get_point_ids(stream, cap, n, ids); });
 }
 VS_API int vslam_rgbd_enable_map_colors(vslam_rgbd* r, int on) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_enable_map_colors") : r->d.enable_map_colors(on);
+  return rgbd_device_only(r, "vslam_rgbd_enable_map_colors", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.enable_map_colors(on); });
 }
 VS_API int vslam_rgbd_get_map_colors(vslam_rgbd* r, int32_t stream, int32_t first_id, int32_t cap, int32_t* n, uint8_t* rgb) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_map_host_refusal(r, "vslam_rgbd_get_map_colors") : r->d.get_map_colors(stream, first_id, cap, n, rgb);
-}
-// ---- undistortion of raw frames (kernels_undistort.h): the device-resident loop only ----
-static int rgbd_undistort_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) takes undistorted frames only; use the device-resident loop";
-  return VSLAM_ERR_STATE;
+  return rgbd_device_only(r, "vslam_rgbd_get_map_colors", RGBD_HOST_NO_MAP, [&](RgbdDev& d) { return d.get_map_colors(stream, first_id, cap, n, rgb); });
 }
 VS_API int vslam_rgbd_set_undistortion(vslam_rgbd* r, int32_t raw_rows, int32_t raw_cols, const int16_t* map_xy, const uint16_t* map_a) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_undistort_host_refusal(r, "vslam_rgbd_set_undistortion") : r->d.set_undistortion(raw_rows, raw_cols, map_xy, map_a);
+  return rgbd_device_only(r, "vslam_rgbd_set_undistortion", RGBD_HOST_NO_UNDISTORT, [&](RgbdDev& d) { return d.set_undistortion(raw_rows, raw_cols, map_xy, map_a); });
 }
 VS_API int vslam_rgbd_get_undistorted(vslam_rgbd* r, int32_t stream, uint8_t* image, uint16_t* depth) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_undistort_host_refusal(r, "vslam_rgbd_get_undistorted") : r->d.get_undistorted(stream, image, depth);
-}
-// ---- histogram equalisation of the intensity image (kernels_equalize.h): the device-resident loop only ----
-static int rgbd_equalize_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not equalise; use the device-resident loop";
-  return VSLAM_ERR_STATE;
+  return rgbd_device_only(r, "vslam_rgbd_get_undistorted", RGBD_HOST_NO_UNDISTORT, [&](RgbdDev& d) { return d.get_undistorted(stream, image, depth); });
 }
 VS_API int vslam_rgbd_set_equalization(vslam_rgbd* r, int on) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_set_equalization") : r->d.set_equalization(on);
+  return rgbd_device_only(r, "vslam_rgbd_set_equalization", RGBD_HOST_NO_EQUALIZE, [&](RgbdDev& d) { return d.set_equalization(on); });
 }
 VS_API int vslam_rgbd_get_equalized(vslam_rgbd* r, int32_t stream, uint8_t* image) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_equalized") : r->d.get_equalized(stream, image);
+  return rgbd_device_only(r, "vslam_rgbd_get_equalized", RGBD_HOST_NO_EQUALIZE, [&](RgbdDev& d) { return d.get_equalized(stream, image); });
 }
-// ---- the static detection mask (kernels_mask.h): the device-resident loop only ----
-static int rgbd_mask_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) takes no detection mask; use the device-resident loop";
-  return VSLAM_ERR_STATE;
+VS_API int vslam_rgbd_set_clahe(vslam_rgbd* r, int on, double clip_limit, int tiles_x, int tiles_y) {
+  return rgbd_device_only(r, "vslam_rgbd_set_clahe", RGBD_HOST_NO_EQUALIZE, [&](RgbdDev& d) { return d.set_clahe(on, clip_limit, tiles_x, tiles_y); });
+}
+VS_API int vslam_rgbd_get_clahe_luts(vslam_rgbd* r, int32_t stream, uint8_t* luts) {
+  return rgbd_device_only(r, "vslam_rgbd_get_clahe_luts", RGBD_HOST_NO_EQUALIZE, [&](RgbdDev& d) { return d.get_clahe_luts(stream, luts); });
 }
 VS_API int vslam_rgbd_set_detection_mask(vslam_rgbd* r, const uint8_t* mask, int32_t row_stride, int32_t margin) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_detection_mask") : r->d.set_detection_mask(mask, row_stride, margin);
+  return rgbd_device_only(r, "vslam_rgbd_set_detection_mask", RGBD_HOST_NO_MASK, [&](RgbdDev& d) { return d.set_detection_mask(mask, row_stride, margin); });
 }
 VS_API int vslam_rgbd_set_frame_masks(vslam_rgbd* r, const uint8_t* masks, int32_t row_stride, size_t image_stride, int32_t margin, int on_device) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_frame_masks") : r->d.set_frame_masks(masks, row_stride, image_stride, margin, on_device != 0);
+  return rgbd_device_only(r, "vslam_rgbd_set_frame_masks", RGBD_HOST_NO_MASK, [&](RgbdDev& d) { return d.set_frame_masks(masks, row_stride, image_stride, margin, on_device != 0); });
 }
 VS_API int vslam_rgbd_get_frame_detection_mask(vslam_rgbd* r, int32_t stream, uint64_t* words) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_get_frame_detection_mask") : r->d.get_frame_detection_mask(stream, words);
+  return rgbd_device_only(r, "vslam_rgbd_get_frame_detection_mask", RGBD_HOST_NO_MASK, [&](RgbdDev& d) { return d.get_frame_detection_mask(stream, words); });
 }
 VS_API int vslam_rgbd_set_undistortion_mask(vslam_rgbd* r, int on, int32_t margin) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_set_undistortion_mask") : r->d.set_undistortion_mask(on, margin);
+  return rgbd_device_only(r, "vslam_rgbd_set_undistortion_mask", RGBD_HOST_NO_MASK, [&](RgbdDev& d) { return d.set_undistortion_mask(on, margin); });
 }
+VS_API int vslam_rgbd_get_detection_mask(vslam_rgbd* r, uint64_t* words) {
+  return rgbd_device_only(r, "vslam_rgbd_get_detection_mask", RGBD_HOST_NO_MASK, [&](RgbdDev& d) { return d.get_detection_mask(words); });
+}
+VS_API int vslam_rgbd_set_bilateral(vslam_rgbd* r, int on, double sigma_color, double sigma_space) {
+  return rgbd_device_only(r, "vslam_rgbd_set_bilateral", RGBD_HOST_NO_BILATERAL, [&](RgbdDev& d) { return d.set_bilateral(on, sigma_color, sigma_space); });
+}
+VS_API int vslam_rgbd_get_bilateral(vslam_rgbd* r, int* on, double* sigma_color, double* sigma_space) {
+  return rgbd_device_only(r, "vslam_rgbd_get_bilateral", RGBD_HOST_NO_BILATERAL, [&](RgbdDev& d) { return d.get_bilateral(on, sigma_color, sigma_space); });
+}
+VS_API int vslam_rgbd_get_filtered_depth(vslam_rgbd* r, int32_t stream, uint16_t* depth, float* lut4098) {
+  return rgbd_device_only(r, "vslam_rgbd_get_filtered_depth", RGBD_HOST_NO_BILATERAL, [&](RgbdDev& d) { return d.get_filtered_depth(stream, depth, lut4098); });
+}
+VS_API int vslam_rgbd_set_color_input(vslam_rgbd* r, int format) {
+  return rgbd_device_only(r, "vslam_rgbd_set_color_input", RGBD_HOST_NO_COLOR, [&](RgbdDev& d) { return d.set_color_input(format); });
+}
+VS_API int vslam_rgbd_get_gray(vslam_rgbd* r, int32_t stream, uint8_t* image) {
+  return rgbd_device_only(r, "vslam_rgbd_get_gray", RGBD_HOST_NO_COLOR, [&](RgbdDev& d) { return d.get_gray(stream, image); });
+}
+VS_API int vslam_rgbd_set_downscale(vslam_rgbd* r, int32_t factor, int32_t full_rows, int32_t full_cols) {
+  return rgbd_device_only(r, "vslam_rgbd_set_downscale", RGBD_HOST_NO_DOWNSCALE, [&](RgbdDev& d) { return d.set_downscale(factor, full_rows, full_cols); });
+}
+VS_API int vslam_rgbd_get_downscaled(vslam_rgbd* r, int32_t stream, uint8_t* image, uint16_t* depth) {
+  return rgbd_device_only(r, "vslam_rgbd_get_downscaled", RGBD_HOST_NO_DOWNSCALE, [&](RgbdDev& d) { return d.get_downscaled(stream, image, depth); });
+}
+VS_API int vslam_rgbd_set_smoothing(vslam_rgbd* r, int mode, int32_t ksize) {
+  return rgbd_device_only(r, "vslam_rgbd_set_smoothing", RGBD_HOST_NO_SMOOTHING, [&](RgbdDev& d) { return d.set_smoothing(mode, ksize); });
+}
+VS_API int vslam_rgbd_get_smoothed(vslam_rgbd* r, int32_t stream, uint8_t* image) {
+  return rgbd_device_only(r, "vslam_rgbd_get_smoothed", RGBD_HOST_NO_SMOOTHING, [&](RgbdDev& d) { return d.get_smoothed(stream, image); });
+}
+// the switches' getters: on the host-driven loop every switch reads as off
 VS_API int vslam_rgbd_get_undistortion_mask(vslam_rgbd* r, int* on, int32_t* margin) {
   if (!r) return VSLAM_ERR_INVALID;
   if (r->on_host) { if (on) *on = 0; if (margin) *margin = 0; return VSLAM_OK; }
   return r->d.get_undistortion_mask(on, margin);
 }
-VS_API int vslam_rgbd_get_detection_mask(vslam_rgbd* r, uint64_t* words) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_mask_host_refusal(r, "vslam_rgbd_get_detection_mask") : r->d.get_detection_mask(words);
-}
-// ---- CLAHE of the intensity image, the equalisation slot's second mode (kernels_clahe.h): the device-resident loop only ----
-VS_API int vslam_rgbd_set_clahe(vslam_rgbd* r, int on, double clip_limit, int tiles_x, int tiles_y) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_set_clahe") : r->d.set_clahe(on, clip_limit, tiles_x, tiles_y);
-}
-VS_API int vslam_rgbd_get_clahe_luts(vslam_rgbd* r, int32_t stream, uint8_t* luts) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_equalize_host_refusal(r, "vslam_rgbd_get_clahe_luts") : r->d.get_clahe_luts(stream, luts);
-}
-// ---- bilateral filtering of the depth image (kernels_bilateral.h): the device-resident loop only ----
-static int rgbd_bilateral_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not filter the depth image; use the device-resident loop";
-  return VSLAM_ERR_STATE;
-}
-VS_API int vslam_rgbd_set_bilateral(vslam_rgbd* r, int on, double sigma_color, double sigma_space) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_bilateral_host_refusal(r, "vslam_rgbd_set_bilateral") : r->d.set_bilateral(on, sigma_color, sigma_space);
-}
-VS_API int vslam_rgbd_get_bilateral(vslam_rgbd* r, int* on, double* sigma_color, double* sigma_space) {
-  if (!r) return VSLAM_ERR_INVALID;
-  if (r->on_host) return rgbd_bilateral_host_refusal(r, "vslam_rgbd_get_bilateral");
-  return r->d.get_bilateral(on, sigma_color, sigma_space);
-}
-VS_API int vslam_rgbd_get_filtered_depth(vslam_rgbd* r, int32_t stream, uint16_t* depth, float* lut4098) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_bilateral_host_refusal(r, "vslam_rgbd_get_filtered_depth") : r->d.get_filtered_depth(stream, depth, lut4098);
-}
-// ---- colour input (kernels_gray.h): the device-resident loop only ----
-static int rgbd_color_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) takes grey frames only; use the device-resident loop";
-  return VSLAM_ERR_STATE;
-}
-VS_API int vslam_rgbd_set_color_input(vslam_rgbd* r, int format) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_color_host_refusal(r, "vslam_rgbd_set_color_input") : r->d.set_color_input(format);
-}
-VS_API int vslam_rgbd_get_gray(vslam_rgbd* r, int32_t stream, uint8_t* image) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_color_host_refusal(r, "vslam_rgbd_get_gray") : r->d.get_gray(stream, image);
-}
-
-// ---- downscale of the incoming frames (the definition above vslam_downscale_u8) -------------------------------------------
-static int rgbd_downscale_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not downscale; use the device-resident loop";
-  return VSLAM_ERR_STATE;
-}
-VS_API int vslam_rgbd_set_downscale(vslam_rgbd* r, int32_t factor, int32_t full_rows, int32_t full_cols) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_downscale_host_refusal(r, "vslam_rgbd_set_downscale") : r->d.set_downscale(factor, full_rows, full_cols);
-}
 VS_API int vslam_rgbd_get_downscale(vslam_rgbd* r, int32_t* factor, int32_t* full_rows, int32_t* full_cols) {
   if (!r) return VSLAM_ERR_INVALID;
-  if (!r->on_host) { r->d.get_downscale(factor, full_rows, full_cols); return VSLAM_OK; }
-  if (factor) *factor = 1;
-  if (full_rows) *full_rows = 0;
-  if (full_cols) *full_cols = 0;
+  if (r->on_host) DownscaleSwitch().get(factor, full_rows, full_cols); else r->d.get_downscale(factor, full_rows, full_cols);
   return VSLAM_OK;
-}
-VS_API int vslam_rgbd_get_downscaled(vslam_rgbd* r, int32_t stream, uint8_t* image, uint16_t* depth) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_downscale_host_refusal(r, "vslam_rgbd_get_downscaled") : r->d.get_downscaled(stream, image, depth);
-}
-
-// ---- smoothing of the intensity image (the definition above vslam_set_smoothing) ------------------------------------------
-static int rgbd_smoothing_host_refusal(vslam_rgbd* r, const char* what) {
-  r->t.err = std::string(what) + ": the host-driven loop (VSLAM_RGBD_HOST=1) does not smooth; use the device-resident loop";
-  return VSLAM_ERR_STATE;
-}
-VS_API int vslam_rgbd_set_smoothing(vslam_rgbd* r, int mode, int32_t ksize) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_smoothing_host_refusal(r, "vslam_rgbd_set_smoothing") : r->d.set_smoothing(mode, ksize);
 }
 VS_API int vslam_rgbd_get_smoothing(vslam_rgbd* r, int* mode, int32_t* ksize) {
   if (!r) return VSLAM_ERR_INVALID;
-  if (!r->on_host) { r->d.get_smoothing(mode, ksize); return VSLAM_OK; }
-  if (mode) *mode = VSLAM_SMOOTH_OFF;
-  if (ksize) *ksize = 0;
+  if (r->on_host) SmoothSwitch().get(mode, ksize); else r->d.get_smoothing(mode, ksize);
   return VSLAM_OK;
-}
-VS_API int vslam_rgbd_get_smoothed(vslam_rgbd* r, int32_t stream, uint8_t* image) {
-  if (!r) return VSLAM_ERR_INVALID;
-  return r->on_host ? rgbd_smoothing_host_refusal(r, "vslam_rgbd_get_smoothed") : r->d.get_smoothed(stream, image);
 }
 
 // ---- motion models (the definition above vslam_set_motion_model) ---------------------------------------------------------

@@ -1,91 +1,64 @@
 // host_switches.h — the stereo context's input-stage switches and their getters: rectification (vslam_set_rectification), the equalisation
-// slot (vslam_set_equalization, vslam_set_clahe), colour input (vslam_set_color_input), the downscale (vslam_set_downscale) and smoothing (vslam_set_smoothing), the stores behind them, and the stand-alone
-// vslam_remap_u8; behind them the motion model and the pose guesses of CAMERA_ODOMETRY (vslam_set_motion_model, vslam_set_pose_guess*),
-// with launch_motion_prior, the head of the frame's launch sequence.  What the switches share with the RGB-D tracker is host_prestage.h; a frame's routing through the stages is route_frame
-// in host_frame.h.  Host code, included by vslam_hip.hip after host_ctx.h and ahead of host_frame.h.
+// slot (vslam_set_equalization, vslam_set_clahe), colour input (vslam_set_color_input), the downscale (vslam_set_downscale) and smoothing
+// (vslam_set_smoothing), and the stand-alone vslam_remap_u8; behind them the motion model and the pose guesses of CAMERA_ODOMETRY
+// (vslam_set_motion_model, vslam_set_pose_guess*) with launch_motion_prior, the head of the frame's launch sequence, and the detection masks.
+// Which slabs the stages own is stage_plan.h's decision: slabs_reconcile is the one function that allocates and frees them, and every
+// setter has one shape — check, unchanged? return, drain, change the switch, reconcile, on failure turn that switch off and reconcile
+// again.  Should that second reconcile fail as well, slabs_settle turns colour input (with the map's colours) and the equalisation slot off
+// too, without a word of its own: the caller learns of the switch it was setting, and the getters of the others show them off.  The checks and what else the switches share with the RGB-D tracker are host_prestage.h; a frame's routing is route_frame in
+// host_frame.h.  Host code, included by vslam_hip.hip after host_ctx.h and ahead of host_frame.h.
 #pragma once
 
-// ---- the stores ------------------------------------------------------------------------------------
-static void rect_free(vslam_ctx* c) {
+// ---- the slabs of the input stages ------------------------------------------------------------------
+// the switch state that the plan (stage_plan.h) is a function of
+static StageSwitches stage_switches(const vslam_ctx* c) {
+  StageSwitches s;
+  s.channels = c->col.format == VSLAM_PIXEL_GRAY8 ? 0 : gray_channels(c->col.format);
+  s.factor = c->ds.factor; s.full_rows = c->ds.full_rows; s.full_cols = c->ds.full_cols;
+  s.remap = c->rect.on; s.raw_rows = c->rect.maps.raw_rows; s.raw_cols = c->rect.maps.raw_cols;
+  s.smooth = c->sm.mode != VSLAM_SMOOTH_OFF; s.slot = c->eq.on;
+  s.rows = c->cfg.c.rows; s.cols = c->cfg.c.cols; s.up_stride = c->up_stride;
+  assert(c->up_stream_stride == (size_t)s.rows * s.up_stride);     // the plan's slabs at the processed size have upload[parity]'s strides
+  return s;
+}
+// The context's slabs brought into agreement with the plan; queues idle.  The one place that allocates or frees them.  Colour slabs that go
+// or change their size (another format, another size of the frames that come in) take the grey pair's getter with them until the next frame.
+static hipError_t slabs_reconcile(vslam_ctx* c) {
+  SlabGeom want[SLAB_OWNED];
+  stage_slabs(stage_switches(c), want);
+  if (!(c->slabs.geo[SLAB_COLOR] == want[SLAB_COLOR])) c->col.have_frame = false;
+  return (hipError_t)stage_slabs_reconcile(c->slabs, want, c->B);
+}
+// Behind a failed reconcile, with the switch that wanted more off again: what is left frees, or puts back a slab that was freed to make room
+// (the colour slabs at the size that comes in again, the rectified pair's own).  Should even that fail, colour input and the slot go off
+// as well (and with the colour the map's colours, as vslam_set_color_input(GRAY8) does), and then the plan only frees.
+static void slabs_settle(vslam_ctx* c) {
+  if (slabs_reconcile(c) == hipSuccess) return;
+  mapcol_free(c);
+  c->col = vslam_ctx::Col();
+  c->eq.release();
+  (void)slabs_reconcile(c);
+}
+static int hip_status(vslam_ctx* c, const char* who, hipError_t e) {
+  return e == hipSuccess ? VSLAM_OK : fail(c, VSLAM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+// What a setter ends in, queues idle and its switch changed: the slabs follow.  When an allocation fails, off() turns that switch off again.
+template <class Off>
+static int slabs_follow(vslam_ctx* c, const char* who, Off&& off) {
+  const hipError_t e = slabs_reconcile(c);
+  if (e != hipSuccess) { off(); slabs_settle(c); }
+  return hip_status(c, who, e);
+}
+// slab `id` of step parity `set` as an image pair: SLAB_UPLOAD is upload[set]; a slab of one pair serves both parities
+static ImgPlanes slab_planes(const vslam_ctx* c, int id, int set) {
+  if (id == SLAB_UPLOAD) return {{c->upload[set][0], c->upload[set][1]}, c->up_stride, c->up_stream_stride};
+  const SlabGeom& g = c->slabs.geo[id];
+  uint8_t* const* p = c->slabs.p[id][g.pairs == 2 ? set : 0];
+  return {{p[0], p[1]}, g.stride, g.stream_stride()};
+}
+static void rect_off(vslam_ctx* c) {
   c->rect.mem.release();
   c->rect = vslam_ctx::Rect();
-}
-static void eq_free(vslam_ctx* c) {
-  c->eq.release();
-  c->eq.keep_mem.release();
-  c->eq.keep[0] = c->eq.keep[1] = nullptr;
-}
-// the rectified pair's own slabs exist exactly while rectification and equalisation are both on and smoothing, which then takes the
-// rectified pair into sm.in, is off (called by the three setters, queues idle)
-static hipError_t eq_keep_sync(vslam_ctx* c) {
-  vslam_ctx::Eq& q = c->eq;
-  const bool want = q.on && c->rect.on && !c->sm.mode;
-  if (want == (q.keep[0] != nullptr)) return hipSuccess;
-  q.keep_mem.release();
-  q.keep[0] = q.keep[1] = nullptr;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && want && e == hipSuccess; ++k) e = q.keep_mem.alloc(&q.keep[k], (size_t)c->B * c->up_stream_stride);
-  if (e != hipSuccess) { q.keep_mem.release(); q.keep[0] = q.keep[1] = nullptr; }
-  return e;
-}
-static void col_free(vslam_ctx* c) {
-  c->col.mem.release();
-  c->col = vslam_ctx::Col();
-}
-static void sm_free(vslam_ctx* c) {
-  c->sm.mem.release();
-  c->sm.out_mem.release();
-  c->sm = vslam_ctx::Sm();
-}
-// the smoothed pair's own slabs exist exactly while smoothing and equalisation are both on (called by the setters of both, queues idle)
-static hipError_t sm_out_sync(vslam_ctx* c) {
-  vslam_ctx::Sm& q = c->sm;
-  const bool want = q.mode && c->eq.on;
-  if (want == (q.out[0] != nullptr)) return hipSuccess;
-  q.out_mem.release();
-  q.out[0] = q.out[1] = nullptr;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && want && e == hipSuccess; ++k) e = q.out_mem.alloc(&q.out[k], (size_t)c->B * c->up_stream_stride);
-  if (e != hipSuccess) { q.out_mem.release(); q.out[0] = q.out[1] = nullptr; }
-  return e;
-}
-static void ds_free(vslam_ctx* c) {
-  c->ds.mem.release();
-  c->ds = vslam_ctx::Ds();
-}
-// the size of the frames that come in: the full size while downscaling, else the raw size while rectification is set, else rows x cols
-static void incoming_size(const vslam_ctx* c, int* rows, int* cols) {
-  if (c->ds.factor > 1) { *rows = c->ds.full_rows; *cols = c->ds.full_cols; }
-  else if (c->rect.on) { *rows = c->rect.maps.raw_rows; *cols = c->rect.maps.raw_cols; }
-  else { *rows = c->cfg.c.rows; *cols = c->cfg.c.cols; }
-}
-// the colour slabs exist while the switch is on, at the size of the frames that come in (called by the three setters that change it,
-// queues idle)
-static hipError_t col_slab_sync(vslam_ctx* c) {
-  vslam_ctx::Col& q = c->col;
-  const int fmt = q.format;
-  int rows, cols;
-  incoming_size(c, &rows, &cols);
-  const int wb = fmt == VSLAM_PIXEL_GRAY8 ? 0 : gray_channels(fmt) * cols;
-  if (fmt != 0 && q.slab[0][0] && q.slab_rows == rows && q.slab_cols == wb) return hipSuccess;
-  col_free(c);
-  q.format = fmt;
-  if (fmt == 0) return hipSuccess;
-  q.slab_rows = rows; q.slab_cols = wb;
-  q.stride = (wb + 63) & ~63;
-  q.stream_stride = (size_t)rows * q.stride;
-  hipError_t e = hipSuccess;
-  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = q.mem.alloc(&q.slab[p][k], (size_t)c->B * q.stream_stride);
-  if (e != hipSuccess) col_free(c);
-  return e;
-}
-// the slabs of the context as image pairs: upload[set], and where k_rectify writes the pair of product set `set` (with equalisation on as
-// well: in slabs of its own, the equalised pair goes to upload[set])
-static ImgPlanes upload_planes(const vslam_ctx* c, int set) { return {{c->upload[set][0], c->upload[set][1]}, c->up_stride, c->up_stream_stride}; }
-static ImgPlanes unsmoothed_planes(const vslam_ctx* c, int set) { return {{c->sm.in[set][0], c->sm.in[set][1]}, c->up_stride, c->up_stream_stride}; }
-static ImgPlanes rectified_planes(const vslam_ctx* c, int set) {
-  if (c->sm.mode) return unsmoothed_planes(c, set);
-  return c->eq.keep[0] ? ImgPlanes{{c->eq.keep[0], c->eq.keep[1]}, c->up_stride, c->up_stream_stride} : upload_planes(c, set);
 }
 // both sides of stream s of a pair, rows x cols, dense
 static int pair_to_host(vslam_ctx* c, const ImgPlanes& x, int s, int rows, int cols, uint8_t* left, uint8_t* right) {
@@ -106,40 +79,31 @@ VS_API int vslam_set_rectification(vslam_ctx* c, int32_t raw_rows, int32_t raw_c
   bool off = false;
   std::string why;
   if (const int rc = remap_maps_check("vslam_set_rectification", 2, raw_rows, raw_cols, rows, cols, xy, a, &off, &why)) return fail(c, rc, why);
-  // while downscaling, the maps address the reduced raw image: full / factor is what this stage is handed
-  if (c->ds.factor > 1) {
-    const int want_rows = off ? rows : raw_rows, want_cols = off ? cols : raw_cols;
-    if (ds_out(c->ds.full_rows, c->ds.factor) != want_rows || ds_out(c->ds.full_cols, c->ds.factor) != want_cols)
-      return fail(c, VSLAM_ERR_INVALID, off ? "vslam_set_rectification: the downscaled frames (vslam_set_downscale) do not have the context's size"
-                                            : "vslam_set_rectification: the raw size is not the size of the downscaled frames (vslam_set_downscale)");
-  }
+  if (const int rc = remap_downscale_check(VS_CONTEXT_WORDS, c->ds, off, raw_rows, raw_cols, rows, cols, &why)) return fail(c, rc, why);
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the old maps and raw slabs
-  rect_free(c);
+  rect_off(c);
   const bool valid_on = c->dmask.valid_on;       // the maps' validity mask: recomputed from new maps, off with them
   const int valid_margin = c->dmask.valid_margin;
   if (valid_on) { mask_valid_free(c); c->dmask.last = 0; }
-  if (off) { (void)eq_keep_sync(c); return col_slab_sync(c) == hipSuccess ? VSLAM_OK : fail(c, VSLAM_ERR_HIP, "vslam_set_rectification: colour slabs"); }
-  vslam_ctx::Rect& q = c->rect;
-  q.raw_stride = (raw_cols + 63) & ~63;
-  q.raw_stream_stride = (size_t)raw_rows * q.raw_stride;
-  hipError_t e = remap_maps_upload(q.mem, q.maps, 2, raw_rows, raw_cols, rows, cols, xy, a);
-  for (int k = 0; k < 2; ++k)
-    for (int p = 0; p < 2 && e == hipSuccess; ++p) e = q.mem.alloc(&q.raw[p][k], (size_t)c->B * q.raw_stream_stride);
-  if (e != hipSuccess) { rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
-  q.on = true;
-  e = eq_keep_sync(c);
-  if (e == hipSuccess) e = col_slab_sync(c);
+  if (off) {                       // the rectified pair's own slabs go; colour frames come in at another size
+    if (slabs_reconcile(c) == hipSuccess) return VSLAM_OK;
+    slabs_settle(c);
+    return fail(c, VSLAM_ERR_HIP, "vslam_set_rectification: colour slabs");
+  }
+  hipError_t e = remap_maps_upload(c->rect.mem, c->rect.maps, 2, raw_rows, raw_cols, rows, cols, xy, a);
+  c->rect.on = e == hipSuccess;
+  if (e == hipSuccess) e = slabs_reconcile(c);
   if (e == hipSuccess && valid_on) e = mask_valid_build(c, valid_margin);
-  if (e != hipSuccess) { mask_valid_free(c); rect_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  if (e != hipSuccess) { mask_valid_free(c); rect_off(c); slabs_settle(c); }
+  return hip_status(c, "vslam_set_rectification", e);
 }
 VS_API int vslam_get_rectified_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
   const int rc = check_stream(c, s);
   if (rc != VSLAM_OK) return rc;
   if (!left || !right) return fail(c, VSLAM_ERR_INVALID, "vslam_get_rectified_images: null output");
   if (!c->rect.on || !c->rect.have_frame) return fail(c, VSLAM_ERR_STATE, "vslam_get_rectified_images: no frame has been rectified since vslam_set_rectification");
-  return pair_to_host(c, rectified_planes(c, c->last_set), s, c->cfg.c.rows, c->cfg.c.cols, left, right);
+  return pair_to_host(c, slab_planes(c, stage_route(stage_switches(c), false).remap.dst, c->last_set), s, c->cfg.c.rows, c->cfg.c.cols, left, right);
 }
 VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t row_stride, const int16_t* map_xy,
                           const uint16_t* map_a, int32_t drows, int32_t dcols, uint8_t* dst) {
@@ -181,16 +145,18 @@ VS_API int vslam_remap_u8(vslam_ctx* c, const uint8_t* src, int32_t rows, int32_
 static int eq_switch(vslam_ctx* c, bool on, const ClaheArgs* geo, double clip_limit) {
   static const char* const names[2] = {"vslam_set_equalization", "vslam_set_clahe"};
   std::string why;
+  const bool was_on = c->eq.on;
   const int rc = c->eq.switch_to(on, geo, clip_limit, c->B, 2, names, &why,
-                                 [&] { (void)hipSetDevice(c->device); sync_all(c); eq_free(c); },     // the frames in flight still read the tables and the slabs
-                                 [&] { const hipError_t e = eq_keep_sync(c); return e == hipSuccess ? sm_out_sync(c) : e; });
-  if (!c->eq.on) (void)sm_out_sync(c);      // switched off: the smoothed pair goes to upload[parity] again (this can only free)
+                                 [&] { (void)hipSetDevice(c->device); sync_all(c); c->eq.release(); },     // the frames in flight still read the tables and the slabs
+                                 [&] { return slabs_reconcile(c); });
+  if ((was_on || rc) && !c->eq.on) slabs_settle(c);      // switched off, or back off behind a failure: the pairs ahead of the slot go to upload[parity] again
   return rc ? fail(c, rc, why) : VSLAM_OK;
 }
 VS_API int vslam_set_equalization(vslam_ctx* c, int on) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_equalization called inside a frame");
-  if ((size_t)c->cfg.c.rows * c->cfg.c.cols > (size_t)VS_EQ_MAX_PIXELS) return fail(c, VSLAM_ERR_INVALID, "vslam_set_equalization: more than 2^24 pixels per image");
+  std::string why;
+  if (const int rc = equalization_size_check(VS_CONTEXT_WORDS, c->cfg.c.rows, c->cfg.c.cols, &why)) return fail(c, rc, why);
   return eq_switch(c, on != 0, nullptr, 0);
 }
 VS_API int vslam_set_clahe(vslam_ctx* c, int on, double clip_limit, int tiles_x, int tiles_y) {
@@ -232,16 +198,15 @@ VS_API int vslam_get_clahe_luts(vslam_ctx* c, int s, uint8_t* luts) {
 VS_API int vslam_set_color_input(vslam_ctx* c, int format) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_color_input called inside a frame");
-  if (format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8) return fail(c, VSLAM_ERR_INVALID, "vslam_set_color_input: unknown pixel format");
+  std::string why;
+  if (const int rc = color_format_check(VS_CONTEXT_WORDS, format, &why)) return fail(c, rc, why);
   if (format == c->col.format) return VSLAM_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the slabs
   if (format == VSLAM_PIXEL_GRAY8) mapcol_free(c);     // no colour left to sample
-  col_free(c);
+  c->col = vslam_ctx::Col();
   c->col.format = format;
-  const hipError_t e = col_slab_sync(c);
-  if (e != hipSuccess) { col_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_color_input: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  return slabs_follow(c, "vslam_set_color_input", [&] { c->col = vslam_ctx::Col(); });
 }
 VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
   const int rc = check_stream(c, s);
@@ -255,37 +220,21 @@ VS_API int vslam_get_gray_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* ri
 VS_API int vslam_set_downscale(vslam_ctx* c, int32_t factor, int32_t full_rows, int32_t full_cols) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_downscale called inside a frame");
-  if (factor != 1) {
-    if (!ds_factor_ok(factor)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_downscale: factor outside 1 .. 4");
-    if (!ds_size_ok(full_rows, full_cols, factor)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_downscale: full size outside 1 .. 32767 or below one block");
-    const int want_rows = c->rect.on ? c->rect.maps.raw_rows : c->cfg.c.rows, want_cols = c->rect.on ? c->rect.maps.raw_cols : c->cfg.c.cols;
-    if (ds_out(full_rows, factor) != want_rows || ds_out(full_cols, factor) != want_cols)
-      return fail(c, VSLAM_ERR_INVALID, c->rect.on ? "vslam_set_downscale: full size / factor is not the raw size of the rectification maps"
-                                                   : "vslam_set_downscale: full size / factor is not the context's image size");
-  }
+  const bool remap = c->rect.on;
+  std::string why;
+  if (const int rc = downscale_check(VS_CONTEXT_WORDS, factor, full_rows, full_cols, remap, remap ? c->rect.maps.raw_rows : c->cfg.c.rows,
+                                     remap ? c->rect.maps.raw_cols : c->cfg.c.cols, &why)) return fail(c, rc, why);
   if (c->sticky != VSLAM_OK) return c->sticky;
-  const vslam_ctx::Ds& q = c->ds;
-  if (factor == 1 ? q.factor == 1 : (q.factor == factor && q.full_rows == full_rows && q.full_cols == full_cols)) return VSLAM_OK;
+  if (c->ds.is(factor, full_rows, full_cols)) return VSLAM_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the slabs
-  ds_free(c);
-  hipError_t e = hipSuccess;
-  if (factor != 1) {
-    vslam_ctx::Ds& d = c->ds;
-    d.factor = factor; d.full_rows = full_rows; d.full_cols = full_cols;
-    d.stride = (full_cols + 63) & ~63;
-    d.stream_stride = (size_t)full_rows * d.stride;
-    for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = d.mem.alloc(&d.full[p][k], (size_t)c->B * d.stream_stride);
-  }
-  if (e == hipSuccess) e = col_slab_sync(c);     // colour frames come in at the new size
-  if (e != hipSuccess) { ds_free(c); (void)col_slab_sync(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_downscale: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  c->ds = vslam_ctx::Ds();
+  if (factor != 1) { c->ds.factor = factor; c->ds.full_rows = full_rows; c->ds.full_cols = full_cols; }     // colour frames come in at the new size, too
+  return slabs_follow(c, "vslam_set_downscale", [&] { c->ds = vslam_ctx::Ds(); });
 }
 VS_API int vslam_get_downscale(vslam_ctx* c, int32_t* factor, int32_t* full_rows, int32_t* full_cols) {
   if (!c) return VSLAM_ERR_INVALID;
-  if (factor) *factor = c->ds.factor;
-  if (full_rows) *full_rows = c->ds.factor > 1 ? c->ds.full_rows : 0;
-  if (full_cols) *full_cols = c->ds.factor > 1 ? c->ds.full_cols : 0;
+  c->ds.get(factor, full_rows, full_cols);
   return VSLAM_OK;
 }
 VS_API int vslam_get_downscaled_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
@@ -297,17 +246,6 @@ VS_API int vslam_get_downscaled_images(vslam_ctx* c, int s, uint8_t* left, uint8
 }
 
 // ---- smoothing of the grey pair ahead of the equalisation slot (kernels_smooth.h) ------------------------------------
-static_assert(VSLAM_SMOOTH_OFF == VS_SMOOTH_OFF && VSLAM_SMOOTH_GAUSSIAN == VS_SMOOTH_GAUSSIAN && VSLAM_SMOOTH_MEDIAN == VS_SMOOTH_MEDIAN, "smoothing modes");
-// what both setters and the stand-alone entry refuse: 0, or VSLAM_ERR_INVALID with *why filled
-static int smooth_check(const char* who, int mode, int32_t ksize, int rows, int cols, std::string* why) {
-  const char* what = nullptr;
-  if (mode != VSLAM_SMOOTH_GAUSSIAN && mode != VSLAM_SMOOTH_MEDIAN) what = ": unknown mode";
-  else if (!smooth_mode_ok(mode, ksize)) what = mode == VSLAM_SMOOTH_GAUSSIAN ? ": a Gaussian has ksize 3, 5 or 7" : ": a median has ksize 3 or 5";
-  else if (!smooth_size_ok(mode, ksize, rows, cols)) what = ": a Gaussian needs rows and cols above ksize / 2";
-  if (!what) return VSLAM_OK;
-  *why = std::string(who) + what;
-  return VSLAM_ERR_INVALID;
-}
 VS_API int vslam_set_smoothing(vslam_ctx* c, int mode, int32_t ksize) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_smoothing called inside a frame");
@@ -315,25 +253,16 @@ VS_API int vslam_set_smoothing(vslam_ctx* c, int mode, int32_t ksize) {
   if (mode != VSLAM_SMOOTH_OFF)
     if (const int rc = smooth_check("vslam_set_smoothing", mode, ksize, c->cfg.c.rows, c->cfg.c.cols, &why)) return fail(c, rc, why);
   if (c->sticky != VSLAM_OK) return c->sticky;
-  vslam_ctx::Sm& q = c->sm;
-  if (mode == VSLAM_SMOOTH_OFF ? q.mode == VSLAM_SMOOTH_OFF : (q.mode == mode && q.ksize == ksize)) return VSLAM_OK;
+  if (c->sm.is(mode, ksize)) return VSLAM_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the slabs
-  if (mode != VSLAM_SMOOTH_OFF && q.mode != VSLAM_SMOOTH_OFF) { q.mode = mode; q.ksize = ksize; q.have_frame = false; return VSLAM_OK; }     // the slabs stay
-  sm_free(c);
-  hipError_t e = hipSuccess;
-  if (mode != VSLAM_SMOOTH_OFF) {
-    for (int p = 0; p < 2; ++p) for (int k = 0; k < 2 && e == hipSuccess; ++k) e = q.mem.alloc(&q.in[p][k], (size_t)c->B * c->up_stream_stride);
-    if (e == hipSuccess) { q.mode = mode; q.ksize = ksize; e = sm_out_sync(c); }
-  }
-  if (e == hipSuccess) e = eq_keep_sync(c);
-  if (e != hipSuccess) { sm_free(c); (void)eq_keep_sync(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_smoothing: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  c->sm = vslam_ctx::Sm();         // from one mode to another the plan is the same: the slabs stay
+  if (mode != VSLAM_SMOOTH_OFF) { c->sm.mode = mode; c->sm.ksize = ksize; }
+  return slabs_follow(c, "vslam_set_smoothing", [&] { c->sm = vslam_ctx::Sm(); });
 }
 VS_API int vslam_get_smoothing(vslam_ctx* c, int* mode, int32_t* ksize) {
   if (!c) return VSLAM_ERR_INVALID;
-  if (mode) *mode = c->sm.mode;
-  if (ksize) *ksize = c->sm.mode ? c->sm.ksize : 0;
+  c->sm.get(mode, ksize);
   return VSLAM_OK;
 }
 VS_API int vslam_get_smoothed_images(vslam_ctx* c, int s, uint8_t* left, uint8_t* right) {
@@ -438,54 +367,6 @@ static int launch_motion_prior(vslam_ctx* c) {
   return VSLAM_OK;
 }
 // ---- detection masks (kernels_mask.h) ------------------------------------------------------------------------------
-// k_mask_pack on `n` streams of `sides` masks; fused when a.corner is set
-static void mask_pack_enqueue(hipStream_t st, const MaskPackArgs& a) {
-  hipLaunchKernelGGL(k_mask_pack, dim3((a.TX + VS_MASK_CW - 1) / VS_MASK_CW, (a.rows + VS_MASK_BR - 1) / VS_MASK_BR, a.n * a.sides), dim3(256), 0, st, a);
-}
-// what both setters refuse about a mask's geometry
-static int mask_args_check(vslam_ctx* c, const char* who, int32_t row_stride, int32_t margin) {
-  if (margin < 0 || margin > VS_MASK_MAX_MARGIN) return fail(c, VSLAM_ERR_INVALID, std::string(who) + ": margin outside 0 .. 64");
-  if (row_stride < c->cfg.c.cols) return fail(c, VSLAM_ERR_INVALID, std::string(who) + ": row stride smaller than image width");
-  return VSLAM_OK;
-}
-// k_mask_apply: corner words [n][2][nw] &= stat (stat_stream_stride 0: shared by the streams, else the stream's own words [n][nw] of side 0)
-static void mask_apply_enqueue(hipStream_t st, const MaskApplyArgs& a) {
-  hipLaunchKernelGGL(k_mask_apply, dim3(((a.nw + 1) / 2 + 255) / 256, a.sides, (a.n + VS_MASK_SB - 1) / VS_MASK_SB), dim3(256), 0, st, a);
-}
-// k_map_valid on `sides` maps of m: the eroded validity words [sides][rows][TX] into dst
-static void map_valid_enqueue(hipStream_t st, const RemapMaps& m, int sides, int margin, unsigned long long* dst) {
-  MapValidArgs v{};
-  for (int k = 0; k < sides; ++k) { v.map_xy[k] = m.xy[k]; v.map_a[k] = m.a[k]; }
-  v.map_stride = m.stride; v.raw_rows = m.raw_rows; v.raw_cols = m.raw_cols;
-  v.rows = m.rows; v.cols = m.cols; v.TX = (m.cols + 63) / 64; v.margin = margin; v.sides = sides; v.dst = dst;
-  hipLaunchKernelGGL(k_map_valid, dim3((v.TX + VS_MASK_CW - 1) / VS_MASK_CW, (v.rows + VS_MASK_BR - 1) / VS_MASK_BR, sides), dim3(256), 0, st, v);
-}
-// The context-wide keep words of `sides` images out of the user's words and the maps' validity words: the one there is, or both ANDed in
-// `comb` ([2][nw]: the validity words copied, the user's applied by k_mask_apply as to one stream's corner words).  Queues idle.
-static hipError_t mask_static_combine(hipStream_t st, int sides, size_t nw, unsigned long long* const* user, unsigned long long* const* valid,
-                                      DeviceStore& comb_mem, unsigned long long** comb, unsigned long long** stat) {
-  comb_mem.release();
-  comb[0] = comb[1] = nullptr;
-  bool both = false;
-  for (int k = 0; k < sides; ++k) { stat[k] = user[k] ? user[k] : valid[k]; both = both || (user[k] && valid[k]); }
-  if (!both) return hipSuccess;
-  unsigned long long* base = nullptr;
-  hipError_t e = comb_mem.alloc(&base, 2 * nw);
-  if (e != hipSuccess) return e;
-  MaskApplyArgs a{};
-  a.corner = base; a.nw = (int32_t)nw; a.n = 1; a.sides = sides;
-  active_all(a.active, 1);
-  for (int k = 0; k < sides && e == hipSuccess; ++k) {
-    if (!(user[k] && valid[k])) continue;
-    comb[k] = base + (size_t)k * nw;
-    e = hipMemcpyAsync(comb[k], valid[k], nw * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
-    a.stat[k] = user[k];
-    stat[k] = comb[k];
-  }
-  if (e == hipSuccess) { mask_apply_enqueue(st, a); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  return e;
-}
 static hipError_t mask_static_sync(vslam_ctx* c) {
   vslam_ctx::DetMask& q = c->dmask;
   return mask_static_combine(c->stream, 2, (size_t)c->cfg.c.rows * c->cfg.TX, q.user, q.valid, q.comb_mem, q.comb, q.stat);
@@ -504,20 +385,15 @@ static void mask_valid_free(vslam_ctx* c) {
 // the validity words of the maps the context holds (queues idle, rectification on)
 static hipError_t mask_valid_build(vslam_ctx* c, int margin) {
   vslam_ctx::DetMask& q = c->dmask;
-  const size_t nw = (size_t)c->cfg.c.rows * c->cfg.TX;
-  q.valid_mem.release();
-  q.valid[0] = q.valid[1] = nullptr;
-  unsigned long long* base = nullptr;
-  hipError_t e = q.valid_mem.alloc(&base, 2 * nw);
-  if (e == hipSuccess) { map_valid_enqueue(c->stream, c->rect.maps, 2, margin, base); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) { q.valid[0] = base; q.valid[1] = base + nw; q.valid_on = true; q.valid_margin = margin; e = mask_static_sync(c); }
+  hipError_t e = mask_valid_words(c->stream, c->rect.maps, 2, margin, (size_t)c->cfg.c.rows * c->cfg.TX, q.valid_mem, q.valid);
+  if (e == hipSuccess) { q.valid_on = true; q.valid_margin = margin; e = mask_static_sync(c); }
   return e;
 }
 VS_API int vslam_set_rectification_mask(vslam_ctx* c, int on, int32_t margin) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification_mask called inside a frame");
-  if (on && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) return fail(c, VSLAM_ERR_INVALID, "vslam_set_rectification_mask: margin outside 0 .. 64");
+  std::string why;
+  if (on) if (const int rc = mask_margin_check("vslam_set_rectification_mask", margin, &why)) return fail(c, rc, why);
   if (on && !c->rect.on) return fail(c, VSLAM_ERR_STATE, "vslam_set_rectification_mask: no rectification maps are set (vslam_set_rectification)");
   if (c->sticky != VSLAM_OK) return c->sticky;
   if (!on && !c->dmask.valid_on) return VSLAM_OK;
@@ -526,8 +402,8 @@ VS_API int vslam_set_rectification_mask(vslam_ctx* c, int on, int32_t margin) {
   c->dmask.last = 0;               // no frame has run under the new setting
   if (!on) { mask_valid_free(c); return VSLAM_OK; }
   const hipError_t e = mask_valid_build(c, margin);
-  if (e != hipSuccess) { mask_valid_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_rectification_mask: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  if (e != hipSuccess) mask_valid_free(c);
+  return hip_status(c, "vslam_set_rectification_mask", e);
 }
 VS_API int vslam_get_rectification_mask(vslam_ctx* c, int* on, int32_t* margin) {
   if (!c) return VSLAM_ERR_INVALID;
@@ -539,45 +415,27 @@ VS_API int vslam_set_detection_mask(vslam_ctx* c, const uint8_t* left, const uin
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_detection_mask called inside a frame");
   const bool off = !left && !right;
-  if (!off) if (int rc = mask_args_check(c, "vslam_set_detection_mask", row_stride, margin)) return rc;
+  std::string why;
+  if (!off) if (const int rc = mask_args_check("vslam_set_detection_mask", c->cfg.c.cols, row_stride, margin, &why)) return fail(c, rc, why);
   if (c->sticky != VSLAM_OK) return c->sticky;
   HIP_TRY(c, hipSetDevice(c->device));
   sync_all(c);                     // the frames in flight still read the old words
   mask_static_free(c);
   c->dmask.last = 0;               // no frame has run under the new setting
   if (off) return VSLAM_OK;
-  vslam_ctx::DetMask& q = c->dmask;
-  const int rows = c->cfg.c.rows, cols = c->cfg.c.cols, TX = c->cfg.TX;
-  const size_t bytes = (size_t)(rows - 1) * row_stride + cols;
   const uint8_t* const src[2] = {left, right};
-  uint8_t* tmp = nullptr;
-  hipError_t e = hipMalloc((void**)&tmp, bytes);
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    if (!src[k]) continue;
-    e = q.user_mem.alloc(&q.user[k], (size_t)rows * TX);
-    if (e == hipSuccess) e = hipMemcpy(tmp, src[k], bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) break;
-    MaskPackArgs a{};
-    a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = rows; a.cols = cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
-    a.dst = q.user[k];
-    active_all(a.active, 1);
-    mask_pack_enqueue(c->stream, a);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // tmp is refilled for the other side
-  }
-  if (tmp) (void)hipFree(tmp);
+  hipError_t e = mask_static_upload(c->stream, 2, src, row_stride, c->cfg.c.rows, c->cfg.c.cols, c->cfg.TX, margin, c->dmask.user_mem, c->dmask.user);
   if (e == hipSuccess) e = mask_static_sync(c);
-  if (e != hipSuccess) { mask_static_free(c); return fail(c, VSLAM_ERR_HIP, std::string("vslam_set_detection_mask: ") + hipGetErrorString(e)); }
-  return VSLAM_OK;
+  if (e != hipSuccess) mask_static_free(c);
+  return hip_status(c, "vslam_set_detection_mask", e);
 }
 VS_API int vslam_set_frame_masks(vslam_ctx* c, const uint8_t* left, const uint8_t* right, int32_t row_stride, size_t image_stride, int32_t margin, int on_device) {
   if (!c) return VSLAM_ERR_INVALID;
   if (c->frame_begun) return fail(c, VSLAM_ERR_STATE, "vslam_set_frame_masks called inside a frame");
   vslam_ctx::DetMask& q = c->dmask;
   if (!left && !right) { q.pending = false; return VSLAM_OK; }
-  if (int rc = mask_args_check(c, "vslam_set_frame_masks", row_stride, margin)) return rc;
-  if (c->B > 1 && image_stride < (size_t)(c->cfg.c.rows - 1) * row_stride + c->cfg.c.cols)
-    return fail(c, VSLAM_ERR_INVALID, "vslam_set_frame_masks: image stride smaller than one mask");
+  std::string why;
+  if (const int rc = frame_masks_check("vslam_set_frame_masks", c->B, c->cfg.c.rows, c->cfg.c.cols, row_stride, image_stride, margin, &why)) return fail(c, rc, why);
   if (c->sticky != VSLAM_OK) return c->sticky;
   q.pending = true; q.on_device = on_device != 0;
   q.src[0] = left; q.src[1] = right; q.row_stride = row_stride; q.image_stride = image_stride; q.margin = margin;

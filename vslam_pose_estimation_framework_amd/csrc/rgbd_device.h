@@ -327,12 +327,7 @@ public:
     bool off = false;
     if (const int rc = remap_maps_check("vslam_rgbd_set_undistortion", 1, raw_rows, raw_cols, p.rows, p.cols, &map_xy, &map_a, &off, &err)) return rc;
     if (pending) { err = "vslam_rgbd_set_undistortion: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
-    // while downscaling, the maps address the reduced raw image: full / factor is what this stage is handed
-    if (ds.factor > 1 && (ds_out(ds.full_rows, ds.factor) != (off ? p.rows : raw_rows) || ds_out(ds.full_cols, ds.factor) != (off ? p.cols : raw_cols))) {
-      err = off ? "vslam_rgbd_set_undistortion: the downscaled frames (vslam_rgbd_set_downscale) do not have the tracker's size"
-                : "vslam_rgbd_set_undistortion: the raw size is not the size of the downscaled frames (vslam_rgbd_set_downscale)";
-      return VSLAM_ERR_INVALID;
-    }
+    if (const int rc = remap_downscale_check(VS_TRACKER_WORDS, ds, off, raw_rows, raw_cols, p.rows, p.cols, &err)) return rc;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
     (void)hipStreamSynchronize(q2);
@@ -371,7 +366,7 @@ public:
   // [tilesX][256] instead of the count table.  The two modes exclude each other; switching one off while the other is on changes nothing.
   int set_equalization(int on) {
     if (pending) { err = "vslam_rgbd_set_equalization: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
-    if ((size_t)p.rows * p.cols > (size_t)VS_EQ_MAX_PIXELS) { err = "vslam_rgbd_set_equalization: more than 2^24 pixels per image"; return VSLAM_ERR_INVALID; }
+    if (const int rc = equalization_size_check(VS_TRACKER_WORDS, p.rows, p.cols, &err)) return rc;
     return eq_switch(on != 0, nullptr, 0);
   }
   int set_clahe(int on, double clip_limit, int tiles_x, int tiles_y) {
@@ -425,30 +420,14 @@ public:
   int set_detection_mask(const uint8_t* mask, int32_t row_stride, int32_t margin) {
     if (orbdet && mask) return orb_mask_refusal("vslam_rgbd_set_detection_mask");
     if (pending) { err = "vslam_rgbd_set_detection_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
-    if (mask && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_detection_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
-    if (mask && row_stride < p.cols) { err = "vslam_rgbd_set_detection_mask: row stride smaller than image width"; return VSLAM_ERR_INVALID; }
+    if (mask) if (const int rc = mask_args_check("vslam_rgbd_set_detection_mask", p.cols, row_stride, margin, &err)) return rc;
     if (!mask && !dmask.user[0]) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q); (void)hipStreamSynchronize(q2);
     dmask_user_free();
     drop_graph();                  // a captured launch sequence holds the launch, or lacks it
     if (!mask) return VSLAM_OK;
-    const int TX = ic->cfg.TX;
-    const size_t bytes = (size_t)(p.rows - 1) * row_stride + p.cols;
-    uint8_t* tmp = nullptr;
-    hipError_t e = hipMalloc((void**)&tmp, bytes);
-    if (e == hipSuccess) e = dmask.mem.alloc(&dmask.user[0], (size_t)p.rows * TX);
-    if (e == hipSuccess) e = hipMemcpy(tmp, mask, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      MaskPackArgs a{};
-      a.src[0] = tmp; a.src_row_stride = row_stride; a.rows = p.rows; a.cols = p.cols; a.TX = TX; a.margin = margin; a.n = 1; a.sides = 1;
-      a.dst = dmask.user[0];
-      active_all(a.active, 1);
-      mask_pack_enqueue(q, a);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipStreamSynchronize(q);
-    }
-    if (tmp) (void)hipFree(tmp);
+    hipError_t e = mask_static_upload(q, 1, &mask, row_stride, p.rows, p.cols, ic->cfg.TX, margin, dmask.mem, dmask.user);
     if (e == hipSuccess) e = dmask_sync();
     if (e != hipSuccess) { dmask_user_free(); return hip_fail(e, "vslam_rgbd_set_detection_mask"); }
     return VSLAM_OK;
@@ -465,7 +444,7 @@ public:
   int set_undistortion_mask(int on, int32_t margin) {
     if (orbdet && on) return orb_mask_refusal("vslam_rgbd_set_undistortion_mask");
     if (pending) { err = "vslam_rgbd_set_undistortion_mask: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
-    if (on && (margin < 0 || margin > VS_MASK_MAX_MARGIN)) { err = "vslam_rgbd_set_undistortion_mask: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
+    if (on) if (const int rc = mask_margin_check("vslam_rgbd_set_undistortion_mask", margin, &err)) return rc;
     if (on && !und.on) { err = "vslam_rgbd_set_undistortion_mask: no undistortion maps are set (vslam_rgbd_set_undistortion)"; return VSLAM_ERR_STATE; }
     if (!on && !dmask.valid_on) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
@@ -488,9 +467,7 @@ public:
     if (orbdet && masks) return orb_mask_refusal("vslam_rgbd_set_frame_masks");
     if (pending) { err = "vslam_rgbd_set_frame_masks: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if (!masks) { dmask.fm_pending = false; return VSLAM_OK; }
-    if (margin < 0 || margin > VS_MASK_MAX_MARGIN) { err = "vslam_rgbd_set_frame_masks: margin outside 0 .. 64"; return VSLAM_ERR_INVALID; }
-    if (row_stride < p.cols) { err = "vslam_rgbd_set_frame_masks: row stride smaller than image width"; return VSLAM_ERR_INVALID; }
-    if (B > 1 && image_stride < (size_t)(p.rows - 1) * row_stride + p.cols) { err = "vslam_rgbd_set_frame_masks: image stride smaller than one mask"; return VSLAM_ERR_INVALID; }
+    if (const int rc = frame_masks_check("vslam_rgbd_set_frame_masks", B, p.rows, p.cols, row_stride, image_stride, margin, &err)) return rc;
     dmask.fm_pending = true; dmask.fm_on_device = on_device;
     dmask.fm_src = masks; dmask.fm_row_stride = row_stride; dmask.fm_image_stride = image_stride; dmask.fm_margin = margin;
     return VSLAM_OK;
@@ -561,15 +538,8 @@ public:
   // caller's device images into what the next stage reads — und.raw_depth while undistorting, else d_depth.  Caller memory is only read.
   int set_downscale(int32_t factor, int32_t full_rows, int32_t full_cols) {
     if (pending) { err = "vslam_rgbd_set_downscale: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
-    if (factor != 1) {
-      if (!ds_factor_ok(factor)) { err = "vslam_rgbd_set_downscale: factor outside 1 .. 4"; return VSLAM_ERR_INVALID; }
-      if (!ds_size_ok(full_rows, full_cols, factor)) { err = "vslam_rgbd_set_downscale: full size outside 1 .. 32767 or below one block"; return VSLAM_ERR_INVALID; }
-      if (ds_out(full_rows, factor) != red_rows() || ds_out(full_cols, factor) != red_cols()) {
-        err = und.on ? "vslam_rgbd_set_downscale: full size / factor is not the raw size of the undistortion maps" : "vslam_rgbd_set_downscale: full size / factor is not the tracker's image size";
-        return VSLAM_ERR_INVALID;
-      }
-    }
-    if (factor == 1 ? ds.factor == 1 : (ds.factor == factor && ds.full_rows == full_rows && ds.full_cols == full_cols)) return VSLAM_OK;
+    if (const int rc = downscale_check(VS_TRACKER_WORDS, factor, full_rows, full_cols, und.on, red_rows(), red_cols(), &err)) return rc;
+    if (ds.is(factor, full_rows, full_cols)) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
     (void)hipStreamSynchronize(q2);
@@ -587,11 +557,7 @@ public:
     ds.factor = factor; ds.full_rows = full_rows; ds.full_cols = full_cols;
     return VSLAM_OK;
   }
-  void get_downscale(int32_t* factor, int32_t* full_rows, int32_t* full_cols) const {
-    if (factor) *factor = ds.factor;
-    if (full_rows) *full_rows = ds.factor > 1 ? ds.full_rows : 0;
-    if (full_cols) *full_cols = ds.factor > 1 ? ds.full_cols : 0;
-  }
+  void get_downscale(int32_t* factor, int32_t* full_rows, int32_t* full_cols) const { ds.get(factor, full_rows, full_cols); }
   // the reduced image and depth image of the last finished frame of `stream` (dense, full / factor; either may be null)
   int get_downscaled(int stream, uint8_t* image, uint16_t* depth) {
     if (int rc = readable(stream)) return rc;
@@ -612,7 +578,7 @@ public:
     if (pending) { err = "vslam_rgbd_set_smoothing: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
     if (mode != VSLAM_SMOOTH_OFF)
       if (const int rc = smooth_check("vslam_rgbd_set_smoothing", mode, ksize, p.rows, p.cols, &err)) return rc;
-    if (mode == VSLAM_SMOOTH_OFF ? sm.mode == VSLAM_SMOOTH_OFF : (sm.mode == mode && sm.ksize == ksize)) return VSLAM_OK;
+    if (sm.is(mode, ksize)) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
     (void)hipStreamSynchronize(q2);
@@ -628,10 +594,7 @@ public:
     sm.mode = mode; sm.ksize = ksize;
     return VSLAM_OK;
   }
-  void get_smoothing(int* mode, int32_t* ksize) const {
-    if (mode) *mode = sm.mode;
-    if (ksize) *ksize = sm.mode ? sm.ksize : 0;
-  }
+  void get_smoothing(int* mode, int32_t* ksize) const { sm.get(mode, ksize); }
   // the smoothed image of the last finished frame of `stream` (dense); equalised in place afterwards while the slot is on
   int get_smoothed(int stream, uint8_t* image) {
     if (int rc = readable(stream)) return rc;
@@ -648,7 +611,7 @@ public:
   int in_bytes() const { return (col.format ? gray_channels(col.format) : 1) * in_cols(); }      // of one row of the intensity image that comes in
   int set_color_input(int format) {
     if (pending) { err = "vslam_rgbd_set_color_input: a frame is in flight (call vslam_rgbd_wait first)"; return VSLAM_ERR_STATE; }
-    if (format < VSLAM_PIXEL_GRAY8 || format > VSLAM_PIXEL_RGBA8) { err = "vslam_rgbd_set_color_input: unknown pixel format"; return VSLAM_ERR_INVALID; }
+    if (const int rc = color_format_check(VS_TRACKER_WORDS, format, &err)) return rc;
     if (format == col.format) return VSLAM_OK;
     (void)hipSetDevice(ic->device);
     (void)hipStreamSynchronize(q);
@@ -786,10 +749,10 @@ private:
   DeviceStore col_mem;
   // downscale of the incoming frames: off while factor is 1.  img: the reduced images [B]; full_depth: the full-size depth images of a host
   // frame [B][full_rows * full_cols], re-packed.  full_dep*: where this frame's full-size depth images are (the staging or caller memory)
-  struct Down { int factor = 1, full_rows = 0, full_cols = 0; bool have_frame = false; ImgPlanes img; uint16_t* full_depth = nullptr; DeviceStore mem; } ds;
+  struct Down : DownscaleSwitch { bool have_frame = false; ImgPlanes img; uint16_t* full_depth = nullptr; DeviceStore mem; } ds;
   const uint16_t* full_dep = nullptr; int32_t full_dep_stride = 0; size_t full_dep_stream = 0;
   // smoothing of the intensity image: off while mode is VSLAM_SMOOTH_OFF.  img: the smoothed images [B]
-  struct Smooth { int mode = 0, ksize = 0; bool have_frame = false; ImgPlanes img; DeviceStore mem; } sm;
+  struct Smooth : SmoothSwitch { bool have_frame = false; ImgPlanes img; DeviceStore mem; } sm;
   // bilateral filtering of the depth image: off while bl.on is false.  depth: the filtered images [B][rows * cols] the space map reads;
   // args: what the three kernels get but for this frame's source (sizes, scales, taps, the range cells [B][4] and the tables [B][4098])
   struct Bilateral { bool on = false, have_frame = false; double sigma_color = 0, sigma_space = 0; uint16_t* depth = nullptr; BilateralArgs args; DeviceStore mem; } bl;
@@ -809,13 +772,8 @@ private:
   void dmask_user_free() { dmask.mem.release(); dmask.user[0] = nullptr; dmask.have_frame = false; (void)dmask_sync(); }
   void dmask_valid_free() { dmask.valid_mem.release(); dmask.valid[0] = nullptr; dmask.valid_on = false; dmask.valid_margin = 0; dmask.have_frame = false; (void)dmask_sync(); }
   hipError_t dmask_valid_build(int margin) {
-    dmask.valid_mem.release();
-    dmask.valid[0] = nullptr;
-    unsigned long long* w = nullptr;
-    hipError_t e = dmask.valid_mem.alloc(&w, (size_t)p.rows * ic->cfg.TX);
-    if (e == hipSuccess) { map_valid_enqueue(q, und.maps, 1, margin, w); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(q);
-    if (e == hipSuccess) { dmask.valid[0] = w; dmask.valid_on = true; dmask.valid_margin = margin; e = dmask_sync(); }
+    hipError_t e = mask_valid_words(q, und.maps, 1, margin, (size_t)p.rows * ic->cfg.TX, dmask.valid_mem, dmask.valid);
+    if (e == hipSuccess) { dmask.valid_on = true; dmask.valid_margin = margin; e = dmask_sync(); }
     return e;
   }
   void dmask_free() {

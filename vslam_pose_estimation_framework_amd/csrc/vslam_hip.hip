@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -32,6 +33,7 @@
 #define VS_API extern "C" __attribute__((visibility("default")))
 
 #include "device_store.h"    // memory a switchable feature owns on the device
+#include "stage_plan.h"      // the stereo context's input stages as a plan: which slabs exist, a frame's route (plain C++)
 #include "host_prestage.h"   // the input stages (grey, remap, equalisation slot) as the stereo context and the RGB-D tracker share them
 #include "host_ctx.h"        // the context: allocation, scratch, timers, configuration, create / destroy / reset, stream lifetime
 #include "host_switches.h"   // the context's input-stage switches and their getters: rectification, equalisation / CLAHE, colour input
